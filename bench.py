@@ -23,6 +23,8 @@ timed steps (encode INCLUDED).  `sentences_per_s` is the same time base.  Per-ph
 under `phases`.  `roofline` is for the dominant kernel, cos_topk_partial: algorithmic FLOPs 2*Q*N_local*d per launch
 (768 FLOP/pair) over its HIP-event duration on its own stream, against the dense bf16 MFMA peak; the HBM streaming
 figure (ceil(Q/256) * N * d * 2 B per launch) is reported beside it.
+`--dump-outputs DIR` writes the last timed step's results (scores, indices, embeddings) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -140,6 +142,38 @@ def cpu_baseline(preset: str, d: int, n_rows: int, k: int):
             "encode_sentences_per_s": round(n_sent / t_enc, 1)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def gather_rows(x, counts, backend, dev):
+    """All ranks' row slices (uneven `counts`) in rank order: padded all-gather (gloo: through host memory)."""
+    on = dev if backend == "nccl" else torch.device("cpu")
+    buf = torch.zeros((max(counts), x.shape[1]), dtype=x.dtype, device=on)
+    buf[:x.shape[0]] = x.to(on)
+    parts = [torch.empty_like(buf) for _ in counts]
+    dist.all_gather(parts, buf)
+    return torch.cat([p[:c] for p, c in zip(parts, counts)])
+
+
+def dump_outputs(out_dir, scores, indices, emb):
+    """What a caller of the timed path receives from one step: top-k scores [Q, k] (float32), their global corpus indices
+    (as float64: exact for every index) and the pooled float32 query embeddings [Q, d].  Beyond DUMP_LIMIT_BYTES in all, a
+    fixed seeded sample of query rows is written (the same rows of every array) and its row numbers as query_rows.npy."""
+    arrays = {"scores": scores.float().cpu().numpy(), "indices": indices.cpu().numpy().astype(np.float64),
+              "embeddings": emb.float().cpu().numpy()}
+    n = arrays["scores"].shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) if n else 1
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        m = (DUMP_LIMIT_BYTES - 1024) // (row_bytes + 8)          # (+8: the float64 row number of query_rows.npy)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as a CHILD torch.distributed.run before this
     process initialises a GPU (an exec from a GPU-initialised process is forbidden on the pool; counting devices is not an
@@ -173,7 +207,11 @@ def main():
     ap.add_argument("--total-rows", type=int, default=8_000_000, help="corpus rows over the whole job (--scaling strong)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of 4 result rows after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (scores, indices, embeddings) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
@@ -272,8 +310,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # sanity of the last result (not timed): sorted lists, indices inside the global corpus
     s_last, i_last, emb_last = out
+    dumped = None
+    if args.dump_outputs:   # (every rank takes part in the gather; rank 0 writes)
+        emb_all = emb_last if world == 1 else gather_rows(emb_last, q_counts, backend, dev)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, s_last, i_last, emb_all)
+    # sanity of the last result (not timed): sorted lists, indices inside the global corpus
     assert s_last.shape == (Q, k) and bool((s_last[:, :-1] >= s_last[:, 1:]).all())
     assert int(i_last.min()) >= 0 and int(i_last.max()) < n_total
     # ... and four of its rows against the oracle's restatement of the reference search (F.cosine_similarity of the float32
@@ -370,6 +413,7 @@ def main():
                             "backend": dist.get_backend() if world > 1 else None,
                             "visible_devices_per_rank": dev_counts},
             "verified": verified,
+            "outputs_dumped": dumped,
             "sentences_per_s": round(Q * args.steps / elapsed, 1),
             "encode_text_from_strings": from_strings,
             "phases": {"encode_ms": round(enc_ms, 4), "search_ms": round(srch_ms, 4),
