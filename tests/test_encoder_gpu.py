@@ -218,23 +218,31 @@ def test_from_pretrained_local_directory(tmp_path):
         assert np.abs(out.cpu().numpy() - g["pooled"]).max() <= POOL_TOL
 
 
-@pytest.mark.parametrize("preset,wdtype", [("bert-base-uncased", "bf16"), ("bert-base-uncased", "mxfp8"),
-                                           ("all-mpnet-base-v2", "bf16"), ("all-MiniLM-L6-v2", "bf16")])
-def test_large_batch_equals_small_batches_bitwise(preset, wdtype):
+@pytest.mark.parametrize("preset,wdtype,n", [
+    pytest.param("bert-base-uncased", "bf16", 1500, id="bert-base-uncased-bf16"),
+    pytest.param("bert-base-uncased", "mxfp8", 1500, id="bert-base-uncased-mxfp8"),
+    pytest.param("all-mpnet-base-v2", "bf16", 1500, id="all-mpnet-base-v2-bf16"),
+    # MiniLM, hidden-384 LayerNorm GEMM dispatch: 2300 sentences (36 986 tokens) = ln_rows_gemm + ln_tail_gemm; 1500 (24 201
+    # tokens) = the 128-token gemm_bf16_kernel form alone; 4700 (76 072 tokens) = one ln_rows_gemm round + the 64-token
+    # remainder launch for 10 536 rows
+    pytest.param("all-MiniLM-L6-v2", "bf16", 2300, id="all-MiniLM-L6-v2-bf16"),
+    pytest.param("all-MiniLM-L6-v2", "bf16", 1500, id="all-MiniLM-L6-v2-bf16-1500"),
+    pytest.param("all-MiniLM-L6-v2", "bf16", 4700, id="all-MiniLM-L6-v2-bf16-4700"),
+])
+def test_large_batch_equals_small_batches_bitwise(preset, wdtype, n):
     """~24 k tokens in one call: every projection launch has more output tiles than CUs, so the persistent workgroups of
     the ping-pong kernel walk several tiles each (next tile's first k-tile fetched during the epilogue, slot parity and
     source offsets carried across tiles) and the LayerNorm GEMMs take their main + tail launches.  Rows are independent
     and every kernel sums over k in the same order whatever the tile, so the result must equal — bit for bit — the same
     sentences encoded 48 at a time (one tile per workgroup, no tail)."""
     cfg = presets.PRESETS[preset]
-    n = 2300 if cfg.hidden == 384 else 1500          # MiniLM: > 32768 tokens, so the LayerNorm GEMMs split main + tail
     flat, cu = presets.synthetic_token_batch(n, seed="big/" + preset, vocab_size=cfg.vocab, max_len=64)
     cu = cu.astype(np.int64)
     enc = NativeEncoder.from_preset(preset, max_tokens=int(cu[-1]), max_seqs=n, weight_dtype=wdtype)
     big = enc.forward_packed(torch.from_numpy(flat).to(DEV), torch.from_numpy(cu.astype(np.int32)).to(DEV))["pooled"]
     torch.cuda.synchronize()
     assert torch.isfinite(big).all()
-    for s in (0, 480, 1452):
+    for s in sorted({0, 480, 1452, n - 48}):     # n - 48: the last rows, which the LayerNorm GEMMs' tail launches compute
         rows = slice(s, s + 48)
         f = flat[cu[s]:cu[s + 48]]
         c = (cu[s:s + 49] - cu[s]).astype(np.int32)
@@ -246,8 +254,8 @@ def test_large_batch_equals_small_batches_bitwise(preset, wdtype):
 def test_repeated_forwards_are_bit_stable(preset):
     """The same batch 60 times through fresh launches: every result equals the first, bit for bit, and is finite.  (Round 3: an
     inline-asm 16-byte global store without the wait state the ISA wants before its data registers are overwritten corrupted one
-    8-feature group in roughly every fourth forward on some boxes and never on others — tools/nan_probe.py; a single forward per
-    test let it through.)"""
+    8-feature group in roughly every fourth forward on some boxes and never on others; a single forward per test let it
+    through.)"""
     cfg = presets.PRESETS[preset]
     n = 2300 if cfg.hidden == 384 else 900
     flat, cu = presets.synthetic_token_batch(n, seed="big/" + preset, vocab_size=cfg.vocab, max_len=64)

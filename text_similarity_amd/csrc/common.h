@@ -138,35 +138,14 @@ __device__ __forceinline__ float guard_eps(float rho_q, float rho_c, int ld) {
     return (float)(e * (1.0 + 1e-6));
 }
 
-__device__ __forceinline__ float gelu_erf(float x) {
-    // 0.5 x (1 + erf(x / sqrt 2)); erf by Abramowitz-Stegun 7.1.26 (|err| < 1.5e-7, far below bf16 output resolution),
-    // raw v_rcp_f32 / v_exp_f32 (1 ulp) with the constants folded: 14 VALU instructions (erff(): ~30; the same formula
-    // with an IEEE-correct reciprocal and a guarded exp: 29).  FFN1's epilogue is VALU-bound, so this matters.
-    //   1 - erf(|x|/sqrt2) = poly(t) * t * exp(-x^2/2),  t = 1 / (1 + p |x| / sqrt2)
-    //   gelu = hx + |hx| (1 - pe) with hx = x/2
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, fabsf(x), 1.0f));
-    float poly = fmaf(1.061405429f, t, -1.453152027f);
-    poly = fmaf(poly, t, 1.421413741f);
-    poly = fmaf(poly, t, -0.284496736f);
-    poly = fmaf(poly, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(x * x * (-0.5f * 1.4426950408889634f));
-    const float pe = poly * t * e;
-    const float hx = 0.5f * x;
-    return fmaf(-fabsf(hx), pe, hx + fabsf(hx));
-}
-
 // GELU of two values without transcendentals, in packed fp32 (v_pk_fma_f32 / v_pk_mul_f32: two values per issue slot).
 //   gelu(x) = x * Phi(x),  Phi(x) ~ 1/2 + xc * S(xc^2),  xc = clamp(x, -4, 4),  S = degree-8 Chebyshev fit of
 //   (Phi(sqrt u) - 1/2) / sqrt u on u in [0, 16]  (fp32 Horner: relative error <= 2.5e-5 for x > 0, absolute error
 //   <= 4e-5 on [-4, 0] — two orders below the bf16 resolution of the stored result; beyond |x| = 4 Phi is frozen at
-//   Phi(+-4) = 1 - 3.2e-5 / 3.2e-5).  26 issue cycles per value against 64 for gelu_erf (rcp + exp + 12 VALU): the FFN1
-//   epilogue is VALU-bound.  Set TSIM_GELU_ERF at build time (-DTSIM_GELU_ERF) to fall back to the A&S erf form.
+//   Phi(+-4) = 1 - 3.2e-5 / 3.2e-5).  26 issue cycles per value against 64 for the Abramowitz-Stegun erf form it replaced
+//   (rcp + exp + 12 VALU): the FFN1 epilogue is VALU-bound.
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ void gelu2(float &a, float &b) {
-#ifdef TSIM_GELU_ERF
-    a = gelu_erf(a);
-    b = gelu_erf(b);
-#else
     const f32x2 x = {a, b};
     const f32x2 xc = {__builtin_amdgcn_fmed3f(a, -4.0f, 4.0f), __builtin_amdgcn_fmed3f(b, -4.0f, 4.0f)};
     const f32x2 u = xc * xc;
@@ -183,58 +162,6 @@ __device__ __forceinline__ void gelu2(float &a, float &b) {
     const f32x2 y = x * phi;
     a = y[0];
     b = y[1];
-#endif
-}
-
-// The same polynomial for N values at once as N INDEPENDENT scalar Horner chains, step by step: no instruction waits for
-// the one before it.  gelu2's packed chain is the cheaper form when issue slots are the limit (a VALU-bound epilogue:
-// 26 issue cycles per value), but a packed fp32 op beside MFMAs costs far more than its slot and every step waits for the
-// previous one (measured in ffn_fused_kernel: ~240 cycles per gelu2 call); where the values sit in the shadow of an MFMA
-// stream this form is the right one.  Bit-identical to gelu2 (same operations per value, fp32 fma).
-template <int N>
-__device__ __forceinline__ void gelu_n(float (&x)[N]) {
-#ifdef TSIM_GELU_ERF
-#pragma unroll
-    for (int i = 0; i < N; ++i) x[i] = gelu_erf(x[i]);
-#else
-    float xc[N], u[N], p[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        xc[i] = __builtin_amdgcn_fmed3f(x[i], -4.0f, 4.0f);
-        u[i] = xc[i] * xc[i];
-        p[i] = 9.56756410e-11f;
-    }
-    constexpr float c[8] = {-8.02642397e-09f, 3.00262883e-07f, -6.72069427e-06f, 1.02510894e-04f,
-                            -1.15122017e-03f, 9.92152281e-03f, -6.64609522e-02f, 3.98939520e-01f};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int i = 0; i < N; ++i) p[i] = fmaf(p[i], u[i], c[k]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) x[i] = x[i] * fmaf(xc[i], p[i], 0.5f);
-#endif
-}
-
-// gelu_n cut into 11 stages (0: clamp + square, 1..8: one Horner step each, 9: Phi, 10: x * Phi) so that a caller can place
-// one stage of N independent operations between the MFMAs of a dependent accumulation chain.  State: xc, u, p (N each).
-template <int ST, int N>
-__device__ __forceinline__ void gelu_stage(float (&x)[N], float (&xc)[N], float (&u)[N], float (&p)[N]) {
-    constexpr float c[8] = {-8.02642397e-09f, 3.00262883e-07f, -6.72069427e-06f, 1.02510894e-04f,
-                            -1.15122017e-03f, 9.92152281e-03f, -6.64609522e-02f, 3.98939520e-01f};
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        if constexpr (ST == 0) {
-            xc[i] = __builtin_amdgcn_fmed3f(x[i], -4.0f, 4.0f);
-            u[i] = xc[i] * xc[i];
-            p[i] = 9.56756410e-11f;
-        } else if constexpr (ST <= 8) {
-            p[i] = fmaf(p[i], u[i], c[ST - 1]);
-        } else if constexpr (ST == 9) {
-            p[i] = fmaf(xc[i], p[i], 0.5f);
-        } else {
-            x[i] = x[i] * p[i];
-        }
-    }
 }
 
 // async global -> LDS copy of 16 bytes per lane; LDS destination = wave-uniform base + lane*16.

@@ -124,9 +124,6 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t *__restrict
 // HBM/MFMA balance point, so operand reuse through L2 (XCD-aware tile order) matters.
 // =====================================================================================================
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RES_LN = 2 };
-#ifndef TSIM_LN_EPI_DIRECT
-#define TSIM_LN_EPI_DIRECT 1   // LayerNorm epilogue: residual / result as 16-byte accesses per lane (0: both tiles through LDS, the first form)
-#endif
 
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NST = 2>
 constexpr int gemm_lds_bytes() {
@@ -319,19 +316,13 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
     const int mbase = m0 + wm * TM + r;
 
     if constexpr (EPI == EPI_RES_LN) {
-        // Residual add + LayerNorm over the N = BN features of each token (two-pass statistics, fp32), with the
-        // residual tile and the result tile moved THROUGH LDS: a lane owns scattered 8-byte groups of 32 different
-        // token rows, so direct global loads/stores touch 32 cache lines per instruction (measured: 18 us of a 55 us
-        // tile).  The [BM x N] bf16 tile is contiguous in memory: it comes in by LDS-DMA in whole 1-KiB pieces and
-        // goes out as 16-byte row-contiguous stores; the scattered accesses hit LDS instead (16-byte slots XORed with
-        // the row so that the 32 rows of a wave spread over the banks).
-#if TSIM_LN_EPI_DIRECT
+        // Residual add + LayerNorm over the N = BN features of each token (two-pass statistics, fp32).
         // DIRECT form (end of round 2): the residual comes in and the result goes out as 16-byte accesses per lane with a
         // v_permlane32_swap between the half-waves (lane (r, h) touches features 8 (gq + h) .. + 7 of its token's row: 32
-        // contiguous bytes per row and instruction pair), the way gemm_xres2 and the fused FFN kernel store.  No residual tile
-        // DMA, no output tile in LDS, two workgroup barriers less; only the row statistics still cross the four feature waves
-        // through LDS.  (The first form, below, moved both tiles through LDS because 8-byte groups per lane touched 32 cache
-        // lines per instruction; timing-only builds put prologue + epilogue at 43 % of this kernel.)
+        // contiguous bytes per row and instruction pair), the way gemm_xres2 stores.  No residual tile DMA, no output tile in
+        // LDS; only the row statistics cross the four feature waves through LDS.  (The first form moved both tiles through LDS
+        // because 8-byte groups per lane touched 32 cache lines per instruction; timing-only builds put prologue + epilogue at
+        // 43 % of this kernel.)
         float *red = reinterpret_cast<float *>(smem);            // [2][WAVES_N][BM] partial sums
         __builtin_amdgcn_s_barrier();                            // every wave is past its last fragment read
 #pragma unroll
@@ -420,105 +411,6 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
                 }
             }
         }
-#else
-        constexpr int SPR = BN / 8;                       // 16-byte slots per tile row
-        constexpr int SWZ = SPR >= 16 ? 15 : SPR - 1;
-        constexpr int TILE_B = BM * BN * 2;
-        constexpr int TPIECES = TILE_B / 1024;
-        static_assert(TILE_B % 1024 == 0 && TILE_B + 2 * WAVES_N * BM * 4 <= NST * STAGE, "epilogue tile must fit the staging LDS");
-        float *red = reinterpret_cast<float *>(smem + TILE_B);   // [2][WAVES_N][BM] partial sums
-        __builtin_amdgcn_s_barrier();                     // every wave is past its last fragment read
-        {
-            const char *rbase = reinterpret_cast<const char *>(res + (int64_t)m0 * N);
-            for (int p = wave; p < TPIECES; p += NW) {
-                const int sl = p * 64 + lane;
-                const int row = sl / SPR, cp = sl % SPR;
-                glds16(rbase + (int64_t)row * (BN * 2) + ((cp ^ (row & SWZ)) << 4), smem + p * 1024);
-            }
-        }
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        auto tile_addr = [&](int row, int nloc) __attribute__((always_inline)) {   // 8-byte group of 4 features
-            return smem + row * (BN * 2) + ((((nloc >> 3) ^ (row & SWZ))) << 4) + ((nloc & 4) << 1);
-        };
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-            const int row = wm * TM + j * 32 + r;
-#pragma unroll
-            for (int i = 0; i < NT; ++i)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const uint2 rv = *reinterpret_cast<const uint2 *>(tile_addr(row, wn * TN + i * 32 + 8 * gq + 4 * h));
-                    acc[i][j][4 * gq + 0] += __uint_as_float(rv.x << 16);
-                    acc[i][j][4 * gq + 1] += __uint_as_float(rv.x & 0xffff0000u);
-                    acc[i][j][4 * gq + 2] += __uint_as_float(rv.y << 16);
-                    acc[i][j][4 * gq + 3] += __uint_as_float(rv.y & 0xffff0000u);
-                }
-        }
-        float mean[MT], rstd[MT];
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-            for (int j = 0; j < MT; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int i = 0; i < NT; ++i)
-#pragma unroll
-                    for (int g = 0; g < 16; ++g) {
-                        // explicit operations, nothing left to contraction: ln_rows_gemm_kernel repeats them literally
-                        if (pass == 0) {
-                            s += acc[i][j][g];
-                        } else {
-                            const float dlt = acc[i][j][g] - mean[j];
-                            s = fmaf(dlt, dlt, s);
-                        }
-                    }
-                s += __shfl_xor(s, 32, 64);
-                if (h == 0) red[(pass * WAVES_N + wn) * BM + wm * TM + j * 32 + r] = s;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < MT; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int w = 0; w < WAVES_N; ++w) s += red[(pass * WAVES_N + w) * BM + wm * TM + j * 32 + r];
-                if (pass == 0)
-                    mean[j] = s / (float)N;
-                else
-                    rstd[j] = 1.0f / sqrtf(s / (float)N + eps);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int n = nbase + i * 32 + 8 * gq;
-                const float4 gv = *reinterpret_cast<const float4 *>(gamma + n);
-                const float4 be = *reinterpret_cast<const float4 *>(beta + n);
-#pragma unroll
-                for (int j = 0; j < MT; ++j) {
-                    const float y0 = fmaf((acc[i][j][4 * gq + 0] - mean[j]) * rstd[j], gv.x, be.x);
-                    const float y1 = fmaf((acc[i][j][4 * gq + 1] - mean[j]) * rstd[j], gv.y, be.y);
-                    const float y2 = fmaf((acc[i][j][4 * gq + 2] - mean[j]) * rstd[j], gv.z, be.z);
-                    const float y3 = fmaf((acc[i][j][4 * gq + 3] - mean[j]) * rstd[j], gv.w, be.w);
-                    uint2 o;
-                    o.x = pack_bf16x2(y0, y1);
-                    o.y = pack_bf16x2(y2, y3);
-                    // each lane overwrites exactly the residual group it read
-                    *reinterpret_cast<uint2 *>(tile_addr(wm * TM + j * 32 + r, wn * TN + i * 32 + 8 * gq + 4 * h)) = o;
-                }
-            }
-        __syncthreads();
-        {
-            char *obase = reinterpret_cast<char *>(out + (int64_t)m0 * N);
-            for (int sl = threadIdx.x; sl < BM * SPR; sl += NW * 64) {
-                const int row = sl / SPR, cp = sl % SPR;
-                if (m0 + row < M)
-                    *reinterpret_cast<uint4 *>(obase + (int64_t)row * (BN * 2) + ((cp ^ (row & SWZ)) << 4)) =
-                        *reinterpret_cast<const uint4 *>(smem + sl * 16);
-            }
-        }
-#endif
     } else {
 #pragma unroll
         for (int i = 0; i < NT; ++i)
@@ -543,26 +435,14 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
     }
 }
 
-// =====================================================================================================
-// GEMM with the activation operand RESIDENT IN REGISTERS (K = 384 layers of MiniLM: QKV and FFN1).
-//
-// At K = 384 a tiled GEMM spends its time in prologues and epilogues: six K-steps per output tile.  Here a workgroup
-// (8 waves) owns 256 tokens for the WHOLE layer: each wave loads its 32 token rows once as MFMA B fragments (K/16 x 4 =
-// 96 VGPRs) and then sweeps every output feature while W streams through LDS exactly like the corpus does in the
-// cosine kernel: 192-feature x 64-k tiles (24 KiB), 3-stage LDS-DMA ring, counted vmcnt, one raw s_barrier per tile, 24
-// MFMAs per tile and wave, XOR-swizzled image read with conflict-free ds_read_b128.  The W stream never restarts
-// between output tiles, so there is one prologue per 256 tokens instead of one per 128x128 tile.
-// Orientation as in gemm_bf16_kernel (token on the lane); the epilogue pairs the two half-waves with
-// v_permlane32_swap so every lane stores 16 contiguous bytes.
-// =====================================================================================================
-constexpr int XR_BN = 192, XR_BK = 64, XR_NSTAGE = 3;
-constexpr int XR_STG_ROW = 208;   // bytes per token row of the output staging image (192 + 16 pad: spreads rows over banks)
+// gemm_plain sends K = 384 projections whose width is a multiple of XR_BN to gemm_xres2 (below).  (192 is the feature tile of
+// the first form of that kernel; the predicate is kept as it was so that every shape keeps its kernel.)
+constexpr int XR_BN = 192;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 #ifdef TSIM_PP_STAMPS
-// DIAGNOSTIC build only (python -m text_similarity_amd.build --stamps; tools/pp_stamps.py --xres): cycles of wave 0 per
-// workgroup: [0] tile-steps, [1] wait (vmcnt + barrier), [2] DMA issue, [3] fragment reads + MFMAs, [4] epilogues,
-// [5] activation reloads, [6] items.
+// DIAGNOSTIC build only (python -m text_similarity_amd.build --stamps; tools/x2_stamps.py): cycles of wave 0 of gemm_xres2 per
+// workgroup: [0] steps, [1] wait (vmcnt + barrier), [3] fragment reads + MFMAs, [4] stores, [6] items.
 __device__ unsigned long long g_xr_stamps[8];
 #define XR_T() __builtin_amdgcn_s_memtime()
 #ifndef TSIM_XR_STAMP_TID
@@ -574,248 +454,6 @@ __device__ unsigned long long g_xr_stamps[8];
 #define XR_ACC(i, v) do { } while (0)
 #endif
 
-template <int K, int EPI, int NW>
-__global__ __launch_bounds__(NW * 64) void gemm_xres_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W,
-                                                        const float *__restrict__ bias, bf16_t *__restrict__ out,
-                                                        int M, int N, int items_total) {
-    constexpr int KSTEPS = K / 16, KG = K / XR_BK;          // 24 k-steps, 6 k-groups
-    constexpr int STAGE = XR_BN * XR_BK * 2;                 // 24 KiB
-    constexpr int PIECES = STAGE / 1024, PPW = PIECES / NW;  // 24 pieces, 3 (8 waves) or 6 (4 waves) per wave
-    constexpr int NSUB = XR_BN / 32;                         // 6 feature sub-tiles of 32
-    constexpr int BMX = NW * 32;                             // tokens per block
-    static_assert(PIECES % NW == 0 && K % XR_BK == 0, "tile shape");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int ntiles = N / XR_BN;
-    // persistent workgroups: a contiguous range of work items (token block of 32*NW, feature tile of 192), feature
-    // tile fastest, so a workgroup changes token block at most a couple of times and the load is balanced to one item
-    const int it0 = (int)((int64_t)items_total * blockIdx.x / gridDim.x);
-    const int it1 = (int)((int64_t)items_total * (blockIdx.x + 1) / gridDim.x);
-    const int total = (it1 - it0) * KG;                      // W tiles this workgroup streams
-    if (total <= 0) return;
-
-    int src_off[PPW];   // byte offset inside a W tile's source of this lane's 16 B
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int sl = (wave * PPW + i) * 64 + lane;
-        const int sr = sl >> 4, ch = (sl & 15) ^ (sr & 15);
-        const int row = sr * 2 + (ch >> 3), c = ch & 7;
-        src_off[i] = row * K * 2 + c * 16;
-    }
-    auto issue = [&](int tt, int stage) {
-        const int t2 = tt < total ? tt : total - 1;           // past-the-end: re-read the last tile (uniform vmcnt)
-        const int j = (it0 + t2 / KG) % ntiles, g = t2 % KG;
-        const char *base = reinterpret_cast<const char *>(W) + ((int64_t)j * XR_BN * K + g * XR_BK) * 2;
-#pragma unroll
-        for (int i = 0; i < PPW; ++i)
-            glds16(base + src_off[i], smem + stage * STAGE + (wave * PPW + i) * 1024);
-    };
-    int aoff[NSUB];
-#pragma unroll
-    for (int i = 0; i < NSUB; ++i) aoff[i] = ((i * 32 + r) >> 1) * 256;   // super-row base; chunk XOR added per ks
-    const int rodd = (r & 1) * 8;
-
-    bf16x8 bx[KSTEPS];   // resident activation fragments: B[k = 8h + j][col r] of k-step s = X[m0 + r][16 s + 8 h + j]
-    int cur_mb = -1, m0 = 0;
-    f32x16 acc[NSUB];
-#pragma unroll
-    for (int i = 0; i < NSUB; ++i)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[i][g] = 0.f;
-
-    // The whole bias vector goes into LDS once per (persistent) workgroup: an ordinary global load inside the loop would make
-    // hipcc drain the W ring (s_waitcnt vmcnt(0)) at its first use, in every epilogue.  Read back with inline-asm ds_read.
-    const uint32_t bias_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + XR_NSTAGE * STAGE +
-                              NW * 32 * XR_STG_ROW;
-    for (int p = wave; p * 256 < N; p += NW)
-        if (p * 256 + lane * 4 < N) glds16(bias + p * 256 + lane * 4, smem + XR_NSTAGE * STAGE + NW * 32 * XR_STG_ROW + p * 1024);
-    wait_vmcnt<0>();
-    // bias[n .. n+3] for the four 8-feature groups of sub-tile i: four reads in flight, one wait
-    auto bias16 = [&](int n, f32x4 (&bv)[4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            asm volatile("ds_read_b128 %0, %1" : "=v"(bv[gq]) : "v"(bias_lds + (n + 8 * gq) * 4) : "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3])::"memory");
-    };
-    [[maybe_unused]] unsigned long long xs_n = 0, xs_x = 0, xs_w = 0, xs_i = 0, xs_c = 0, xs_e = 0, xs_it = 0;   // (diagnostic build only)
-    // vmcnt bookkeeping across an epilogue: its NS global stores are YOUNGER than the two W tiles in flight, and vmcnt
-    // retires in issue order, so "all but my PPW youngest operations" (the plain ring wait) would drain every store of the
-    // epilogue before the next MFMA could start — for the next TWO steps (the tile waited for in step s was issued in step
-    // s-2).  Those two waits leave NS more operations outstanding instead.  Only when every store was issued for certain
-    // (all 64 lanes active: no exec-zero skip) — otherwise the plain, draining wait.
-    constexpr int NS = 12;   // global store instructions per wave and epilogue (both epilogue forms)
-    static_assert(BMX * 12 / (NW * 64) == 6, "store count of the staged epilogue");
-    int stores_younger = 0;
-    issue(0, 0);
-    issue(1, 1);
-    for (int tt = 0; tt < total; ++tt) {
-        const int stage = tt % XR_NSTAGE;
-        const int g = tt % KG;
-        const int item = it0 + tt / KG;
-        const unsigned long long xt0 = XR_T();
-        if (g == 0 && item / ntiles != cur_mb) {              // wave-uniform: new token block -> reload fragments
-            cur_mb = item / ntiles;
-            m0 = cur_mb * BMX + wave * 32;
-            const bf16_t *xp = X + (int64_t)(m0 + r) * K + 8 * h;
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 16 * s);
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));   // retire these ordinary loads here
-            stores_younger = 0;   // ... and with them (vmcnt(0)) everything older
-        }
-        const unsigned long long xt1 = XR_T();
-#ifdef TSIM_XRES_DRAIN   // A/B: the plain ring wait everywhere (drains the epilogue's stores)
-        stores_younger = 0;
-#endif
-        if (stores_younger > 0) {
-            wait_vmcnt<PPW + NS>();
-            --stores_younger;
-        } else {
-            wait_vmcnt<PPW>();
-        }
-        __builtin_amdgcn_s_barrier();
-        const unsigned long long xt2 = XR_T();
-        issue(tt + 2, (stage + 2) % XR_NSTAGE);
-        const unsigned long long xt3 = XR_T();
-        const char *ws = smem + stage * STAGE;
-        // the k-group index selects which resident fragments to use: unrolled switch keeps bx[] in registers
-#pragma unroll
-        for (int gg = 0; gg < KG; ++gg) {
-            if (g == gg) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-                    for (int i = 0; i < NSUB; ++i) {
-                        const int sr = (i * 32 + r) >> 1;
-                        const int ch = (rodd + 2 * ks + h) ^ (sr & 15);
-                        const bf16x8 a = *reinterpret_cast<const bf16x8 *>(ws + aoff[i] + (ch << 4));
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bx[gg * 4 + ks], acc[i], 0, 0, 0);
-                    }
-                }
-            }
-        }
-#ifdef TSIM_PP_STAMPS
-#pragma unroll
-        for (int i = 0; i < NSUB; ++i) asm volatile("" : "+v"(acc[i]));
-#endif
-        const unsigned long long xt4 = XR_T();
-        xs_n += 1; xs_x += xt1 - xt0; xs_w += xt2 - xt1; xs_i += xt3 - xt2; xs_c += xt4 - xt3;
-        if (g == KG - 1) {
-            if constexpr (EPI == EPI_GELU) {
-                // VALU-bound epilogue: direct 16-byte stores (the LDS-staged form below costs four more barriers
-                // per item and measured 6 % slower here, 7 % faster for the bias-only epilogue)
-                // epilogue of output tile j: acc[i][q]: feature n0 + i*32 + (q&3) + 8*(q>>2) + 4*h, token m0 + r
-                const int n0 = (item % ntiles) * XR_BN;
-                const int64_t m = m0 + r;
-    #pragma unroll
-                for (int i = 0; i < NSUB; ++i) {
-                    uint32_t pk[8];   // pk[2*gq], pk[2*gq+1]: this lane's 4 features of group gq as packed bf16
-                    f32x4 bvs[4];
-                    bias16(n0 + i * 32 + 4 * h, bvs);
-    #pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const f32x4 bv = bvs[gq];
-                        float y0 = acc[i][4 * gq] + bv[0], y1 = acc[i][4 * gq + 1] + bv[1];
-                        float y2 = acc[i][4 * gq + 2] + bv[2], y3 = acc[i][4 * gq + 3] + bv[3];
-                        if constexpr (EPI == EPI_GELU) {
-                            gelu2(y0, y1); gelu2(y2, y3);
-                        }
-                        pk[2 * gq] = pack_bf16x2(y0, y1);
-                        pk[2 * gq + 1] = pack_bf16x2(y2, y3);
-                    }
-                    // lane (r,0) holds features 8gq+0..3, lane (r,1) features 8gq+4..7.  Swap so that the low half-wave
-                    // owns features 8gq..8gq+7 of group gq (even gq) and the high half-wave those of group gq+1: one
-                    // 16-byte store per lane and group pair (cdna_hip_programming.md T21).
-    #pragma unroll
-                    for (int gq = 0; gq < 4; gq += 2) {
-                        uint32_t a0 = pk[2 * gq], a1 = pk[2 * gq + 1], b0 = pk[2 * gq + 2], b1 = pk[2 * gq + 3];
-                        auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                        auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                        a0 = s0[0]; b0 = s0[1]; a1 = s1[0]; b1 = s1[1];
-                        if (m < M) {
-                            uint4 o = make_uint4(a0, a1, b0, b1);
-                            *reinterpret_cast<uint4 *>(out + m * N + n0 + i * 32 + 8 * gq + 8 * h) = o;
-                        }
-                    }
-    #pragma unroll
-                    for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
-                }
-                if (m0 + 32 <= M) stores_younger = 2;   // wave-uniform: all 12 stores of this wave were issued
-            } else {
-                // epilogue of output tile j: acc[i][q]: feature n0 + i*32 + (q&3) + 8*(q>>2) + 4*h, token m0 + r.
-                // A lane owns 32-byte pieces of 32 different token rows, so direct stores touch 32 cache lines per
-                // instruction (measured: ~11 of 15.7 us per item).  The tile goes out THROUGH LDS instead, half a tile (96
-                // features) at a time: 16-byte pieces into a padded [256 tokens][208 B] image, then every thread stores
-                // row-contiguous 16-byte chunks (192 B per token row).  LDS accesses are inline asm so that hipcc does not
-                // drain the W ring (vmcnt(0)) in front of them; the image lies behind the ring.
-                const int n0 = (item % ntiles) * XR_BN;
-                const int mb0 = cur_mb * BMX;
-                const uint32_t stg = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + XR_NSTAGE * STAGE;
-    #pragma unroll
-                for (int half = 0; half < 2; ++half) {
-    #pragma unroll
-                    for (int il = 0; il < 3; ++il) {
-                        const int i = half * 3 + il;
-                        uint32_t pk[8];   // pk[2*gq], pk[2*gq+1]: this lane's 4 features of group gq as packed bf16
-                        f32x4 bvs[4];
-                        bias16(n0 + i * 32 + 4 * h, bvs);
-    #pragma unroll
-                        for (int gq = 0; gq < 4; ++gq) {
-                            const f32x4 bv = bvs[gq];
-                            float y0 = acc[i][4 * gq] + bv[0], y1 = acc[i][4 * gq + 1] + bv[1];
-                            float y2 = acc[i][4 * gq + 2] + bv[2], y3 = acc[i][4 * gq + 3] + bv[3];
-                            if constexpr (EPI == EPI_GELU) {
-                                gelu2(y0, y1); gelu2(y2, y3);
-                            }
-                            pk[2 * gq] = pack_bf16x2(y0, y1);
-                            pk[2 * gq + 1] = pack_bf16x2(y2, y3);
-                        }
-                        // lane (r,0) holds features 8gq+0..3, lane (r,1) features 8gq+4..7: swap so that the low half-wave
-                        // owns all 8 features of group gq (even gq) and the high half-wave those of group gq+1 (T21)
-    #pragma unroll
-                        for (int gq = 0; gq < 4; gq += 2) {
-                            uint32_t a0 = pk[2 * gq], a1 = pk[2 * gq + 1], b0 = pk[2 * gq + 2], b1 = pk[2 * gq + 3];
-                            auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                            auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                            u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-                            const uint32_t addr = stg + (wave * 32 + r) * XR_STG_ROW + (il * 32 + 8 * gq + 8 * h) * 2;
-                            asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(o) : "memory");
-                        }
-    #pragma unroll
-                        for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    // 256 rows x 12 chunks of 16 B = 3072 chunks over NW*64 threads
-                    constexpr int NCP = BMX * 12 / (NW * 64);   // 16-byte chunks per thread: all reads in flight, one wait
-                    u32x4 cv[NCP];
-    #pragma unroll
-                    for (int c = 0; c < NCP; ++c) {
-                        const int idx = c * NW * 64 + (int)threadIdx.x;
-                        asm volatile("ds_read_b128 %0, %1" : "=v"(cv[c]) : "v"(stg + (idx / 12) * XR_STG_ROW + (idx % 12) * 16) : "memory");
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    #pragma unroll
-                    for (int c = 0; c < NCP; ++c) {
-                        asm volatile("" : "+v"(cv[c]));
-                        const int idx = c * NW * 64 + (int)threadIdx.x;
-                        const int row = idx / 12, ch = idx % 12;
-                        if (mb0 + row < M)
-                            *reinterpret_cast<u32x4 *>(out + (int64_t)(mb0 + row) * N + n0 + half * 96 + ch * 8) = cv[c];
-                    }
-                    __builtin_amdgcn_s_barrier();   // image may be overwritten
-                }
-                if (mb0 + BMX <= M) stores_younger = 2;   // every thread issued its 12 stores
-            }
-            xs_e += XR_T() - xt4; xs_it += 1;
-        }
-    }
-    wait_vmcnt<0>();
-    XR_ACC(0, xs_n); XR_ACC(5, xs_x); XR_ACC(1, xs_w); XR_ACC(2, xs_i); XR_ACC(3, xs_c); XR_ACC(4, xs_e); XR_ACC(6, xs_it);
-}
-
 template <int... I, class Fn>
 __device__ __forceinline__ void ff_static_for(std::integer_sequence<int, I...>, Fn &&f) {   // f(integral_constant<I>) for each I
     (f(std::integral_constant<int, I>{}), ...);
@@ -824,25 +462,22 @@ __device__ __forceinline__ void ff_static_for(std::integer_sequence<int, I...>, 
 // =====================================================================================================
 // gemm_xres2: the register-resident K = 384 projection with the EPILOGUE OVERLAPPED.
 //
-// In gemm_xres_kernel every sixth tile-step all eight waves stop feeding the matrix pipe and run the epilogue of a
-// 192-feature item together (bias, GELU, packing, stores): 28 % of the kernel's time with the MFMA pipe idle, plus the
+// In the first form of this kernel (192-feature items; removed) every sixth tile-step all eight waves stop feeding the matrix
+// pipe and run the epilogue of a 192-feature item together (bias, GELU, packing, stores): 28 % of the kernel's time with the MFMA pipe idle, plus the
 // activation reloads (profiles/README.md).  Here an item is 96 features (three 32-feature sub-tiles, W tiles of 96 x 128 k:
 // the same 24 KiB per step, three steps per item) and there are TWO accumulator sets (2 x 48 VGPRs beside the 96 of the
 // resident activations): while the 24 MFMAs of a step accumulate item i, the wave finishes one sub-tile of item i-1 in
 // their shadow — two accumulator registers (GELU, bf16 pack) after every k-step, the half-wave swap and the two 16-byte
 // stores at the end of the step.  The bias is not added in the epilogue: the accumulators START from it.
-// Same k order per output as gemm_xres_kernel (ascending), so rows stay batch-invariant bit for bit.
+// k order per output ascending, so rows stay batch-invariant bit for bit.
 // =====================================================================================================
-// TWO STEPS PER BARRIER (TSIM_X2_PAIR).  Stamps (tools/x2_stamps.py): of a step's ~3 200 cycles a wave spends ~1 000 in the ring wait
+// TWO STEPS PER BARRIER.  Stamps (tools/x2_stamps.py): of a step's ~3 200 cycles a wave spends ~1 000 in the ring wait
 // + workgroup barrier and both waves of a SIMD sit there together — a cost per BARRIER, not per MFMA.  With six ring slots the
 // tiles are synchronised in pairs: one vmcnt wait + barrier in front of every even step covers the tiles of steps st and st + 1
 // (both issued four steps earlier), the odd step runs straight on; a step issues the tile of step st + 4 into the slot the pair
 // before the current one has left (everyone is past that pair: they passed this pair's barrier).
 // MEASURED: QKV 73.1 -> 71.2 us, FFN1 119.6 -> 115.3 us (-3 %): the wait is mostly not a per-barrier constant.
-#ifndef TSIM_X2_PAIR
-#define TSIM_X2_PAIR 1
-#endif
-constexpr int X2_BN = 96, X2_BK = 128, X2_NSTAGE = TSIM_X2_PAIR ? 6 : 3, X2_PD = TSIM_X2_PAIR ? 4 : 2, X2_KG = 3, X2_NSUB = 3;
+constexpr int X2_BN = 96, X2_BK = 128, X2_NSTAGE = 6, X2_PD = 4, X2_KG = 3, X2_NSUB = 3;
 
 template <int EPI, bool PK>   // PK: the output goes out in the block-packed layout (see packed_off)
 __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W,
@@ -900,20 +535,11 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
     int old_m0 = 0, old_n0 = 0;
     int st = 0;                       // steps done
     int ring = 0;                     // st % X2_NSTAGE, kept as a counter
-    int young1 = 0, young2 = 0;       // global stores issued in the previous step / the one before (-1: unknown)
-    [[maybe_unused]] int young3 = 0;  // ... and the one before that (pairs)
+    int young1 = 0, young2 = 0, young3 = 0;   // global stores issued in the last three steps, youngest first (-1: unknown)
 
     // epilogue of ONE finished sub-tile whose 16 registers have been packed into pk[8] (pk[2gq], pk[2gq+1] = the lane's four
     // features 8gq + 4h .. +3 of group gq): swap half-waves so that every lane owns 8 contiguous features, two 16-byte stores
-    // EARLY STORES (round 3).  Stamps (tools/x2_stamps.py): the two 16-byte stores of a sub-tile, issued between a step's MFMA
-    // stream and the next barrier, cost their wave 650-750 cycles per step (a store instruction touches 32 rows x 32 B and is
-    // issue-bound), during which it feeds nothing to the matrix pipe — and both partners of a SIMD sit in that segment or at the
-    // barrier for ~30 % of a step.  Here the shadow epilogue runs at double density over the first four k-steps (all of pk[] is
-    // ready after k-step 3) and the two stores go out INSIDE the stream, behind k-steps 4 and 6: while a wave queues at the
-    // address path its partner has the matrix pipe.  Same values, same addresses; only the issue position moves.
-#ifndef TSIM_X2_EARLY_STORE
-#define TSIM_X2_EARLY_STORE 0   // measured EQUAL to stores at the end of the step (2.61-2.62 ms per forward either way; the
-#endif                          // micro-benchmark agrees: 2 480 vs 2 598 cycles per step): what costs is the store's PATTERN
+    // at the end of the step.  (Issuing them inside the MFMA stream instead measured equal: what costs is the store's PATTERN.)
     // (the store is inline asm in the SGPR-base + 32-bit-offset form: inside the stream there is no room for a 64-bit address
     // per store; the output is < 4 GiB, checked by the launcher.  All vmcnt bookkeeping of this kernel is manual anyway.)
     uint32_t old_rowoff = 0;   // byte offset of this lane's 16-byte column group in its token row of the PREVIOUS item's block
@@ -933,18 +559,14 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             // pads its own stores but cannot see into an asm statement — without it the next instruction now and then replaced the
             // data under the store: a corrupted 16-byte group, non-finite rows after the LayerNorm, the whole sequence after the
             // next attention, in ~20 % of the forwards on some boxes and none on others)
-#ifdef TSIM_X2_DIAG_NO_STORE_NOP   // (control build for tools/nan_probe.py: the fault as it was)
-            asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(voff), "v"(o), "s"(ob) : "memory");
-#else
             asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(ob) : "memory");
-#endif
 #else
         asm volatile("" ::"v"(voff), "v"(o));
 #endif
     };
     auto finish2 = [&](float y0, float y1) __attribute__((always_inline)) -> uint32_t {
 #if !(defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 2))   // (bit 2: TIMING-ONLY, no activation function)
-        // (two independent scalar chains, gelu_n<2>, instead of the packed one: measured equal, 2.633 vs 2.632 ms per forward)
+        // (two independent scalar Horner chains instead of the packed one: measured equal, 2.633 vs 2.632 ms per forward)
         if constexpr (EPI == EPI_GELU) gelu2(y0, y1);
 #endif
         return pack_bf16x2(y0, y1);
@@ -984,68 +606,31 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
         for (int g = 0; g < X2_KG; ++g) {
             // (opaque on purpose: with six steps per loop trip and six slots hipcc knows the slot of every unrolled step, hoists the
             // 6 x 8 fragment addresses out of the loop as invariants and spills all 48 of them)
-            if constexpr (TSIM_X2_PAIR) asm volatile("" : "+s"(ring));
-            const int stage = TSIM_X2_PAIR ? ring : st % X2_NSTAGE;
+            asm volatile("" : "+s"(ring));
+            const int stage = ring;
             [[maybe_unused]] const unsigned long long xs0 = XR_T();
-            // ring wait: the tile of this step was issued two steps ago; the stores of the last two steps are younger than it
-            if constexpr (TSIM_X2_EARLY_STORE) {
-                // issue order inside a step: piece a (k-step 1), piece b (3), store 1 (4), piece c (5), store 2 (6).  Younger than
-                // the pieces of step st-2: its store 2, and everything of step st-1.
-                const int extra = (young1 >= 0 && young2 >= 0) ? young1 + (young2 >> 1) : 0;   // 0 (or unknown: drain), 1, 2, 3
-                if (extra == 3) wait_vmcnt<PPW + 3>();
-                else if (extra == 2) wait_vmcnt<PPW + 2>();
-                else if (extra == 1) wait_vmcnt<PPW + 1>();
-                else wait_vmcnt<PPW>();
-            } else if constexpr (TSIM_X2_PAIR) {
-                // even step: the tiles of this step and the next must have landed.  Younger than the next step's pieces: the pieces
-                // of steps st + 2 and st + 3 and the stores of the last three steps
-                if ((st & 1) == 0) {
-#if defined(TSIM_X2_PAIR_DBG) && (TSIM_X2_PAIR_DBG & 4)
-                    const int ys = 0;
-#else
-                    const int ys = (young1 >= 0 && young2 >= 0 && young3 >= 0) ? young1 + young2 + young3 : 0;
-#endif
-                    if (ys == 6) wait_vmcnt<2 * PPW + 6>();
-                    else if (ys == 4) wait_vmcnt<2 * PPW + 4>();
-                    else if (ys == 2) wait_vmcnt<2 * PPW + 2>();
-                    else wait_vmcnt<2 * PPW>();               // none, or unknown store count: always safe
-#if defined(TSIM_X2_PAIR_DBG) && (TSIM_X2_PAIR_DBG & 2)
-                    wait_vmcnt<0>();
-#endif
-                    __builtin_amdgcn_s_barrier();
-                }
-#if defined(TSIM_X2_PAIR_DBG) && (TSIM_X2_PAIR_DBG & 1)
-                else __builtin_amdgcn_s_barrier();
-#endif
-                __builtin_amdgcn_sched_barrier(0);            // (the odd step has no barrier to fence hipcc's scheduler either)
-            } else {
-            if (young1 == 0 && young2 == 0) wait_vmcnt<PPW>();
-            else if (young1 >= 0 && young2 >= 0 && young1 + young2 == 2) wait_vmcnt<PPW + 2>();
-            else if (young1 >= 0 && young2 >= 0 && young1 + young2 == 4) wait_vmcnt<PPW + 4>();
-            else wait_vmcnt<PPW>();                           // unknown store count: drain (always safe)
+            // ring wait, even step: the tiles of this step and the next must have landed.  Younger than the next step's pieces:
+            // the pieces of steps st + 2 and st + 3 and the stores of the last three steps
+            if ((st & 1) == 0) {
+                const int ys = (young1 >= 0 && young2 >= 0 && young3 >= 0) ? young1 + young2 + young3 : 0;
+                if (ys == 6) wait_vmcnt<2 * PPW + 6>();
+                else if (ys == 4) wait_vmcnt<2 * PPW + 4>();
+                else if (ys == 2) wait_vmcnt<2 * PPW + 2>();
+                else wait_vmcnt<2 * PPW>();               // none, or unknown store count: always safe
+                __builtin_amdgcn_s_barrier();
             }
-            if constexpr (!TSIM_X2_PAIR) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);            // (the odd step has no barrier to fence hipcc's scheduler either)
             [[maybe_unused]] const unsigned long long xs1 = XR_T();
             // Right behind the barrier all eight waves have LDS-DMA to issue and queue at the CU's one address path while the
             // matrix pipe idles; the tile is not needed for two steps, so its three pieces are dropped between the k-steps'
-            // MFMAs instead (TSIM_X2_SPREAD=0: all three at the head of the step).
-#ifndef TSIM_X2_SPREAD
-#define TSIM_X2_SPREAD 1
-#endif
+            // MFMAs instead.
             static_assert(PPW == 3, "issue schedule below places three pieces");
-            static_assert(!(TSIM_X2_PAIR && TSIM_X2_EARLY_STORE), "the pair form counts stores at the end of a step");
-            if constexpr (!TSIM_X2_SPREAD) issue(st + X2_PD, (stage + X2_PD) % X2_NSTAGE);
-            const char *ws = smem + stage * STAGE;
             uint32_t pk[8];
-#ifndef TSIM_X2_ASMPIPE
-#define TSIM_X2_ASMPIPE 1
-#endif
-#if TSIM_X2_ASMPIPE
             // The step's 24 fragment reads (n = 3 ks + i) roll PF reads ahead of their MFMAs with COUNTED lgkmcnt waits, as in the
-            // search kernel's tile loop: hipcc's own schedule of the plain loads below waits lgkmcnt(0) in front of every k-step,
-            // i.e. for the three reads it has just issued (timing-only builds: the bare loop without stores, activation and W
-            // stream ran at 43 % of the MFMA rate).  No other LDS instruction is issued between these reads (LDS-DMA counts in
-            // vmcnt), so the counts are exact.
+            // search kernel's tile loop: hipcc's own schedule of plain loads waits lgkmcnt(0) in front of every k-step, i.e. for
+            // the three reads it has just issued (timing-only builds: the bare loop without stores, activation and W stream ran
+            // at 43 % of the MFMA rate).  No other LDS instruction is issued between these reads (LDS-DMA counts in vmcnt), so the
+            // counts are exact.
             {
                 constexpr int PF = 3, NRD = 8 * X2_NSUB;
                 lds_u32x4 fr[PF + 1];
@@ -1063,35 +648,12 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
                     lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
                     cur[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]), bx[g * 8 + ks], cur[i], 0, 0, 0);
                     if constexpr (i == X2_NSUB - 1) {
-                        if constexpr (TSIM_X2_SPREAD && (ks == 1 || ks == 3 || ks == 5))
+                        if constexpr (ks == 1 || ks == 3 || ks == 5)
                             issue_pieces(st + X2_PD, (stage + X2_PD) % X2_NSTAGE, ks >> 1, (ks >> 1) + 1);
-                        if constexpr (OLD && !TSIM_X2_EARLY_STORE) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);   // in the MFMAs' shadow
-                        if constexpr (OLD && TSIM_X2_EARLY_STORE) {
-                            if constexpr (ks < 4) {
-                                pk[2 * ks] = finish2(old[g][4 * ks], old[g][4 * ks + 1]);
-                                pk[2 * ks + 1] = finish2(old[g][4 * ks + 2], old[g][4 * ks + 3]);
-                            }
-                            if constexpr (ks == 4) store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-                            if constexpr (ks == 6) store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
-                        }
+                        if constexpr (OLD) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);   // in the MFMAs' shadow
                     }
                 });
             }
-#else
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-                for (int i = 0; i < X2_NSUB; ++i) {
-                    const bf16x8 a = *reinterpret_cast<const bf16x8 *>(ws + i * 8192 + cks[ks]);
-                    cur[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bx[g * 8 + ks], cur[i], 0, 0, 0);
-                }
-                if constexpr (TSIM_X2_SPREAD) {
-                    if (ks == 1 || ks == 3 || ks == 5) issue_pieces(st + X2_PD, (stage + X2_PD) % X2_NSTAGE, ks >> 1, (ks >> 1) + 1);
-                }
-                if constexpr (OLD) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);   // in the MFMAs' shadow
-            }
-#endif
-            (void)ws;
 #ifdef TSIM_PP_STAMPS
 #pragma unroll
             for (int i = 0; i < X2_NSUB; ++i) asm volatile("" : "+v"(cur[i]));
@@ -1101,21 +663,13 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             young2 = young1;
             young1 = 0;
             if constexpr (OLD) {
-                if constexpr (TSIM_X2_EARLY_STORE) {
+                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
+                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
 #if defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 1)
-                    young1 = 0;
+                young1 = 0;
 #else
-                    young1 = old_m0 + 32 <= M ? 2 : -1;      // both stores of this step were issued for certain / unknown
+                young1 = old_m0 + 32 <= M ? 2 : -1;      // both stores of this step were issued for certain / unknown
 #endif
-                } else {
-                    store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-                    store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
-#if defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 1)
-                    young1 = 0;
-#else
-                    young1 = old_m0 + 32 <= M ? 2 : -1;
-#endif
-                }
             }
             ++st;
             ring = ring + 1 == X2_NSTAGE ? 0 : ring + 1;
@@ -1152,43 +706,6 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
     XR_ACC(0, x2_n); XR_ACC(1, x2_w); XR_ACC(3, x2_c); XR_ACC(4, x2_e); XR_ACC(6, x2_n / 3);
 }
 
-// =====================================================================================================
-// ffn_fused: FFN1 -> GELU -> FFN2 -> +residual -> LayerNorm in ONE kernel (hidden 384; the [T, F] intermediate never leaves
-// the CU).  Unfused, a MiniLM layer writes and re-reads 412 MB of h = GELU(x W1^T + b1) through HBM: more traffic than all its
-// other tensors together, and the two projections around it sit at a third of the HBM roofline and a quarter of the MFMA
-// roofline at once (profiles/README.md).
-//
-// Workgroup = 128 tokens = 4 token groups of 32, TWO waves per group with different ROLES (partners w and w+4 share a SIMD):
-//   producer (waves 0-3): holds the group's x rows as MFMA B fragments (96 VGPRs); per phase s it scores ONE 32-feature chunk
-//          h^T[32 features x 32 tokens] = W1[chunk s] . x^T (24 MFMAs, accumulator starts from b1), applies GELU, rounds to
-//          bf16 and writes the tile to a 2-KiB LDS slot — in the accumulator's own layout, which IS the B-operand layout of
-//          the second product (cdna_hip_programming.md §3 "An accumulator tile as the next MFMA's operand");
-//          GELU + rounding of chunk s-1 run in the shadow of chunk s's MFMA chain (two accumulators);
-//   consumer (waves 4-7): holds the group's whole output row block y^T[384 features x 32 tokens] (12 accumulator tiles = 192
-//          VGPRs, starting from b2); per phase it adds chunk s-2: y^T[t] += W2[rows of t, chunk] . h (2 MFMAs per tile, 24).
-// The producer runs two chunks ahead of the consumer (two h slots per group), so on every SIMD one wave's GELU / LDS traffic
-// runs beside the other's MFMAs, and neither role needs more than ~230 registers: 96 + 192 in one wave would not fit.
-// The k order inside a k-step of the second product is the accumulator's row order (16 s + 8 (j >> 2) + 4 h + (j & 3)): W2 is
-// re-laid at load time (pack_ffn_w2_kernel) so that its A fragments are plain 16-byte reads.
-// W streams through a ring of five 24-KiB LDS slots by LDS-DMA, unit 2s = W1[chunk s], unit 2s+1 = W2[.., chunk s-2]: both
-// matrices are stored as the exact LDS images (pack_ffn_w*_kernel), so every DMA piece is 1 KiB of contiguous memory.  One
-// raw s_barrier per phase (it also publishes the h slot); phase s waits for its two units with vmcnt(3) (one younger unit
-// stays in flight) and issues units 2s+3, 2s+4.
-// Staging: 48 KiB per phase for 48 MFMAs per SIMD = 31 B/clk/CU at the full MFMA rate — the order of the measured L2 -> LDS
-// rates, so this kernel runs near the staging bound; what it removes is the HBM round trip of h.
-// Epilogue (consumers): residual added in the accumulator layout (16-byte loads + v_permlane32_swap, the store path
-// backwards), two-pass LayerNorm statistics inside the wave, 16-byte row stores.
-// Summation order per output: chunks ascending, the permuted k order inside: independent of what else is in the batch.
-// =====================================================================================================
-constexpr int FF_UNIT = 24576, FF_NSLOT = 5, FF_XB = 16384;   // ring unit, ring slots, h fragments (4 groups x 2 x 2 KiB)
-#ifdef TSIM_PP_STAMPS
-// DIAGNOSTIC build: [0..3] producer wave 0: phases, wait (vmcnt + barrier), DMA issue, work; [4..7] the same for consumer wave 4
-__device__ unsigned long long g_ff_stamps[8];
-#define FF_T() __builtin_amdgcn_s_memtime()
-#else
-#define FF_T() 0ull
-#endif
-
 // W [BN rows, K] -> per k-tile of BK the W-region LDS image of gemm_bf16_kernel<.., BN, BK, ..>: 16-byte slot sl of the image
 // (super-row sr = sl >> 4 of 256 B = 256 / (2 BK) tile rows, slot chp = sl & 15) holds chunk ch = chp ^ (sr & 15) of the super-row.
 __global__ __launch_bounds__(256) void pack_gemm_w_kernel(const uint4 *__restrict__ W, uint4 *__restrict__ img, int BN, int BK, int K) {
@@ -1212,362 +729,27 @@ __global__ __launch_bounds__(256) void pack_frag_w_kernel(const uint4 *__restric
     const int nt = N / 32, s = blk / nt, j = blk % nt, r = lane & 31, h = lane >> 5;
     img[u] = W[((int64_t)(32 * j + r) * K + 16 * s + 8 * h) / 8];
 }
-// W1 [F, 384] -> per 32-row chunk the K1-style LDS image: row rr, 16-byte slot c holds source chunk c ^ (rr & 15) (low 4 bits)
-__global__ __launch_bounds__(256) void pack_ffn_w1_kernel(const uint4 *__restrict__ W, uint4 *__restrict__ img, int F) {
-    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;      // 16-byte unit of the image
-    if (u >= (int64_t)F * 48) return;
-    const int c = (int)(u / 1536), sl = (int)(u % 1536);            // chunk, slot in the chunk image (32 rows x 48 slots)
-    const int rr = sl / 48, cc = sl % 48;
-    img[u] = W[((int64_t)(c * 32 + rr) * 48) + (cc ^ (rr & 15))];
-}
-// W2 [384, F] -> per 32-column chunk c: image [384 rows][4 slots of 16 B]; slot s' of row ro holds k-step s, half hh with
-// (2 s + hh) = s' ^ ((ro >> 2) & 3), its 8 elements in the accumulator's k order: W2[ro][32 c + 16 s + 8 (j >> 2) + 4 hh + (j & 3)]
-__global__ __launch_bounds__(256) void pack_ffn_w2_kernel(const bf16_t *__restrict__ W, bf16_t *__restrict__ img, int F) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;      // element of the image
-    if (e >= (int64_t)384 * F) return;
-    const int c = (int)(e / (384 * 32)), o = (int)(e % (384 * 32));
-    const int ro = o / 32, sp = (o % 32) / 8, j = o % 8;
-    const int sh = sp ^ ((ro >> 2) & 3), s = sh >> 1, hh = sh & 1;
-    img[e] = W[(int64_t)ro * F + 32 * c + 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3)];
-}
-
-__global__ __launch_bounds__(512) void ffn_fused_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W1img,
-                                                        const bf16_t *__restrict__ W2img, const float *__restrict__ b1,
-                                                        const float *__restrict__ b2, const float *__restrict__ gamma,
-                                                        const float *__restrict__ beta, float eps, bf16_t *__restrict__ out,
-                                                        int M, int F) {
-    constexpr int K = 384, KSTEPS = 24, PPU = 3;             // pieces of a 24-KiB unit per wave (24 / 8)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tg = wave & 3, consumer = wave >> 2;
-    const int r = lane & 31, hh = lane >> 5;
-    const int nchunks = F / 32, nphases = nchunks + 2, nunits = 2 * nphases;
-    const int m0 = blockIdx.x * 128 + tg * 32;
-    char *ring = smem;
-    char *xbuf = smem + FF_NSLOT * FF_UNIT;                   // h fragments of (group, chunk parity): xbuf + (tg * 2 + par) * 2048
-    const uint32_t b1_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + FF_NSLOT * FF_UNIT + FF_XB;
-
-    // unit u of phase u/2: even = W1 image of chunk u/2 (producer); odd = W2 image of chunk u/2 - 2 (consumer, two phases behind)
-    // pieces [i0, i1) of this wave's PPU pieces of unit u
-    auto issue_pieces = [&](int u, int i0, int i1) __attribute__((always_inline)) {
-        const int uu = u < nunits ? u : nunits - 1;           // past-the-end: re-read the last unit (uniform vmcnt)
-        int c = (uu & 1) ? (uu >> 1) - 2 : (uu >> 1);
-        c = c < 0 ? 0 : (c >= nchunks ? nchunks - 1 : c);     // units outside the chunk range are never consumed: any valid source
-        const char *src = reinterpret_cast<const char *>((uu & 1) ? W2img : W1img) + (int64_t)c * FF_UNIT;
-        char *dst = ring + (uu % FF_NSLOT) * FF_UNIT;
-#ifdef TSIM_FF_DIAG_NODMA   // DIAGNOSTIC (results wrong): the kernel without its W stream
-        (void)src; (void)dst;
-#else
-        for (int i = i0; i < i1; ++i)
-            glds16(src + (wave * PPU + i) * 1024 + lane * 16, dst + (wave * PPU + i) * 1024);
-#endif
-    };
-    auto issue_unit = [&](int u) __attribute__((always_inline)) { issue_pieces(u, 0, PPU); };
-    // Issue schedule inside a phase.  Right behind the barrier every wave of the CU has LDS-DMA to issue, the CU's address path
-    // takes one wave-instruction at a time (~16 cycles per KiB) and a wave whose next instruction is such a load waits for
-    // its turn: with all six pieces up front every wave sat ~500-600 cycles in that queue while the matrix pipe idled (stamps).
-    // So only the unit that is needed NEXT phase goes out at once; the pieces of the unit after it are dropped between the
-    // phase's MFMAs (TSIM_FF_SPREAD=0: the first form).
-#ifndef TSIM_FF_SPREAD
-#define TSIM_FF_SPREAD 1
-#endif
-    // b1 -> LDS (read per chunk inside the loop: an ordinary global load there would drain the ring)
-    for (int p = wave; p * 256 < F; p += 8)
-        if (p * 256 + lane * 4 < F) glds16(b1 + p * 256 + lane * 4, smem + FF_NSLOT * FF_UNIT + FF_XB + p * 1024);
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-
-    if (!consumer) {
-        // ================================================================ producer: FFN1 + GELU, one chunk per phase
-        bf16x8 bx[KSTEPS];   // B[k = 8 hh + j][col r] of k-step s = X[m0 + r][16 s + 8 hh + j]; rows past M repeat the last one
-        {
-            const int64_t row = m0 + r < M ? m0 + r : M - 1;
-            const bf16_t *xp = X + row * K + 8 * hh;
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 16 * s);
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));   // retired before any LDS-DMA is in flight
-        }
-        issue_unit(0);
-        issue_unit(1);
-        issue_unit(2);
-        const int w1off = r * 768;                             // + (s >> 3) * 256 + (((2 (s & 7) + hh) ^ (r & 15)) << 4)
-        int w1x[8];
-#pragma unroll
-        for (int bb = 0; bb < 8; ++bb) w1x[bb] = ((2 * bb + hh) ^ (r & 15)) << 4;
-        const uint32_t slot0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)xbuf) + tg * 4096 + lane * 32;
-        // Phase ph: the 24 MFMAs of chunk ph, and in their shadow GELU + bf16 of chunk ph-1 (whose accumulator was finished in
-        // the phase before) as sixteen independent polynomial chains (gelu_n): the accumulation chain of a chunk and the
-        // activation of the previous one overlap instead of following each other.  h of chunk c is published at the end of
-        // phase c+1 and read by the consumer in phase c+2.
-        f32x16 hprev;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) hprev[q] = 0.f;
-        [[maybe_unused]] unsigned long long fs_w = 0, fs_i = 0, fs_k = 0;
-        auto phase = [&](int ph, auto has_mfma, auto has_prev) __attribute__((always_inline)) {
-            constexpr bool MM = decltype(has_mfma)::value, PV = decltype(has_prev)::value;
-            [[maybe_unused]] const unsigned long long t0 = FF_T();
-            wait_vmcnt<PPU>();                                 // units 2ph, 2ph+1 landed (2ph+2 may be in flight)
-            __builtin_amdgcn_s_barrier();                      // ... for everyone; everyone is past phase ph-1
-            [[maybe_unused]] const unsigned long long t1 = FF_T();
-            issue_unit(2 * ph + 3);
-            if constexpr (!MM || !TSIM_FF_SPREAD) issue_unit(2 * ph + 4);
-            [[maybe_unused]] const unsigned long long t2 = FF_T();
-            f32x16 hacc;
-            [[maybe_unused]] f32x16 hacc1;   // FF_NACC = 2: odd k-steps accumulate here (two independent chains), added at the end
-            if constexpr (MM) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) hacc1[q] = 0.f;
-                f32x4 bv[4];
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    asm volatile("ds_read_b128 %0, %1" : "=v"(bv[gq]) : "v"(b1_lds + (32 * ph + 8 * gq + 4 * hh) * 4) : "memory");
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3])::"memory");
-#pragma unroll
-                for (int q = 0; q < 16; ++q) hacc[q] = bv[q >> 2][q & 3];
-            }
-            // the accumulation chain is ONE dependent MFMA after the other: fragment reads roll PF k-steps ahead (counted waits)
-            constexpr int PF = 6;
-            lds_u32x4 fr[PF + 1];
-            const uint32_t tb = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)(ring + ((2 * ph) % FF_NSLOT) * FF_UNIT)) + w1off;
-            auto rd = [&](auto nc) __attribute__((always_inline)) {
-                constexpr int n = decltype(nc)::value;
-                lds_read_b128_imm<(n >> 3) * 256>(fr[n % (PF + 1)], tb + w1x[n & 7]);
-            };
-            if constexpr (MM) ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
-            uint32_t hw[8];   // registers 8s .. 8s+7 of the finished tile, GELU'd and packed: the B fragment of k-step s
-            // GELU of chunk ph-1 in 11 stages, each cut into two halves of 8 independent operations: ONE half behind EVERY MFMA of
-            // the chain (32 issue cycles: the time the next, dependent MFMA has to wait for its accumulator anyway).  The first
-            // form put a whole 16-operation stage behind every second MFMA: that pair then cost 64 cycles of VALU issue plus the
-            // full dependency stall of the back-to-back MFMA behind it (stamps: 1 989 cycles of work per phase for 768 of MFMA).
-            float gv[2][8], gxc[2][8], gu[2][8], gp[2][8];
-            if constexpr (PV) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) gv[q >> 3][q & 7] = hprev[q];
-            }
-            ff_static_for(std::make_integer_sequence<int, KSTEPS>{}, [&](auto sc) __attribute__((always_inline)) {
-                constexpr int s = decltype(sc)::value;
-                if constexpr (MM) {
-                    if constexpr (s + PF < KSTEPS) rd(std::integral_constant<int, s + PF>{});
-                    constexpr int younger = s + PF < KSTEPS ? PF : KSTEPS - 1 - s;
-                    lgkm_wait_counted<younger>(fr[s % (PF + 1)]);
-#ifndef TSIM_FF_NACC
-#define TSIM_FF_NACC 2
-#endif
-                    if constexpr (TSIM_FF_NACC == 2 && (s & 1))
-                        hacc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[s % (PF + 1)]), bx[s], hacc1, 0, 0, 0);
-                    else
-                        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[s % (PF + 1)]), bx[s], hacc, 0, 0, 0);
-                    if constexpr (TSIM_FF_SPREAD && (s == 5 || s == 11 || s == 17)) issue_pieces(2 * ph + 4, s / 6, s / 6 + 1);
-                }
-#ifdef TSIM_FF_GELU_PAIRED   // A/B: the first form
-                if constexpr (PV && (s & 1) && s / 2 <= 10) {
-                    gelu_stage<s / 2, 8>(gv[0], gxc[0], gu[0], gp[0]);
-                    gelu_stage<s / 2, 8>(gv[1], gxc[1], gu[1], gp[1]);
-                }
-#else
-#ifndef TSIM_FF_DIAG_NOGELU   // (defined: TIMING-ONLY, wrong results: the producer without its activation VALU work)
-                if constexpr (PV && s / 2 <= 10) gelu_stage<s / 2, 8>(gv[s & 1], gxc[s & 1], gu[s & 1], gp[s & 1]);
-#endif
-#endif
-                if constexpr (PV && s == 23) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) hw[e] = pack_bf16x2(gv[(2 * e) >> 3][(2 * e) & 7], gv[(2 * e + 1) >> 3][(2 * e + 1) & 7]);
-                }
-            });
-            if constexpr (PV) {
-                const u32x4 f0 = {hw[0], hw[1], hw[2], hw[3]}, f1 = {hw[4], hw[5], hw[6], hw[7]};
-                // slot of chunk ph-1's parity: its previous content (chunk ph-3) was read by the consumer in phase ph-1
-                asm volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
-                             ::"v"(slot0 + ((ph - 1) & 1) * 2048), "v"(f0), "v"(f1) : "memory");
-            }
-            if constexpr (MM) {
-                if constexpr (TSIM_FF_NACC == 2) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) hprev[q] = hacc[q] + hacc1[q];
-                } else {
-                    hprev = hacc;
-                }
-            }
-#ifdef TSIM_PP_STAMPS
-            { const unsigned long long t3 = FF_T(); fs_w += t1 - t0; fs_i += t2 - t1; fs_k += t3 - t2; }
-#endif
-        };
-        phase(0, std::true_type{}, std::false_type{});
-        for (int ph = 1; ph < nchunks; ++ph) phase(ph, std::true_type{}, std::true_type{});
-        phase(nchunks, std::false_type{}, std::true_type{});
-        phase(nchunks + 1, std::false_type{}, std::false_type{});      // the consumer's last phase: ring + barrier only
-        wait_vmcnt<0>();                                       // past-the-end units must not outlive the workgroup
-#ifdef TSIM_PP_STAMPS
-        if (threadIdx.x == 0) {
-            atomicAdd(&g_ff_stamps[0], (unsigned long long)nphases); atomicAdd(&g_ff_stamps[1], fs_w);
-            atomicAdd(&g_ff_stamps[2], fs_i); atomicAdd(&g_ff_stamps[3], fs_k);
-        }
-#endif
-        return;
-    }
-    // ==================================================================== consumer: FFN2 into the whole row block
-    f32x16 y[12];    // y[t][q]: output feature 32 t + (q & 3) + 8 (q >> 2) + 4 hh of token m0 + r; starts from b2
-#pragma unroll
-    for (int t = 0; t < 12; ++t)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(b2 + 32 * t + 8 * gq + 4 * hh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[t][4 * gq + e] = bv[e];
-        }
-#pragma unroll
-    for (int t = 0; t < 12; ++t) asm volatile("" : "+v"(y[t]));   // retire the b2 loads before any LDS-DMA is in flight
-    issue_unit(0);
-    issue_unit(1);
-    issue_unit(2);
-    const int w2row = r * 64;                                  // + t * 2048 + (((2 s + hh) ^ ((r >> 2) & 3)) << 4)
-    const int w2x0 = ((0 + hh) ^ ((r >> 2) & 3)) << 4, w2x1 = ((2 + hh) ^ ((r >> 2) & 3)) << 4;
-    const char *hslot0 = xbuf + tg * 4096 + lane * 32;
-    [[maybe_unused]] unsigned long long cs_w = 0, cs_i = 0, cs_k = 0;
-    for (int ph = 0; ph < nphases; ++ph) {
-        [[maybe_unused]] const unsigned long long t0 = FF_T();
-        wait_vmcnt<PPU>();
-        __builtin_amdgcn_s_barrier();                          // units landed; the producer's h of chunk ph-2 is written
-        [[maybe_unused]] const unsigned long long t1 = FF_T();
-        issue_unit(2 * ph + 3);
-        if (ph < 2 || !TSIM_FF_SPREAD) issue_unit(2 * ph + 4);
-        [[maybe_unused]] const unsigned long long t2 = FF_T();
-        if (ph >= 2) {
-            const uint32_t hs = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)(hslot0 + ((ph - 2) & 1) * 2048));
-            lds_u32x4 hv0, hv1;
-            lds_read_b128_imm<0>(hv0, hs);
-            lds_read_b128_imm<16>(hv1, hs);
-            constexpr int PF = 4;
-            lds_u32x4 fr[PF + 1];
-            const uint32_t un = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)(ring + ((2 * ph + 1) % FF_NSLOT) * FF_UNIT)) + w2row;
-            const uint32_t ua0 = un + w2x0, ua1 = un + w2x1;
-            auto rd = [&](auto nc) __attribute__((always_inline)) {    // read n: tile n >> 1, k-step n & 1
-                constexpr int n = decltype(nc)::value;
-                lds_read_b128_imm<(n >> 1) * 2048>(fr[n % (PF + 1)], (n & 1) ? ua1 : ua0);
-            };
-            ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
-            lgkm_wait_counted<PF>(hv0);                        // the two h reads are older than the PF fragment reads
-            asm volatile("" : "+v"(hv1));
-            const bf16x8 h0 = __builtin_bit_cast(bf16x8, hv0), h1 = __builtin_bit_cast(bf16x8, hv1);
-            ff_static_for(std::make_integer_sequence<int, 24>{}, [&](auto nc) __attribute__((always_inline)) {
-                constexpr int n = decltype(nc)::value;
-                if constexpr (n + PF < 24) rd(std::integral_constant<int, n + PF>{});
-                constexpr int younger = n + PF < 24 ? PF : 23 - n;
-                lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
-                y[n >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]), (n & 1) ? h1 : h0,
-                                                                   y[n >> 1], 0, 0, 0);
-                if constexpr (TSIM_FF_SPREAD && (n == 5 || n == 11 || n == 17)) issue_pieces(2 * ph + 4, n / 6, n / 6 + 1);
-            });
-        }
-#ifdef TSIM_PP_STAMPS
-        {
-#pragma unroll
-            for (int t = 0; t < 12; ++t) asm volatile("" : "+v"(y[t]));
-            const unsigned long long t3 = FF_T();
-            cs_w += t1 - t0; cs_i += t2 - t1; cs_k += t3 - t2;
-        }
-#endif
-    }
-    wait_vmcnt<0>();
-#ifdef TSIM_PP_STAMPS
-    if (threadIdx.x == 256) {
-        atomicAdd(&g_ff_stamps[4], (unsigned long long)nphases); atomicAdd(&g_ff_stamps[5], cs_w);
-        atomicAdd(&g_ff_stamps[6], cs_i); atomicAdd(&g_ff_stamps[7], cs_k);
-    }
-#endif
-
-    // ---------------------------------------------------------------- epilogue: + residual, LayerNorm, store
-    const int64_t m = m0 + r;
-    const bool live = m < M;
-    const int64_t mr = live ? m : M - 1;
-#pragma unroll
-    for (int t = 0; t < 12; ++t)
-#pragma unroll
-        for (int gq = 0; gq < 4; gq += 2) {
-            // the lane's 16 bytes: the 8 features of group gq + hh; the swap turns them back into the accumulator layout
-            const uint4 o = *reinterpret_cast<const uint4 *>(X + mr * K + 32 * t + 8 * gq + 8 * hh);
-            auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
-            auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
-            const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
-            y[t][4 * gq + 0] += __uint_as_float(a0 << 16);
-            y[t][4 * gq + 1] += __uint_as_float(a0 & 0xffff0000u);
-            y[t][4 * gq + 2] += __uint_as_float(a1 << 16);
-            y[t][4 * gq + 3] += __uint_as_float(a1 & 0xffff0000u);
-            y[t][4 * gq + 4] += __uint_as_float(c0 << 16);
-            y[t][4 * gq + 5] += __uint_as_float(c0 & 0xffff0000u);
-            y[t][4 * gq + 6] += __uint_as_float(c1 << 16);
-            y[t][4 * gq + 7] += __uint_as_float(c1 & 0xffff0000u);
-        }
-    float s1 = 0.f;
-#pragma unroll
-    for (int t = 0; t < 12; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) s1 += y[t][q];
-    s1 += __shfl_xor(s1, 32, 64);
-    const float mean = s1 * (1.0f / 384.0f);
-    float s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < 12; ++t)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const float dlt = y[t][q] - mean;
-            s2 = fmaf(dlt, dlt, s2);
-        }
-    s2 += __shfl_xor(s2, 32, 64);
-    const float rstd = 1.0f / sqrtf(s2 * (1.0f / 384.0f) + eps);
-#pragma unroll
-    for (int t = 0; t < 12; ++t) {
-        uint32_t pk[8];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int n = 32 * t + 8 * gq + 4 * hh;
-            const f32x4 gv = *reinterpret_cast<const f32x4 *>(gamma + n), bv = *reinterpret_cast<const f32x4 *>(beta + n);
-            const float o0 = (y[t][4 * gq + 0] - mean) * rstd * gv[0] + bv[0], o1 = (y[t][4 * gq + 1] - mean) * rstd * gv[1] + bv[1];
-            const float o2 = (y[t][4 * gq + 2] - mean) * rstd * gv[2] + bv[2], o3 = (y[t][4 * gq + 3] - mean) * rstd * gv[3] + bv[3];
-            pk[2 * gq] = pack_bf16x2(o0, o1);
-            pk[2 * gq + 1] = pack_bf16x2(o2, o3);
-        }
-#pragma unroll
-        for (int gq = 0; gq < 4; gq += 2) {
-            auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
-            auto s1w = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
-            if (live) *reinterpret_cast<uint4 *>(out + m * K + 32 * t + 8 * gq + 8 * hh) = make_uint4(s0[0], s1w[0], s0[1], s1w[1]);
-        }
-    }
-}
-
 // =====================================================================================================
 // ln_rows_gemm: out = LayerNorm(X W^T + bias + res) for hidden 384 with 256 tokens per workgroup — the O-projection and FFN2 of
-// a MiniLM layer wherever whole rounds of 256-token tiles exist (the rest of the tokens goes through gemm_bf16_kernel<128 / 32,
-// 384, ..>, whose rows carry the same bits: same k order, same MFMA shape, accumulators from the bias, the same statistics).
+// a MiniLM layer wherever whole rounds of 256-token tiles exist (the rest of the tokens goes through ln_tail_gemm_kernel or
+// gemm_bf16_kernel<128 / 64, 384, ..>, whose rows carry the same bits: same k order, same MFMA shape, accumulators from the
+// bias, the same statistics).
 //
 // Why (round 3).  LDS is the binding resource of the LayerNorm GEMM: an LDS-DMA write moves 64 B per LDS cycle, a ds_read_b128
 // 256 B, and at BM = 128, BK = 64 a k-tile stages 64 KiB (1 024 LDS cycles) and is read 160 KiB (640) for 1 536 cycles of MFMA
 // per SIMD — measured: staging alone 71 of 80 us (profiles/README.md).  The W tile is 3/4 of the staged bytes and is re-staged for
 // every token tile, so the tile must hold more tokens; gemm_bf16_kernel's 2 x 4 wave grid at BM = 256 needs 192 accumulator
 // registers beside ~110 others and spills (measured 115 us per launch instead of 80).  Here every WAVE owns 32 token rows and ALL
-// 384 features (12 accumulator tiles = 192 VGPRs, the layout of ffn_fused_kernel's consumer): LayerNorm statistics never leave the
+// 384 features (12 accumulator tiles = 192 VGPRs): LayerNorm statistics never leave the
 // wave — no barrier, no LDS round trip, no parameter staging in the epilogue — and the k loop is the asm-pipelined form of the
 // other kernels: 32-k tiles (16 KiB of X + 24 KiB of W as packed images) through a three-slot LDS-DMA ring with counted vmcnt (two
 // tiles in flight across the barrier), fragment reads rolling four ahead with counted lgkmcnt, 24 MFMAs per wave and tile.
 // Per k-tile: 40 KiB staged (640 LDS cycles) + 208 KiB read (832) for 1 536 MFMA cycles per SIMD.
 // =====================================================================================================
-// NW = waves = 32-token row blocks per workgroup, NST = ring slots.  <8, 3>: the main form (256 tokens, 120 KiB).  <2, 5>: the
-// REMAINDER form — 64 tokens per workgroup, and since such a launch has far fewer workgroups than CUs, a five-slot ring (140 KiB)
-// that keeps three tiles in flight: a remainder's cost is its k loop's LATENCY (k-tiles x time per tile, whatever the token
-// count), and an LDS-DMA tile takes ~1.1 us from issue to landing.  Every wave runs the same instruction stream on its rows in
-// both forms: same bits.
+// NW = waves = 32-token row blocks per workgroup, LR_NST = ring slots: <8, 3> (256 tokens, 120 KiB).
 constexpr int LR_BK = 32, LR_WBYTES = 384 * LR_BK * 2;
 
-// STAG (stagger): an LDS-DMA instruction costs the ISSUING wave 60-185 cycles (five pieces per wave and tile: ~650 cycles
-// against 768 of MFMA), and when all eight waves issue right behind the barrier no MFMA runs anywhere on the CU meanwhile
-// (measured: 2 700 cycles per tile for 1 536 of matrix work).  With STAG the second half of the waves — the SIMD partners of
-// the first half — issue their pieces AFTER their MFMAs: on every SIMD one wave feeds the matrix pipe while the other queues
-// at the address path.  Their tile then has one tile period less to land, hence one ring slot more (four: exactly 160 KiB).
-// Measured EQUAL to the plain three-slot form (profiles/README.md, round 3) and left as an opt-in (TSIM_LN_ROWS_STAG=1).
-template <int NW, int LR_NST, bool STAG = false>
+template <int NW, int LR_NST>
 __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
                                                                const float *__restrict__ bias, const bf16_t *__restrict__ res,
                                                                const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -1637,8 +819,7 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         constexpr int stage = decltype(stc)::value;
         wait_vmcnt<(LR_NST - 2) * PPW>();  // my pieces of tile kt (those of kt + 1 .. kt + NST - 2 stay in flight)
         __builtin_amdgcn_s_barrier();      // everyone's landed; everyone is past tile kt - 1
-        const bool late = STAG && wave >= NW / 2;
-        if (!late) issue(kt + LR_NST - 1, (stage + LR_NST - 1) % LR_NST);
+        issue(kt + LR_NST - 1, (stage + LR_NST - 1) % LR_NST);
         constexpr int PF = 4, NRD = 24;
         lds_u32x4 bfr[2], fr[PF + 1];
         const uint32_t so = stage * STAGE;
@@ -1659,11 +840,6 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
             acc[n % 12] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]),
                                                                    __builtin_bit_cast(bf16x8, bfr[n / 12]), acc[n % 12], 0, 0, 0);
         });
-        if (late) {
-#pragma unroll
-            for (int t = 0; t < 12; ++t) asm volatile("" : "+v"(acc[t]));   // keep the issue behind the MFMA stream
-            issue(kt + LR_NST - 1, (stage + LR_NST - 1) % LR_NST);
-        }
     };
     int kt = 0;
     for (; kt + LR_NST <= nk; kt += LR_NST)
@@ -2043,7 +1219,7 @@ struct tsim_encoder {
     int relw = 0;
     struct Layer {
         bf16_t *wqkv, *wo, *w1, *w2;
-        bf16_t *pqkv = nullptr, *po = nullptr, *p1 = nullptr, *p2 = nullptr;     // tile-major copies for the ping-pong GEMM
+        bf16_t *pqkv = nullptr, *po = nullptr;     // tile-major copies for the ping-pong GEMM (QKV and O-projection)
         bf16_t *lo = nullptr, *l2 = nullptr;   // H = 384: O-proj / FFN2 weights as the k-tile LDS images of the LayerNorm GEMM
         bf16_t *lo32 = nullptr, *l232 = nullptr;   // ... and as MFMA fragment images (pack_frag_w_kernel) for ln_rows_gemm / ln_tail_gemm
         uint8_t *qqkv = nullptr, *qo = nullptr, *q1 = nullptr, *q2 = nullptr;   // MXFP8 weights: e4m3 bytes (tile-major) ...
@@ -2175,21 +1351,6 @@ static int launch_gemm(const bf16_t *X, const bf16_t *W, const float *bias, cons
     return TSIM_OK;
 }
 
-template <int EPI, int NW>
-static int gemm_xres_nw(const bf16_t *X, const bf16_t *W, const float *bias, bf16_t *out, int M, int N, hipStream_t st) {
-    constexpr int lds = XR_NSTAGE * XR_BN * XR_BK * 2 + NW * 32 * XR_STG_ROW + 8192;   // ring | output image | bias (N <= 2048)
-    if (N > 2048) return fail(TSIM_EUNSUPPORTED, "gemm_xres: N=%d > 2048", N);
-    auto kern = gemm_xres_kernel<384, EPI, NW>;
-    static DevOnce lds_once;
-    TSIM_MAX_LDS(lds_once, kern, lds);
-    const int items = ((M + NW * 32 - 1) / (NW * 32)) * (N / XR_BN);
-    const int slots = 256 * (8 / NW);             // persistent workgroups: one (8 waves) or two (4 waves) per CU
-    const int grid = items < slots ? items : slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, X, W, bias, out, M, N, items);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
-}
-
 template <int EPI, bool PK>
 static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_t *out, int M, int N, hipStream_t st) {
     constexpr int lds = X2_NSTAGE * X2_BN * X2_BK * 2 + 8192;   // ring | bias (N <= 2048)
@@ -2201,26 +1362,6 @@ static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_
     const int items = ((M + 255) / 256) * (N / X2_BN);
     const int grid = items < 256 ? items : 256;             // persistent workgroups, one per CU
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, X, W, bias, out, M, N, items);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
-}
-
-template <int EPI>
-static int gemm_xres(const bf16_t *X, const bf16_t *W, const float *bias, bf16_t *out, int M, int N, hipStream_t st) {
-    static int v2 = -1;
-    if (v2 < 0) { const char *e = getenv("TSIM_XRES2"); v2 = e ? atoi(e) : 1; }
-    if (v2 && N % X2_BN == 0) return gemm_xres2<EPI, false>(X, W, bias, out, M, N, st);
-    return gemm_xres_nw<EPI, 8>(X, W, bias, out, M, N, st);   // 8 waves = 256 tokens per workgroup (4-wave groups measured slower)
-}
-
-static int ffn_fused(const bf16_t *X, const bf16_t *W1img, const bf16_t *W2img, const float *b1, const float *b2,
-                     const float *gamma, const float *beta, float eps, bf16_t *out, int M, int F, hipStream_t st) {
-    const int lds = FF_NSLOT * FF_UNIT + FF_XB + ((F * 4 + 1023) / 1024) * 1024;   // ring | h exchange | b1
-    if (lds > 160 * 1024) return fail(TSIM_EUNSUPPORTED, "ffn_fused: F=%d needs %d B of LDS", F, lds);
-    static DevOnce lds_once;
-    TSIM_MAX_LDS(lds_once, ffn_fused_kernel, 160 * 1024);
-    hipLaunchKernelGGL(ffn_fused_kernel, dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, X, W1img, W2img, b1, b2, gamma,
-                       beta, eps, out, M, F);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
@@ -2401,12 +1542,12 @@ static int ln_tail_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias
 }
 
 // LayerNorm GEMM of width 384 over rows [0, M) in workgroups of NW * 32 token rows (the last one may be partial)
-template <int NW, int NST, bool STAG = false>
+template <int NW, int NST>
 static int ln_rows_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
                         const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked) {
-    constexpr int lds = NST * (NW * 32 * LR_BK * 2 + LR_WBYTES);   // <8, 3>: 120 KiB, <2, 5>: 140 KiB
+    constexpr int lds = NST * (NW * 32 * LR_BK * 2 + LR_WBYTES);   // <8, 3>: 120 KiB
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = ln_rows_gemm_kernel<NW, NST, STAG>;
+    auto kern = ln_rows_gemm_kernel<NW, NST>;
     static DevOnce lds_once;
     TSIM_MAX_LDS(lds_once, kern, lds);
     if (K % LR_BK != 0 || K < NST * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: K=%d", K);
@@ -2418,22 +1559,14 @@ static int ln_rows_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias
 
 // The block-packed qkv / h1 layout (packed_off) needs gemm_xres2 as the producer on both projections
 static bool use_packed_layout(int H, int F) {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("TSIM_PACKED_ACT"), *x2 = getenv("TSIM_XRES2"), *xr = getenv("TSIM_GEMM_XRES"), *bg = getenv("TSIM_GEMM_BIG");
-        on = (e ? atoi(e) : 1) && (x2 ? atoi(x2) : 1) && (xr ? atoi(xr) : 1) && (bg ? atoi(bg) != 2 : 1);
-    }
-    return on && H == 384 && (3 * H) % X2_BN == 0 && F % X2_BN == 0 && F <= 2048;
+    return H == 384 && (3 * H) % X2_BN == 0 && F % X2_BN == 0 && F <= 2048;
 }
 
 template <int EPI>
 static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, bf16_t *out, int M, int N,
                       int K, hipStream_t st) {
-    static int use_xres = -1, big = -1;
-    if (use_xres < 0) { const char *e = getenv("TSIM_GEMM_XRES"); use_xres = e ? atoi(e) : 1; }
-    if (big < 0) { const char *e = getenv("TSIM_GEMM_BIG"); big = e ? atoi(e) : 1; }
-    if (use_xres && big != 2 && K == 384 && N % XR_BN == 0) return gemm_xres<EPI>(X, W, bias, out, M, N, st);
-    if (big && (K >= 768 || big == 2) && gemm_pp_supported(N, K))
+    if (K == 384 && N % XR_BN == 0) return gemm_xres2<EPI, false>(X, W, bias, out, M, N, st);
+    if (K >= 768 && gemm_pp_supported(N, K))
         return gemm_pp(EPI == EPI_GELU ? PP_EPI_GELU : PP_EPI_BIAS, X, Wp ? Wp : W, Wp != nullptr, bias, out, M, N, K, st);
     if (N % 128 == 0)
         return launch_gemm<128, 128, 64, 2, 2, EPI>(X, W, bias, nullptr, nullptr, nullptr, 0.f, out, M, N, K, st);
@@ -2444,12 +1577,7 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                        const float *gamma, const float *beta, float eps, bf16_t *out, int M, int N, int K, float *ybuf,
                        hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false) {
     if (xpacked && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed operand layout is a hidden-384 form");
-    static int use_img = -1;
-    if (use_img < 0) { const char *e = getenv("TSIM_LN_WIMG"); use_img = e ? atoi(e) : 1; }
-    if (!use_img) Wimg = nullptr;
-    static int big = -1;
-    if (big < 0) { const char *e = getenv("TSIM_GEMM_BIG"); big = e ? atoi(e) : 1; }
-    if (big && ybuf && N >= 512 && N % 256 == 0 && gemm_pp_supported(N, K)) {
+    if (ybuf && N >= 512 && N % 256 == 0 && gemm_pp_supported(N, K)) {
         // wide rows: a workgroup cannot own whole 768-feature rows at a 256-token tile, so the projection writes
         // fp32 sums and a row kernel adds the residual and normalises (HBM-bound, 8 B per element)
         int rc = gemm_pp(PP_EPI_F32, X, Wp ? Wp : W, Wp != nullptr, bias, ybuf, M, N, K, st);
@@ -2458,25 +1586,16 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
     }
     switch (N) {
         case 384: {
-            // 128-token tiles, one workgroup per CU: mt tiles take ceil(mt/256) rounds and a nearly empty last round
-            // costs a full one.  A small remainder is launched separately with 32-token tiles (4x more, 4x shorter
-            // workgroups), e.g. 525 tiles = 2 rounds + 13 tiles -> 2 rounds + a quarter round.
-            static int split = -1;
-            if (split < 0) { const char *e = getenv("TSIM_LN_TAIL"); split = e ? atoi(e) : 1; }
-            // (64-token tiles measured slower: 64 x 384 x 32-k with two workgroups per CU 2.96 ms per forward, 64 x 384 x 64-k 3.08,
-            // against 2.74: the W tile is re-staged for half as many tokens)
             // 256-token tiles, one 32-token row block per wave (ln_rows_gemm_kernel), for whole rounds of 256 tiles and for a last
-            // round that is at least half full; everything else — and every small batch — goes through the 128- / 32-token
-            // forms below.  All forms give a row the same bits (bit-wise large-vs-small-batch test).
-            static int rows256 = -1;
-            if (rows256 < 0) { const char *e = getenv("TSIM_LN_ROWS256"); rows256 = e ? atoi(e) : 1; }
+            // round that is at least half full; everything else — and every small batch — goes through the forms below.  All
+            // forms give a row the same bits (bit-wise large-vs-small-batch test).
             bool after_rows = false;   // the rest below is the remainder of a ln_rows launch: a true tail
-            if (rows256 && Wimg32) {
+            if (Wimg32) {
                 const int t256 = M / 256;
                 const int use = (t256 % 256) >= 128 ? t256 : (t256 / 256) * 256;
                 if (use > 0) {
-                    // (a four-slot ring with the second half of the waves issuing behind their MFMAs — STAG = true — measured equal,
-                    // 68.5 vs 66-68 us per launch; not instantiated)
+                    // (a four-slot ring with the second half of the waves issuing behind their MFMAs measured equal, 68.5 vs 66-68 us
+                    // per launch)
                     int rc = ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked);
                     const int m1 = use * 256;
                     if (rc || m1 == M) return rc;
@@ -2484,38 +1603,28 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                     after_rows = true;
                 }
                 // few rows (a remainder, or a small batch): one round of 32-row workgroups that stream W straight into registers
-                static int frag_tail = -1;
-                if (frag_tail < 0) { const char *e = getenv("TSIM_LN_TAIL_FRAG"); frag_tail = e ? atoi(e) : 1; }
-                if (frag_tail && M <= 256 * 32 && K % (16 * LT_PF) == 0)
+                if (M <= 256 * 32 && K % (16 * LT_PF) == 0)
                     return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked);
-                // a remainder of at most 128 workgroups of 64 rows: the deep-ring form (TSIM_LN_ROWS_TAIL=0: the 64- / 32-token
-                // tiles of gemm_bf16_kernel below)
-                static int rows_tail = -1;
-                if (rows_tail < 0) { const char *e = getenv("TSIM_LN_ROWS_TAIL"); rows_tail = e ? atoi(e) : 0; }
-                if (rows_tail && after_rows && M <= 128 * 64 && K >= 5 * LR_BK)
-                    return ln_rows_gemm<2, 5>(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked);
             }
+            // 128-token tiles, one workgroup per CU: mt tiles take ceil(mt/256) rounds and a nearly empty last round costs a full
+            // one.  A small remainder is launched separately with 64-token tiles (2x more, 2x shorter workgroups).
+            // (64-token tiles throughout measured slower: 64 x 384 x 32-k with two workgroups per CU 2.96 ms per forward, 64 x 384
+            // x 64-k 3.08, against 2.74: the W tile is re-staged for half as many tokens)
             const int mt = (M + 127) / 128, full = (mt / 256) * 256, rem = mt - full;
             // (four 32-k ring slots instead of two 64-k ones — prefetch distance 3 — measured 2.5 % SLOWER per forward: the deep
             // path issues a k-tile's DMA pieces in one burst ahead of the MFMAs instead of behind each k-step's)
             auto main_launch = [&](int rows) {
                 return launch_gemm<128, 384, 64, 2, 4, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, rows, N, K, st, Wimg, xpacked);
             };
-            if (split && rem > 0 && rem <= 96 && (full > 0 || after_rows)) {
+            if (rem > 0 && rem <= 96 && (full > 0 || after_rows)) {
                 const int m_main = full * 128;
                 if (full > 0) {
                     int rc = main_launch(m_main);
                     if (rc) return rc;
                 }
-                // (a three-slot ring for the remainder launch measured no different: 2.744-2.751 vs 2.751-2.752 ms per forward)
-                // TSIM_LN_TAIL_BM: token rows per workgroup of the remainder launch (32: four waves, 64: eight waves = 7 instead of
-                // 13 DMA pieces per wave and k-tile)
-                static int tail_bm = -1;
-                if (tail_bm < 0) { const char *e = getenv("TSIM_LN_TAIL_BM"); tail_bm = e ? atoi(e) : 64; }
-                if (tail_bm == 64)
-                    return launch_gemm<64, 384, 64, 2, 4, EPI_RES_LN>(X + (int64_t)m_main * K, W, bias, res + (int64_t)m_main * N,
-                                                                      gamma, beta, eps, out + (int64_t)m_main * N, M - m_main, N, K, st, Wimg, xpacked);
-                return launch_gemm<32, 384, 64, 1, 4, EPI_RES_LN>(X + (int64_t)m_main * K, W, bias, res + (int64_t)m_main * N,
+                // remainder launch: 64 token rows (eight waves) per workgroup.  (A three-slot ring measured no different:
+                // 2.744-2.751 vs 2.751-2.752 ms per forward.)
+                return launch_gemm<64, 384, 64, 2, 4, EPI_RES_LN>(X + (int64_t)m_main * K, W, bias, res + (int64_t)m_main * N,
                                                                   gamma, beta, eps, out + (int64_t)m_main * N, M - m_main, N, K, st, Wimg, xpacked);
             }
             return main_launch(M);
@@ -2595,8 +1704,6 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
         } else if (H >= 512 && H % 256 == 0 && gemm_pp_supported(H, H) && gemm_pp_supported(F, H) && gemm_pp_supported(H, F)) {
             if ((rc = repack(d.wqkv, 3 * H, H * 2, (void **)&d.pqkv))) return bail(rc);
             if ((rc = repack(d.wo, H, H * 2, (void **)&d.po))) return bail(rc);
-            if ((rc = repack(d.w1, F, H * 2, (void **)&d.p1))) return bail(rc);
-            if ((rc = repack(d.w2, H, F * 2, (void **)&d.p2))) return bail(rc);
         }
         if (!mx && H == 384 && F % 64 == 0) {   // LayerNorm GEMM (BN = 384, BK = 64): W as contiguous k-tile images
             if ((rc = dev_alloc(e, (size_t)H * H * 2, (void **)&d.lo))) return bail(rc);
@@ -2612,14 +1719,6 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
             hipLaunchKernelGGL(pack_frag_w_kernel, dim3((unsigned)((H * F / 8 + 255) / 256)), dim3(256), 0, 0,
                                reinterpret_cast<const uint4 *>(d.w2), reinterpret_cast<uint4 *>(d.l232), 384, F);
             if (hipGetLastError() != hipSuccess) return bail(fail(TSIM_EHIP, "LayerNorm GEMM weight packing failed"));
-        }
-        if (!mx && H == 384 && F % 64 == 0 && F <= 4096) {   // fused FFN (ffn_fused_kernel): both matrices as LDS images
-            if ((rc = dev_alloc(e, (size_t)F * H * 2, (void **)&d.p1))) return bail(rc);
-            if ((rc = dev_alloc(e, (size_t)F * H * 2, (void **)&d.p2))) return bail(rc);
-            hipLaunchKernelGGL(pack_ffn_w1_kernel, dim3((unsigned)((F * 48 + 255) / 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const uint4 *>(d.w1), reinterpret_cast<uint4 *>(d.p1), F);
-            hipLaunchKernelGGL(pack_ffn_w2_kernel, dim3((unsigned)((384 * F + 255) / 256)), dim3(256), 0, 0, d.w2, d.p2, F);
-            if (hipGetLastError() != hipSuccess) return bail(fail(TSIM_EHIP, "FFN weight packing failed"));
         }
         std::vector<float> bq(3 * (size_t)H);
         memcpy(bq.data(), lw.bq, H * 4);
@@ -2685,11 +1784,6 @@ extern "C" int tsim_gemm_mxfp8(const void *xq, const void *xs, const void *wq, c
 }
 
 #ifdef TSIM_PP_STAMPS
-extern "C" int tsim_debug_ff_stamps(unsigned long long *out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsim::g_ff_stamps), 64) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(tsim::g_ff_stamps), z, 64) != hipSuccess) return 1; }
-    return 0;
-}
 extern "C" int tsim_debug_xr_stamps(unsigned long long *out8, int reset) {
     if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsim::g_xr_stamps), 64) != hipSuccess) return 1;
     if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(tsim::g_xr_stamps), z, 64) != hipSuccess) return 1; }
@@ -2737,9 +1831,7 @@ extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, con
         const bool pk = !mx && !rel && use_packed_layout(H, F);
         const int32_t *col = rel ? (tok_col ? tok_col : tok_pos) : nullptr;
         const int qblocks = (max_len + 31) / 32 > 0 ? (max_len + 31) / 32 : 1;
-        static int att_xcd = -1;
-        if (att_xcd < 0) { const char *ev = getenv("TSIM_ATT_XCD"); att_xcd = ev ? atoi(ev) : 1; }
-        const dim3 agrid((unsigned)(att_xcd ? ((B + 7) / 8) * 8 : B), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks);
+        const dim3 agrid((unsigned)(((B + 7) / 8) * 8), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks);   // xcd_map = 1
         for (int l = 0; l < c.num_layers; ++l) {
             const tsim_encoder::Layer &L = e->layers[l];
             if (mx) {   // projections on MXFP8 operands (v_mfma_scale_f32_32x32x64_f8f6f4); x0's image comes fused from the
@@ -2753,13 +1845,13 @@ extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, con
     do {                                                                                                       \
         if (rel)                                                                                               \
             hipLaunchKernelGGL((attention_kernel<D, true>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col,  \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, att_xcd);                                \
+                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
         else if (pk)                                                                                           \
             hipLaunchKernelGGL((attention_kernel<D, false, true>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col, \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, att_xcd);                                \
+                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
         else                                                                                                   \
             hipLaunchKernelGGL((attention_kernel<D, false>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col, \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, att_xcd);                                \
+                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
     } while (0)
             if (dh == 16) ATT(16); else if (dh == 32) ATT(32); else ATT(64);
 #undef ATT
@@ -2774,15 +1866,6 @@ extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, con
                 continue;
             }
             if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32))) return rc;
-            static int fused = -1;
-            // OFF by default: at the bench shape (67 k tokens = 525 blocks of 128 on 256 CUs: three rounds) the fused kernel
-            // takes 256 us per layer against 245 us for FFN1 + FFN2 + tail (profiles/README.md, round 2); kept for shapes that
-            // fill whole rounds and as the starting point of the next round
-            if (fused < 0) { const char *ev = getenv("TSIM_FFN_FUSED"); fused = ev ? atoi(ev) : 0; }
-            if (fused && H == 384 && L.p1 && L.p2) {
-                if ((rc = ffn_fused(e->x1, L.p1, L.p2, L.b1, L.b2, L.g2, L.be2, c.ln_eps, e->x0, T, F, st))) return rc;
-                continue;
-            }
             if (pk) {
                 if ((rc = gemm_xres2<EPI_GELU, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
             } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;

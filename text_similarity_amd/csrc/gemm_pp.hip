@@ -645,9 +645,7 @@ static int launch_pp(const void *X, const void *W, const uint8_t *xs, const uint
     TSIM_MAX_LDS(lds_once, kern, lds);
     const int mtiles = (M + PP_BM - 1) / PP_BM, ntiles = N / BN;
     const int total = ((mtiles + 7) / 8) * 8 * ntiles;
-    static int persist = -1;
-    if (persist < 0) { const char *e = getenv("TSIM_PP_PERSIST"); persist = e ? atoi(e) : 1; }
-    const int grid = persist && total > 256 ? 256 : total;     // one persistent workgroup per CU (a multiple of 8)
+    const int grid = total > 256 ? 256 : total;     // one persistent workgroup per CU (a multiple of 8)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, X, W, xs, ws, bias, out, out_s, M, N, K, mtiles, ntiles, wpk);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
@@ -656,32 +654,19 @@ static int launch_pp(const void *X, const void *W, const uint8_t *xs, const uint
 bool gemm_pp_supported(int N, int K) { return N % 128 == 0 && K % PP_BK == 0 && K >= 2 * PP_BK; }
 bool gemm_pp_mx_supported(int N, int K) { return N % 256 == 0 && K % 128 == 0 && K >= 256; }
 
-static int pp_ksec() {
-    static int ksec = -1;
-    if (ksec < 0) { const char *e = getenv("TSIM_PP_KSEC"); ksec = e ? atoi(e) : 2; }
-    return ksec;
-}
-
 int gemm_pp_tile_width(int N) { return N % 256 != 0 ? 128 : 256; }
 
 int gemm_pp(int epi, const bf16_t *X, const bf16_t *W, int w_packed, const float *bias, void *out, int M, int N, int K,
             hipStream_t st) {
     if (!gemm_pp_supported(N, K)) return fail(TSIM_EUNSUPPORTED, "gemm_pp: N=%d K=%d not tileable by 128x64", N, K);
     if (M <= 0) return TSIM_OK;
-    const int ksec = pp_ksec();
     // feature tile: 256 wide unless N is not a multiple of 256 (the 128-wide tile stages 1.5x the bytes per FLOP and
     // measured slower on the N = 768 projections even though it fills the last round of workgroups better)
-    static int bn_env = -1;
-    if (bn_env < 0) { const char *e = getenv("TSIM_PP_BN"); bn_env = e ? atoi(e) : 0; }
-    int bn = gemm_pp_tile_width(N);
-    if (N % 256 == 0 && bn_env == 128 && !w_packed) bn = 128;   // (a packed W fixes the tile width it was packed for)
-#define PP_GO(E)                                                                                              \
-    do {                                                                                                      \
-        if (bn == 128)                                                                                        \
-            return ksec == 1 ? launch_pp<E, 1, false, 128>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st) \
-                             : launch_pp<E, 2, false, 128>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st); \
-        return ksec == 1 ? launch_pp<E, 1, false, 256>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st)     \
-                         : launch_pp<E, 2, false, 256>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st);    \
+    const int bn = gemm_pp_tile_width(N);
+#define PP_GO(E)                                                                                                   \
+    do {                                                                                                           \
+        if (bn == 128) return launch_pp<E, 2, false, 128>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st); \
+        return launch_pp<E, 2, false, 256>(X, W, nullptr, nullptr, bias, out, nullptr, M, N, K, w_packed, st);                \
     } while (0)
     switch (epi) {
         case PP_EPI_BIAS: PP_GO(PP_EPI_BIAS);

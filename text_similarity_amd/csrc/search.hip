@@ -1101,20 +1101,12 @@ static bool plan_fullmax(int64_t Q, int64_t N, int D, int kneed, TopkPlan *p) {
 // Two-phase main pass (large shards): phase A = the first K1_PHASE_A_ROWS rows, phase B = the rest.
 constexpr int64_t K1_PHASE_A_ROWS = 131072;
 static bool plan_two_phase(int64_t Q, int64_t N, int D, int k, TopkPlan *pa, TopkPlan *pb) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("TSIM_K1_PHASES"); on = e ? atoi(e) : 1; }
     // one or two query blocks: the chip is filled by corpus chunks alone and two extra launches cost more than the tighter
     // bound saves (Q = 256: 0.37 -> 0.44 ms); from four query blocks on the second phase wins (Q = 4096: -3 %)
-    if (!on || N < 4 * K1_PHASE_A_ROWS || Q <= 768) return false;
+    if (N < 4 * K1_PHASE_A_ROWS || Q <= 768) return false;
     plan_topk(Q, K1_PHASE_A_ROWS, D, k, pa);
     plan_topk(Q, N - K1_PHASE_A_ROWS, D, k, pb);
     return true;
-}
-
-static float guard_c1() {
-    static float c1 = -1.f;
-    if (c1 < 0.f) { const char *e = getenv("TSIM_GUARD_C1"); c1 = e ? (float)atof(e) : 4.0f; if (!(c1 >= 1.f)) c1 = 1.f; }
-    return c1;
 }
 
 template <typename T, bool COS>
@@ -1157,12 +1149,10 @@ static void launch_finalize(const TopkPlan &p, const float *part_s, const int *p
                             int64_t *out_i, int64_t idx_offset, const GuardArgs &g, hipStream_t st) {
     const dim3 grid((unsigned)((Q + 3) / 4));
     constexpr int LBW = KL == 16 ? 8 : 4;   // (eight lists of 32 at a time spill)
-    static int wide_on = -1;
-    if (wide_on < 0) { const char *e = getenv("TSIM_FIN_WIDE"); wide_on = e ? atoi(e) : 1; }
-    if (wide_on && Q <= 1024 && d <= 384)
+    if (Q <= 1024 && d <= 384)
         hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, COS, 16, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
                            xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
-    else if (wide_on && Q <= 1024)
+    else if (Q <= 1024)
         hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, COS, 8, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
                            xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
     else
@@ -1220,7 +1210,7 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
     const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
 
     GuardArgs g;
-    g.c1 = guard_c1();
+    g.c1 = 4.0f;
     // unit rows only: float32 accumulation of ld exact products of unit rows, any order, rounding or truncation per step
     // (ld * 2^-23 |a||b|, |a|,|b| <= 1 + 2^-10) + the final rounding of the exact score
     g.floor = (float)ld * 1.1920929e-7f * 1.003f + 2.4e-7f;
@@ -1242,9 +1232,7 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
     if (k <= TOPK_MAX_LISTS) {
         TopkPlan p, pp;
         plan_topk(Q, N, ld, k, &p);
-        static int prepass_on = -1;
-        if (prepass_on < 0) { const char *e = getenv("TSIM_K1_PREPASS"); prepass_on = e ? atoi(e) : 1; }
-        if (prepass_on && plan_prepass(Q, N, p, &pp)) {
+        if (plan_prepass(Q, N, p, &pp)) {
             // threshold pre-pass: block maxima over the first rows, KL-th largest per query -> initial shared bounds
             const int64_t S = (int64_t)pp.nchunks * pp.rows_per_chunk;
             int rc0 = k1_launch_blockmax(pp, ld, uq, Q, uc, S, bmax, st);
@@ -1256,10 +1244,6 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
             TSIM_HIP_CHECK(hipMemsetAsync(gthr, 0x80, (size_t)Q * 4, st));
         }
         if (!ctl_cleared) TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, ctl_bytes, st));
-#ifdef TSIM_PP_STAMPS
-        if (getenv("TSIM_K1_DIAG_NOSEL"))   // DIAGNOSTIC: thresholds nothing can pass (results are wrong): the time without selection
-            TSIM_HIP_CHECK(hipMemsetAsync(gthr, 0x7f, (size_t)Q * 4, st));
-#endif
         hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
         g_ev_start = g_ev_stop = nullptr;
         if (ev0) TSIM_HIP_CHECK(hipEventRecord(ev0, st));

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Whole-call and main-pass duration of tsim_cosine_topk_ex (float32 rows given: the product path) for small query batches —
-BASELINE config 4's regime (Q = 256 per batch).  A/B knobs are environment variables read by the library (TSIM_K1_PREPASS,
-TSIM_K1_PHASES) or variant libraries (TSIM_LIB).  Usage: python tools/q_call_time.py [N] [d] [Q ...]"""
+BASELINE config 4's regime (Q = 256 per batch).  A/B variants are separate libraries (TSIM_LIB).
+Usage: python tools/q_call_time.py [N] [d] [Q ...]"""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
