@@ -171,7 +171,8 @@ typedef struct tsim_layer_weights_host {
 } tsim_layer_weights_host;
 
 typedef struct tsim_encoder_weights_host {
-    const float *word_emb, *pos_emb, *type_emb /* row 0 is added; NULL for MPNet */, *emb_ln_g, *emb_ln_b;
+    const float *word_emb, *pos_emb, *type_emb /* row 0 (tsim_encoder_set_token_types: all rows); NULL for MPNet */,
+        *emb_ln_g, *emb_ln_b;
     const float *rel_bias;
     const tsim_layer_weights_host *layers;
 } tsim_encoder_weights_host;
@@ -194,13 +195,37 @@ int tsim_encoder_forward(tsim_encoder *enc, const int32_t *tok_ids, const int32_
                          int32_t max_len, float *pooled_f32, void *unit_f16, int ld_unit, float *unit_rho_max,
                          void *last_hidden_bf16, void *stream);
 
-/* Kernels cannot raise HF's IndexError: a token id outside [0, vocab), a position row outside [0, max_pos) or a token whose
+/* ---------------------------------------------------------------------------------------------
+ * Cross-encoder re-ranking: `cross_encoder.predict([[query, text], ...])`   /root/reference/src/pipeline/ranking_pipeline.py:27-33
+ * (the reference takes a sentence_transformers CrossEncoder, i.e. HF BertForSequenceClassification on
+ * `[CLS] a [SEP] b [SEP]` with token types 0 / 1).  BERT only.
+ *
+ * BERT only (TSIM_EINVAL for MPNet): upload all n_types rows of the token-type table [n_types, hidden] (HF
+ * embeddings.token_type_embeddings).  Untyped forwards keep adding row 0 of it. */
+int tsim_encoder_set_token_types(tsim_encoder *enc, const float *type_emb_host, int32_t n_types);
+/* Sequence-classification head, float32 host arrays in nn.Linear layout: pool_w [H,H], pool_b [H] (HF bert.pooler.dense),
+ * cls_w [num_labels,H], cls_b [num_labels] (HF classifier); 1 <= num_labels <= 32.  BERT only (TSIM_EINVAL for MPNet).
+ * logits[b] = cls_w . tanh(pool_w . h[CLS of b] + pool_b) + cls_b, with h the final bf16 hidden state read in place; every sum
+ * in float32 in an order fixed by H alone (rows are batch-composition invariant bit for bit).  A zero-length sequence
+ * reads a zero CLS row. */
+int tsim_encoder_set_cls_head(tsim_encoder *enc, const float *pool_w_host, const float *pool_b_host,
+                              const float *cls_w_host, const float *cls_b_host, int32_t num_labels);
+/* tsim_encoder_forward plus tok_type int32 [T] (token-type row of each token; NULL = all 0, bit-identical to
+ * tsim_encoder_forward) and logits_f32 [B, num_labels] (NULL = no head).  logits_f32 without a head, or tok_type without a
+ * type table: TSIM_EINVAL.  A type id outside [0, n_types) is clamped and raises TSIM_ENC_ERR_TOKEN_TYPE. */
+int tsim_encoder_forward_ex(tsim_encoder *enc, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos,
+                            const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B, int32_t max_len,
+                            float *pooled_f32, void *unit_f16, int ld_unit, float *unit_rho_max,
+                            void *last_hidden_bf16, float *logits_f32, void *stream);
+
+/* Kernels cannot raise HF's IndexError: a token id outside [0, vocab), a token type outside [0, n_types), a position row outside [0, max_pos) or a token whose
  * column is >= the max_len passed to tsim_encoder_forward is clamped / computed anyway and leaves a bit in a per-encoder
  * flag word.  This call copies the word to *flags_host, clears it and SYNCHRONISES `stream` (the only entry point that
  * does): 0 = every forward since the last call was clean.  The Python wrappers call it at the end of encode_text. */
 #define TSIM_ENC_ERR_TOKEN_ID 1
 #define TSIM_ENC_ERR_POSITION 2
 #define TSIM_ENC_ERR_MAX_LEN 4
+#define TSIM_ENC_ERR_TOKEN_TYPE 8
 int tsim_encoder_error_flags(tsim_encoder *enc, int32_t *flags_host, void *stream);
 
 /* ---- tokenizer (host code, no GPU): BERT WordPiece for pure-ASCII sentences -------------------------------------------------

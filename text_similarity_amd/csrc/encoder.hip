@@ -44,20 +44,24 @@ __device__ __forceinline__ int64_t packed_off(int64_t t, int f, int W) {   // el
 }
 
 // =====================================================================================================
-// embeddings: x[t] = LayerNorm(word[id] + pos[pos_id] (+ type[0]))        one wave per token, fp32 math
+// embeddings: x[t] = LayerNorm(word[id] + pos[pos_id] (+ type[type_id]))        one wave per token, fp32 math
 // HBM-bound: reads 2-3 rows of H floats, writes H bf16.
+// TYPED: tok_type [T] picks the token-type row (BERT sentence pairs); untyped, row 0 is added (type_tab = the table, or
+// NULL for MPNet).  Both forms issue the same row loads before the sums, and a typed call whose ids are all 0 computes the
+// untyped call's bits.
 // =====================================================================================================
-template <int VPL>  // values per lane = H / 64
+template <int VPL, bool TYPED = false>  // values per lane = H / 64
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t *__restrict__ ids,
                                                        const int32_t *__restrict__ pos,
                                                        const float *__restrict__ word,
                                                        const float *__restrict__ pos_emb,
-                                                       const float *__restrict__ type0,
+                                                       const float *__restrict__ type_tab,
                                                        const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, float eps, int T, int H,
                                                        bf16_t *__restrict__ out, int vocab, int max_pos,
                                                        const int32_t *__restrict__ col, int max_len,
-                                                       int *__restrict__ err_flags) {
+                                                       int *__restrict__ err_flags,
+                                                       const int32_t *__restrict__ tok_type = nullptr, int n_types = 0) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= T) return;
@@ -65,14 +69,20 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t *__restrict
     // outside the tables) and an error bit is left for tsim_encoder_error_flags.  A token whose column is >= the max_len
     // the caller promised would be skipped by the attention grid: flagged as well.
     int id = ids[t], ps = pos[t];
+    int ty = 0;
+    if constexpr (TYPED) ty = tok_type[t];
     int bad = 0;
     if (id < 0 || id >= vocab) { bad |= TSIM_ENC_ERR_TOKEN_ID; id = id < 0 ? 0 : vocab - 1; }
     if (ps < 0 || ps >= max_pos) { bad |= TSIM_ENC_ERR_POSITION; ps = ps < 0 ? 0 : max_pos - 1; }
     if (col[t] >= max_len || col[t] < 0) bad |= TSIM_ENC_ERR_MAX_LEN;
+    if constexpr (TYPED) {
+        if (ty < 0 || ty >= n_types) { bad |= TSIM_ENC_ERR_TOKEN_TYPE; ty = ty < 0 ? 0 : n_types - 1; }
+    }
     if (bad && lane == 0) atomicOr(err_flags, bad);
     const float *w = word + (int64_t)id * H;
     const float *p = pos_emb + (int64_t)ps * H;
-    // all row loads first, the sums after them: with `if (type0)` inside the loop every iteration was a branch with its own
+    const float *type_row = TYPED ? type_tab + (int64_t)ty * H : type_tab;
+    // all row loads first, the sums after them: with `if (type_row)` inside the loop every iteration was a branch with its own
     // s_waitcnt vmcnt(0) — six dependent memory round trips per token (50 us per forward for a kernel that moves 155 MB)
     float v[VPL], pv[VPL], tv[VPL];
 #pragma unroll
@@ -80,15 +90,15 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t *__restrict
         v[i] = w[lane + i * 64];
         pv[i] = p[lane + i * 64];
     }
-    if (type0) {   // wave-uniform
+    if (type_row) {   // wave-uniform
 #pragma unroll
-        for (int i = 0; i < VPL; ++i) tv[i] = type0[lane + i * 64];
+        for (int i = 0; i < VPL; ++i) tv[i] = type_row[lane + i * 64];
     }
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         float a = v[i];
-        if (type0) a += tv[i];      // HF order: (word + token_type) + position
+        if (type_row) a += tv[i];   // HF order: (word + token_type) + position
         a += pv[i];
         v[i] = a;
         s += a;
@@ -1190,6 +1200,74 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const bf16_t *__restri
 }
 
 // =====================================================================================================
+// sequence-classification head (HF BertPooler + classifier):  pooled = tanh(W_p x + b_p),  logits = W_c pooled + b_c
+// with x the CLS row (first token) of each sequence in the final hidden state.  One workgroup of H threads per CLS_ROWS
+// sequences: the rows are staged in LDS as float32 ([feature][row], so a thread reads its k-th inputs of all rows with two
+// 16-byte LDS loads); thread j owns pooled feature j and sums k = 0 .. H-1 in ascending order with one fma per term (W_p
+// is stored transposed: one coalesced row of W_p^T per k).  Each logit is one wave's dot product: lane l takes features
+// l, l+64, ... in ascending order, then the xor butterfly of wave_sum.  Every sum therefore runs in an order fixed by H
+// alone — not by B nor by the sequence's slot in the batch — so rows are batch-composition invariant bit for bit.
+// A zero-length sequence reads a zero row.  VALU only: per sequence 2 H^2 + 2 H L FLOP against the encoder's ~24 H^2
+// per token and layer.
+// =====================================================================================================
+constexpr int CLS_ROWS = 8;
+constexpr int CLS_MAX_H = 768;
+constexpr int CLS_MAX_LABELS = 32;
+
+__global__ __launch_bounds__(CLS_MAX_H) void cls_head_kernel(const bf16_t *__restrict__ x, const int32_t *__restrict__ cu,
+                                                             int B, int H, const float *__restrict__ wpT,
+                                                             const float *__restrict__ bp, const float *__restrict__ wc,
+                                                             const float *__restrict__ bc, int n_labels,
+                                                             float *__restrict__ logits) {
+    __shared__ __attribute__((aligned(16))) float xs[CLS_MAX_H][CLS_ROWS];   // CLS rows, [feature][row]
+    __shared__ float ps[CLS_ROWS][CLS_MAX_H];                               // pooled rows
+    const int j = threadIdx.x;   // blockDim.x == H
+    const int b0 = blockIdx.x * CLS_ROWS;
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) {
+        const int b = b0 + r;
+        float v = 0.f;
+        if (b < B) {
+            const int t0 = cu[b];
+            if (cu[b + 1] > t0) v = bf16_to_f32(x[(int64_t)t0 * H + j]);
+        }
+        xs[j][r] = v;
+    }
+    __syncthreads();
+    float acc[CLS_ROWS];
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += 8) {   // H % 64 == 0
+        float w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[u] = wpT[(int64_t)(k0 + u) * H + j];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float4 lo = *reinterpret_cast<const float4 *>(&xs[k0 + u][0]);
+            const float4 hi = *reinterpret_cast<const float4 *>(&xs[k0 + u][4]);
+            const float xv[CLS_ROWS] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int r = 0; r < CLS_ROWS; ++r) acc[r] = fmaf(w[u], xv[r], acc[r]);
+        }
+    }
+    const float bj = bp[j];
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) ps[r][j] = tanhf(acc[r] + bj);
+    __syncthreads();
+    const int lane = j & 63, wave = j >> 6, n_waves = H >> 6;
+    const int n_out = CLS_ROWS * n_labels;
+    for (int o = wave; o < n_out; o += n_waves) {   // wave-uniform
+        const int r = o / n_labels, c = o - r * n_labels;
+        const int b = b0 + r;
+        if (b >= B) break;   // o grows with r: every later output of this wave is past B as well
+        float s = 0.f;
+        for (int i = lane; i < H; i += 64) s = fmaf(wc[(int64_t)c * H + i], ps[r][i], s);
+        s = wave_sum(s);
+        if (lane == 0) logits[(int64_t)b * n_labels + c] = s + bc[c];
+    }
+}
+
+// =====================================================================================================
 // host side
 // =====================================================================================================
 static uint16_t host_f32_to_bf16(float f) {
@@ -1217,6 +1295,10 @@ struct tsim_encoder {
     // weights
     float *word = nullptr, *pos = nullptr, *type0 = nullptr, *emb_g = nullptr, *emb_b = nullptr, *relb = nullptr;
     int relw = 0;
+    int n_types = 0;   // rows of the token-type table at type0 (tsim_encoder_set_token_types); 0: row 0 only, untyped calls only
+    // sequence-classification head (tsim_encoder_set_cls_head), float32: W_p transposed [in][out], b_p, W_c [labels][H], b_c
+    float *head_wpT = nullptr, *head_bp = nullptr, *head_wc = nullptr, *head_bc = nullptr;
+    int n_labels = 0;
     struct Layer {
         bf16_t *wqkv, *wo, *w1, *w2;
         bf16_t *pqkv = nullptr, *po = nullptr;     // tile-major copies for the ping-pong GEMM (QKV and O-projection)
@@ -1797,11 +1879,54 @@ extern "C" void tsim_encoder_destroy(tsim_encoder *e) {
     delete e;
 }
 
+extern "C" int tsim_encoder_set_token_types(tsim_encoder *e, const float *type_emb_host, int32_t n_types) {
+    TSIM_REQUIRE(e && type_emb_host, "encoder_set_token_types: null pointer");
+    TSIM_REQUIRE(e->cfg.arch == TSIM_ARCH_BERT, "encoder_set_token_types: BERT only (MPNet has no token-type table)");
+    TSIM_REQUIRE(n_types >= 1, "encoder_set_token_types: n_types=%d < 1", n_types);
+    float *tab = nullptr;
+    if (int rc = upload_f32(e, type_emb_host, (size_t)n_types * e->cfg.hidden, &tab)) return rc;
+    e->type0 = tab;   // row 0 serves the untyped calls from now on (the previous one-row copy stays allocated until destroy)
+    e->n_types = n_types;
+    return TSIM_OK;
+}
+
+extern "C" int tsim_encoder_set_cls_head(tsim_encoder *e, const float *pool_w_host, const float *pool_b_host,
+                                         const float *cls_w_host, const float *cls_b_host, int32_t num_labels) {
+    TSIM_REQUIRE(e && pool_w_host && pool_b_host && cls_w_host && cls_b_host, "encoder_set_cls_head: null pointer");
+    TSIM_REQUIRE(e->cfg.arch == TSIM_ARCH_BERT, "encoder_set_cls_head: BERT only");
+    TSIM_REQUIRE(num_labels >= 1 && num_labels <= CLS_MAX_LABELS, "encoder_set_cls_head: num_labels=%d outside [1, %d]", num_labels,
+                 CLS_MAX_LABELS);
+    const int H = e->cfg.hidden;
+    TSIM_REQUIRE(H % 64 == 0 && H <= CLS_MAX_H, "encoder_set_cls_head: hidden=%d unsupported", H);
+    std::vector<float> wT((size_t)H * H);
+    for (int o = 0; o < H; ++o)
+        for (int k = 0; k < H; ++k) wT[(size_t)k * H + o] = pool_w_host[(size_t)o * H + k];
+    int rc;
+    if ((rc = upload_f32(e, wT.data(), wT.size(), &e->head_wpT))) return rc;
+    if ((rc = upload_f32(e, pool_b_host, H, &e->head_bp))) return rc;
+    if ((rc = upload_f32(e, cls_w_host, (size_t)num_labels * H, &e->head_wc))) return rc;
+    if ((rc = upload_f32(e, cls_b_host, num_labels, &e->head_bc))) return rc;
+    e->n_labels = num_labels;
+    return TSIM_OK;
+}
+
 extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, const int32_t *tok_pos,
                                     const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B,
                                     int32_t max_len, float *pooled_f32, void *unit_bf16, int ld_unit, float *unit_rho_max,
                                     void *last_hidden_bf16, void *stream) {
+    return tsim_encoder_forward_ex(e, tok_ids, nullptr, tok_pos, tok_col, cu_seqlens, T, B, max_len, pooled_f32, unit_bf16, ld_unit,
+                                   unit_rho_max, last_hidden_bf16, nullptr, stream);
+}
+
+extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos,
+                                       const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B,
+                                       int32_t max_len, float *pooled_f32, void *unit_bf16, int ld_unit, float *unit_rho_max,
+                                       void *last_hidden_bf16, float *logits_f32, void *stream) {
     TSIM_REQUIRE(e && cu_seqlens && (T == 0 || (tok_ids && tok_pos)), "encoder_forward: null pointer");   // T = 0: only empty sequences
+    TSIM_REQUIRE(!tok_type || e->n_types > 0, "encoder_forward: tok_type given but no token-type table was set "
+                 "(tsim_encoder_set_token_types)");
+    TSIM_REQUIRE(!logits_f32 || e->n_labels > 0, "encoder_forward: logits requested but no classification head was set "
+                 "(tsim_encoder_set_cls_head)");
     TSIM_REQUIRE(T >= 0 && B >= 0 && T <= e->cfg.max_tokens && B <= e->cfg.max_seqs,
                  "encoder_forward: T=%d B=%d exceed capacity (%d tokens, %d sequences)", T, B, e->cfg.max_tokens, e->cfg.max_seqs);
     // position rows: BERT uses 0 .. len-1, MPNet pad_id+1 .. pad_id+len (modeling_mpnet create_position_ids_from_input_ids)
@@ -1821,8 +1946,12 @@ extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, con
         // column of a token inside its sequence: tok_col when given (MPNet), else tok_pos (BERT: position == column)
         const int32_t *colp = tok_col ? tok_col : tok_pos;
         const int col_limit = tok_col || c.arch == TSIM_ARCH_BERT ? max_len : c.max_pos;   // MPNet without tok_col: pos is not a column
-#define EMBED(V) hipLaunchKernelGGL(embed_ln_kernel<V>, dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags)
-        if (H == 64) EMBED(1); else if (H == 384) EMBED(6); else EMBED(12);
+#define EMBED(V) hipLaunchKernelGGL(embed_ln_kernel<V>, dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, nullptr, 0)
+#define EMBED_T(V) hipLaunchKernelGGL((embed_ln_kernel<V, true>), dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, tok_type, e->n_types)
+        if (tok_type) {
+            if (H == 64) EMBED_T(1); else if (H == 384) EMBED_T(6); else EMBED_T(12);
+        } else if (H == 64) EMBED(1); else if (H == 384) EMBED(6); else EMBED(12);
+#undef EMBED_T
 #undef EMBED
         TSIM_HIP_CHECK(hipGetLastError());
         const float scale = 1.0f / sqrtf((float)dh);
@@ -1883,6 +2012,11 @@ extern "C" int tsim_encoder_forward(tsim_encoder *e, const int32_t *tok_ids, con
             return fail(TSIM_EINVAL, "encoder: pooled / unit outputs must be 16-byte aligned");
         if (H <= 512) POOL(1); else POOL(2);
 #undef POOL
+        TSIM_HIP_CHECK(hipGetLastError());
+    }
+    if (logits_f32) {   // CLS rows straight from the final hidden state (x0); sequences without tokens read zeros
+        hipLaunchKernelGGL(cls_head_kernel, dim3((unsigned)((B + CLS_ROWS - 1) / CLS_ROWS)), dim3((unsigned)H), 0, st, e->x0, cu_seqlens,
+                           B, H, e->head_wpT, e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32);
         TSIM_HIP_CHECK(hipGetLastError());
     }
     return TSIM_OK;

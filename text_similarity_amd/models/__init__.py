@@ -1,0 +1,3 @@
+from .cross_encoder import CrossEncoder
+
+__all__ = ["CrossEncoder"]

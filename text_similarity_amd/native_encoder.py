@@ -97,7 +97,27 @@ class NativeEncoder:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().tsim_encoder_create(C.byref(cc), C.byref(ew), C.byref(handle)), "encoder_create")
         self._h = handle
+        self.n_types = 0
+        self.num_labels = 0
+        if cfg.arch == "bert":   # the whole token-type table: sentence pairs use row 1 (untyped forwards keep adding row 0)
+            tt = w["embeddings.token_type_embeddings.weight"]
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().tsim_encoder_set_token_types(handle, _ptr(tt), tt.shape[0]), "encoder_set_token_types")
+            self.n_types = int(tt.shape[0])
         self._weights_host = w  # float32 source weights: what save_pretrained writes (the handle holds bf16 / fp8 copies)
+
+    def set_cls_head(self, pool_w, pool_b, cls_w, cls_b) -> None:
+        """HF BertForSequenceClassification head: ``bert.pooler.dense`` (pool_w [H,H], pool_b [H]) and ``classifier``
+        (cls_w [num_labels,H], cls_b [num_labels]), float32, 1 <= num_labels <= 32.  BERT only."""
+        pw, pb, cw, cb = (_f32(a) for a in (pool_w, pool_b, cls_w, cls_b))
+        H = self.cfg.hidden
+        n = cw.shape[0] if cw.ndim == 2 else 0
+        if pw.shape != (H, H) or pb.shape != (H,) or cw.shape != (n, H) or cb.shape != (n,):
+            raise ValueError(f"head shapes {pw.shape} {pb.shape} {cw.shape} {cb.shape} do not fit hidden={H}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().tsim_encoder_set_cls_head(self._h, _ptr(pw), _ptr(pb), _ptr(cw), _ptr(cb), n),
+                       "encoder_set_cls_head")
+        self.num_labels = n
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -128,7 +148,7 @@ class NativeEncoder:
 
     # ------------------------------------------------------------------ input validation
     ERR_BITS = {1: "a token id outside [0, vocab_size)", 2: "a position id outside the position table",
-                4: "a sequence longer than the max_len passed to forward_packed"}
+                4: "a sequence longer than the max_len passed to forward_packed", 8: "a token type id outside the type table"}
 
     @staticmethod
     def check_lengths(cfg: EncoderConfig, max_len: int) -> None:
@@ -140,7 +160,7 @@ class NativeEncoder:
                              f"{cfg.arch} table has {cfg.max_pos} (max {cfg.max_pos - need + int(max_len)} tokens)")
 
     def check(self) -> None:
-        """Raise if any forward since the last check saw an out-of-range token id / position id or a sequence longer than
+        """Raise if any forward since the last check saw an out-of-range token id / type id / position id or a sequence longer than
         its promised max_len (the kernels clamp and go on; HF would have raised IndexError).  Synchronises the stream."""
         flags = C.c_int32(0)
         with torch.cuda.device(self.device):
@@ -184,10 +204,13 @@ class NativeEncoder:
 
     def forward_packed(self, flat_ids: torch.Tensor, cu: torch.Tensor, pos: Optional[torch.Tensor] = None,
                        cols: Optional[torch.Tensor] = None, max_len: Optional[int] = None, pooled: bool = True,
-                       unit: bool = False, hidden: bool = False, rho: Optional[torch.Tensor] = None):
+                       unit: bool = False, hidden: bool = False, rho: Optional[torch.Tensor] = None,
+                       types: Optional[torch.Tensor] = None, logits: bool = False):
         """flat_ids int32 [T], cu int32 [B+1] on the GPU.  Returns dict with 'pooled' f32 [B,H],
-        'unit' float16 [B,pad_dim(H)] (L2-normalised rows for the search kernel), 'hidden' bf16 [T,H] as requested.
-        ``rho``: a device float32 word raised to the largest rounding residual of the unit rows (ops.l2norm_rows)."""
+        'unit' float16 [B,pad_dim(H)] (L2-normalised rows for the search kernel), 'hidden' bf16 [T,H], 'logits' f32
+        [B, num_labels] (the head of ``set_cls_head`` on each sequence's first token) as requested.
+        ``rho``: a device float32 word raised to the largest rounding residual of the unit rows (ops.l2norm_rows).
+        ``types``: int32 [T] token-type ids (BERT; None = all 0)."""
         ops._need_gpu(flat_ids, cu)
         flat_ids = flat_ids.to(torch.int32).contiguous()
         cu = cu.to(torch.int32).contiguous()
@@ -197,6 +220,15 @@ class NativeEncoder:
             cols = cols2 if cols is None else cols
         pos = pos.to(torch.int32).contiguous()
         cols = None if cols is None else cols.to(torch.int32).contiguous()
+        if types is not None:
+            ops._need_gpu(types)
+            if self.n_types == 0:
+                raise ValueError(f"token type ids need a token-type table; {self.cfg.arch} has none")
+            types = types.to(torch.int32).contiguous()
+            if types.numel() != T:
+                raise ValueError(f"types has {types.numel()} entries for {T} tokens")
+        if logits and self.num_labels == 0:
+            raise ValueError("logits need a classification head: call set_cls_head first")
         if max_len is None:   # longest sequence in the batch: sizes the attention grid (one host sync; pass it to avoid)
             max_len = int((cu[1:] - cu[:-1]).max().item()) if B else 0
         self.check_lengths(self.cfg, max_len)
@@ -206,13 +238,16 @@ class NativeEncoder:
         p = torch.empty((B, H), dtype=torch.float32, device=dev) if pooled else None
         u = torch.empty((B, ops.pad_dim(H)), dtype=ops.UNIT_DTYPE, device=dev) if unit else None
         hd = torch.empty((T, H), dtype=torch.bfloat16, device=dev) if hidden else None
+        lg = torch.empty((B, self.num_labels), dtype=torch.float32, device=dev) if logits else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tsim_encoder_forward(
-                self._h, flat_ids.data_ptr(), pos.data_ptr(), cols.data_ptr() if cols is not None else None,
+            _lib.check(_lib.lib().tsim_encoder_forward_ex(
+                self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
+                cols.data_ptr() if cols is not None else None,
                 cu.data_ptr(), T, B, int(max_len), p.data_ptr() if p is not None else None,
                 u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
                 rho.data_ptr() if (rho is not None and u is not None) else None,
-                hd.data_ptr() if hd is not None else None, torch.cuda.current_stream(dev).cuda_stream),
+                hd.data_ptr() if hd is not None else None, lg.data_ptr() if lg is not None else None,
+                torch.cuda.current_stream(dev).cuda_stream),
                 "encoder_forward")
         if pooled:
             out["pooled"] = p
@@ -220,6 +255,8 @@ class NativeEncoder:
             out["unit"] = u
         if hidden:
             out["hidden"] = hd
+        if logits:
+            out["logits"] = lg
         return out
 
     # ------------------------------------------------------------------ padded (HF-style) call
@@ -234,15 +271,26 @@ class NativeEncoder:
         cols = nz[:, 1].to(torch.int32)
         return flat, cu, cols, nz
 
-    def __call__(self, input_ids=None, attention_mask=None, **kwargs):
+    def __call__(self, input_ids=None, attention_mask=None, token_type_ids=None, **kwargs):
         """HF AutoModel contract used by the wrappers: returns (last_hidden_state [B,S,H] float32,).
         Positions whose mask is 0 come back as zeros (the reference never reads them: the pooler multiplies
-        by the mask, modules.py:165)."""
+        by the mask, modules.py:165).  ``token_type_ids`` [B,S] (BERT) selects the token-type row of each token; None or
+        all zeros is the untyped forward."""
         ops._need_gpu(input_ids)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         B, S = input_ids.shape
         flat, cu, cols, nz = self.pack(input_ids, attention_mask)
+        types = None
+        if token_type_ids is not None:
+            if tuple(token_type_ids.shape) != (B, S):
+                raise ValueError(f"token_type_ids shape {tuple(token_type_ids.shape)} != input_ids shape {(B, S)}")
+            ops._need_gpu(token_type_ids)
+            types = token_type_ids[attention_mask.bool()].to(torch.int32)
+            if self.cfg.arch != "bert" and bool((types != 0).any()):
+                raise ValueError(f"{self.cfg.arch} has no token-type table: token_type_ids must be None or all zeros")
+            if self.n_types == 0:
+                types = None
         if self.cfg.arch == "mpnet":
             # position ids come from input_ids over the WHOLE padded row (masked non-pad tokens count too)
             ne = (input_ids != self.cfg.pad_id).to(torch.int32)
@@ -259,6 +307,6 @@ class NativeEncoder:
                 raise ValueError(f"batch slice has {t1 - t0} tokens > encoder capacity {self.max_tokens}")
             if t1 > t0:
                 r = self.forward_packed(flat[t0:t1], (cu[s:e + 1] - cu[s]), pos[t0:t1], cols[t0:t1], S,
-                                        pooled=False, hidden=True)
+                                        pooled=False, hidden=True, types=None if types is None else types[t0:t1])
                 out[nz[t0:t1, 0], nz[t0:t1, 1]] = r["hidden"].float()
         return (out,)

@@ -165,6 +165,20 @@ def synthetic_weights(preset: str, cfg: EncoderConfig | None = None, bf16_exact:
     return out
 
 
+def synthetic_head_weights(preset: str, num_labels: int, cfg: EncoderConfig | None = None) -> Dict[str, np.ndarray]:
+    """Deterministic float32 weights of a BertForSequenceClassification head for a preset: ``pooler.dense`` [H, H] and
+    ``classifier`` [num_labels, H] (HF names without the ``bert.`` prefix), drawn like the encoder's linear layers
+    (matrices U(-a, a), a = 2 * 0.02 * sqrt(3); biases std 0.02) from the same counter-based streams, bf16-exact."""
+    cfg = cfg or PRESETS[preset]
+    H, a = cfg.hidden, 0.02 * np.sqrt(3.0)
+    out = {}
+    for name, shape, scale in (("pooler.dense.weight", (H, H), 2 * a), ("pooler.dense.bias", (H,), a),
+                               ("classifier.weight", (num_labels, H), 2 * a), ("classifier.bias", (num_labels,), a)):
+        u = uniform01(f"{preset}/{name}", int(np.prod(shape))) * np.float32(2.0) - np.float32(1.0)
+        out[name] = bf16_round((u * np.float32(scale)).reshape(shape).astype(np.float32))
+    return out
+
+
 # --------------------------------------------------------------------------- synthetic text
 def synthetic_vocab(size: int = 30522) -> Dict[str, int]:
     """WordPiece-style vocab: BERT special tokens at their usual ids, then ``w00000``-style
