@@ -128,6 +128,17 @@ int tsim_cos_sim(const float *a, int64_t na, const float *b, int64_t nb, int d, 
 int tsim_mean_pool(const void *hidden, int hidden_dtype, const int32_t *mask, int64_t B, int S, int H,
                    float *out, void *stream);
 
+/* The pooling strategies of /root/reference/src/modules/modules.py:154-195 on the padded layout (mode: TSIM_POOL_*, see
+ * tsim_encoder_forward_head).  Mask entries weight the sums (MEAN, MEAN_SQRT_LEN); for CLS and MAX a token is in when its
+ * mask entry is non-zero, and CLS takes the first such token.  mode MEAN == tsim_mean_pool bit for bit. */
+int tsim_pool(const void *hidden, int hidden_dtype, const int32_t *mask, int64_t B, int S, int H, int mode,
+              float *out, void *stream);
+/* Dense + Normalize of sentence-transformers on float32 rows x [B, d_in]: out [B, d_out] = act(w x + b), then
+ * x / max(|x|, 1e-12) when normalize (tsim_encoder_forward_head gives the arithmetic).  w == NULL: no projection
+ * (d_out == d_in; act and Normalize only).  b may be NULL.  x, w and out 16-byte aligned. */
+int tsim_dense_rows(const float *x, int64_t B, int d_in, const float *w, const float *b, int d_out, int act,
+                    int normalize, float *out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * A3  context_embedder(**features)[0]  — the HF AutoModel forward the reference calls at
  *     /root/reference/src/models/sentence_encoder.py:33,107-108,118 (layer arithmetic:
@@ -217,6 +228,48 @@ int tsim_encoder_forward_ex(tsim_encoder *enc, const int32_t *tok_ids, const int
                             const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B, int32_t max_len,
                             float *pooled_f32, void *unit_f16, int ld_unit, float *unit_rho_max,
                             void *last_hidden_bf16, float *logits_f32, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sentence-embedding heads: the pooling strategies of /root/reference/src/modules/modules.py:154-195
+ * (AvgPoolingStrategy, CLSPoolingStrategy, BertPoolingStrategy = tanh(Linear(CLS row))) and the sentence-transformers
+ * module chain a checkpoint directory declares in modules.json (Pooling -> optional Dense -> optional Normalize), which the
+ * reference reaches through its --pooling switch (src/training/train_sts.py:41-44) and HF checkpoints.
+ * Pooling modes (rows of one sequence, float32 sums over the tokens in ascending order):
+ *   MEAN           sum / max(len, 1e-9)            (A4; the default forward)
+ *   CLS            the first token's row            (the reference's `embeddings[:0:]` is an empty slice; its evident
+ *                                                    meaning, `embeddings[:, 0]`, is what runs)
+ *   MAX            elementwise max over the tokens
+ *   MEAN_SQRT_LEN  sum / sqrt(max(len, 1e-9))
+ * A zero-length sequence pools to a zero row in every mode (sentence-transformers' max would give -1e9 there; tokenised
+ * text always carries special tokens, so the case does not come from text).
+ * Dense:     out[b] = act(W x[b] + bias), W [d_out, d_in] in nn.Linear layout, float32; every output element is one fmaf
+ *            chain over the d_in products in an order fixed by d_in alone, so rows are batch-composition invariant bit
+ *            for bit.  8 <= d_in, d_out <= 1024, both multiples of 8.
+ * Normalize: sentence-transformers' F.normalize(x, dim=1) = x / max(|x|_2, 1e-12), evaluated as tsim_l2norm_rows does
+ *            (float64 sum of squares in its canonical order, float64 scale) and rounded once to float32. */
+#define TSIM_POOL_MEAN 0
+#define TSIM_POOL_CLS 1
+#define TSIM_POOL_MAX 2
+#define TSIM_POOL_MEAN_SQRT_LEN 3
+#define TSIM_ACT_IDENTITY 0
+#define TSIM_ACT_TANH 1
+typedef struct tsim_sentence_head {
+    int32_t pool_mode;               /* TSIM_POOL_* */
+    int32_t d_out;                   /* 0 = no Dense */
+    const float *dense_w, *dense_b;  /* DEVICE, caller-owned: [d_out, hidden], [d_out] or NULL (no bias) */
+    int32_t dense_act;               /* TSIM_ACT_* */
+    int32_t normalize;               /* 0 / 1 */
+} tsim_sentence_head;
+
+/* tsim_encoder_forward_ex without logits, plus a head.  emb_f32 [B, d_out ? d_out : hidden] = the final rows (may be NULL);
+ * unit_f16 [B, ld_unit] = exactly tsim_l2norm_rows(final rows, eps 1e-8) with unit_rho_max raised as it does (final width
+ * <= 768).  The head is fused into the kernel that writes the final rows: the pooling kernel without a Dense, the Dense
+ * kernel otherwise; the pre-Dense rows live in encoder scratch (no allocation).  head == NULL: bit-identical to
+ * tsim_encoder_forward_ex with emb_f32 as pooled_f32.  Bad head: TSIM_EINVAL. */
+int tsim_encoder_forward_head(tsim_encoder *enc, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos,
+                              const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B, int32_t max_len,
+                              const tsim_sentence_head *head, float *emb_f32, void *unit_f16, int ld_unit,
+                              float *unit_rho_max, void *last_hidden_bf16, void *stream);
 
 /* Kernels cannot raise HF's IndexError: a token id outside [0, vocab), a token type outside [0, n_types), a position row outside [0, max_pos) or a token whose
  * column is >= the max_len passed to tsim_encoder_forward is clamped / computed anyway and leaves a bit in a per-encoder

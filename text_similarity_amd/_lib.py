@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("TSIM_LIB") or os.path.join(_HERE, "libtsim.so")   # T
 TSIM_F32, TSIM_BF16 = 0, 1
 ARCH_BERT, ARCH_MPNET = 0, 1
 W_BF16, W_MXFP8 = 0, 1
+POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
+ACT_IDENTITY, ACT_TANH = 0, 1
 
 
 class TsimError(RuntimeError):
@@ -36,6 +38,11 @@ class LayerWeightsC(C.Structure):
 class EncoderWeightsC(C.Structure):
     _fields_ = [("word_emb", _FP), ("pos_emb", _FP), ("type_emb", _FP), ("emb_ln_g", _FP), ("emb_ln_b", _FP),
                 ("rel_bias", _FP), ("layers", C.POINTER(LayerWeightsC))]
+
+
+class SentenceHeadC(C.Structure):
+    _fields_ = [("pool_mode", C.c_int32), ("d_out", C.c_int32), ("dense_w", C.c_void_p), ("dense_b", C.c_void_p),
+                ("dense_act", C.c_int32), ("normalize", C.c_int32)]
 
 
 _lib = None
@@ -66,6 +73,9 @@ _SIGS = {
     "tsim_cos_sim": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "tsim_mean_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p]),
+    "tsim_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tsim_dense_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p]),
     "tsim_quantize_mxfp8": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsim_gemm_mxfp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                   C.c_int, C.c_void_p]),
@@ -81,6 +91,9 @@ _SIGS = {
     "tsim_encoder_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "tsim_encoder_forward_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_int32, C.POINTER(SentenceHeadC), C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 DECLARED_SYMBOLS = tuple(_SIGS)

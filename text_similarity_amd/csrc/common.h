@@ -105,6 +105,8 @@ __device__ __forceinline__ unit_t f64_to_f16(double v) {
     return (unit_t)f;
 }
 __device__ __forceinline__ unit_t canonical_unit_elem(float x, double inv) { return f64_to_f16((double)x * inv); }
+// the same scale rounded once to float32: sentence-transformers' Normalize (F.normalize, eps 1e-12) on a float32 row
+__device__ __forceinline__ float canonical_scale_f32(float x, double inv) { return (float)((double)x * inv); }
 
 // ---- the search's exactness guard (search.hip; restated in oracle/search_ref.guard_eps) ------------------------------------
 // A stored half row is u^ = u + delta, u = x / max(|x|, eps) the exact unit row, rho = |delta|_2 its rounding residual.

@@ -1108,8 +1108,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DH <= 32 ? 
 // tokens in ascending order in float32, and the squared norm is taken in the canonical element order of
 // tsim_l2norm_rows (element j on lane j % 64, ascending, then the xor butterfly) from a wave-private LDS copy of the
 // pooled row, so pooled and unit rows keep their bits.
+// MODE (TSIM_POOL_*, the head of tsim_encoder_forward_head): MEAN is the kernel above, unchanged; CLS takes the first token's
+// row, MAX the elementwise max over the tokens, MEAN_SQRT_LEN the MEAN sum divided by sqrt(len).  An empty sequence pools to
+// a zero row in every mode.  NORM: sentence-transformers' Normalize on the pooled row, x / max(|x|, 1e-12) with the
+// canonical order and float64 scale of tsim_l2norm_rows, rounded once to float32; the unit rows are then taken from the
+// normalised row (a second canonical pass), so they are tsim_l2norm_rows(final rows) bit for bit.
 // =====================================================================================================
-template <int NP>   // 16-byte pieces per lane = ceil(H / 512)
+template <int NP, int MODE = TSIM_POOL_MEAN, bool NORM = false>   // NP: 16-byte pieces per lane = ceil(H / 512)
 __global__ __launch_bounds__(256) void pool_packed_kernel(const bf16_t *__restrict__ x,
                                                           const int32_t *__restrict__ cu, int B, int H,
                                                           float *__restrict__ pooled, unit_t *__restrict__ unit,
@@ -1123,7 +1128,7 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const bf16_t *__restri
 #pragma unroll
     for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) s[p][e] = 0.f;
+        for (int e = 0; e < 8; ++e) s[p][e] = MODE == TSIM_POOL_MAX ? -INFINITY : 0.f;
     // the loop is latency-bound (one dependent-free load per token): four tokens' loads are issued together, the adds stay in
     // token order
     auto add_row = [&](int p, const uint4 &v) __attribute__((always_inline)) {
@@ -1134,38 +1139,102 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const bf16_t *__restri
             s[p][2 * q + 1] += __uint_as_float(wv[q] & 0xffff0000u);
         }
     };
+    if constexpr (MODE == TSIM_POOL_CLS) {
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int f0 = (lane + 64 * p) * 8;
-        if (f0 >= H) continue;
-        const bf16_t *xp = x + f0;
-        // eight tokens per round trip, the ragged end included: a token past the end re-reads the last row (no branch around a
-        // load: that would put a full wait behind it) and adds zeros — most sequences of the benchmark are one or two round trips
-        for (int t = t0; t < t1; t += 8) {
-            uint4 v[8];
+        for (int p = 0; p < NP; ++p) {
+            const int f0 = (lane + 64 * p) * 8;
+            if (f0 >= H || t1 <= t0) continue;
+            const uint4 v = *reinterpret_cast<const uint4 *>(x + (int64_t)t0 * H + f0);
+            const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const uint4 *>(xp + (int64_t)(t + u < t1 ? t + u : t1 - 1) * H);
+            for (int q = 0; q < 4; ++q) {
+                s[p][2 * q] = __uint_as_float(wv[q] << 16);
+                s[p][2 * q + 1] = __uint_as_float(wv[q] & 0xffff0000u);
+            }
+        }
+    } else if constexpr (MODE == TSIM_POOL_MAX) {
+        // same round trips as the sums; re-reading the last row past the ragged end leaves a max unchanged
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (t + u >= t1) v[u] = make_uint4(0u, 0u, 0u, 0u);
-                add_row(p, v[u]);
+        for (int p = 0; p < NP; ++p) {
+            const int f0 = (lane + 64 * p) * 8;
+            if (f0 >= H) continue;
+            const bf16_t *xp = x + f0;
+            for (int t = t0; t < t1; t += 8) {
+                uint4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const uint4 *>(xp + (int64_t)(t + u < t1 ? t + u : t1 - 1) * H);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const uint32_t wv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        s[p][2 * q] = fmaxf(s[p][2 * q], __uint_as_float(wv[q] << 16));
+                        s[p][2 * q + 1] = fmaxf(s[p][2 * q + 1], __uint_as_float(wv[q] & 0xffff0000u));
+                    }
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int f0 = (lane + 64 * p) * 8;
+            if (f0 >= H) continue;
+            const bf16_t *xp = x + f0;
+            // eight tokens per round trip, the ragged end included: a token past the end re-reads the last row (no branch around a
+            // load: that would put a full wait behind it) and adds zeros — most sequences of the benchmark are one or two round trips
+            for (int t = t0; t < t1; t += 8) {
+                uint4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const uint4 *>(xp + (int64_t)(t + u < t1 ? t + u : t1 - 1) * H);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (t + u >= t1) v[u] = make_uint4(0u, 0u, 0u, 0u);
+                    add_row(p, v[u]);
+                }
             }
         }
     }
-    const float den = fmaxf((float)(t1 - t0), 1e-9f);
+    const float den = MODE == TSIM_POOL_MEAN_SQRT_LEN ? sqrtf(fmaxf((float)(t1 - t0), 1e-9f)) : fmaxf((float)(t1 - t0), 1e-9f);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         const int f0 = (lane + 64 * p) * 8;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) s[p][e] = s[p][e] / den;
+        for (int e = 0; e < 8; ++e) {
+            if constexpr (MODE == TSIM_POOL_MEAN || MODE == TSIM_POOL_MEAN_SQRT_LEN) s[p][e] = s[p][e] / den;
+            else if constexpr (MODE == TSIM_POOL_MAX) s[p][e] = t1 > t0 ? s[p][e] : 0.f;
+        }
         if (f0 < H) {
             const float4 lo = make_float4(s[p][0], s[p][1], s[p][2], s[p][3]), hi = make_float4(s[p][4], s[p][5], s[p][6], s[p][7]);
-            if (pooled) {
+            if (!NORM && pooled) {
                 *reinterpret_cast<float4 *>(pooled + (int64_t)b * H + f0) = lo;
                 *reinterpret_cast<float4 *>(pooled + (int64_t)b * H + f0 + 4) = hi;
             }
             *reinterpret_cast<float4 *>(&rows[w][f0]) = lo;
             *reinterpret_cast<float4 *>(&rows[w][f0 + 4]) = hi;
+        }
+    }
+    if constexpr (NORM) {   // Normalize: the final row replaces the pooled one in registers, in LDS and in `pooled`
+        __builtin_amdgcn_wave_barrier();
+        double ss = 0.0;
+        for (int jx = lane; jx < H; jx += 64) {
+            const float v = rows[w][jx];
+            ss = fma((double)v, (double)v, ss);
+        }
+        const double inv = canonical_inv_norm(ss, 1e-12f);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int f0 = (lane + 64 * p) * 8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[p][e] = canonical_scale_f32(s[p][e], inv);
+            if (f0 < H) {
+                const float4 lo = make_float4(s[p][0], s[p][1], s[p][2], s[p][3]), hi = make_float4(s[p][4], s[p][5], s[p][6], s[p][7]);
+                if (pooled) {
+                    *reinterpret_cast<float4 *>(pooled + (int64_t)b * H + f0) = lo;
+                    *reinterpret_cast<float4 *>(pooled + (int64_t)b * H + f0 + 4) = hi;
+                }
+                *reinterpret_cast<float4 *>(&rows[w][f0]) = lo;
+                *reinterpret_cast<float4 *>(&rows[w][f0 + 4]) = hi;
+            }
         }
     }
     if (unit) {  // identical bits to tsim_l2norm_rows(pooled): same element order, same float64 scale
@@ -1268,6 +1337,154 @@ __global__ __launch_bounds__(CLS_MAX_H) void cls_head_kernel(const bf16_t *__res
 }
 
 // =====================================================================================================
+// Dense + Normalize of a sentence-transformers head (tsim_dense_rows, tsim_encoder_forward_head):
+//   y[b] = act(W x[b] + bias), then y / max(|y|, 1e-12) when `normalize`, then (optional) unit rows of y.
+// A workgroup owns DN_ROWS = 16 rows and all d_out columns; its DN_WAVES = 8 waves (two per SIMD, so one wave's loads hide
+// behind the other's MFMAs) split the 16-column tiles: wave v computes tiles v, v + 8, ... with
+// v_mfma_f32_16x16x4_f32 (A = 16 rows x 4 k of x, B = 4 k x 16 columns of W^T, one float per lane each).  That MFMA is bit for
+// bit a k-ordered fmaf chain from C, so every output element is ONE fmaf chain from +0 over its d_in products, in the order
+// k = k0 + 4g + j for k0 = 0, 16, ..; j = 0..3; g = 0..3 (lane group g holds k0 + 4g .. k0 + 4g + 3 of a 16-byte load) — fixed
+// by d_in alone, so rows are batch-composition invariant.  A half chunk (d_in % 16 == 8) adds fmaf(0, 0, acc) = acc.
+// x and W come straight from L2 (W is read once per workgroup: 0.6 MB at 384 x 384), the next chunk's loads are issued before
+// the current chunk's MFMAs.  The tiles go through LDS ([row][column], float32) so the row epilogue (bias, tanh, the canonical
+// Normalize and unit rows of tsim_l2norm_rows) runs one wave per row with element j on lane j % 64 — the order of
+// tsim_l2norm_rows, so unit rows equal tsim_l2norm_rows(out) bit for bit.  w == NULL: no projection (d_out == d_in).
+// =====================================================================================================
+constexpr int DN_ROWS = 16;
+constexpr int DN_MAX = 1024;
+constexpr int DN_WAVES = 8;
+
+// 16 bytes at p when ok, else zeros (a `ok ? *p : zero` of two lvalues selects an ADDRESS and puts the zero on the stack)
+__device__ __forceinline__ float4 load4_or_zero(const float *p, bool ok) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) v = *reinterpret_cast<const float4 *>(p);
+    return v;
+}
+
+template <int NT>   // 16-column tiles per wave: d_out <= 16 DN_WAVES NT
+__global__ __launch_bounds__(64 * DN_WAVES) void dense_rows_kernel(const float *__restrict__ x, int B, int d_in, const float *__restrict__ wt,
+                                                         const float *__restrict__ bias, int d_out, int act, int normalize,
+                                                         float *__restrict__ out, unit_t *__restrict__ unit, int ld_unit,
+                                                         float *__restrict__ rho_max) {
+    extern __shared__ __attribute__((aligned(16))) float ys[];   // [DN_ROWS][d_out]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * DN_ROWS;
+    if (wt) {
+        const int i = lane & 15, g = lane >> 4;
+        const int ntt = (d_out + 15) >> 4;
+        const float *xp = x + (int64_t)min(r0 + i, B - 1) * d_in + 4 * g;   // rows past B re-read the last row, never stored
+        const float *wp[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) wp[t] = wt + (int64_t)min((wv + DN_WAVES * t) * 16 + i, d_out - 1) * d_in + 4 * g;
+        f32x4 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float4 a = load4_or_zero(xp, 4 * g < d_in), bw[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) bw[t] = load4_or_zero(wp[t], wv + DN_WAVES * t < ntt && 4 * g < d_in);
+        for (int k0 = 0; k0 < d_in; k0 += 16) {
+            const int k1 = k0 + 16;
+            const bool kin = k1 + 4 * g < d_in;
+            const float4 an = load4_or_zero(xp + k1, kin);
+            float4 bn[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bn[t] = load4_or_zero(wp[t] + k1, wv + DN_WAVES * t < ntt && kin);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (wv + DN_WAVES * t < ntt) {   // wave-uniform
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bw[t].x, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bw[t].y, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bw[t].z, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bw[t].w, acc[t], 0, 0, 0);
+                }
+            }
+            a = an;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bw[t] = bn[t];
+        }
+        // C/D: column lane & 15 of the tile, rows 4g .. 4g + 3
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int col = (wv + DN_WAVES * t) * 16 + i;
+            if (col < d_out) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ys[(4 * g + r) * d_out + col] = acc[t][r];
+            }
+        }
+    } else {   // no projection: the rows themselves
+        for (int k = threadIdx.x; k < DN_ROWS * d_out; k += 64 * DN_WAVES) {
+            const int r = k / d_out;
+            ys[k] = r0 + r < B ? x[(int64_t)(r0 + r) * d_in + (k - r * d_out)] : 0.f;
+        }
+    }
+    __syncthreads();
+    for (int r = wv; r < DN_ROWS; r += DN_WAVES) {   // wave-uniform; every lane touches only its own elements j = lane + 64 m
+        const int b = r0 + r;
+        if (b >= B) break;
+        float *y = ys + r * d_out;
+        for (int j = lane; j < d_out; j += 64) {
+            float v = y[j];
+            if (bias) v += bias[j];
+            if (act == TSIM_ACT_TANH) v = tanhf(v);
+            y[j] = v;
+        }
+        if (normalize) {
+            double ss = 0.0;
+            for (int j = lane; j < d_out; j += 64) ss = fma((double)y[j], (double)y[j], ss);
+            const double inv = canonical_inv_norm(ss, 1e-12f);
+            for (int j = lane; j < d_out; j += 64) y[j] = canonical_scale_f32(y[j], inv);
+        }
+        if (out)
+            for (int j = lane; j < d_out; j += 64) out[(int64_t)b * d_out + j] = y[j];
+        if (unit) {   // tsim_l2norm_rows(y, eps 1e-8), element for element
+            double ss = 0.0;
+            for (int j = lane; j < d_out; j += 64) ss = fma((double)y[j], (double)y[j], ss);
+            const double inv = canonical_inv_norm(ss, 1e-8f);
+            double r2 = 0.0;
+            for (int j = lane; j < ld_unit; j += 64) {
+                unit_t hv = (unit_t)0;
+                if (j < d_out) {
+                    hv = canonical_unit_elem(y[j], inv);
+                    const double de = (double)(float)hv - (double)y[j] * inv;
+                    r2 = fma(de, de, r2);
+                }
+                unit[(int64_t)b * ld_unit + j] = hv;
+            }
+            if (rho_max) {
+                const float rho = rho_round_up(sqrt(wave_sum_f64(r2)));
+                if (lane == 0) rho_publish(rho_max, rho);
+            }
+        }
+    }
+}
+
+static int dense_rows_launch(const float *x, int B, int d_in, const float *w, const float *bias, int d_out, int act, int normalize,
+                             float *out, unit_t *unit, int ld_unit, float *rho_max, hipStream_t st) {
+    if (B <= 0) return TSIM_OK;
+    const dim3 grid((unsigned)((B + DN_ROWS - 1) / DN_ROWS));
+    const size_t lds = (size_t)DN_ROWS * d_out * sizeof(float);
+#define DENSE(NT) hipLaunchKernelGGL(dense_rows_kernel<NT>, grid, dim3(64 * DN_WAVES), lds, st, x, B, d_in, w, bias, d_out, act, normalize, out, unit, ld_unit, rho_max)
+    const int nt = ((d_out + 15) / 16 + DN_WAVES - 1) / DN_WAVES;   // tiles per wave
+    if (nt <= 1) DENSE(1); else if (nt <= 2) DENSE(2); else if (nt <= 3) DENSE(3); else if (nt <= 4) DENSE(4);
+    else if (nt <= 6) DENSE(6); else DENSE(8);
+#undef DENSE
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+// shared argument checks of tsim_dense_rows and the head of tsim_encoder_forward_head
+static int dense_check(int d_in, int d_out, int act, const float *w) {
+    TSIM_REQUIRE(d_in >= 8 && d_in <= DN_MAX && d_in % 8 == 0, "dense: d_in=%d outside [8, %d] or not a multiple of 8", d_in, DN_MAX);
+    TSIM_REQUIRE(d_out >= 8 && d_out <= DN_MAX && d_out % 8 == 0, "dense: d_out=%d outside [8, %d] or not a multiple of 8", d_out,
+                 DN_MAX);
+    TSIM_REQUIRE(w || d_out == d_in, "dense: without a weight matrix d_out (%d) must equal d_in (%d)", d_out, d_in);
+    TSIM_REQUIRE(act == TSIM_ACT_IDENTITY || act == TSIM_ACT_TANH, "dense: unknown activation %d (TSIM_ACT_IDENTITY, TSIM_ACT_TANH)",
+                 act);
+    TSIM_REQUIRE(((uintptr_t)w & 15) == 0, "dense: the weight matrix must be 16-byte aligned");
+    return TSIM_OK;
+}
+
+// =====================================================================================================
 // host side
 // =====================================================================================================
 static uint16_t host_f32_to_bf16(float f) {
@@ -1313,6 +1530,9 @@ struct tsim_encoder {
     // activations
     bf16_t *x0 = nullptr, *x1 = nullptr, *qkv = nullptr, *ctx = nullptr, *h1 = nullptr;
     float *ybuf = nullptr;   // fp32 pre-LayerNorm sums (wide models only)
+    // pre-Dense rows of a sentence head (tsim_encoder_forward_head) [max_seqs, H] float32: only when qkv, dead after the last
+    // layer and used for them otherwise, is too small (max_seqs > 1.5 Tp: batches of mostly empty sequences)
+    float *head_x = nullptr;
     uint8_t *aq = nullptr, *as = nullptr, *hq = nullptr, *hs = nullptr;   // MXFP8 images of a projection's input ([Tp,H] / [Tp,F])
     int *err_flags = nullptr;   // TSIM_ENC_ERR_* bits raised by kernels since the last tsim_encoder_error_flags
 };
@@ -1826,6 +2046,8 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
         if ((rc = dev_alloc(e, Tp * H * 4, (void **)&e->ybuf))) return bail(rc);
         if (hipMemset(e->ybuf, 0, Tp * H * 4) != hipSuccess) return bail(fail(TSIM_EHIP, "hipMemset failed"));
     }
+    if ((size_t)cfg->max_seqs * H * 4 > Tp * 3 * H * 2 && (rc = dev_alloc(e, (size_t)cfg->max_seqs * H * 4, (void **)&e->head_x)))
+        return bail(rc);
     if (mx) {
         struct { uint8_t **p; size_t n; } qb[] = {{&e->aq, Tp * H}, {&e->as, Tp * H / 32}, {&e->hq, Tp * F}, {&e->hs, Tp * F / 32}};
         for (auto &a : qb) {
@@ -2020,4 +2242,68 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
         TSIM_HIP_CHECK(hipGetLastError());
     }
     return TSIM_OK;
+}
+
+// Sentence-embedding head: CLS / max / mean / mean-sqrt-len pooling, Dense, Normalize
+// (/root/reference/src/modules/modules.py:154-195 and the sentence-transformers modules.json chain; include/tsim.h)
+extern "C" int tsim_encoder_forward_head(tsim_encoder *e, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos,
+                                         const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B, int32_t max_len,
+                                         const tsim_sentence_head *head, float *emb_f32, void *unit_f16, int ld_unit,
+                                         float *unit_rho_max, void *last_hidden_bf16, void *stream) {
+    if (!head)
+        return tsim_encoder_forward_ex(e, tok_ids, tok_type, tok_pos, tok_col, cu_seqlens, T, B, max_len, emb_f32, unit_f16, ld_unit,
+                                       unit_rho_max, last_hidden_bf16, nullptr, stream);
+    TSIM_REQUIRE(e, "encoder_forward_head: null encoder");
+    const int H = e->cfg.hidden, mode = head->pool_mode, d_out = head->d_out;
+    TSIM_REQUIRE(mode >= TSIM_POOL_MEAN && mode <= TSIM_POOL_MEAN_SQRT_LEN, "encoder_forward_head: unknown pool_mode %d", mode);
+    TSIM_REQUIRE(head->normalize == 0 || head->normalize == 1, "encoder_forward_head: normalize=%d is not 0 / 1", head->normalize);
+    TSIM_REQUIRE(d_out >= 0, "encoder_forward_head: d_out=%d < 0", d_out);
+    if (d_out) {
+        TSIM_REQUIRE(head->dense_w, "encoder_forward_head: d_out=%d without dense_w", d_out);
+        if (int rc = dense_check(H, d_out, head->dense_act, head->dense_w)) return rc;
+    } else {
+        TSIM_REQUIRE(!head->dense_w && !head->dense_b, "encoder_forward_head: dense weights given with d_out = 0");
+    }
+    const int width = d_out ? d_out : H;
+    TSIM_REQUIRE(!unit_f16 || width <= 768, "encoder_forward_head: unit rows need a final width <= 768 (got %d)", width);
+    TSIM_REQUIRE(!unit_f16 || (ld_unit >= width && ld_unit % 8 == 0), "encoder_forward_head: ld_unit=%d (final width %d)", ld_unit,
+                 width);
+    TSIM_REQUIRE(H % 8 == 0 && H <= 1024, "encoder_forward_head: pooling needs hidden %% 8 == 0 and <= 1024 (got %d)", H);
+    TSIM_REQUIRE((((uintptr_t)emb_f32 | (uintptr_t)unit_f16) & 15) == 0, "encoder_forward_head: outputs must be 16-byte aligned");
+    // the layers (validates the rest; writes neither pooled nor unit rows)
+    if (int rc = tsim_encoder_forward_ex(e, tok_ids, tok_type, tok_pos, tok_col, cu_seqlens, T, B, max_len, nullptr, nullptr, 0,
+                                         nullptr, last_hidden_bf16, nullptr, stream))
+        return rc;
+    if (B == 0 || (!emb_f32 && !unit_f16)) return TSIM_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // without a Dense the pooling kernel writes the final rows (Normalize and unit rows fused); with one it writes the pre-Dense
+    // rows into scratch: qkv (dead after the last layer, [Tp, 3H] bf16 = 1.5 Tp rows of H floats) or head_x
+    float *px = d_out ? (e->head_x ? e->head_x : reinterpret_cast<float *>(e->qkv)) : emb_f32;
+    unit_t *pu = d_out ? nullptr : static_cast<unit_t *>(unit_f16);
+    const bool norm = !d_out && head->normalize;
+    const unsigned g = (unsigned)((B + 3) / 4);
+#define POOL(NP, M, N) hipLaunchKernelGGL((pool_packed_kernel<NP, M, N>), dim3(g), dim3(256), 0, st, e->x0, cu_seqlens, B, H, px, pu, ld_unit, pu ? unit_rho_max : nullptr)
+#define POOL_NP(M, N) do { if (H <= 512) POOL(1, M, N); else POOL(2, M, N); } while (0)
+#define POOL_M(N) do { switch (mode) { case TSIM_POOL_MEAN: POOL_NP(TSIM_POOL_MEAN, N); break; case TSIM_POOL_CLS: POOL_NP(TSIM_POOL_CLS, N); break; \
+                                       case TSIM_POOL_MAX: POOL_NP(TSIM_POOL_MAX, N); break; default: POOL_NP(TSIM_POOL_MEAN_SQRT_LEN, N); } } while (0)
+    if (norm) POOL_M(true); else POOL_M(false);
+#undef POOL_M
+#undef POOL_NP
+#undef POOL
+    TSIM_HIP_CHECK(hipGetLastError());
+    if (d_out)
+        return dense_rows_launch(px, B, H, head->dense_w, head->dense_b, d_out, head->dense_act, head->normalize, emb_f32,
+                                 static_cast<unit_t *>(unit_f16), ld_unit, unit_f16 ? unit_rho_max : nullptr, st);
+    return TSIM_OK;
+}
+
+// sentence-transformers Dense / Normalize (and BertPoolingStrategy's tanh(Linear(.)), modules.py:184-195) on float32 rows
+extern "C" int tsim_dense_rows(const float *x, int64_t B, int d_in, const float *w, const float *b, int d_out, int act, int normalize,
+                               float *out, void *stream) {
+    TSIM_REQUIRE(x && out, "dense_rows: null pointer");
+    TSIM_REQUIRE(B >= 0 && B <= INT32_MAX - DN_ROWS, "dense_rows: bad row count %lld", (long long)B);
+    TSIM_REQUIRE(normalize == 0 || normalize == 1, "dense_rows: normalize=%d is not 0 / 1", normalize);
+    if (int rc = dense_check(d_in, d_out, act, w)) return rc;
+    TSIM_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "dense_rows: x and out must be 16-byte aligned");
+    return dense_rows_launch(x, (int)B, d_in, w, b, d_out, act, normalize, out, nullptr, 0, nullptr, reinterpret_cast<hipStream_t>(stream));
 }

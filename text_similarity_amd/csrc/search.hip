@@ -5,6 +5,7 @@
 //   /root/reference/src/pipeline/search_pipeline.py:73-78   expand_as + F.cosine_similarity + torch.topk
 //   /root/reference/src/utils/metrics.py:81-101             cos_sim
 //   /root/reference/src/modules/modules.py:158-171          AvgPoolingStrategy.forward
+//   /root/reference/src/modules/modules.py:174-181          CLSPoolingStrategy.forward (and max / mean-sqrt-len pooling)
 #include <math.h>
 #include <stdlib.h>
 
@@ -947,8 +948,11 @@ __global__ __launch_bounds__(256) void cos_sim_kernel(const float *__restrict__ 
 
 // =====================================================================================================
 // masked mean-pool on a padded [B,S,H] tensor (A4).  One thread per (b, h); HBM-bound.
+// MODE (TSIM_POOL_*, tsim_pool): MEAN is the A4 kernel unchanged; MEAN_SQRT_LEN divides the same sum by sqrt(max(sum of the
+// mask, 1e-9)); CLS takes the first token whose mask entry is non-zero (the packed layout's first token), MAX the elementwise
+// max over those tokens.  No token: a zero row, as the packed forward gives.
 // =====================================================================================================
-template <typename T>
+template <typename T, int MODE = TSIM_POOL_MEAN>
 __global__ __launch_bounds__(256) void mean_pool_kernel(const T *__restrict__ hidden,
                                                         const int32_t *__restrict__ mask, int S, int H,
                                                         float *__restrict__ out) {
@@ -957,13 +961,30 @@ __global__ __launch_bounds__(256) void mean_pool_kernel(const T *__restrict__ hi
     if (hh >= H) return;
     const T *hp = hidden + bidx * S * (int64_t)H + hh;
     const int32_t *mp = mask + bidx * S;
+    if constexpr (MODE == TSIM_POOL_CLS || MODE == TSIM_POOL_MAX) {
+        float v = MODE == TSIM_POOL_MAX ? -INFINITY : 0.f;
+        bool any = false;
+        for (int s = 0; s < S; ++s) {
+            if (mp[s] == 0) continue;
+            const float x = load_as_f32<T>(hp + (int64_t)s * H);
+            if (MODE == TSIM_POOL_CLS) {
+                v = x;
+                any = true;
+                break;
+            }
+            v = fmaxf(v, x);
+            any = true;
+        }
+        out[bidx * H + hh] = any ? v : 0.f;
+        return;
+    }
     float sum = 0.f, msum = 0.f;
     for (int s = 0; s < S; ++s) {
         const float m = (float)mp[s];
         sum = fmaf(load_as_f32<T>(hp + (int64_t)s * H), m, sum);
         msum += m;
     }
-    out[bidx * H + hh] = sum / fmaxf(msum, 1e-9f);
+    out[bidx * H + hh] = sum / (MODE == TSIM_POOL_MEAN_SQRT_LEN ? sqrtf(fmaxf(msum, 1e-9f)) : fmaxf(msum, 1e-9f));
 }
 
 // =====================================================================================================
@@ -1363,6 +1384,27 @@ extern "C" int tsim_mean_pool(const void *hidden, int hidden_dtype, const int32_
                            mask, S, H, out);
     else
         return fail(TSIM_EINVAL, "mean_pool: unknown dtype %d", hidden_dtype);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+// CLSPoolingStrategy / max / mean-sqrt-len pooling on the padded layout (/root/reference/src/modules/modules.py:154-181)
+extern "C" int tsim_pool(const void *hidden, int hidden_dtype, const int32_t *mask, int64_t B, int S, int H, int mode, float *out,
+                         void *stream) {
+    TSIM_REQUIRE(hidden && mask && out, "pool: null pointer");
+    TSIM_REQUIRE(B >= 0 && S > 0 && H > 0 && B < 65536, "pool: bad shape B=%lld S=%d H=%d", (long long)B, S, H);
+    TSIM_REQUIRE(mode >= TSIM_POOL_MEAN && mode <= TSIM_POOL_MEAN_SQRT_LEN, "pool: unknown mode %d", mode);
+    TSIM_REQUIRE(hidden_dtype == TSIM_F32 || hidden_dtype == TSIM_BF16, "pool: unknown dtype %d", hidden_dtype);
+    if (mode == TSIM_POOL_MEAN) return tsim_mean_pool(hidden, hidden_dtype, mask, B, S, H, out, stream);
+    if (B == 0) return TSIM_OK;
+    dim3 grid((unsigned)((H + 255) / 256), (unsigned)B);
+    hipStream_t st = as_stream(stream);
+#define PL(T, M) hipLaunchKernelGGL((mean_pool_kernel<T, M>), grid, dim3(256), 0, st, (const T *)hidden, mask, S, H, out)
+#define PL_T(T) do { if (mode == TSIM_POOL_CLS) PL(T, TSIM_POOL_CLS); else if (mode == TSIM_POOL_MAX) PL(T, TSIM_POOL_MAX); \
+                     else PL(T, TSIM_POOL_MEAN_SQRT_LEN); } while (0)
+    if (hidden_dtype == TSIM_F32) PL_T(float); else PL_T(bf16_t);
+#undef PL_T
+#undef PL
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }

@@ -9,6 +9,7 @@ What is reproduced is the *intended* behaviour: ``encode_text`` 
 from __future__ import annotations
 
 import os
+import warnings
 from typing import List, Union
 
 import numpy as np
@@ -16,9 +17,12 @@ import torch
 from torch import nn
 
 from ..dataset.dataset import EmbeddingsFeatures
-from ..modules.modules import AvgPoolingStrategy, PoolingStrategy
+from ..modules.modules import AvgPoolingStrategy, PoolingStrategy, SentenceEmbeddingHead, st_modules
 from ..native_encoder import NativeEncoder
 from .modeling import BaseEncoderModel, _native_from_dir
+from .st_format import read_sentence_transformers_dir, write_sentence_transformers_modules
+
+_RESOLVE = object()   # encode_packed(head=...): look the head up from the wrapper's pooler
 
 
 def _native_wordpiece(tokenizer):
@@ -102,10 +106,28 @@ class _EncodeMixin:
         pooler = getattr(self, "pooler", None) or AvgPoolingStrategy(self.params)
         return self.projection(pooler(hidden, features))
 
-    def encode_packed(self, flat_ids: torch.Tensor, cu: torch.Tensor, unit: bool = False, cu_host: np.ndarray = None):
-        """Device-resident pre-tokenised input (the benchmark path): pooled f32 [B,H] (+ unit float16 rows).
-        ``cu_host``: the same offsets on the host, when the caller has them (saves a device->host copy and its sync)."""
+    def _native_head(self, device):
+        """The SentenceHead of the wrapper's pooler for the native forward: None (the mean pool) for AvgPoolingStrategy or no
+        pooler; a pooler of another class without a native form keeps the mean pool and raises a UserWarning naming it."""
+        pooler = getattr(self, "pooler", None)
+        if pooler is None or isinstance(pooler, AvgPoolingStrategy):
+            return None
+        if callable(getattr(pooler, "native_head", None)):
+            return pooler.native_head(device)
+        warnings.warn(f"pooler {type(pooler).__name__} has no native form: the native forward returns mean-pooled embeddings "
+                      "(use AvgPoolingStrategy, CLSPoolingStrategy, BertPoolingStrategy or SentenceEmbeddingHead)", UserWarning,
+                      stacklevel=3)
+        return None
+
+    def encode_packed(self, flat_ids: torch.Tensor, cu: torch.Tensor, unit: bool = False, cu_host: np.ndarray = None,
+                      head=_RESOLVE):
+        """Device-resident pre-tokenised input (the benchmark path): the embeddings f32 [B, width] (+ their unit float16
+        rows), pooled by the wrapper's pooler when it has a native form (``head``: a NativeEncoder SentenceHead or None to
+        override it).  ``cu_host``: the same offsets on the host, when the caller has them (saves a device->host copy and its
+        sync)."""
         enc: NativeEncoder = self.context_embedder
+        if head is _RESOLVE:
+            head = self._native_head(cu.device)
         B = cu.numel() - 1
         outs, units = [], []
         cu_h = (cu.cpu().numpy() if cu_host is None else np.asarray(cu_host)).astype(np.int64)
@@ -117,12 +139,13 @@ class _EncodeMixin:
             if cu_h[e] - cu_h[s] > enc.max_tokens:
                 raise ValueError("a single sequence exceeds the encoder token capacity")
             r = enc.forward_packed(flat_ids[cu_h[s]:cu_h[e]], cu[s:e + 1] - cu[s], pooled=True, unit=unit,
-                                   max_len=int(np.diff(cu_h[s:e + 1]).max()))
+                                   max_len=int(np.diff(cu_h[s:e + 1]).max()), head=head)
             outs.append(r["pooled"])
             if unit:
                 units.append(r["unit"])
             s = e
-        pooled = torch.cat(outs) if outs else torch.empty((0, enc.cfg.hidden), device=cu.device)
+        width = head.width(enc.cfg.hidden) if head is not None else enc.cfg.hidden
+        pooled = torch.cat(outs) if outs else torch.empty((0, width), device=cu.device)
         return (pooled, torch.cat(units)) if unit else pooled
 
     def encode_text(self, documents: List[str], output_np: bool = False) -> Union[torch.Tensor, np.ndarray]:
@@ -136,8 +159,10 @@ class _EncodeMixin:
         enc: NativeEncoder = self.context_embedder
         dev = enc.device
         n = len(documents)
+        head = self._native_head(dev)
         if n == 0:
-            out = torch.empty((0, enc.cfg.hidden), dtype=torch.float32, device=dev)
+            out = torch.empty((0, head.width(enc.cfg.hidden) if head is not None else enc.cfg.hidden), dtype=torch.float32,
+                              device=dev)
             return out.cpu().numpy() if output_np else out
         t_start = time.perf_counter()
         order = np.argsort([len(s) for s in documents], kind="stable")
@@ -163,7 +188,7 @@ class _EncodeMixin:
                 np.cumsum(lens, out=cu[1:])
                 flat_d = torch.from_numpy(flat).to(dev, non_blocking=True)
                 cu_d = torch.from_numpy(cu.astype(np.int32)).to(dev, non_blocking=True)
-                parts.append(self.projection(self.encode_packed(flat_d, cu_d, cu_host=cu)))
+                parts.append(self.projection(self.encode_packed(flat_d, cu_d, cu_host=cu, head=head)))
         pooled = torch.cat(parts) if len(parts) > 1 else parts[0]
         out = torch.empty_like(pooled)
         out[torch.from_numpy(order).to(dev)] = pooled      # un-sort (sentence_encoder.py:168)
@@ -172,7 +197,11 @@ class _EncodeMixin:
         return out.cpu().numpy() if output_np else out
 
     def get_sentence_embedding_dimension(self):
-        return self.context_embedder.config.hidden_size
+        hidden = self.context_embedder.config.hidden_size
+        pooler = getattr(self, "pooler", None)
+        if pooler is not None and callable(getattr(pooler, "output_width", None)):
+            return pooler.output_width(hidden)
+        return hidden
 
 
 class OnnxSentenceTransformerWrapper(_EncodeMixin, BaseEncoderModel):
@@ -225,6 +254,26 @@ class SentenceTransformerWrapper(_EncodeMixin, BaseEncoderModel):
         assert params is not None, "Parameters not found, need to pass model parameters for the model to work"
         return cls(pooler=pooler, merge_strategy=merge_strategy, loss=loss, params=params,
                    context_embedder=_native_from_dir(path, params), parallel_mode=parallel_mode)
+
+    @classmethod
+    def from_sentence_transformers(cls, path, params=None, merge_strategy=None, loss=None, parallel_mode=True):
+        """A local sentence-transformers directory: modules.json naming the Transformer (at "" or "0_Transformer", read by
+        NativeEncoder.from_pretrained), its Pooling, at most one Dense and an optional trailing Normalize, which become a
+        :class:`SentenceEmbeddingHead` pooler run by the native forward.  Anything else is refused with a ValueError that
+        names the file and field (models/st_format.py).  The truncation length stays ``params.sequence_max_len``."""
+        assert params is not None, "Parameters not found, need to pass model parameters for the model to work"
+        spec = read_sentence_transformers_dir(path)
+        enc = _native_from_dir(os.path.join(path, spec.transformer_path) if spec.transformer_path else path, params)
+        return cls(pooler=SentenceEmbeddingHead.from_spec(spec, params), merge_strategy=merge_strategy, loss=loss,
+                   params=params, context_embedder=enc, parallel_mode=parallel_mode)
+
+    def save_pretrained(self, path):
+        """BaseEncoderModel.save_pretrained, plus, for a pooler other than the default mean pool, the sentence-transformers
+        module files (modules.json, 1_Pooling/, 2_Dense/, N_Normalize/) that from_sentence_transformers reads back."""
+        super().save_pretrained(path)
+        if callable(getattr(self.pooler, "native_head", None)):
+            pooling, dense, normalize = st_modules(self.pooler)
+            write_sentence_transformers_modules(path, self.context_embedder.config.hidden_size, pooling, dense, normalize)
 
     @classmethod
     def from_preset(cls, preset: str, params, **kw):

@@ -41,6 +41,39 @@ def layer_names(cfg: EncoderConfig, l: int) -> Dict[str, str]:
     return a
 
 
+class SentenceHead:
+    """What the native forward runs after the last layer instead of the mean pool (include/tsim.h tsim_sentence_head):
+    a pooling mode ('mean' | 'cls' | 'max' | 'mean_sqrt_len'), an optional Dense (``dense_w`` [d_out, hidden] and
+    ``dense_b`` [d_out] float32 tensors on the encoder's device, ``act`` 'identity' | 'tanh') and an optional Normalize."""
+
+    def __init__(self, mode="mean", dense_w: Optional[torch.Tensor] = None, dense_b: Optional[torch.Tensor] = None,
+                 act="identity", normalize: bool = False):
+        self.mode = ops.pool_mode_id(mode)
+        self.act = ops.activation_id(act)
+        self.normalize = bool(normalize)
+        if dense_w is None and dense_b is not None:
+            raise ValueError("a Dense bias needs a Dense weight")
+        for t in (dense_w, dense_b):
+            if t is not None:
+                ops._need_gpu(t)
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError("Dense weights must be contiguous float32 device tensors")
+        if dense_w is not None and (dense_w.dim() != 2 or (dense_b is not None and tuple(dense_b.shape) != (dense_w.shape[0],))):
+            raise ValueError(f"Dense shapes {tuple(dense_w.shape)} / {None if dense_b is None else tuple(dense_b.shape)}")
+        self.dense_w, self.dense_b = dense_w, dense_b
+
+    def width(self, hidden: int) -> int:
+        return int(self.dense_w.shape[0]) if self.dense_w is not None else int(hidden)
+
+    def c_struct(self, hidden: int) -> "_lib.SentenceHeadC":
+        if self.dense_w is not None and self.dense_w.shape[1] != hidden:
+            raise ValueError(f"Dense in_features {self.dense_w.shape[1]} != hidden {hidden}")
+        return _lib.SentenceHeadC(pool_mode=self.mode, d_out=self.width(hidden) if self.dense_w is not None else 0,
+                                  dense_w=self.dense_w.data_ptr() if self.dense_w is not None else None,
+                                  dense_b=self.dense_b.data_ptr() if self.dense_b is not None else None,
+                                  dense_act=self.act, normalize=int(self.normalize))
+
+
 class NativeEncoder:
     def __init__(self, cfg: EncoderConfig, weights: Dict[str, np.ndarray], max_tokens: int = 65536,
                  max_seqs: int = 8192, device: Optional[torch.device] = None, weight_dtype: str = "bf16"):
@@ -205,12 +238,14 @@ class NativeEncoder:
     def forward_packed(self, flat_ids: torch.Tensor, cu: torch.Tensor, pos: Optional[torch.Tensor] = None,
                        cols: Optional[torch.Tensor] = None, max_len: Optional[int] = None, pooled: bool = True,
                        unit: bool = False, hidden: bool = False, rho: Optional[torch.Tensor] = None,
-                       types: Optional[torch.Tensor] = None, logits: bool = False):
+                       types: Optional[torch.Tensor] = None, logits: bool = False, head: Optional[SentenceHead] = None):
         """flat_ids int32 [T], cu int32 [B+1] on the GPU.  Returns dict with 'pooled' f32 [B,H],
         'unit' float16 [B,pad_dim(H)] (L2-normalised rows for the search kernel), 'hidden' bf16 [T,H], 'logits' f32
         [B, num_labels] (the head of ``set_cls_head`` on each sequence's first token) as requested.
         ``rho``: a device float32 word raised to the largest rounding residual of the unit rows (ops.l2norm_rows).
-        ``types``: int32 [T] token-type ids (BERT; None = all 0)."""
+        ``types``: int32 [T] token-type ids (BERT; None = all 0).
+        ``head``: a :class:`SentenceHead` run in place of the mean pool: 'pooled' is then its final rows [B, head.width(H)] and
+        'unit' their unit rows (tsim_encoder_forward_head); not with ``logits``."""
         ops._need_gpu(flat_ids, cu)
         flat_ids = flat_ids.to(torch.int32).contiguous()
         cu = cu.to(torch.int32).contiguous()
@@ -232,23 +267,37 @@ class NativeEncoder:
         if max_len is None:   # longest sequence in the batch: sizes the attention grid (one host sync; pass it to avoid)
             max_len = int((cu[1:] - cu[:-1]).max().item()) if B else 0
         self.check_lengths(self.cfg, max_len)
+        if head is not None and logits:
+            raise ValueError("a sentence head and logits are separate forwards")
         H = self.cfg.hidden
+        W = head.width(H) if head is not None else H
         out = {}
         dev = flat_ids.device
-        p = torch.empty((B, H), dtype=torch.float32, device=dev) if pooled else None
-        u = torch.empty((B, ops.pad_dim(H)), dtype=ops.UNIT_DTYPE, device=dev) if unit else None
+        p = torch.empty((B, W), dtype=torch.float32, device=dev) if pooled else None
+        u = torch.empty((B, ops.pad_dim(W)), dtype=ops.UNIT_DTYPE, device=dev) if unit else None
         hd = torch.empty((T, H), dtype=torch.bfloat16, device=dev) if hidden else None
         lg = torch.empty((B, self.num_labels), dtype=torch.float32, device=dev) if logits else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tsim_encoder_forward_ex(
-                self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
-                cols.data_ptr() if cols is not None else None,
-                cu.data_ptr(), T, B, int(max_len), p.data_ptr() if p is not None else None,
-                u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
-                rho.data_ptr() if (rho is not None and u is not None) else None,
-                hd.data_ptr() if hd is not None else None, lg.data_ptr() if lg is not None else None,
-                torch.cuda.current_stream(dev).cuda_stream),
-                "encoder_forward")
+            if head is not None:
+                hc = head.c_struct(H)
+                if head.dense_w is not None and head.dense_w.device != dev:
+                    raise ValueError(f"Dense weights on {head.dense_w.device}, tokens on {dev}")
+                _lib.check(_lib.lib().tsim_encoder_forward_head(
+                    self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
+                    cols.data_ptr() if cols is not None else None, cu.data_ptr(), T, B, int(max_len), C.byref(hc),
+                    p.data_ptr() if p is not None else None, u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
+                    rho.data_ptr() if (rho is not None and u is not None) else None, hd.data_ptr() if hd is not None else None,
+                    torch.cuda.current_stream(dev).cuda_stream), "encoder_forward_head")
+            else:
+                _lib.check(_lib.lib().tsim_encoder_forward_ex(
+                    self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
+                    cols.data_ptr() if cols is not None else None,
+                    cu.data_ptr(), T, B, int(max_len), p.data_ptr() if p is not None else None,
+                    u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
+                    rho.data_ptr() if (rho is not None and u is not None) else None,
+                    hd.data_ptr() if hd is not None else None, lg.data_ptr() if lg is not None else None,
+                    torch.cuda.current_stream(dev).cuda_stream),
+                    "encoder_forward")
         if pooled:
             out["pooled"] = p
         if unit:

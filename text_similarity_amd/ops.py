@@ -225,6 +225,86 @@ def mean_pool(hidden: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     return out
 
 
+POOL_MODES = {"mean": _lib.POOL_MEAN, "cls": _lib.POOL_CLS, "max": _lib.POOL_MAX, "mean_sqrt_len": _lib.POOL_MEAN_SQRT_LEN}
+ACTIVATIONS = {"identity": _lib.ACT_IDENTITY, "tanh": _lib.ACT_TANH}
+
+
+def pool_mode_id(mode) -> int:
+    """'mean' | 'cls' | 'max' | 'mean_sqrt_len' (or the TSIM_POOL_* integer) -> TSIM_POOL_*."""
+    if isinstance(mode, str):
+        if mode not in POOL_MODES:
+            raise ValueError(f"unknown pooling mode {mode!r} (one of {sorted(POOL_MODES)})")
+        return POOL_MODES[mode]
+    if int(mode) not in POOL_MODES.values():
+        raise ValueError(f"unknown pooling mode {mode!r}")
+    return int(mode)
+
+
+def activation_id(act) -> int:
+    """'identity' | 'tanh' (or the TSIM_ACT_* integer) -> TSIM_ACT_*."""
+    if isinstance(act, str):
+        if act not in ACTIVATIONS:
+            raise ValueError(f"unknown activation {act!r} (one of {sorted(ACTIVATIONS)})")
+        return ACTIVATIONS[act]
+    if int(act) not in ACTIVATIONS.values():
+        raise ValueError(f"unknown activation {act!r}")
+    return int(act)
+
+
+def pool(hidden: torch.Tensor, mask: torch.Tensor, mode="mean") -> torch.Tensor:
+    """Pooling of a padded [B, S, H] float32/bf16 tensor with an attention mask [B, S] -> float32 [B, H]
+    (/root/reference/src/modules/modules.py:154-181; include/tsim.h tsim_pool).  ``mode`` 'mean' is :func:`mean_pool` bit for
+    bit; 'cls' takes the first token whose mask is set, 'max' the elementwise max over those tokens, 'mean_sqrt_len' the
+    masked sum over sqrt(sum of the mask).  A row without tokens pools to zeros."""
+    _need_gpu(hidden, mask)
+    m_id = pool_mode_id(mode)
+    if hidden.dim() != 3:
+        raise ValueError("pool expects hidden states [batch, seq_len, hidden]")
+    if hidden.dtype not in (torch.float32, torch.bfloat16):
+        hidden = hidden.float()
+    hidden = hidden.contiguous()
+    m = mask.to(torch.int32).contiguous()
+    B, S, H = hidden.shape
+    if tuple(m.shape) != (B, S):
+        raise ValueError(f"mask shape {tuple(m.shape)} != {(B, S)}")
+    out = torch.empty((B, H), dtype=torch.float32, device=hidden.device)
+    dt = _lib.TSIM_F32 if hidden.dtype == torch.float32 else _lib.TSIM_BF16
+    with torch.cuda.device(hidden.device):
+        _lib.check(_lib.lib().tsim_pool(hidden.data_ptr(), dt, m.data_ptr(), B, S, H, m_id, out.data_ptr(), _stream(hidden)),
+                   "pool")
+    return out
+
+
+def dense_rows(x: torch.Tensor, w: Optional[torch.Tensor], b: Optional[torch.Tensor] = None, act="identity",
+               normalize: bool = False) -> torch.Tensor:
+    """sentence-transformers Dense (+ Normalize) on float32 rows: act(x @ w.T + b), then x / max(|x|, 1e-12) when
+    ``normalize``.  x [B, d_in], w [d_out, d_in] (nn.Linear layout) or None (no projection), b [d_out] or None; d_in, d_out
+    multiples of 8 in [8, 1024].  Every output element is one float32 fma chain in an order fixed by d_in (include/tsim.h)."""
+    ts = [t for t in (x, w, b) if t is not None]
+    _need_gpu(*ts)
+    a_id = activation_id(act)
+    if x.dim() != 2:
+        raise ValueError("dense_rows expects a 2-D tensor")
+    x = x.float().contiguous()
+    B, d_in = x.shape
+    d_out = d_in
+    if w is not None:
+        w = w.detach().float().contiguous()
+        if w.dim() != 2 or w.shape[1] != d_in:
+            raise ValueError(f"dense_rows: weight shape {tuple(w.shape)} does not take rows of width {d_in}")
+        d_out = w.shape[0]
+    if b is not None:
+        b = b.detach().float().contiguous()
+        if tuple(b.shape) != (d_out,):
+            raise ValueError(f"dense_rows: bias shape {tuple(b.shape)} != ({d_out},)")
+    out = torch.empty((B, d_out), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().tsim_dense_rows(x.data_ptr(), B, d_in, w.data_ptr() if w is not None else None,
+                                              b.data_ptr() if b is not None else None, d_out, a_id, int(bool(normalize)),
+                                              out.data_ptr(), _stream(x)), "dense_rows")
+    return out
+
+
 def quantize_mxfp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """[rows, K] bf16 -> (e4m3 bytes uint8 [rows, K], E8M0 block scales uint8 [rows, K/32]) — the operand format of
     the fp8 encoder variant (``NativeEncoder(weight_dtype="mxfp8")``).  K % 32 == 0."""
