@@ -97,6 +97,43 @@ int tsim_cosine_topk(const void *eq_unit, int64_t Q, const void *ec_unit, int64_
                      int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact inner-product search (sentence-transformers models scored by dot product; hnswlib's space='ip').
+ *
+ * Operands.  The corpus rows c_r (float32 or bf16, x_dtype) are scaled by ONE power of two per corpus, S = the smallest 2^e
+ * >= max_r |c_r|, and stored as half(c_r / S) (each element rounded once; scaling by 2^e is exact), so every element and every
+ * MFMA score lies in [-1, 1].  S comes from a device "max-norm word" (float, caller-owned, zeroed once): tsim_max_norm_rows
+ * raises it to an upper bound of the rows' L2 norms (float64 in the canonical order of tsim_l2norm_rows, rounded up); a row
+ * with a non-finite element, or a norm beyond the float range, makes it +inf — never a fault — and the caller can read it.
+ * tsim_dot_scale(word) is the host form of the one rule every kernel uses: 1 for an all-zero corpus (word 0), +inf for a
+ * non-finite word, else the smallest power of two >= word.  Several tsim_max_norm_rows calls may accumulate into one word;
+ * rows made before the word grew must be made again (their S changed).
+ * tsim_dot_scaled_rows writes out[r, :d] = half(x[r, :] / S), out[r, d:ld_out] = 0, and raises rho_max (may be NULL) to the
+ * largest residual || out[r] - x[r] / S ||_2, rounded up, where a subnormal half element counts with the larger of its
+ * rounding error and its own magnitude: the bound holds whether or not the f16 MFMA flushes subnormal inputs.  A non-finite
+ * word gives zero rows (NaN where x is not finite) and rho 2. */
+int tsim_max_norm_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, float *maxnorm, void *stream);
+int tsim_dot_scaled_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm,
+                         void *out_f16, int ld_out, float *rho_max, void *stream);
+double tsim_dot_scale(float maxnorm_host);
+/* Top-k by inner product: out_scores[q, j] = float32(q . c) of the float32 rows, summed in float64 in the canonical lane order
+ * of the exact re-score (oracle/search_ref._lane_sum) and rounded once; order (score desc, index asc).  eq_unit: the queries'
+ * unit rows (tsim_l2norm_rows, eps 1e-8); ec_scaled: tsim_dot_scaled_rows of the float32 corpus ec_f32 under ec_maxnorm, with
+ * ec_rho_max its measured residual maximum.  eq_f32, ec_f32, ec_maxnorm and ec_rho_max are REQUIRED (NULL: TSIM_EINVAL; the
+ * a-priori residual bound does not cover flushed subnormals).  The rest as tsim_cosine_topk_ex: same workspace
+ * (tsim_cosine_topk_workspace_bytes), out_status, idx_offset, 1 <= k <= 64, -1 / -inf padding, stream.
+ * Guard.  The MFMA score m approximates q.c / (nq S), nq = max(|q|, 1e-8) — monotone in q.c for a fixed query, so the main
+ * pass selects by the right quantity — and |m - q.c / (nq S)| <= eps_q = guard_eps(rho_q, rho_c, ld) by the same
+ * Cauchy-Schwarz argument as for cosine (|c / S| <= 1), rho_q measured flush-safe from the query's two rows, rho_c =
+ * *ec_rho_max.  The guard converts between the domains with the query's float64 nq and S, slack on the safe side: the first
+ * pass stands when (cut + eps_q) nq S < the k-th exact score; otherwise every row with m > k-th exact / (nq S) - eps_q is
+ * collected (status 1), and brute force (status 2) takes over as for cosine.  A zero query scores 0 against every row: its
+ * result is the first k rows by index. */
+int tsim_dot_topk_ex(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_scaled,
+                     const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                     int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

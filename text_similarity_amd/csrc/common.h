@@ -140,6 +140,31 @@ __device__ __forceinline__ float guard_eps(float rho_q, float rho_c, int ld) {
     return (float)(e * (1.0 + 1e-6));
 }
 
+// ---- inner-product search (tsim_dot_topk_ex): corpus rows scaled by one power of two ------------------------------------------
+// The max-norm word of a set of rows is a float >= max_r |c_r| (float64 norm in the canonical order, rounded up); a row with a
+// non-finite element, or a norm beyond the float range, makes it +inf.  S = dot_scale(word) is the smallest power of two not
+// below it (1 for an all-zero set, +inf for a non-finite word); the stored rows are half(c_r / S), |c_r / S| <= 1.  Every
+// kernel that needs S derives it from the word with this one function, so rows and search always agree on it.
+__host__ __device__ inline double dot_scale(float maxnorm) {
+    if (!(maxnorm <= 3.4028234663852886e38f)) return INFINITY;   // inf or NaN
+    if (maxnorm <= 0.f) return 1.0;
+    int e = 0;
+    const double fr = frexp((double)maxnorm, &e);   // maxnorm = fr 2^e, fr in [0.5, 1)
+    return ldexp(1.0, fr == 0.5 ? e - 1 : e);
+}
+// the smallest float >= v (v >= 0 finite)
+__device__ __forceinline__ float f32_round_up(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return f;
+}
+// Residual of one scaled element v -> half h: |h - v| when the f16 MFMA keeps subnormal inputs, |v| when it flushes them to
+// zero; for a subnormal (or zero) h the larger of the two, so the bound holds either way.
+__device__ __forceinline__ double flush_safe_err(double h, double v) {
+    const double e = h - v;
+    return fabs(h) < 6.103515625e-05 ? fmax(fabs(e), fabs(v)) : e;   // 2^-14: smallest normal half
+}
+
 // GELU of two values without transcendentals, in packed fp32 (v_pk_fma_f32 / v_pk_mul_f32: two values per issue slot).
 //   gelu(x) = x * Phi(x),  Phi(x) ~ 1/2 + xc * S(xc^2),  xc = clamp(x, -4, 4),  S = degree-8 Chebyshev fit of
 //   (Phi(sqrt u) - 1/2) / sqrt u on u in [0, 16]  (fp32 Horner: relative error <= 2.5e-5 for x > 0, absolute error

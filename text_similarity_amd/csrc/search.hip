@@ -9,6 +9,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "k1_topk.h"
 
@@ -59,6 +61,60 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const T *__restrict__ 
     }
     if (rho_max) {
         const float rho = rho_round_up(sqrt(wave_sum_f64(r2)));
+        if (lane == 0) rho_publish(rho_max, rho);
+    }
+}
+
+// =====================================================================================================
+// Operands of the inner-product search (tsim_dot_topk_ex), one wave per row like l2norm_rows.
+//   max_norm_rows:   raises *maxnorm to an upper bound of the rows' L2 norms (common.h dot_scale); +inf for a row with a
+//                    non-finite element.  Read-then-atomic like rho_publish.
+//   dot_scaled_rows: out[r] = half(x[r] / S), S = dot_scale(*maxnorm), zero-padded to ld_out; rho_max raised to the row's
+//                    residual || out[r] - x[r] / S ||_2 with every subnormal element counted as kept AND as flushed
+//                    (flush_safe_err).  A non-finite word gives S = inf, zero rows (NaN where x is not finite) and rho = 2.
+// =====================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void max_norm_rows_kernel(const T *__restrict__ x, int64_t rows, int d, int64_t ld_in,
+                                                            float *__restrict__ maxnorm) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const T *xr = x + row * ld_in;
+    double ss = 0.0;
+    for (int j = lane; j < d; j += 64) {
+        const double v = (double)load_as_f32<T>(xr + j);
+        ss = fma(v, v, ss);
+    }
+    const double n = sqrt(wave_sum_f64(ss));
+    // (1 + 1e-12) covers the float64 rounding of the sum and the root; beyond the float range (or NaN) -> inf
+    const float word = n < 3.0e38 ? f32_round_up(n * (1.0 + 1e-12)) : INFINITY;
+    if (lane == 0) rho_publish(maxnorm, word);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dot_scaled_rows_kernel(const T *__restrict__ x, int64_t rows, int d, int64_t ld_in,
+                                                              const float *__restrict__ maxnorm, unit_t *__restrict__ out,
+                                                              int ld_out, float *__restrict__ rho_max) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double S = dot_scale(*maxnorm);
+    const double inv = 1.0 / S;   // a power of two: x * inv is exact (0 when S = inf)
+    const T *xr = x + row * ld_in;
+    unit_t *o = out + row * (int64_t)ld_out;
+    double r2 = 0.0;
+    for (int j = lane; j < ld_out; j += 64) {
+        unit_t hv = (unit_t)0;
+        if (j < d) {
+            const double v = (double)load_as_f32<T>(xr + j) * inv;
+            hv = f64_to_f16(v);
+            const double e = flush_safe_err((double)(float)hv, v);
+            r2 = fma(e, e, r2);
+        }
+        o[j] = hv;
+    }
+    if (rho_max) {
+        const float rho = S < INFINITY ? rho_round_up(sqrt(wave_sum_f64(r2))) : 2.f;
         if (lane == 0) rho_publish(rho_max, rho);
     }
 }
@@ -115,6 +171,14 @@ template <typename T, bool COS>
 __device__ __forceinline__ void exact_load_query(ExactQuery<T> &q, const T *row, int d, int lane) {
     if (d <= 64 * (XS_MAXI / 2)) exact_load_query_ni<T, COS, XS_MAXI / 2>(q, row, d, lane);   // wave-uniform
     else exact_load_query_ni<T, COS, XS_MAXI>(q, row, d, lane);
+}
+// the norm exact_load_query<T, true> sets, from the elements already held (the same fma chain: the +0 terms change nothing)
+template <typename T>
+__device__ __forceinline__ double exact_query_norm(const ExactQuery<T> &q) {
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < XS_MAXI; ++i) ss = fma(q.v[i], q.v[i], ss);
+    return fmax(sqrt(wave_sum_f64(ss)), XS_EPS);
 }
 
 // per-lane partial sums of the query against one row: dot (and |row|^2 for COS)
@@ -231,6 +295,13 @@ __device__ __forceinline__ float float_below(float f) {   // the next float towa
 enum { CTL_NFLAG = 0, CTL_NUNRES = 1, CTL_WORDS = 4 };
 // per-query status written to out_status (all results are exact; the status says which pass produced them)
 enum { ST_PASS1 = 0, ST_WIDENED = 1, ST_BRUTE = 2 };
+// score modes of the kernels that see exact scores:
+//   SM_UNIT: inner product of the unit rows as stored;  SM_COS: cosine of the float32 rows (tsim_cosine_topk_ex);
+//   SM_DOT:  inner product of the float32 rows (tsim_dot_topk_ex).  The corpus operand is half(c / S) (dot_scaled_rows), the
+//            query operand the unit row of q, so the MFMA score approximates q.c / (nq S), nq = max(|q|, 1e-8) (the scale
+//            the unit row was made with): monotone in q.c for a fixed query, and bounded by guard_eps exactly as for COS.
+//            Exact scores live in the other domain; dot_bound_up / guard_tau_dot convert with nqs = nq S.
+enum { SM_UNIT = 0, SM_COS = 1, SM_DOT = 2 };
 
 struct GuardArgs {
     // COS (float32 rows given): eps = guard_eps(rho_q, rho_c, ld) — a BOUND on |MFMA score - exact score| for the query against
@@ -249,9 +320,12 @@ struct GuardArgs {
     float *flag_eps;   // [Q] per slot: the query's eps (COS)
     int *unres_q;      // [Q] queries left to the brute-force pass, compact
     int *status;       // [Q] or null
+    const float *c_maxnorm;   // SM_DOT: the corpus rows' max-norm word (device), S = dot_scale(*c_maxnorm)
 };
 
-// rho of a query row: || stored half row - exact unit row ||_2 from the float32 row already held in `q` (all 64 lanes take part)
+// rho of a query row: || stored half row - exact unit row ||_2 from the float32 row already held in `q` (all 64 lanes take part).
+// FLUSH (SM_DOT): subnormal elements count with the larger of their kept and flushed errors (flush_safe_err).
+template <bool FLUSH = false>
 __device__ __forceinline__ float query_rho(const ExactQuery<float> &q, const unit_t *urow, int d, int lane) {
     double r2 = 0.0;
     const double inv = 1.0 / q.norm;
@@ -261,7 +335,8 @@ __device__ __forceinline__ float query_rho(const ExactQuery<float> &q, const uni
         row_elems_f64<unit_t, NI>(u, urow, d, lane);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const double e = u[i] - q.v[i] * inv;   // (0 - 0 beyond d)
+            double e = u[i] - q.v[i] * inv;   // (0 - 0 beyond d)
+            if constexpr (FLUSH) e = flush_safe_err(u[i], q.v[i] * inv);
             r2 = fma(e, e, r2);
         }
     };
@@ -277,6 +352,21 @@ __device__ __forceinline__ float guard_tau(float target, float eps) {
     float tau = float_below((float)((double)target - (double)eps));
     if ((double)tau + (double)eps >= (double)target) tau = float_below(tau);
     return tau;
+}
+// SM_DOT conversions between the MFMA domain (q.c / (nq S)) and the exact one (q.c), nqs = nq S (float64, > 0).  The float64
+// operations round to within 2^-52 of the true value each; the 1e-15 slack puts every result on the safe side.
+//   dot_bound_up:  an upper bound of the exact score of any row whose MFMA score is <= m, given |MFMA - exact / nqs| <= eps;
+//   guard_tau_dot: a collection threshold for rows whose exact score could reach sk: every such row has an MFMA score > tau.
+__device__ __forceinline__ double dot_bound_up(float m, float eps, double nqs) {
+    const double b = ((double)m + (double)eps) * nqs;
+    return b + fabs(b) * 1e-15;
+}
+__device__ __forceinline__ float guard_tau_dot(float sk, float eps, double nqs) {
+    if (!(eps < 3.0e38f) || !(sk > -3.0e38f) || !(nqs > 0.0 && nqs < INFINITY)) return -3.4028234e38f;
+    const double t = (double)sk / nqs;
+    const double lo = t - (double)eps - (fabs(t) + (double)eps) * 1e-15;
+    if (!(lo > -3.0e38)) return -3.4028234e38f;
+    return float_below((float)lo);   // (float)lo is within one float of lo: one step down is below it
 }
 
 // The KL best entries of a query's partial lists by (MFMA score desc, index asc): lane t < KL returns the t-th
@@ -446,7 +536,7 @@ __global__ __launch_bounds__(256) void thr_update_kernel(const float *__restrict
 // NB: rows per exact re-score batch, LB: lists per walk round trip.  <4, 4>: 120 registers, four waves per SIMD (large Q: the
 // kernel is latency-bound and lives on occupancy); <16 or 8, 8>: everything in flight at once for Q <= 1024, where at most one
 // workgroup per CU exists anyway.
-template <int KL, typename T, bool COS, int NB, int LB>
+template <int KL, typename T, int SM, int NB, int LB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 : KL == 16 ? 4 : 2))) void cos_topk_finalize_kernel(const float *__restrict__ part_s,
                                                                 const int *__restrict__ part_i, int P2,
                                                                 int64_t Q, int64_t N, const T *__restrict__ xq, int64_t ldq,
@@ -455,6 +545,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
                                                                 float *__restrict__ out_s,
                                                                 int64_t *__restrict__ out_i,
                                                                 int64_t idx_offset, GuardArgs g) {
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
@@ -478,7 +569,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
 
     // 2. exact re-score: the wave works on one candidate at a time (coalesced row reads)
     ExactQuery<T> eqr;
-    exact_load_query<T, COS>(eqr, xq + q * ldq, d, lane);
+    exact_load_query<T, COS>(eqr, xq + q * ldq, d, lane);   // (DOT: the norm is taken in the guard, not held across the loop)
     float cs = -INFINITY;
 #pragma unroll 1
     for (int t0 = 0; t0 < nvalid; t0 += NB) {   // NB candidates per step: their row reads overlap, their wave sums share shuffles
@@ -513,6 +604,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
     const bool filtered = bkey > K1_GTHR_INIT;
     bool safe = N <= KL || (nvalid < KL && !filtered);
     float tau = 0.f, eps = 0.f;
+    double nqs = 1.0;
+    (void)nqs;
     if (!safe) {
         const float err = wave_max(lane < nvalid ? fabsf(my_s - cs) : 0.f);
         if constexpr (COS) {
@@ -520,6 +613,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
             // the bound must hold on the candidates too; if it does not, the unit rows are not the canonical images of the
             // float32 rows (or rho_c_max is stale): trust nothing, score the whole shard exactly
             if (!(err <= eps)) eps = INFINITY;
+        } else if constexpr (DOT) {
+            eqr.norm = exact_query_norm(eqr);   // nq = max(|q|, 1e-8): converts between the score domains
+            eps = guard_eps(query_rho<true>(eqr, uq + q * g.ld, d, lane), *g.rho_c_max, g.ld);
+            nqs = eqr.norm * dot_scale(*g.c_maxnorm);
+            const double inv_nqs = 1.0 / nqs;   // (a consistency check, not the proof: one reciprocal, no per-lane division)
+            const float derr = wave_max(lane < nvalid ? (float)fabs((double)my_s - (double)cs * inv_nqs) : 0.f);
+            if (!(derr <= eps)) eps = INFINITY;   // (as for COS: the rows are not the images of the float32 rows)
         } else {
             eps = fmaxf(g.c1 * err, g.floor);
         }
@@ -527,8 +627,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
         if (filtered) cut = fmaxf(cut, ordered_to_float(bkey));
         const unsigned long long kth = __ballot(lane < nvalid && rank == k - 1);   // at most one lane
         const float sk = kth ? __shfl(cs, __ffsll((long long)kth) - 1, 64) : -INFINITY;   // fewer than k candidates: no k-th score
-        safe = kth != 0 && (double)cut + (double)eps < (double)sk;
-        tau = guard_tau(sk, eps);   // rows at or below tau cannot reach sk
+        if constexpr (DOT) {
+            safe = kth != 0 && dot_bound_up(cut, eps, nqs) < (double)sk;
+            tau = guard_tau_dot(sk, eps, nqs);
+        } else {
+            safe = kth != 0 && (double)cut + (double)eps < (double)sk;
+            tau = guard_tau(sk, eps);   // rows at or below tau cannot reach sk
+        }
     }
     if (lane == 0) {
         if (!safe) {
@@ -603,13 +708,14 @@ __device__ __forceinline__ void wg_select_topk(const float *sc, const int *ix, i
 // =====================================================================================================
 constexpr int COLL_CAP = 1024;   // entries per slot
 
-template <typename T, bool COS>
+template <typename T, int SM>
 __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long long *__restrict__ coll_buf,
                                                              const int *__restrict__ coll_cnt, int64_t Q, int64_t N,
                                                              const T *__restrict__ xq, int64_t ldq,
                                                              const T *__restrict__ xc, int64_t ldc, int d, int k,
                                                              float *__restrict__ out_s, int64_t *__restrict__ out_i,
                                                              int64_t idx_offset, GuardArgs g) {
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
     __shared__ float sc[COLL_CAP];
     __shared__ int ix[COLL_CAP];
     __shared__ float red_s[4];
@@ -626,13 +732,16 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
         bool resolved = cnt <= COLL_CAP;
         if (resolved) {   // workgroup-uniform
             ExactQuery<T> eqr;
-            exact_load_query<T, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
+            exact_load_query<T, COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
+            double nqs = 1.0;
+            if constexpr (DOT) nqs = eqr.norm * dot_scale(*g.c_maxnorm);
             float err = 0.f;
             for (int e = wave; e < n; e += 4) {
                 const unsigned long long ent = coll_buf[(int64_t)slot * COLL_CAP + e];
                 const int row = (int)(ent >> 32);
                 const float s = exact_score<T, COS>(eqr, xc + (int64_t)row * ldc, d, lane);
-                err = fmaxf(err, fabsf(__uint_as_float((uint32_t)ent) - s));
+                if constexpr (DOT) err = fmaxf(err, (float)fabs((double)__uint_as_float((uint32_t)ent) - (double)s / nqs));
+                else err = fmaxf(err, fabsf(__uint_as_float((uint32_t)ent) - s));
                 if (lane == 0) {
                     sc[e] = s;
                     ix[e] = row;
@@ -652,14 +761,15 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             // difference seen on this larger sample with half the safety factor of the first pass (not below 1).
             const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
             float eps;
-            if constexpr (COS) {
+            if constexpr (COS || DOT) {
                 eps = g.flag_eps[slot];
                 if (!(errmax <= eps)) eps = INFINITY;
             } else {
                 eps = fmaxf(fmaxf(0.5f * g.c1, 1.f) * errmax, g.floor);
             }
             const float thr = ordered_to_float(g.flag_thr[slot]);
-            resolved = n >= k && (double)thr + (double)eps < (double)s_top[k - 1];
+            if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)s_top[k - 1];
+            else resolved = n >= k && (double)thr + (double)eps < (double)s_top[k - 1];
         }
         if (threadIdx.x == 0) {
             if (!resolved) g.unres_q[atomicAdd(g.ctl + CTL_NUNRES, 1)] = q;
@@ -753,21 +863,23 @@ __global__ __launch_bounds__(256) void bf_merge_kernel(int64_t Q, int nch, int k
 // k > 28: every query goes to the widening pass (or straight to the brute-force pass: all_brute).  gthr[q] = B, the k-th
 // largest block maximum = a lower bound of the k-th best MFMA score: k rows score >= B on the MFMA, hence >= B - eps exactly,
 // so the k-th best EXACT score is >= B - eps and every row of the exact top-k has an MFMA score >= B - 2 eps: that is the
-// collection threshold.  One wave per query (COS: the query's rho comes from its two rows).
-template <bool COS>
+// collection threshold.  One wave per query (COS, DOT: the query's rho comes from its two rows).  DOT: the argument holds with
+// the exact scores taken in the MFMA domain (q.c / (nq S), a monotone map), so the threshold needs no conversion here.
+template <int SM>
 __global__ __launch_bounds__(256) void flag_all_kernel(int64_t Q, const int *__restrict__ gthr, bool all_brute,
                                                        const float *__restrict__ xq, int64_t ldq, const unit_t *__restrict__ uq,
                                                        int d, GuardArgs g) {
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q == 0 && lane == 0) g.ctl[all_brute ? CTL_NUNRES : CTL_NFLAG] = (int)Q;
     if (q >= Q) return;
     float eps = g.floor;
-    if constexpr (COS) {
+    if constexpr (COS || DOT) {
         if (!all_brute) {
             ExactQuery<float> eqr;
             exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);
-            eps = guard_eps(query_rho(eqr, uq + q * g.ld, d, lane), guard_rho_c(g), g.ld);
+            eps = guard_eps(query_rho<DOT>(eqr, uq + q * g.ld, d, lane), guard_rho_c(g), g.ld);
         }
     }
     if (lane != 0) return;
@@ -1022,6 +1134,40 @@ extern "C" int tsim_l2norm_rows(const void *x, int x_dtype, int64_t rows, int d,
     return TSIM_OK;
 }
 
+template <typename F>
+static int dot_prep_launch(const char *what, const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, F launch) {
+    TSIM_REQUIRE(rows >= 0 && d > 0 && ld_in >= d, "%s: bad shape rows=%lld d=%d ld_in=%lld", what, (long long)rows, d,
+                 (long long)ld_in);
+    if (rows == 0) return TSIM_OK;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (x_dtype == TSIM_F32) launch(grid, (const float *)x);
+    else if (x_dtype == TSIM_BF16) launch(grid, (const bf16_t *)x);
+    else return fail(TSIM_EINVAL, "%s: unknown dtype %d", what, x_dtype);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+extern "C" int tsim_max_norm_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, float *maxnorm, void *stream) {
+    TSIM_REQUIRE(x && maxnorm, "max_norm_rows: null pointer");
+    return dot_prep_launch("max_norm_rows", x, x_dtype, rows, d, ld_in, [&](dim3 grid, auto xt) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+        hipLaunchKernelGGL(max_norm_rows_kernel<T>, grid, dim3(256), 0, as_stream(stream), xt, rows, d, ld_in, maxnorm);
+    });
+}
+
+extern "C" int tsim_dot_scaled_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm,
+                                    void *out_f16, int ld_out, float *rho_max, void *stream) {
+    TSIM_REQUIRE(x && maxnorm && out_f16, "dot_scaled_rows: null pointer");
+    TSIM_REQUIRE(ld_out >= d, "dot_scaled_rows: ld_out=%d < d=%d", ld_out, d);
+    return dot_prep_launch("dot_scaled_rows", x, x_dtype, rows, d, ld_in, [&](dim3 grid, auto xt) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+        hipLaunchKernelGGL(dot_scaled_rows_kernel<T>, grid, dim3(256), 0, as_stream(stream), xt, rows, d, ld_in, maxnorm,
+                           (unit_t *)out_f16, ld_out, rho_max);
+    });
+}
+
+extern "C" double tsim_dot_scale(float maxnorm) { return dot_scale(maxnorm); }
+
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
 
 extern "C" void tsim_time_next_topk(void *start_event, void *stop_event) {
@@ -1130,7 +1276,7 @@ static bool plan_two_phase(int64_t Q, int64_t N, int D, int k, TopkPlan *pa, Top
     return true;
 }
 
-template <typename T, bool COS>
+template <typename T, int SM>
 static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const unit_t *eq, const unit_t *ec, int ld,
                        const T *xq, int64_t ldq, const T *xc, int64_t ldc, int d, int k, float *out_s, int64_t *out_i,
                        int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
@@ -1147,7 +1293,7 @@ static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const 
         int rc = k1_launch_collect(cp, ld, eq, Q, ec, N, g.flag_thr, coll, st);
         if (rc) return rc;
         const unsigned wg = (unsigned)(Q < 2048 ? Q : 2048);
-        hipLaunchKernelGGL((widen_finalize_kernel<T, COS>), dim3(wg), dim3(256), 0, st, coll.buf, coll.cnt, Q, N, xq, ldq, xc,
+        hipLaunchKernelGGL((widen_finalize_kernel<T, SM>), dim3(wg), dim3(256), 0, st, coll.buf, coll.cnt, Q, N, xq, ldq, xc,
                            ldc, d, k, out_s, out_i, idx_offset, g);
         TSIM_HIP_CHECK(hipGetLastError());
     }
@@ -1155,7 +1301,8 @@ static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const 
     float *bf_s = reinterpret_cast<float *>(ws + w.bf_s);
     int *bf_i = reinterpret_cast<int *>(ws + w.bf_i);
     const unsigned us = (unsigned)(Q < 64 ? Q : 64);
-    hipLaunchKernelGGL((bf_partial_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, xq, ldq, xc, ldc, d, k,
+    // (brute force has no guard: DOT scores exactly like UNIT, on the float32 rows)
+    hipLaunchKernelGGL((bf_partial_kernel<T, SM == SM_COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, xq, ldq, xc, ldc, d, k,
                        bf_s, bf_i, g);
     TSIM_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)(Q < 1024 ? Q : 1024)), dim3(256), 0, st, Q, w.bf_nch, k, bf_s, bf_i,
@@ -1164,20 +1311,20 @@ static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const 
     return TSIM_OK;
 }
 
-template <int KL, typename T, bool COS>
+template <int KL, typename T, int SM>
 static void launch_finalize(const TopkPlan &p, const float *part_s, const int *part_i, int64_t Q, int64_t N, const T *xq,
                             int64_t ldq, const T *xc, int64_t ldc, int d, int k, const unit_t *uq, const int *gthr, float *out_s,
                             int64_t *out_i, int64_t idx_offset, const GuardArgs &g, hipStream_t st) {
     const dim3 grid((unsigned)((Q + 3) / 4));
     constexpr int LBW = KL == 16 ? 8 : 4;   // (eight lists of 32 at a time spill)
     if (Q <= 1024 && d <= 384)
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, COS, 16, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
+        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 16, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
                            xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
     else if (Q <= 1024)
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, COS, 8, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
+        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 8, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
                            xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
     else
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, COS, 4, 4>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
+        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 4, 4>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
                            xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
 }
 }  // namespace tsim
@@ -1203,25 +1350,27 @@ extern "C" size_t tsim_cosine_topk_workspace_bytes(int64_t Q, int64_t N, int k) 
     return w.total;
 }
 
-extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
-                                   const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld, int k,
-                                   float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
-                                   void *workspace, size_t workspace_bytes, void *stream) {
-    TSIM_REQUIRE(eq && ec && out_scores && out_idx, "cosine_topk: null pointer");
-    TSIM_REQUIRE(Q > 0 && N > 0, "cosine_topk: empty input Q=%lld N=%lld", (long long)Q, (long long)N);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "cosine_topk: k=%d outside 1..%d", k, TOPK_MAX_K);
-    TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "cosine_topk: shard too large for 32-bit row ids");
-    TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "cosine_topk: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)",
-                 tsim_pad_dim(d), ld);
-    TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "cosine_topk: embedding matrices must be 16-byte aligned");
-    TSIM_REQUIRE((eq_f32 == nullptr) == (ec_f32 == nullptr), "cosine_topk: pass both float32 matrices or neither");
-    const bool cosf = eq_f32 != nullptr;
-    if (cosf) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "cosine_topk: float32 row strides %lld/%lld < d=%d", (long long)ldq_f32,
+// One search call.  sm: SM_UNIT (no float32 matrices), SM_COS or SM_DOT (float32 matrices given; DOT also ec_maxnorm and
+// ec_rho_max, checked by tsim_dot_topk_ex).  `what` names the entry point in error messages.
+static int topk_search(int sm, const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d,
+                       int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(eq && ec && out_scores && out_idx, "%s: null pointer", what);
+    TSIM_REQUIRE(Q > 0 && N > 0, "%s: empty input Q=%lld N=%lld", what, (long long)Q, (long long)N);
+    TSIM_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_MAX_K);
+    TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: shard too large for 32-bit row ids", what);
+    TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "%s: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)",
+                 what, tsim_pad_dim(d), ld);
+    TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "%s: embedding matrices must be 16-byte aligned", what);
+    TSIM_REQUIRE((eq_f32 == nullptr) == (ec_f32 == nullptr), "%s: pass both float32 matrices or neither", what);
+    const bool cosf = eq_f32 != nullptr;   // (SM_COS or SM_DOT)
+    if (cosf) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
                            (long long)ldc_f32, d);
     SearchWs w;
     plan_workspace(Q, N, k, &w);
     if (!workspace || workspace_bytes < w.total)
-        return fail(TSIM_ENOMEM, "cosine_topk: workspace %zu B < %zu B", workspace_bytes, w.total);
+        return fail(TSIM_ENOMEM, "%s: workspace %zu B < %zu B", what, workspace_bytes, w.total);
     char *ws = reinterpret_cast<char *>(workspace);
     float *part_s = reinterpret_cast<float *>(ws + w.part_s);
     int *part_i = reinterpret_cast<int *>(ws + w.part_i);
@@ -1244,6 +1393,7 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
     g.flag_thr = reinterpret_cast<int *>(ws + w.flag_thr);
     g.unres_q = reinterpret_cast<int *>(ws + w.unres_q);
     g.status = out_status;
+    g.c_maxnorm = ec_maxnorm;
     // ctl .. coll_cnt are contiguous: one memset clears the control words and the per-slot counters — or the threshold kernel of
     // the pre-pass does (nothing in front of it touches them)
     const size_t ctl_bytes = w.coll_cnt + align256((size_t)Q * 4) - w.ctl;
@@ -1293,16 +1443,21 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
             if (rc) return rc;
         }
         if (ev1) TSIM_HIP_CHECK(hipEventRecord(ev1, st));
-        if (cosf) {
-            if (p.KL == 16) launch_finalize<16, float, true>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k,
-                                                             uq, gthr, out_scores, out_idx, idx_offset, g, st);
-            else launch_finalize<32, float, true>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, uq, gthr,
-                                                  out_scores, out_idx, idx_offset, g, st);
+        if (sm == SM_COS) {
+            if (p.KL == 16) launch_finalize<16, float, SM_COS>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k,
+                                                               uq, gthr, out_scores, out_idx, idx_offset, g, st);
+            else launch_finalize<32, float, SM_COS>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, uq, gthr,
+                                                    out_scores, out_idx, idx_offset, g, st);
+        } else if (sm == SM_DOT) {
+            if (p.KL == 16) launch_finalize<16, float, SM_DOT>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k,
+                                                               uq, gthr, out_scores, out_idx, idx_offset, g, st);
+            else launch_finalize<32, float, SM_DOT>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, uq, gthr,
+                                                    out_scores, out_idx, idx_offset, g, st);
         } else {
-            if (p.KL == 16) launch_finalize<16, unit_t, false>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr,
-                                                               out_scores, out_idx, idx_offset, g, st);
-            else launch_finalize<32, unit_t, false>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr, out_scores,
-                                                    out_idx, idx_offset, g, st);
+            if (p.KL == 16) launch_finalize<16, unit_t, SM_UNIT>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr,
+                                                                 out_scores, out_idx, idx_offset, g, st);
+            else launch_finalize<32, unit_t, SM_UNIT>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr, out_scores,
+                                                      out_idx, idx_offset, g, st);
         }
         TSIM_HIP_CHECK(hipGetLastError());
     } else {
@@ -1317,20 +1472,44 @@ extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t 
             launch_thr_select(bmax, fp.P2, Q, k, gthr, st);
             TSIM_HIP_CHECK(hipGetLastError());
         }
-        if (cosf)
-            hipLaunchKernelGGL(flag_all_kernel<true>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok, eq_f32, ldq_f32,
+        if (sm == SM_COS)
+            hipLaunchKernelGGL(flag_all_kernel<SM_COS>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok, eq_f32, ldq_f32,
+                               uq, d, g);
+        else if (sm == SM_DOT)
+            hipLaunchKernelGGL(flag_all_kernel<SM_DOT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok, eq_f32, ldq_f32,
                                uq, d, g);
         else
-            hipLaunchKernelGGL(flag_all_kernel<false>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok,
+            hipLaunchKernelGGL(flag_all_kernel<SM_UNIT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok,
                                (const float *)nullptr, (int64_t)0, uq, d, g);
         TSIM_HIP_CHECK(hipGetLastError());
         run_collect = ok;
     }
-    if (cosf)
-        return search_tail<float, true>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
-                                        idx_offset, g, run_collect, st);
-    return search_tail<unit_t, false>(w, ws, Q, N, uq, uc, ld, uq, ld, uc, ld, ld, k, out_scores, out_idx, idx_offset, g,
+    if (sm == SM_COS)
+        return search_tail<float, SM_COS>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
+                                          idx_offset, g, run_collect, st);
+    if (sm == SM_DOT)
+        return search_tail<float, SM_DOT>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
+                                          idx_offset, g, run_collect, st);
+    return search_tail<unit_t, SM_UNIT>(w, ws, Q, N, uq, uc, ld, uq, ld, uc, ld, ld, k, out_scores, out_idx, idx_offset, g,
                                       run_collect, st);
+}
+
+extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                   const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld, int k,
+                                   float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N,
+                       d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_dot_topk_ex(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                                int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(eq_f32 && ec_f32, "dot_topk: the float32 matrices are required");
+    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "dot_topk: the corpus rows' max-norm word and measured rho_max are required");
+    return topk_search(SM_DOT, "dot_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, k,
+                       out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_cosine_topk(const void *eq, int64_t Q, const void *ec, int64_t N, int d, int ld, int k,

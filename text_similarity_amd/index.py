@@ -10,9 +10,16 @@ Deleting marks a tombstone; the matrices are compacted (one device gather) befor
 nothing afterwards and labels stay stable.  On disk (``index.bin``, a numpy ``.npz`` written without pickling): the
 float32 live rows, their labels, ``d`` (unit rows are recomputed on load; a file written by the first version of this
 index holds bf16 unit rows only, which then ARE the float32 rows).  k <= 64, d <= 768.
+
+``space='ip'`` ranks by inner product instead (hnswlib's space for dot-product models; ``knn_query`` distances are
+``1 - q.c``): the half rows are the float32 rows divided by one power of two S >= the largest row norm
+(:func:`ops.dot_scaled_rows`), and an ``add_items`` batch that raises S re-derives all of them.  Rows with a non-finite
+element are refused there.  The file records the space; a file without it is a cosine index, and loading a file of the
+other space raises ``ValueError``.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Iterable, Optional, Sequence, Tuple
 
@@ -23,9 +30,12 @@ from . import ops
 
 
 class GpuFlatIndex:
+    SPACES = ("cosine", "ip")
+
     def __init__(self, space: str = "cosine", dim: int = 0, device: Optional[torch.device] = None):
-        if space != "cosine":
-            raise ValueError("GpuFlatIndex implements the cosine space only")
+        if space not in self.SPACES:
+            raise ValueError(f"GpuFlatIndex implements the spaces {self.SPACES}, not {space!r}")
+        self.space = space
         self.dim = int(dim)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self._rows: Optional[torch.Tensor] = None      # [capacity, ld] float16 unit rows
@@ -33,6 +43,7 @@ class GpuFlatIndex:
         self._labels: Optional[torch.Tensor] = None    # [capacity] int64
         self._dead: Optional[torch.Tensor] = None      # [capacity] bool
         self._rho: Optional[torch.Tensor] = None       # [1] float32: largest rounding residual of any unit row ever stored
+        self._maxnorm: Optional[torch.Tensor] = None   # ip: [1] float32 max-norm word of every row ever stored (S derives from it)
         self._n = 0
         self._n_dead = 0
 
@@ -70,7 +81,10 @@ class GpuFlatIndex:
         xf = x.to(self.device, dtype=torch.float32).contiguous()
         if self._rho is None:
             self._rho = ops.new_rho(self.device)
-        unit = ops.l2norm_rows(xf, rho=self._rho)       # the word only grows: deleted rows leave the bound conservative
+        if self.space == "ip":
+            unit = self._ip_rows(xf)
+        else:
+            unit = ops.l2norm_rows(xf, rho=self._rho)   # the word only grows: deleted rows leave the bound conservative
         self._reserve(self._n + n)
         self._rows[self._n:self._n + n] = unit
         self._f32[self._n:self._n + n] = xf
@@ -89,7 +103,8 @@ class GpuFlatIndex:
         self._n_dead += k
 
     def knn_query(self, data, k: int = 1) -> Tuple[np.ndarray, np.ndarray]:
-        """(labels [Q,k] int64, distances [Q,k] float32 = 1 - cosine), best first — hnswlib's return convention."""
+        """(labels [Q,k] int64, distances [Q,k] float32 = 1 - cosine, or 1 - q.c for 'ip'), best first — hnswlib's return
+        convention."""
         labels, scores = self.search(data, k)
         return labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
 
@@ -106,7 +121,12 @@ class GpuFlatIndex:
             Q = q.shape[0]
             return (torch.full((Q, k), -1, dtype=torch.int64, device=self.device),
                     torch.full((Q, k), float("-inf"), device=self.device))
-        s, i = ops.cosine_topk(qn, self._rows[:self._n], self.dim, k, eq_f32=qf, ec_f32=self._f32[:self._n], rho_c=self._rho)
+        if self.space == "ip":
+            s, i = ops.dot_topk(qn, self._rows[:self._n], self.dim, k, eq_f32=qf, ec_f32=self._f32[:self._n], rho_c=self._rho,
+                                scale_c=self._maxnorm)
+        else:
+            s, i = ops.cosine_topk(qn, self._rows[:self._n], self.dim, k, eq_f32=qf, ec_f32=self._f32[:self._n],
+                                   rho_c=self._rho)
         lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
         return lab, s
 
@@ -118,16 +138,20 @@ class GpuFlatIndex:
         labels = self._labels[:self._n].cpu().numpy() if self._n else np.zeros((0,), np.int64)
         rows = self._f32[:self._n].cpu().numpy() if self._n else np.zeros((0, self.dim), np.float32)
         with open(path, "wb") as f:
-            np.savez(f, rows_f32=rows, labels=labels, dim=np.int64(self.dim))
+            np.savez(f, rows_f32=rows, labels=labels, dim=np.int64(self.dim), space=np.array(self.space))
 
     def load_index(self, path: str, max_elements: int = 0):
         if os.path.isdir(path):
             path = os.path.join(path, "index.bin")
         z = np.load(path, allow_pickle=False)
+        space = str(z["space"]) if "space" in z.files else "cosine"
+        if space != self.space:
+            raise ValueError(f"{path} holds a {space!r} index; this index is {self.space!r}")
         self.dim = int(z["dim"])
         labels = z["labels"]
         self._rows = self._f32 = self._labels = self._dead = None
         self._rho = ops.new_rho(self.device)
+        self._maxnorm = None
         self._n = self._n_dead = 0
         if "rows_f32" in z.files:
             rows = z["rows_f32"]
@@ -138,12 +162,29 @@ class GpuFlatIndex:
         if n:
             xf = torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
             self._f32[:n] = xf
-            self._rows[:n] = ops.l2norm_rows(xf, rho=self._rho)
+            self._rows[:n] = self._ip_rows(xf) if self.space == "ip" else ops.l2norm_rows(xf, rho=self._rho)
         if n:
             self._labels[:n] = torch.from_numpy(labels).to(self.device)
             self._n = n
 
     # ------------------------------------------------------------------ internals
+    def _ip_rows(self, xf: torch.Tensor) -> torch.Tensor:
+        """Half rows of a new batch for the 'ip' space.  The batch's max norm (read back: one synchronisation per batch) joins
+        the index's word; when that raises S, every stored row is re-derived under the new S with a fresh residual word."""
+        batch = float(ops.max_norm_rows(xf).item())
+        if not math.isfinite(batch):
+            raise ValueError("add_items: rows with non-finite elements (or norms beyond the float32 range) cannot be indexed "
+                             "in the 'ip' space")
+        old = 0.0 if self._maxnorm is None else float(self._maxnorm.item())
+        if self._maxnorm is None:
+            self._maxnorm = ops.new_rho(self.device)
+        if batch > old:
+            self._maxnorm.fill_(batch)
+            if self._n and ops.dot_scale(batch) != ops.dot_scale(old):
+                self._rho.zero_()
+                self._rows[:self._n] = ops.dot_scaled_rows(self._f32[:self._n], self._maxnorm, self._rho)[0]
+        return ops.dot_scaled_rows(xf, self._maxnorm, self._rho)[0]
+
     def _reserve(self, n: int):
         if self.dim == 0:
             return

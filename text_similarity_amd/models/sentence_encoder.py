@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import os
 import warnings
-from typing import List, Union
+from typing import List, Optional, Union
 
 import numpy as np
 import torch
@@ -20,7 +20,8 @@ from ..dataset.dataset import EmbeddingsFeatures
 from ..modules.modules import AvgPoolingStrategy, PoolingStrategy, SentenceEmbeddingHead, st_modules
 from ..native_encoder import NativeEncoder
 from .modeling import BaseEncoderModel, _native_from_dir
-from .st_format import read_sentence_transformers_dir, write_sentence_transformers_modules
+from .st_format import (read_sentence_transformers_dir, similarity_fn, write_sentence_transformers_modules,
+                        write_similarity_fn_name)
 
 _RESOLVE = object()   # encode_packed(head=...): look the head up from the wrapper's pooler
 
@@ -228,8 +229,11 @@ class SentenceTransformerWrapper(_EncodeMixin, BaseEncoderModel):
     unused on the embed-and-search path."""
 
     def __init__(self, pooler: PoolingStrategy = None, merge_strategy=None, loss=None, *args,
-                 parallel_mode: bool = True, projection: nn.Module = None, **kwargs):
+                 parallel_mode: bool = True, projection: nn.Module = None, similarity_fn_name: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        # the score function the checkpoint was trained for ('cosine' | 'dot'; None: not declared): the search pipelines'
+        # default score_function
+        self.similarity_fn_name = None if similarity_fn_name is None else similarity_fn(similarity_fn_name)
         self.pooler = pooler if pooler is not None else AvgPoolingStrategy(self.params)
         self.merge_strategy = merge_strategy
         self.loss = loss
@@ -265,7 +269,7 @@ class SentenceTransformerWrapper(_EncodeMixin, BaseEncoderModel):
         spec = read_sentence_transformers_dir(path)
         enc = _native_from_dir(os.path.join(path, spec.transformer_path) if spec.transformer_path else path, params)
         return cls(pooler=SentenceEmbeddingHead.from_spec(spec, params), merge_strategy=merge_strategy, loss=loss,
-                   params=params, context_embedder=enc, parallel_mode=parallel_mode)
+                   params=params, context_embedder=enc, parallel_mode=parallel_mode, similarity_fn_name=spec.similarity_fn_name)
 
     def save_pretrained(self, path):
         """BaseEncoderModel.save_pretrained, plus, for a pooler other than the default mean pool, the sentence-transformers
@@ -274,6 +278,8 @@ class SentenceTransformerWrapper(_EncodeMixin, BaseEncoderModel):
         if callable(getattr(self.pooler, "native_head", None)):
             pooling, dense, normalize = st_modules(self.pooler)
             write_sentence_transformers_modules(path, self.context_embedder.config.hidden_size, pooling, dense, normalize)
+        if self.similarity_fn_name is not None:
+            write_similarity_fn_name(path, self.similarity_fn_name)
 
     @classmethod
     def from_preset(cls, preset: str, params, **kw):

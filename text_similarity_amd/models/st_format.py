@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import json
 import os
+import warnings
 from dataclasses import dataclass
 from typing import Optional
 
@@ -26,6 +27,9 @@ UNSUPPORTED_POOL_FLAGS = ("pooling_mode_weightedmean_tokens", "pooling_mode_last
 ACTIVATIONS = {"torch.nn.modules.activation.Tanh": "tanh", "torch.nn.modules.linear.Identity": "identity"}
 ACTIVATION_NAMES = {v: k for k, v in ACTIVATIONS.items()}
 MAX_DENSE = 1024   # widths of the native Dense kernel: multiples of 8 in [8, 1024]
+# config_sentence_transformers.json similarity_fn_name -> score function of the search pipelines ("cosine" | "dot")
+ST_CONFIG = "config_sentence_transformers.json"
+SIMILARITY_FNS = {"cosine": "cosine", "dot": "dot", "dot_product": "dot"}
 
 
 @dataclass
@@ -44,6 +48,7 @@ class HeadSpec:
     pooling: str                     # 'mean' | 'cls' | 'max' | 'mean_sqrt_len'
     dense: Optional[DenseSpec] = None
     normalize: bool = False
+    similarity_fn_name: Optional[str] = None   # 'cosine' | 'dot' | None (the checkpoint does not say)
 
     @property
     def width(self) -> int:
@@ -111,6 +116,35 @@ def _dense(path: str, d_in: int) -> DenseSpec:
     return DenseSpec(fin, fout, ACTIVATIONS[act_name], np.ascontiguousarray(w), None if b is None else np.ascontiguousarray(b))
 
 
+def similarity_fn(name, where: str = "similarity_fn_name") -> str:
+    """'cosine' -> 'cosine'; 'dot' / 'dot_product' -> 'dot'; anything else warns and keeps 'cosine'."""
+    if name in SIMILARITY_FNS:
+        return SIMILARITY_FNS[name]
+    warnings.warn(f"{where}: similarity function {name!r} is not supported by the search (cosine, dot); ranking by cosine",
+                  stacklevel=2)
+    return "cosine"
+
+
+def read_similarity_fn_name(path: str) -> Optional[str]:
+    """The score function ``path``/config_sentence_transformers.json declares ('cosine' | 'dot'), or None when the file or the
+    key is absent."""
+    f = os.path.join(path, ST_CONFIG)
+    if not os.path.exists(f):
+        return None
+    name = _load_json(f, "the sentence-transformers config").get("similarity_fn_name")
+    return None if name is None else similarity_fn(name, f"{f}: similarity_fn_name")
+
+
+def write_similarity_fn_name(path: str, name: str) -> None:
+    """Set similarity_fn_name in ``path``/config_sentence_transformers.json, keeping the file's other keys."""
+    f = os.path.join(path, ST_CONFIG)
+    cfg = _load_json(f, "the sentence-transformers config") if os.path.exists(f) else {}
+    cfg["similarity_fn_name"] = similarity_fn(name)
+    os.makedirs(path, exist_ok=True)
+    with open(f, "w") as fh:
+        json.dump(cfg, fh, indent=2)
+
+
 def read_sentence_transformers_dir(path: str) -> HeadSpec:
     """Parse ``path``/modules.json and the module directories it names.  Accepted chain: Transformer (at "" or
     "0_Transformer"), one Pooling, at most one Dense after it, and an optional Normalize as the last module."""
@@ -153,6 +187,7 @@ def read_sentence_transformers_dir(path: str) -> HeadSpec:
             raise ValueError(f"{where}: unknown module type {typ!r} ({TRANSFORMER}, {POOLING}, {DENSE}, {NORMALIZE})")
     if spec is None or not spec.pooling:
         raise ValueError(f"{mf}: needs a Transformer and a Pooling module")
+    spec.similarity_fn_name = read_similarity_fn_name(path)
     return spec
 
 

@@ -104,34 +104,41 @@ def cosine_topk(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, k: int, id
     1 <= k <= 64, d <= 768.  Query sets above MAX_QUERIES_PER_CALL rows are searched in slices (queries are independent).
     ``out`` = (scores, idx): preallocated contiguous [Q,k] float32 / int64 tensors to write into (e.g. two views of one
     exchange buffer, :func:`packed_result_buffer`)."""
+    return _topk("cosine_topk", eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, None, out)
+
+
+def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out):
+    """cosine_topk (scale_c is None) and dot_topk (scale_c = the corpus rows' max-norm word)."""
     _need_gpu(eq_unit, ec_unit)
     if eq_unit.dtype != UNIT_DTYPE or ec_unit.dtype != UNIT_DTYPE:
-        raise ValueError("cosine_topk expects float16 unit rows from l2norm_rows")
+        raise ValueError(f"{what} expects float16 rows from l2norm_rows" + (" / dot_scaled_rows" if scale_c is not None else ""))
     ld = pad_dim(d)
     if eq_unit.shape[1] != ld or ec_unit.shape[1] != ld or not eq_unit.is_contiguous() or not ec_unit.is_contiguous():
-        raise ValueError(f"cosine_topk: rows must be contiguous with stride pad_dim({d})={ld}")
+        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d})={ld}")
     if (eq_f32 is None) != (ec_f32 is None):
-        raise ValueError("cosine_topk: pass both float32 matrices or neither")
+        raise ValueError(f"{what}: pass both float32 matrices or neither")
     Q, N = eq_unit.shape[0], ec_unit.shape[0]
     dev = eq_unit.device
     if ec_unit.device != dev:
-        raise ValueError(f"cosine_topk: operands on different devices ({dev} vs {ec_unit.device})")
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {ec_unit.device})")
     qf = cf = 0
     ldq = ldc = 0
     if eq_f32 is not None:
         _need_gpu(eq_f32, ec_f32)
         for t, rows, name in ((eq_f32, Q, "eq_f32"), (ec_f32, N, "ec_f32")):
             if t.dtype != torch.float32 or t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.device != dev:
-                raise ValueError(f"cosine_topk: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
+                raise ValueError(f"{what}: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
         qf, cf, ldq, ldc = eq_f32.data_ptr(), ec_f32.data_ptr(), eq_f32.stride(0), ec_f32.stride(0)
     if rho_c is not None:
         _check_rho(rho_c, dev)
+    if scale_c is not None:
+        _check_rho(scale_c, dev)
     if out is not None:
         scores, idx = out
         _need_gpu(scores, idx)
         if (scores.shape != (Q, k) or idx.shape != (Q, k) or scores.dtype != torch.float32 or idx.dtype != torch.int64
                 or not scores.is_contiguous() or not idx.is_contiguous() or scores.device != dev or idx.device != dev):
-            raise ValueError(f"cosine_topk: out must be contiguous float32 / int64 [{Q}, {k}] tensors on {dev}")
+            raise ValueError(f"{what}: out must be contiguous float32 / int64 [{Q}, {k}] tensors on {dev}")
     else:
         scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
         idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
@@ -143,16 +150,89 @@ def cosine_topk(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, k: int, id
         step = min(Q, MAX_QUERIES_PER_CALL)
         nbytes = L.tsim_cosine_topk_workspace_bytes(step, N, k)
         if nbytes == 0:
-            raise ValueError(f"cosine_topk: unsupported shape Q={Q} N={N} k={k} (1 <= k <= 64)")
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k} (1 <= k <= 64)")
         ws = _workspace(dev, nbytes)
         for q0 in range(0, Q, step):
             nq = min(step, Q - q0)
-            _lib.check(L.tsim_cosine_topk_ex(eq_unit.data_ptr() + q0 * ld * 2, qf + q0 * ldq * 4 if qf else 0, ldq, nq,
-                                             ec_unit.data_ptr(), cf, ldc, rho_c.data_ptr() if rho_c is not None else 0, N, d, ld, k,
-                                             scores.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8,
-                                             status.data_ptr() + q0 * 4 if return_status else 0,
-                                             idx_offset, ws.data_ptr(), ws.numel(), _stream(eq_unit)), "cosine_topk")
+            qargs = (eq_unit.data_ptr() + q0 * ld * 2, qf + q0 * ldq * 4 if qf else 0, ldq, nq, ec_unit.data_ptr(), cf, ldc)
+            rest = (N, d, ld, k, scores.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8,
+                    status.data_ptr() + q0 * 4 if return_status else 0, idx_offset, ws.data_ptr(), ws.numel(), _stream(eq_unit))
+            rho_p = rho_c.data_ptr() if rho_c is not None else 0
+            if scale_c is None:
+                rc = L.tsim_cosine_topk_ex(*qargs, rho_p, *rest)
+            else:
+                rc = L.tsim_dot_topk_ex(*qargs, scale_c.data_ptr(), rho_p, *rest)
+            _lib.check(rc, what)
     return (scores, idx, status) if return_status else (scores, idx)
+
+
+def max_norm_rows(x: torch.Tensor, maxnorm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raise the max-norm word ``maxnorm`` (device float32 [1], zeroed by the caller; a fresh one when None) to an upper bound
+    of the L2 norms of the rows of ``x`` [rows, d] (float32/bf16) and return it.  A row with a non-finite element makes it
+    +inf.  The inner-product search scales its corpus rows by :func:`dot_scale` of this word."""
+    _need_gpu(x)
+    x = _rows_operand(x, "max_norm_rows")
+    if maxnorm is None:
+        maxnorm = new_rho(x.device)
+    _check_rho(maxnorm, x.device)
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().tsim_max_norm_rows(x.data_ptr(), dt, x.shape[0], x.shape[1], x.stride(0), maxnorm.data_ptr(),
+                                                 _stream(x)), "max_norm_rows")
+    return maxnorm
+
+
+def dot_scale(maxnorm) -> float:
+    """S, the power of two the inner-product search divides corpus rows by, for a max-norm word (a float, or the device word,
+    which is read back): the smallest 2^e >= the word; 1.0 for 0 (an all-zero corpus); inf for a non-finite word."""
+    if isinstance(maxnorm, torch.Tensor):
+        maxnorm = float(maxnorm.item())
+    return float(_lib.lib().tsim_dot_scale(float(maxnorm)))
+
+
+def dot_scaled_rows(x: torch.Tensor, maxnorm: Optional[torch.Tensor] = None, rho: Optional[torch.Tensor] = None):
+    """Corpus operand of :func:`dot_topk`: [rows, d] float32/bf16 -> ``(rows, rho, scale)``.  ``rows`` = half(x / S) zero-padded
+    to [rows, pad_dim(d)], S = :func:`dot_scale` of the max-norm word ``scale`` (device float32 [1]); ``rho`` (device float32
+    [1]) raised to the rows' largest residual ||rows_r - x_r / S||_2, counting subnormal halves as kept and as flushed.
+    ``maxnorm`` None: a fresh word from :func:`max_norm_rows` of ``x``; given: a word that already covers ``x`` (e.g. a whole
+    index's), used as it is.  ``rho`` None: a fresh word; given: accumulated into.  No host synchronisation."""
+    _need_gpu(x)
+    x = _rows_operand(x, "dot_scaled_rows")
+    rows, d = x.shape
+    ld = pad_dim(d)
+    if maxnorm is None:
+        maxnorm = max_norm_rows(x)
+    _check_rho(maxnorm, x.device)
+    if rho is None:
+        rho = new_rho(x.device)
+    _check_rho(rho, x.device)
+    out = torch.empty((rows, ld), dtype=UNIT_DTYPE, device=x.device)
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().tsim_dot_scaled_rows(x.data_ptr(), dt, rows, d, x.stride(0), maxnorm.data_ptr(), out.data_ptr(), ld,
+                                                   rho.data_ptr(), _stream(x)), "dot_scaled_rows")
+    return out, rho, maxnorm
+
+
+def _rows_operand(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dim() != 2:
+        raise ValueError(f"{what} expects a 2-D tensor")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    return x.contiguous()
+
+
+def dot_topk(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, k: int, eq_f32: torch.Tensor, ec_f32: torch.Tensor,
+             rho_c: torch.Tensor, scale_c: torch.Tensor, idx_offset: int = 0, return_status: bool = False,
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Exact top-k by inner product (dot-product sentence-transformers models; hnswlib space='ip'): scores [Q,k] = float32(q.c)
+    of the float32 rows (float64 sum in the canonical lane order, one rounding), idx [Q,k] i64, ordered by (score desc, index
+    asc).  ``eq_unit``: the queries' unit rows (:func:`l2norm_rows`); ``(ec_scaled, rho_c, scale_c)``: :func:`dot_scaled_rows`
+    of ``ec_f32``.  All four float32/word arguments are required (include/tsim.h tsim_dot_topk_ex); the rest as
+    :func:`cosine_topk`.  A zero query returns the first k rows with score 0."""
+    if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
+        raise ValueError("dot_topk needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (dot_scaled_rows)")
+    return _topk("dot_topk", eq_unit, ec_scaled, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out)
 
 
 def packed_result_bytes(Q: int, k: int) -> int:

@@ -8,6 +8,11 @@ the fused MFMA cosine + top-k kernel and chunks are merged on the GPU.  Shipped 
 ``__call__`` passes the stored corpus, and k is clamped by the chunk size (``reference_k_clamp=True`` restores the
 reference's clamp by ``len(queries)``, :78).  Ordering within a result list is (score desc, index asc); the
 reference asks for ``sorted=False`` and leaves it undefined.
+
+``score_function`` ("cosine" | "dot") picks what ``SentenceMiningPipeline`` and ``SemanticSearchPipeline`` rank by: cosine,
+or the inner product of the float32 embeddings for models trained for dot-product scoring (exact as well,
+:func:`ops.dot_topk`).  The default is the model's ``similarity_fn_name`` (read from a sentence-transformers checkpoint's
+config_sentence_transformers.json) when it has one, else cosine.
 """
 from __future__ import annotations
 
@@ -19,6 +24,18 @@ import os
 
 from .. import ops
 from ..index import GpuFlatIndex
+
+
+SCORE_FUNCTIONS = {"cosine": "cosine", "dot": "dot", "dot_product": "dot"}
+
+
+def resolve_score_function(score_function, model) -> str:
+    """'cosine' | 'dot' from the pipeline argument, else the model's similarity_fn_name, else 'cosine'."""
+    if score_function is None:
+        score_function = getattr(model, "similarity_fn_name", None) or "cosine"
+    if score_function not in SCORE_FUNCTIONS:
+        raise ValueError(f"score_function={score_function!r}: one of 'cosine', 'dot'")
+    return SCORE_FUNCTIONS[score_function]
 
 
 class Pipeline:
@@ -51,8 +68,9 @@ class SearchPipeline(Pipeline):
 
 class SentenceMiningPipeline(SearchPipeline):
     def __init__(self, corpus_chunk_size: int, *args, reference_k_clamp: bool = False, verbose: bool = False,
-                 **kwargs):
+                 score_function: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        self.score_function = resolve_score_function(score_function, self.model)
         self.corpus_chunk_size = int(corpus_chunk_size)
         self.reference_k_clamp = reference_k_clamp
         self.verbose = verbose
@@ -62,7 +80,9 @@ class SentenceMiningPipeline(SearchPipeline):
     def search_tensors(self, query_embeddings: torch.Tensor, corpus=None, max_num_results: int = 10):
         """Device-level search: returns (scores [Q,k] f32, indices [Q,k] i64) over the whole corpus.  Scores are the
         reference's ``F.cosine_similarity`` of the float32 embeddings (search_pipeline.py:76-77) and the order is exact for
-        them: half-precision unit rows feed the MFMA kernel for candidate selection only.  1 <= max_num_results <= 64, width <= 768."""
+        them: half-precision unit rows feed the MFMA kernel for candidate selection only.  With ``score_function='dot'`` the
+        scores are the inner products of the float32 embeddings (each chunk scaled by its own power of two for the MFMA
+        pass; results do not depend on the chunking).  1 <= max_num_results <= 64, width <= 768."""
         corpus = self.corpus if corpus is None else corpus
         n = len(corpus)
         d = query_embeddings.shape[1]
@@ -76,8 +96,13 @@ class SentenceMiningPipeline(SearchPipeline):
             if isinstance(chunk, list):
                 chunk = self.model.encode_text(chunk)
             cf = chunk.to(self.params.device, dtype=torch.float32).contiguous()
-            cn, rho = ops.l2norm_rows(cf, return_rho=True)     # rho: the chunk's rounding-residual maximum (guard bound)
-            s, i = ops.cosine_topk(qn, cn, d, min(k, cn.shape[0]), idx_offset=start, eq_f32=qf, ec_f32=cf, rho_c=rho)
+            if self.score_function == "dot":
+                cn, rho, scale = ops.dot_scaled_rows(cf)
+                s, i = ops.dot_topk(qn, cn, d, min(k, cn.shape[0]), eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale,
+                                    idx_offset=start)
+            else:
+                cn, rho = ops.l2norm_rows(cf, return_rho=True)     # rho: the chunk's rounding-residual maximum (guard bound)
+                s, i = ops.cosine_topk(qn, cn, d, min(k, cn.shape[0]), idx_offset=start, eq_f32=qf, ec_f32=cf, rho_c=rho)
             if s.shape[1] < k:   # short last chunk: pad so lists stack
                 pad = k - s.shape[1]
                 s = torch.cat([s, torch.full((s.shape[0], pad), float("-inf"), device=s.device)], 1)
@@ -120,13 +145,16 @@ class SemanticSearchPipeline(SearchPipeline):
     ``num_indexed``.  Differences: results are exact; ``ef`` / ``ef_construction`` / ``M`` are accepted and unused (the
     reference's ``assert max_num_results < ef`` has no meaning here); ``add_to_index`` also appends the texts to
     ``self.corpus`` — the reference only grows the index, so its new ids cannot be mapped back to text.
-    ``max_num_results`` up to 64 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768."""
+    ``max_num_results`` up to 64 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768.
+    ``score_function='dot'`` keeps an inner-product index (``GpuFlatIndex(space='ip')``); an index file of the other space
+    at ``index_path`` raises ``ValueError``."""
 
-    def __init__(self, index_path, *args, **kwargs):
+    def __init__(self, index_path, *args, score_function: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
+        self.score_function = resolve_score_function(score_function, self.model)
         hidden = getattr(self.params.model_parameters, "hidden_size", None) or self.model.get_sentence_embedding_dimension()
-        self.index = GpuFlatIndex(space="cosine", dim=hidden, device=self.params.device)
+        self.index = GpuFlatIndex(space="ip" if self.score_function == "dot" else "cosine", dim=hidden, device=self.params.device)
         if os.path.exists(os.path.join(self.index_path, "index.bin")):
             self.index.load_index(self.index_path)
         else:

@@ -1,30 +1,59 @@
 #!/usr/bin/env python3
-"""Quick timing of tsim_cosine_topk on the GPU box: python tools/bench_search.py [N] [d] [Q ...]"""
-import sys, os, json
+"""Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot] [--spread]
+
+--score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
+one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --spread: corpus row norms spread
+log-uniformly over two decades (dot only; the default rows are Gaussian)."""
+import argparse
+import json
+import os
+import sys
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from text_similarity_amd import ops
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-d = int(sys.argv[2]) if len(sys.argv) > 2 else 384
-Qs = [int(a) for a in sys.argv[3:]] or [256, 1024, 4096, 16384]
+ap = argparse.ArgumentParser()
+ap.add_argument("N", nargs="?", type=int, default=1_000_000)
+ap.add_argument("d", nargs="?", type=int, default=384)
+ap.add_argument("Q", nargs="*", type=int, default=[256, 1024, 4096, 16384])
+ap.add_argument("--score", choices=("cosine", "dot"), default="cosine")
+ap.add_argument("--spread", action="store_true")
+a = ap.parse_args()
+N, d, Qs = a.N, a.d, a.Q
 dev = "cuda:0"
 g = torch.Generator(device=dev).manual_seed(4321)
-corpus = ops.l2norm_rows(torch.randn((N, d), generator=g, device=dev))
+cf = torch.randn((N, d), generator=g, device=dev)
+if a.spread:
+    cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
+if a.score == "dot":
+    corpus, rho, scale = ops.dot_scaled_rows(cf)
+else:
+    corpus = ops.l2norm_rows(cf)
+    del cf
 for Q in Qs:
-    q = ops.l2norm_rows(torch.randn((Q, d), generator=g, device=dev))
+    qf = torch.randn((Q, d), generator=g, device=dev)
+    q = ops.l2norm_rows(qf)
+    if a.score == "dot":
+        def run(status=False):
+            return ops.dot_topk(q, corpus, d, 10, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=status)
+    else:
+        def run(status=False):
+            return ops.cosine_topk(q, corpus, d, 10, return_status=status)
     for _ in range(2):
-        ops.cosine_topk(q, corpus, d, 10)
+        run()
     torch.cuda.synchronize()
     iters = 5 if Q <= 4096 else 2
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        ops.cosine_topk(q, corpus, d, 10)
+        run()
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
     pairs = Q * N
-    print(json.dumps({"Q": Q, "N": N, "d": d, "ms": round(ms, 4), "Gpairs_s": round(pairs / ms / 1e6, 1),
-                      "TFLOPs": round(2 * pairs * d / ms / 1e9, 1),
-                      "stream_GBs": round(-(-Q // 256) * N * d * 2 / ms / 1e6, 1)}), flush=True)
+    rec = {"score": a.score, "spread": a.spread, "Q": Q, "N": N, "d": d, "ms": round(ms, 4),
+           "Gpairs_s": round(pairs / ms / 1e6, 1), "TFLOPs": round(2 * pairs * d / ms / 1e9, 1),
+           "stream_GBs": round(-(-Q // 256) * N * d * 2 / ms / 1e6, 1)}
+    rec["status_counts"] = torch.bincount(run(True)[2].long(), minlength=3).tolist()
+    print(json.dumps(rec), flush=True)
