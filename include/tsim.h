@@ -134,6 +134,31 @@ int tsim_dot_topk_ex(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, 
                      int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Top-k for k up to TSIM_TOPK_MAX_K: the per-query `torch.topk` of /root/reference/src/pipeline/search_pipeline.py:78 and
+ * hnswlib's `knn_query` (search_pipeline.py:138) take any k; retrieve-then-rerank and
+ * recall@100 / recall@1000 evaluations ask for 100 to 1 000 candidates per query.
+ * tsim_cosine_topk_large / tsim_dot_topk_large take the argument lists of tsim_cosine_topk_ex / tsim_dot_topk_ex and return
+ * the same results (scores, order, padding, out_status, idx_offset) for 1 <= k <= TSIM_TOPK_MAX_K; else TSIM_EINVAL.
+ * For k <= 64 they ARE those entries: the same kernels, the same workspace, the same bits.  For k > 64: the k-th largest of
+ * >= 2k block maxima of the MFMA scores over the whole shard is a proven lower bound of the k-th best (the k > 28 argument of
+ * tsim_cosine_topk_ex, which does not depend on k); every row whose MFMA score exceeds bound - 2 eps_q is collected (at most
+ * the smallest power of two >= max(4k, 1 024) rows per query), re-scored exactly, sorted, and the guard of the widening pass
+ * decides (status 1).  An overflowing collection, a failed guard, or a shard too small for 2k partitions goes to an exact
+ * brute-force pass (status 2) that keeps its lists sorted in LDS.
+ * workspace: tsim_topk_large_workspace_bytes(Q, N, k), the exact byte count the call uses (0 outside 1..TSIM_TOPK_MAX_K;
+ * equal to tsim_cosine_topk_workspace_bytes for k <= 64).  It grows with Q x k; callers slice large query sets. */
+#define TSIM_TOPK_MAX_K 1024
+size_t tsim_topk_large_workspace_bytes(int64_t Q, int64_t N, int k);
+int tsim_cosine_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q,
+                           const void *ec_unit, const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N,
+                           int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
+                           int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream);
+int tsim_dot_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_scaled,
+                        const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                        int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */
@@ -142,7 +167,8 @@ void tsim_time_next_topk(void *start_event, void *stop_event);
 /* Merge `nlists` sorted candidate lists per query (the per-shard results of tsim_cosine_topk on the
  * shards of a partitioned corpus, or the per-chunk results of search_pipeline.py:60 `corpus_chunk_size`
  * chunking): scores/idx are [nlists, Q, k_in]; output [Q, k_out] by (score desc, index asc);
- * entries with idx < 0 are ignored. */
+ * entries with idx < 0 are ignored, an entry equal in (score, index) to the one before it is emitted once, unused slots are
+ * (-inf, -1).  64 < k_out <= TSIM_TOPK_MAX_K runs a sort-and-merge kernel with the same output. */
 int tsim_topk_merge(const float *scores, const int64_t *idx, int nlists, int64_t Q, int k_in,
                     int k_out, float *out_scores, int64_t *out_idx, void *stream);
 /* The same with the lists `list_stride_scores` / `list_stride_idx` ELEMENTS apart (>= Q * k_in): merges the per-rank

@@ -1001,6 +1001,404 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
 }
 
 // =====================================================================================================
+// k > 64 (tsim_cosine_topk_large / tsim_dot_topk_large, tsim_topk_merge_strided with k_out > 64).  The threshold and collect
+// stages are those of the k > 28 path (flag_all_kernel); what changes is everything that held k entries: lists live in LDS
+// sorted by (score desc, index asc), new entries are sorted with a bitonic network and merged in by rank (each entry's place
+// in the other list by binary search), never selected one round at a time.  Padding is (-inf, PAD): it ranks behind every
+// real entry, a real entry with score -inf included; NaN scores become padding (the list kernels never select them either).
+// =====================================================================================================
+constexpr int LK_MAX_K = 1024;   // TSIM_TOPK_MAX_K
+constexpr int LK_NB = 1024;      // entries of one block merged into a running list
+
+template <typename I>
+__device__ __forceinline__ I lk_pad();
+template <>
+__device__ __forceinline__ int lk_pad<int>() { return 0x7fffffff; }
+template <>
+__device__ __forceinline__ int64_t lk_pad<int64_t>() { return INT64_MAX; }
+
+template <typename I>
+__device__ __forceinline__ bool lk_before(float s1, I i1, float s2, I i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
+
+// sort s/ix[0..n) by (score desc, index asc); n a power of two; a 256-thread workgroup; entries written before the call
+// must be behind a barrier, and the sorted list is behind one on return
+template <typename I>
+__device__ __forceinline__ void lk_sort(float *s, I *ix, int n) {
+    for (int size = 2; size <= n; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < n / 2; t += 256) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const float si = s[i], sj = s[j];
+                const I ii = ix[i], ij = ix[j];
+                if ((i & size) == 0 ? lk_before(sj, ij, si, ii) : lk_before(si, ii, sj, ij)) {
+                    s[i] = sj;
+                    s[j] = si;
+                    ix[i] = ij;
+                    ix[j] = ii;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// number of entries of the sorted list a[0..n) that rank before (s, i) (LE: before it or equal to it)
+template <typename I, bool LE>
+__device__ __forceinline__ int lk_count(const float *as, const I *ai, int n, float s, I i) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const bool p = LE ? !lk_before(s, i, as[mid], ai[mid]) : lk_before(as[mid], ai[mid], s, i);
+        lo = p ? mid + 1 : lo;
+        hi = p ? hi : mid;
+    }
+    return lo;
+}
+
+// Merge the sorted block b[0..nb) into the sorted list t[0..kp): afterwards t holds the first kp of both.  kp + nb <= 2048.
+// Ranks: t's entry i lands at i + (block entries before it), the block's entry j at j + (list entries before or equal to
+// it) — a permutation of 0 .. kp+nb-1 even where entries are equal.
+// DEDUP (tsim_topk_merge): an entry equal in (score, index) to the one before it in the merged order is dropped, and the
+// list is refilled with padding behind the survivors.  m_s / m_i: kp + nb entries of scratch; wsum: 4 ints.
+template <typename I, bool DEDUP>
+__device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *bs, const I *bi, int nb, float *m_s, I *m_i,
+                                         int *wsum) {
+    constexpr int R = 2048 / 256;
+    float vs[R] = {};
+    I vi[R] = {};
+    int rk[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int t = threadIdx.x + 256 * r;
+        rk[r] = 0x7fffffff;
+        if (t < kp) {
+            vs[r] = ts[t];
+            vi[r] = ti[t];
+            rk[r] = t + lk_count<I, false>(bs, bi, nb, vs[r], vi[r]);
+        } else if (t < kp + nb) {
+            vs[r] = bs[t - kp];
+            vi[r] = bi[t - kp];
+            if (vi[r] != lk_pad<I>()) rk[r] = t - kp + lk_count<I, true>(ts, ti, kp, vs[r], vi[r]);   // (padding: rank >= kp)
+        }
+    }
+    __syncthreads();
+    if constexpr (!DEDUP) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (rk[r] < kp) {
+                ts[rk[r]] = vs[r];
+                ti[rk[r]] = vi[r];
+            }
+        __syncthreads();
+    } else {
+        const int n = kp + nb;
+        for (int t = threadIdx.x; t < n; t += 256) {   // block padding never got a rank: it is all alike
+            m_s[t] = -INFINITY;
+            m_i[t] = lk_pad<I>();
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (rk[r] < n) {
+                m_s[rk[r]] = vs[r];
+                m_i[rk[r]] = vi[r];
+            }
+        __syncthreads();
+        // survivors: real entries not equal to their predecessor; thread t owns positions 8t .. 8t+7
+        constexpr int PER = 2048 / 256;
+        int keep = 0;
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            const int p = threadIdx.x * PER + e;
+            keep |= (p < n && m_i[p] != lk_pad<I>() && !(p > 0 && m_s[p] == m_s[p - 1] && m_i[p] == m_i[p - 1])) << e;
+        }
+        const int mine = __popc(keep);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int x = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        int base = x - mine, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            base += w < wave ? wsum[w] : 0;
+            total += wsum[w];
+        }
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            if ((keep >> e) & 1) {
+                const int p = threadIdx.x * PER + e;
+                if (base < kp) {
+                    ts[base] = m_s[p];
+                    ti[base] = m_i[p];
+                }
+                ++base;
+            }
+        }
+        for (int t = total + threadIdx.x; t < kp; t += 256) {
+            ts[t] = -INFINITY;
+            ti[t] = lk_pad<I>();
+        }
+        __syncthreads();
+    }
+}
+
+// Append (s, i) to the block b (LDS counter *nb) when it ranks before the list's k-th entry (ws, wi); NaN is dropped.
+template <typename I>
+__device__ __forceinline__ void lk_offer(float *bs, I *bi, int *nb, float s, I i, float ws, I wi) {
+    if (s == s && lk_before(s, i, ws, wi)) {
+        const int p = atomicAdd(nb, 1);
+        bs[p] = s;
+        bi[p] = i;
+    }
+}
+
+// Sort the block (n entries, padded to a power of two) and merge it into the running list; workgroup-uniform n.
+template <typename I, bool DEDUP>
+__device__ __forceinline__ void lk_absorb(float *ts, I *ti, int kp, float *bs, I *bi, int n, float *m_s, I *m_i, int *wsum) {
+    int np = 1;
+    while (np < n) np <<= 1;
+    for (int t = n + threadIdx.x; t < np; t += 256) {
+        bs[t] = -INFINITY;
+        bi[t] = lk_pad<I>();
+    }
+    __syncthreads();
+    lk_sort(bs, bi, np);
+    lk_merge<I, DEDUP>(ts, ti, kp, bs, bi, np, m_s, m_i, wsum);
+}
+
+// Exact scores of the rows held by lanes 0 .. nvalid-1 (my_i), eight at a time (exact_score_batch: the bits of exact_score).
+template <typename T, bool COS>
+__device__ __forceinline__ float lk_wave_scores(const ExactQuery<T> &q, const T *xc, int64_t ldc, int my_i, int nvalid, int d,
+                                                int lane) {
+    constexpr int NB = 8;
+    float mine = 0.f;
+    for (int t0 = 0; t0 < nvalid; t0 += NB) {
+        const float s = exact_score_batch<T, COS, NB>(q, xc, ldc, my_i, t0, nvalid, d, lane);
+        if (lane >= t0 && lane < t0 + NB) mine = s;
+    }
+    return mine;
+}
+
+// widen_finalize for k > 64: one workgroup per flagged slot.  Every collected row (at most cap, a power of two >= 4k) is
+// re-scored exactly, the entries are sorted in LDS, the first k written; the guard is widen_finalize_kernel's.
+// Dynamic LDS: cap floats + cap ints.
+template <typename T, int SM>
+__global__ __launch_bounds__(256) void widen_finalize_large_kernel(const unsigned long long *__restrict__ coll_buf,
+                                                                   const int *__restrict__ coll_cnt, int cap, int64_t Q,
+                                                                   const T *__restrict__ xq, int64_t ldq,
+                                                                   const T *__restrict__ xc, int64_t ldc, int d, int k,
+                                                                   float *__restrict__ out_s, int64_t *__restrict__ out_i,
+                                                                   int64_t idx_offset, GuardArgs g) {
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *sc = reinterpret_cast<float *>(smem);
+    int *ix = reinterpret_cast<int *>(sc + cap);
+    __shared__ float s_err[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int nflag = g.ctl[CTL_NFLAG];
+    nflag = nflag < Q ? nflag : (int)Q;
+    for (int slot = blockIdx.x; slot < nflag; slot += gridDim.x) {
+        const int q = g.flag_q[slot];
+        const int n = coll_cnt[slot];
+        bool resolved = n <= cap;
+        if (resolved) {   // workgroup-uniform
+            int np = 64;
+            while (np < n || np < k) np <<= 1;   // <= cap (a power of two >= 4k)
+            ExactQuery<T> eqr;
+            exact_load_query<T, COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
+            double nqs = 1.0;
+            if constexpr (DOT) nqs = eqr.norm * dot_scale(*g.c_maxnorm);
+            float err = 0.f;
+            for (int g0 = wave * 64; g0 < np; g0 += 256) {   // wave-uniform
+                const int e = g0 + lane;
+                float s = -INFINITY;
+                int row = 0x7fffffff;
+                if (g0 < n) {
+                    const unsigned long long ent = coll_buf[(int64_t)slot * cap + (e < n ? e : g0)];
+                    const int my_row = (int)(ent >> 32);
+                    const int nvalid = n - g0 < 64 ? n - g0 : 64;
+                    const float es = lk_wave_scores<T, COS>(eqr, xc, ldc, my_row, nvalid, d, lane);
+                    if (e < n) {
+                        const float ms = __uint_as_float((uint32_t)ent);
+                        if constexpr (DOT) err = fmaxf(err, (float)fabs((double)ms - (double)es / nqs));
+                        else err = fmaxf(err, fabsf(ms - es));
+                        if (es == es) {
+                            s = es;
+                            row = my_row;
+                        }
+                    }
+                }
+                sc[e] = s;
+                ix[e] = row;
+            }
+            err = wave_max(err);
+            if (lane == 0) s_err[wave] = err;
+            __syncthreads();
+            lk_sort(sc, ix, np);
+            for (int t = threadIdx.x; t < k; t += 256) {
+                const int row = ix[t];
+                out_s[(int64_t)q * k + t] = row == 0x7fffffff ? -INFINITY : sc[t];
+                out_i[(int64_t)q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
+            }
+            // the guard of widen_finalize_kernel, on the k-th entry
+            const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
+            float eps;
+            if constexpr (COS || DOT) {
+                eps = g.flag_eps[slot];
+                if (!(errmax <= eps)) eps = INFINITY;
+            } else {
+                eps = fmaxf(fmaxf(0.5f * g.c1, 1.f) * errmax, g.floor);
+            }
+            const float thr = ordered_to_float(g.flag_thr[slot]);
+            const float sk = ix[k - 1] == 0x7fffffff ? -INFINITY : sc[k - 1];
+            if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)sk;
+            else resolved = n >= k && (double)thr + (double)eps < (double)sk;
+        }
+        if (threadIdx.x == 0) {
+            if (!resolved) g.unres_q[atomicAdd(g.ctl + CTL_NUNRES, 1)] = q;
+            if (g.status) g.status[q] = resolved ? ST_WIDENED : ST_BRUTE;
+        }
+        __syncthreads();
+    }
+}
+
+// Brute force for k > 64.  bf_large_partial: workgroup (chunk c, slot u) scores the chunk's rows exactly in blocks of LK_NB and
+// keeps a running sorted list of kp >= k entries in LDS (only rows ahead of its k-th entry are sorted and merged in); writes
+// the first k, sorted, padding (-inf, INT_MAX) included.  bf_large_merge: one workgroup per slot merges the chunk lists.
+template <typename T, bool COS>
+__global__ __launch_bounds__(256) void bf_large_partial_kernel(int64_t Q, int64_t N, int rows_per_chunk,
+                                                               const T *__restrict__ xq, int64_t ldq,
+                                                               const T *__restrict__ xc, int64_t ldc, int d, int k, int kp,
+                                                               float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
+    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB];
+    __shared__ int top_i[LK_MAX_K], blk_i[LK_NB];
+    __shared__ int s_nb;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nch = gridDim.x, chunk = blockIdx.x;
+    int nu = g.ctl[CTL_NUNRES];
+    nu = nu < Q ? nu : (int)Q;
+    const int64_t r0 = (int64_t)chunk * rows_per_chunk;
+    const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
+    for (int u = blockIdx.y; u < nu; u += gridDim.y) {
+        const int q = g.unres_q[u];
+        ExactQuery<T> eqr;
+        exact_load_query<T, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
+        for (int t = threadIdx.x; t < kp; t += 256) {
+            top_s[t] = -INFINITY;
+            top_i[t] = 0x7fffffff;
+        }
+        if (threadIdx.x == 0) s_nb = 0;
+        __syncthreads();
+        for (int64_t b = r0; b < r1; b += LK_NB) {
+            const int nb = (int)(r1 - b < LK_NB ? r1 - b : LK_NB);
+            const float ws = top_s[k - 1];
+            const int wi = top_i[k - 1];
+            for (int g0 = wave * 64; g0 < nb; g0 += 256) {   // wave-uniform
+                const int e = g0 + lane;
+                const int nvalid = nb - g0 < 64 ? nb - g0 : 64;
+                const int row = (int)(b + (e < nb ? e : g0));
+                const float s = lk_wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+                if (e < nb) lk_offer(blk_s, blk_i, &s_nb, s, row, ws, wi);
+            }
+            __syncthreads();
+            const int n = s_nb;
+            if (n > 0) lk_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
+            if (threadIdx.x == 0) s_nb = 0;
+            __syncthreads();
+        }
+        for (int t = threadIdx.x; t < k; t += 256) {
+            bf_s[((int64_t)u * nch + chunk) * k + t] = top_s[t];
+            bf_i[((int64_t)u * nch + chunk) * k + t] = top_i[t];
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void bf_large_merge_kernel(int64_t Q, int nch, int k, int kp, const float *__restrict__ bf_s,
+                                                             const int *__restrict__ bf_i, float *__restrict__ out_s,
+                                                             int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
+    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB];
+    __shared__ int top_i[LK_MAX_K], blk_i[LK_NB];
+    __shared__ int s_nb;
+    int nu = g.ctl[CTL_NUNRES];
+    nu = nu < Q ? nu : (int)Q;
+    for (int u = blockIdx.x; u < nu; u += gridDim.x) {
+        const int q = g.unres_q[u];
+        for (int t = threadIdx.x; t < kp; t += 256) {
+            top_s[t] = -INFINITY;
+            top_i[t] = 0x7fffffff;
+        }
+        if (threadIdx.x == 0) s_nb = 0;
+        __syncthreads();
+        for (int c = 0; c < nch; ++c) {
+            const float ws = top_s[k - 1];
+            const int wi = top_i[k - 1];
+            for (int t = threadIdx.x; t < k; t += 256) {
+                const int64_t at = ((int64_t)u * nch + c) * k + t;
+                lk_offer(blk_s, blk_i, &s_nb, bf_s[at], bf_i[at], ws, wi);
+            }
+            __syncthreads();
+            const int n = s_nb;
+            if (n > 0) lk_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
+            if (threadIdx.x == 0) s_nb = 0;
+            __syncthreads();
+        }
+        for (int t = threadIdx.x; t < k; t += 256) {
+            const int row = top_i[t];
+            out_s[(int64_t)q * k + t] = row == 0x7fffffff ? -INFINITY : top_s[t];
+            out_i[(int64_t)q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
+        }
+        if (threadIdx.x == 0 && g.status) g.status[q] = ST_BRUTE;
+        __syncthreads();
+    }
+}
+
+// topk_merge for 64 < k_out <= 1024: one workgroup per query; the nlists * k_in entries pass in blocks of LK_NB through the
+// running list (kp >= k_out) with duplicates of (score, index) dropped.  Same output as topk_merge_kernel.
+__global__ __launch_bounds__(256) void topk_merge_large_kernel(const float *__restrict__ scores, const int64_t *__restrict__ idx,
+                                                               int nlists, int64_t Q, int k_in, int k_out, int kp,
+                                                               int64_t lstride_s, int64_t lstride_i, float *__restrict__ out_s,
+                                                               int64_t *__restrict__ out_i) {
+    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB], m_s[LK_MAX_K + LK_NB];
+    __shared__ int64_t top_i[LK_MAX_K], blk_i[LK_NB], m_i[LK_MAX_K + LK_NB];
+    __shared__ int s_nb, wsum[4];
+    const int64_t E = (int64_t)nlists * k_in;
+    for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
+        for (int t = threadIdx.x; t < kp; t += 256) {
+            top_s[t] = -INFINITY;
+            top_i[t] = INT64_MAX;
+        }
+        if (threadIdx.x == 0) s_nb = 0;
+        __syncthreads();
+        for (int64_t e0 = 0; e0 < E; e0 += LK_NB) {
+            const float ws = top_s[k_out - 1];
+            const int64_t wi = top_i[k_out - 1];
+            for (int64_t e = e0 + threadIdx.x; e < E && e < e0 + LK_NB; e += 256) {
+                const int l = (int)(e / k_in), j = (int)(e % k_in);
+                const int64_t off = q * k_in + j;
+                const int64_t i = idx[(int64_t)l * lstride_i + off];
+                if (i >= 0) lk_offer(blk_s, blk_i, &s_nb, scores[(int64_t)l * lstride_s + off], i, ws, wi);
+            }
+            __syncthreads();
+            const int n = s_nb;
+            if (n > 0) lk_absorb<int64_t, true>(top_s, top_i, kp, blk_s, blk_i, n, m_s, m_i, wsum);
+            if (threadIdx.x == 0) s_nb = 0;
+            __syncthreads();
+        }
+        for (int t = threadIdx.x; t < k_out; t += 256) {
+            const bool pad = top_i[t] == INT64_MAX;
+            out_s[q * k_out + t] = pad ? -INFINITY : top_s[t];
+            out_i[q * k_out + t] = pad ? -1 : top_i[t];
+        }
+        __syncthreads();
+    }
+}
+
+// =====================================================================================================
 // dense cos_sim (A8): float32, rows normalised by division exactly like the reference, 64x64 tiles.
 // Evaluation-sized inputs only; not on the search path.
 // =====================================================================================================
@@ -1177,7 +1575,9 @@ extern "C" void tsim_time_next_topk(void *start_event, void *stop_event) {
 
 namespace tsim {
 constexpr int TOPK_MAX_LISTS = 28;   // largest k the list kernels (KL = 32) serve
-constexpr int TOPK_MAX_K = BF_MAXK;  // largest k at all (widening / brute-force passes)
+constexpr int TOPK_MAX_K = BF_MAXK;  // largest k of tsim_cosine_topk_ex / tsim_dot_topk_ex (widening / brute-force passes)
+constexpr int TOPK_LARGE_MAX_K = TSIM_TOPK_MAX_K;   // largest k of the _large entries
+static_assert(TOPK_LARGE_MAX_K == LK_MAX_K, "LDS lists of the k > 64 kernels");
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1218,6 +1618,43 @@ static void plan_workspace(int64_t Q, int64_t N, int k, SearchWs *w) {
     w->unres_q = take((size_t)Q * 4);
     w->coll_cnt = take((size_t)Q * 4);
     w->coll_buf = take((size_t)Q * COLL_CAP * 8);
+    w->bf_s = take((size_t)Q * w->bf_nch * k * 4);
+    w->bf_i = take((size_t)Q * w->bf_nch * k * 4);
+    w->total = o;
+}
+
+// Workspace of a k > 64 call.  cap: collect-buffer entries per slot, the smallest power of two >= 4k and >= 1 024 (the bound
+// of flag_all_kernel sits near rank 1.4 k on Gaussian rows, the 2 eps band adds a few hundred).  kp: LDS list length of the
+// brute-force pass.  Its chunk lists (Q x chunks x k entries of 8 B) are held to BFL_BUDGET by using fewer chunks.
+constexpr size_t BFL_BUDGET = (size_t)256 << 20;
+struct LargeWs {
+    size_t gthr, bmax, ctl, flag_q, flag_thr, flag_eps, unres_q, coll_cnt, coll_buf, bf_s, bf_i, total;
+    int cap, kp, bf_nch, bf_rows;
+};
+
+static void plan_workspace_large(int64_t Q, int64_t N, int k, LargeWs *w) {
+    w->cap = 1024;
+    while (w->cap < 4 * k) w->cap <<= 1;
+    w->kp = 64;
+    while (w->kp < k) w->kp <<= 1;
+    int64_t nch = (int64_t)(BFL_BUDGET / ((size_t)Q * k * 8));
+    const int64_t max_ch = (N + LK_NB - 1) / LK_NB;
+    if (nch > 64) nch = 64;
+    if (nch > max_ch) nch = max_ch;
+    if (nch < 1) nch = 1;
+    w->bf_nch = (int)nch;
+    w->bf_rows = (int)((N + nch - 1) / nch);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    w->gthr = take((size_t)Q * 4);
+    w->bmax = take((size_t)Q * K1_PREPASS_MAX_P2 * 4);
+    w->ctl = take(CTL_WORDS * 4);   // ctl .. coll_cnt contiguous: one memset
+    w->flag_q = take((size_t)Q * 4);
+    w->flag_thr = take((size_t)Q * 4);
+    w->flag_eps = take((size_t)Q * 4);
+    w->unres_q = take((size_t)Q * 4);
+    w->coll_cnt = take((size_t)Q * 4);
+    w->coll_buf = take((size_t)Q * w->cap * 8);
     w->bf_s = take((size_t)Q * w->bf_nch * k * 4);
     w->bf_i = take((size_t)Q * w->bf_nch * k * 4);
     w->total = o;
@@ -1311,6 +1748,87 @@ static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const 
     return TSIM_OK;
 }
 
+// k > 64: collect with the call's capacity, re-score and sort per slot, then brute force for what is left (all launches leave at
+// once when there is nothing to do)
+template <typename T, int SM>
+static int search_tail_large(const LargeWs &w, char *ws, int64_t Q, int64_t N, const unit_t *eq, const unit_t *ec, int ld,
+                             const T *xq, int64_t ldq, const T *xc, int64_t ldc, int d, int k, float *out_s, int64_t *out_i,
+                             int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
+    if (run_collect) {
+        TopkPlan cp;
+        plan_collect(Q, N, ld, &cp);
+        K1Collect coll{};
+        coll.qcount = g.ctl + CTL_NFLAG;
+        coll.qmap = g.flag_q;
+        coll.buf = reinterpret_cast<unsigned long long *>(ws + w.coll_buf);
+        coll.cnt = reinterpret_cast<int *>(ws + w.coll_cnt);
+        coll.cap = w.cap;
+        int rc = k1_launch_collect(cp, ld, eq, Q, ec, N, g.flag_thr, coll, st);
+        if (rc) return rc;
+        const unsigned wg = (unsigned)(Q < 2048 ? Q : 2048);
+        hipLaunchKernelGGL((widen_finalize_large_kernel<T, SM>), dim3(wg), dim3(256), (size_t)w.cap * 8, st, coll.buf, coll.cnt,
+                           w.cap, Q, xq, ldq, xc, ldc, d, k, out_s, out_i, idx_offset, g);
+        TSIM_HIP_CHECK(hipGetLastError());
+    }
+    float *bf_s = reinterpret_cast<float *>(ws + w.bf_s);
+    int *bf_i = reinterpret_cast<int *>(ws + w.bf_i);
+    const unsigned us = (unsigned)(Q < 64 ? Q : 64);
+    hipLaunchKernelGGL((bf_large_partial_kernel<T, SM == SM_COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, xq, ldq,
+                       xc, ldc, d, k, w.kp, bf_s, bf_i, g);
+    TSIM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bf_large_merge_kernel, dim3((unsigned)(Q < 1024 ? Q : 1024)), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s,
+                       bf_i, out_s, out_i, idx_offset, g);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+// GuardArgs of one call over the workspace words at the given offsets
+static GuardArgs make_guard(char *ws, size_t ctl, size_t flag_q, size_t flag_thr, size_t flag_eps, size_t unres_q, int ld,
+                            const float *ec_rho_max, const float *ec_maxnorm, int32_t *out_status) {
+    GuardArgs g;
+    g.c1 = 4.0f;
+    // unit rows only: float32 accumulation of ld exact products of unit rows, any order, rounding or truncation per step
+    // (ld * 2^-23 |a||b|, |a|,|b| <= 1 + 2^-10) + the final rounding of the exact score
+    g.floor = (float)ld * 1.1920929e-7f * 1.003f + 2.4e-7f;
+    g.rho_c_max = ec_rho_max;
+    g.rho_c_default = rho_apriori(ld);
+    g.ld = ld;
+    g.flag_eps = reinterpret_cast<float *>(ws + flag_eps);
+    g.ctl = reinterpret_cast<int *>(ws + ctl);
+    g.flag_q = reinterpret_cast<int *>(ws + flag_q);
+    g.flag_thr = reinterpret_cast<int *>(ws + flag_thr);
+    g.unres_q = reinterpret_cast<int *>(ws + unres_q);
+    g.status = out_status;
+    g.c_maxnorm = ec_maxnorm;
+    return g;
+}
+
+// k > 28: no list kernel.  Block maxima over the whole shard give a lower bound of the k-th best MFMA score; flag_all_kernel
+// turns it into every query's collection threshold (or hands every query to brute force: *ok = false, shard too small).
+// The control words must be cleared on the stream before.
+static int threshold_all(int sm, int64_t Q, int64_t N, int ld, int d, int k, const unit_t *uq, const unit_t *uc, const float *eq_f32,
+                         int64_t ldq_f32, float *bmax, int *gthr, const GuardArgs &g, bool *ok, hipStream_t st) {
+    TopkPlan fp;
+    *ok = plan_fullmax(Q, N, ld, k, &fp);
+    if (*ok) {
+        int rc0 = k1_launch_blockmax(fp, ld, uq, Q, uc, N, bmax, st);
+        if (rc0) return rc0;
+        launch_thr_select(bmax, fp.P2, Q, k, gthr, st);
+        TSIM_HIP_CHECK(hipGetLastError());
+    }
+    if (sm == SM_COS)
+        hipLaunchKernelGGL(flag_all_kernel<SM_COS>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok, eq_f32, ldq_f32,
+                           uq, d, g);
+    else if (sm == SM_DOT)
+        hipLaunchKernelGGL(flag_all_kernel<SM_DOT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok, eq_f32, ldq_f32,
+                           uq, d, g);
+    else
+        hipLaunchKernelGGL(flag_all_kernel<SM_UNIT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok,
+                           (const float *)nullptr, (int64_t)0, uq, d, g);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
 template <int KL, typename T, int SM>
 static void launch_finalize(const TopkPlan &p, const float *part_s, const int *part_i, int64_t Q, int64_t N, const T *xq,
                             int64_t ldq, const T *xc, int64_t ldc, int d, int k, const unit_t *uq, const int *gthr, float *out_s,
@@ -1350,15 +1868,24 @@ extern "C" size_t tsim_cosine_topk_workspace_bytes(int64_t Q, int64_t N, int k) 
     return w.total;
 }
 
+extern "C" size_t tsim_topk_large_workspace_bytes(int64_t Q, int64_t N, int k) {
+    if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_LARGE_MAX_K) return 0;
+    if (k <= TOPK_MAX_K) return tsim_cosine_topk_workspace_bytes(Q, N, k);
+    LargeWs w;
+    plan_workspace_large(Q, N, k, &w);
+    return w.total;
+}
+
 // One search call.  sm: SM_UNIT (no float32 matrices), SM_COS or SM_DOT (float32 matrices given; DOT also ec_maxnorm and
-// ec_rho_max, checked by tsim_dot_topk_ex).  `what` names the entry point in error messages.
+// ec_rho_max, checked by tsim_dot_topk_ex).  `what` names the entry point in error messages.  kmax: the entry's largest k
+// (k > TOPK_MAX_K takes the k > 64 plan: tsim_cosine_topk_large / tsim_dot_topk_large).
 static int topk_search(int sm, const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                        const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d,
                        int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
-                       void *workspace, size_t workspace_bytes, void *stream) {
+                       void *workspace, size_t workspace_bytes, void *stream, int kmax = TOPK_MAX_K) {
     TSIM_REQUIRE(eq && ec && out_scores && out_idx, "%s: null pointer", what);
     TSIM_REQUIRE(Q > 0 && N > 0, "%s: empty input Q=%lld N=%lld", what, (long long)Q, (long long)N);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_MAX_K);
+    TSIM_REQUIRE(k >= 1 && k <= kmax, "%s: k=%d outside 1..%d", what, k, kmax);
     TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: shard too large for 32-bit row ids", what);
     TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "%s: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)",
                  what, tsim_pad_dim(d), ld);
@@ -1367,6 +1894,29 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
     const bool cosf = eq_f32 != nullptr;   // (SM_COS or SM_DOT)
     if (cosf) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
                            (long long)ldc_f32, d);
+    hipStream_t st = as_stream(stream);
+    const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
+    if (k > TOPK_MAX_K) {
+        LargeWs w;
+        plan_workspace_large(Q, N, k, &w);
+        if (!workspace || workspace_bytes < w.total)
+            return fail(TSIM_ENOMEM, "%s: workspace %zu B < %zu B", what, workspace_bytes, w.total);
+        char *ws = reinterpret_cast<char *>(workspace);
+        const GuardArgs g = make_guard(ws, w.ctl, w.flag_q, w.flag_thr, w.flag_eps, w.unres_q, ld, ec_rho_max, ec_maxnorm, out_status);
+        TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, w.coll_cnt + align256((size_t)Q * 4) - w.ctl, st));
+        bool ok = false;
+        int rc = threshold_all(sm, Q, N, ld, d, k, uq, uc, eq_f32, ldq_f32, reinterpret_cast<float *>(ws + w.bmax),
+                               reinterpret_cast<int *>(ws + w.gthr), g, &ok, st);
+        if (rc) return rc;
+        if (sm == SM_COS)
+            return search_tail_large<float, SM_COS>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores,
+                                                    out_idx, idx_offset, g, ok, st);
+        if (sm == SM_DOT)
+            return search_tail_large<float, SM_DOT>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores,
+                                                    out_idx, idx_offset, g, ok, st);
+        return search_tail_large<unit_t, SM_UNIT>(w, ws, Q, N, uq, uc, ld, uq, ld, uc, ld, ld, k, out_scores, out_idx, idx_offset,
+                                                  g, ok, st);
+    }
     SearchWs w;
     plan_workspace(Q, N, k, &w);
     if (!workspace || workspace_bytes < w.total)
@@ -1376,24 +1926,7 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
     int *part_i = reinterpret_cast<int *>(ws + w.part_i);
     int *gthr = reinterpret_cast<int *>(ws + w.gthr);   // per-query shared threshold words, re-initialised every call
     float *bmax = reinterpret_cast<float *>(ws + w.bmax);
-    hipStream_t st = as_stream(stream);
-    const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
-
-    GuardArgs g;
-    g.c1 = 4.0f;
-    // unit rows only: float32 accumulation of ld exact products of unit rows, any order, rounding or truncation per step
-    // (ld * 2^-23 |a||b|, |a|,|b| <= 1 + 2^-10) + the final rounding of the exact score
-    g.floor = (float)ld * 1.1920929e-7f * 1.003f + 2.4e-7f;
-    g.rho_c_max = ec_rho_max;
-    g.rho_c_default = rho_apriori(ld);
-    g.ld = ld;
-    g.flag_eps = reinterpret_cast<float *>(ws + w.flag_eps);
-    g.ctl = reinterpret_cast<int *>(ws + w.ctl);
-    g.flag_q = reinterpret_cast<int *>(ws + w.flag_q);
-    g.flag_thr = reinterpret_cast<int *>(ws + w.flag_thr);
-    g.unres_q = reinterpret_cast<int *>(ws + w.unres_q);
-    g.status = out_status;
-    g.c_maxnorm = ec_maxnorm;
+    const GuardArgs g = make_guard(ws, w.ctl, w.flag_q, w.flag_thr, w.flag_eps, w.unres_q, ld, ec_rho_max, ec_maxnorm, out_status);
     // ctl .. coll_cnt are contiguous: one memset clears the control words and the per-slot counters — or the threshold kernel of
     // the pre-pass does (nothing in front of it touches them)
     const size_t ctl_bytes = w.coll_cnt + align256((size_t)Q * 4) - w.ctl;
@@ -1461,28 +1994,11 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
         }
         TSIM_HIP_CHECK(hipGetLastError());
     } else {
-        // k > 28: no list kernel.  Block maxima over the whole shard give a lower bound of the k-th best MFMA score; every row
-        // above (bound - margin) is collected and re-scored; widen_finalize's guard decides whether that was enough.
+        // k > 28: no list kernel.  Every row above (bound - margin) is collected and re-scored; widen_finalize's guard decides
+        // whether that was enough.
         TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, ctl_bytes, st));
-        TopkPlan fp;
-        const bool ok = plan_fullmax(Q, N, ld, k, &fp);
-        if (ok) {
-            int rc0 = k1_launch_blockmax(fp, ld, uq, Q, uc, N, bmax, st);
-            if (rc0) return rc0;
-            launch_thr_select(bmax, fp.P2, Q, k, gthr, st);
-            TSIM_HIP_CHECK(hipGetLastError());
-        }
-        if (sm == SM_COS)
-            hipLaunchKernelGGL(flag_all_kernel<SM_COS>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok, eq_f32, ldq_f32,
-                               uq, d, g);
-        else if (sm == SM_DOT)
-            hipLaunchKernelGGL(flag_all_kernel<SM_DOT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok, eq_f32, ldq_f32,
-                               uq, d, g);
-        else
-            hipLaunchKernelGGL(flag_all_kernel<SM_UNIT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !ok,
-                               (const float *)nullptr, (int64_t)0, uq, d, g);
-        TSIM_HIP_CHECK(hipGetLastError());
-        run_collect = ok;
+        int rc = threshold_all(sm, Q, N, ld, d, k, uq, uc, eq_f32, ldq_f32, bmax, gthr, g, &run_collect, st);
+        if (rc) return rc;
     }
     if (sm == SM_COS)
         return search_tail<float, SM_COS>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
@@ -1512,6 +2028,24 @@ extern "C" int tsim_dot_topk_ex(const void *eq, const float *eq_f32, int64_t ldq
                        out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
+extern "C" int tsim_cosine_topk_large(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                      const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld,
+                                      int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N,
+                       d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream, TOPK_LARGE_MAX_K);
+}
+
+extern "C" int tsim_dot_topk_large(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                   const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
+                                   int64_t N, int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
+                                   int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(eq_f32 && ec_f32, "dot_topk: the float32 matrices are required");
+    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "dot_topk: the corpus rows' max-norm word and measured rho_max are required");
+    return topk_search(SM_DOT, "dot_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, k,
+                       out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream, TOPK_LARGE_MAX_K);
+}
+
 extern "C" int tsim_cosine_topk(const void *eq, int64_t Q, const void *ec, int64_t N, int d, int ld, int k,
                                 float *out_scores, int64_t *out_idx, int64_t idx_offset, void *workspace,
                                 size_t workspace_bytes, void *stream) {
@@ -1528,6 +2062,14 @@ extern "C" int tsim_topk_merge_strided(const float *scores, const int64_t *idx, 
                  "topk_merge: list strides %lld / %lld < Q * k_in = %lld", (long long)list_stride_scores,
                  (long long)list_stride_idx, (long long)(Q * k_in));
     if (Q == 0) return TSIM_OK;
+    if (k_out > TOPK_MAX_K && k_out <= TOPK_LARGE_MAX_K) {   // sort-and-merge in LDS instead of k_out rounds of a wave max
+        int kp = 64;
+        while (kp < k_out) kp <<= 1;
+        hipLaunchKernelGGL(topk_merge_large_kernel, dim3((unsigned)(Q < 4096 ? Q : 4096)), dim3(256), 0, as_stream(stream), scores,
+                           idx, nlists, Q, k_in, k_out, kp, list_stride_scores, list_stride_idx, out_scores, out_idx);
+        TSIM_HIP_CHECK(hipGetLastError());
+        return TSIM_OK;
+    }
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, as_stream(stream), scores,
                        idx, nlists, Q, k_in, k_out, list_stride_scores, list_stride_idx, out_scores, out_idx);
     TSIM_HIP_CHECK(hipGetLastError());

@@ -9,7 +9,7 @@ Layout: float32 rows ``[capacity, d]`` as given (the reference's scores are cosi
 Deleting marks a tombstone; the matrices are compacted (one device gather) before the next query, so deleted rows cost
 nothing afterwards and labels stay stable.  On disk (``index.bin``, a numpy ``.npz`` written without pickling): the
 float32 live rows, their labels, ``d`` (unit rows are recomputed on load; a file written by the first version of this
-index holds bf16 unit rows only, which then ARE the float32 rows).  k <= 64, d <= 768.
+index holds bf16 unit rows only, which then ARE the float32 rows).  k <= 1024, d <= 768.
 
 ``space='ip'`` ranks by inner product instead (hnswlib's space for dot-product models; ``knn_query`` distances are
 ``1 - q.c``): the half rows are the float32 rows divided by one power of two S >= the largest row norm

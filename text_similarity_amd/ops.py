@@ -87,6 +87,9 @@ def _check_rho(rho, dev):
 
 
 MAX_QUERIES_PER_CALL = 16384    # workspace grows by ~16 KB + 512 k bytes per query: larger query sets are searched in slices
+MAX_K = 1024                    # include/tsim.h TSIM_TOPK_MAX_K; k > 64 runs tsim_cosine_topk_large / tsim_dot_topk_large
+_LIST_MAX_K = 64                # largest k of tsim_cosine_topk_ex / tsim_dot_topk_ex
+MAX_LARGE_WORKSPACE = 1 << 30   # k > 64: queries per call are halved until one call's workspace fits
 
 
 def cosine_topk(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, k: int, idx_offset: int = 0,
@@ -101,7 +104,8 @@ def cosine_topk(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, k: int, id
     ``ec_unit`` from :func:`l2norm_rows` (tightens the guard's proven error bound; without it the a-priori bound of a
     correctly rounded unit row is used — results are exact either way, more queries take the widening pass).
     ``return_status`` adds an int32 [Q] tensor: 0 = first pass, 1 = widened, 2 = brute force (include/tsim.h).
-    1 <= k <= 64, d <= 768.  Query sets above MAX_QUERIES_PER_CALL rows are searched in slices (queries are independent).
+    1 <= k <= 1024 (MAX_K), d <= 768.  Query sets above MAX_QUERIES_PER_CALL rows are searched in slices (queries are
+    independent); for k > 64 also so that one call's workspace stays within MAX_LARGE_WORKSPACE bytes.
     ``out`` = (scores, idx): preallocated contiguous [Q,k] float32 / int64 tensors to write into (e.g. two views of one
     exchange buffer, :func:`packed_result_buffer`)."""
     return _topk("cosine_topk", eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, None, out)
@@ -148,9 +152,14 @@ def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_statu
     L = _lib.lib()
     with torch.cuda.device(dev):
         step = min(Q, MAX_QUERIES_PER_CALL)
-        nbytes = L.tsim_cosine_topk_workspace_bytes(step, N, k)
+        large = k > _LIST_MAX_K
+        wsb = L.tsim_topk_large_workspace_bytes if large else L.tsim_cosine_topk_workspace_bytes
+        nbytes = wsb(step, N, k)
         if nbytes == 0:
-            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k} (1 <= k <= 64)")
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k} (1 <= k <= {MAX_K})")
+        while large and step > 1 and nbytes > MAX_LARGE_WORKSPACE:
+            step = (step + 1) // 2
+            nbytes = wsb(step, N, k)
         ws = _workspace(dev, nbytes)
         for q0 in range(0, Q, step):
             nq = min(step, Q - q0)
@@ -159,9 +168,9 @@ def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_statu
                     status.data_ptr() + q0 * 4 if return_status else 0, idx_offset, ws.data_ptr(), ws.numel(), _stream(eq_unit))
             rho_p = rho_c.data_ptr() if rho_c is not None else 0
             if scale_c is None:
-                rc = L.tsim_cosine_topk_ex(*qargs, rho_p, *rest)
+                rc = (L.tsim_cosine_topk_large if large else L.tsim_cosine_topk_ex)(*qargs, rho_p, *rest)
             else:
-                rc = L.tsim_dot_topk_ex(*qargs, scale_c.data_ptr(), rho_p, *rest)
+                rc = (L.tsim_dot_topk_large if large else L.tsim_dot_topk_ex)(*qargs, scale_c.data_ptr(), rho_p, *rest)
             _lib.check(rc, what)
     return (scores, idx, status) if return_status else (scores, idx)
 

@@ -82,7 +82,7 @@ class SentenceMiningPipeline(SearchPipeline):
         reference's ``F.cosine_similarity`` of the float32 embeddings (search_pipeline.py:76-77) and the order is exact for
         them: half-precision unit rows feed the MFMA kernel for candidate selection only.  With ``score_function='dot'`` the
         scores are the inner products of the float32 embeddings (each chunk scaled by its own power of two for the MFMA
-        pass; results do not depend on the chunking).  1 <= max_num_results <= 64, width <= 768."""
+        pass; results do not depend on the chunking).  1 <= max_num_results <= 1024, width <= 768."""
         corpus = self.corpus if corpus is None else corpus
         n = len(corpus)
         d = query_embeddings.shape[1]
@@ -145,7 +145,7 @@ class SemanticSearchPipeline(SearchPipeline):
     ``num_indexed``.  Differences: results are exact; ``ef`` / ``ef_construction`` / ``M`` are accepted and unused (the
     reference's ``assert max_num_results < ef`` has no meaning here); ``add_to_index`` also appends the texts to
     ``self.corpus`` — the reference only grows the index, so its new ids cannot be mapped back to text.
-    ``max_num_results`` up to 64 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768.
+    ``max_num_results`` up to 1024 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768.
     ``score_function='dot'`` keeps an inner-product index (``GpuFlatIndex(space='ip')``); an index file of the other space
     at ``index_path`` raises ``ValueError``."""
 

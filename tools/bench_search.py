@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot] [--spread]
+[--k K ...]
 
 --score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
 one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --spread: corpus row norms spread
-log-uniformly over two decades (dot only; the default rows are Gaussian)."""
+log-uniformly over two decades (dot only; the default rows are Gaussian).  --k: the k values to time (default 10; up to 1024,
+k > 64 runs the _large entries); one line per (Q, k)."""
 import argparse
 import json
 import os
@@ -19,6 +21,7 @@ ap.add_argument("d", nargs="?", type=int, default=384)
 ap.add_argument("Q", nargs="*", type=int, default=[256, 1024, 4096, 16384])
 ap.add_argument("--score", choices=("cosine", "dot"), default="cosine")
 ap.add_argument("--spread", action="store_true")
+ap.add_argument("--k", nargs="+", type=int, default=[10])
 a = ap.parse_args()
 N, d, Qs = a.N, a.d, a.Q
 dev = "cuda:0"
@@ -31,15 +34,15 @@ if a.score == "dot":
 else:
     corpus = ops.l2norm_rows(cf)
     del cf
-for Q in Qs:
+for Q, k in [(Q, k) for Q in Qs for k in a.k]:
     qf = torch.randn((Q, d), generator=g, device=dev)
     q = ops.l2norm_rows(qf)
     if a.score == "dot":
         def run(status=False):
-            return ops.dot_topk(q, corpus, d, 10, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=status)
+            return ops.dot_topk(q, corpus, d, k, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=status)
     else:
         def run(status=False):
-            return ops.cosine_topk(q, corpus, d, 10, return_status=status)
+            return ops.cosine_topk(q, corpus, d, k, return_status=status)
     for _ in range(2):
         run()
     torch.cuda.synchronize()
@@ -52,7 +55,7 @@ for Q in Qs:
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
     pairs = Q * N
-    rec = {"score": a.score, "spread": a.spread, "Q": Q, "N": N, "d": d, "ms": round(ms, 4),
+    rec = {"score": a.score, "spread": a.spread, "Q": Q, "N": N, "d": d, "k": k, "ms": round(ms, 4),
            "Gpairs_s": round(pairs / ms / 1e6, 1), "TFLOPs": round(2 * pairs * d / ms / 1e9, 1),
            "stream_GBs": round(-(-Q // 256) * N * d * 2 / ms / 1e6, 1)}
     rec["status_counts"] = torch.bincount(run(True)[2].long(), minlength=3).tolist()
