@@ -1530,6 +1530,7 @@ struct tsim_encoder {
     // activations
     bf16_t *x0 = nullptr, *x1 = nullptr, *qkv = nullptr, *ctx = nullptr, *h1 = nullptr;
     float *ybuf = nullptr;   // fp32 pre-LayerNorm sums (wide models only)
+    float *lnimg = nullptr;  // hidden 384: ln_split's accumulator images (LS_MAX_BLOCKS row blocks at most)
     // pre-Dense rows of a sentence head (tsim_encoder_forward_head) [max_seqs, H] float32: only when qkv, dead after the last
     // layer and used for them otherwise, is too small (max_seqs > 1.5 Tp: batches of mostly empty sequences)
     float *head_x = nullptr;
@@ -1688,16 +1689,16 @@ static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_
 // =====================================================================================================
 typedef __attribute__((ext_vector_type(4))) uint32_t lt_u32x4;
 constexpr int LT_PF = 12;   // k-steps in flight (4 loads each: vmcnt <= 63 allows 16; K / 16 must be a multiple)
+
+// The GEMM part of one ln_tail wave: acc = bias + X W^T + res for token rows m0 .. m0 + 31 and features 96 wn .. + 95, in the
+// calling wave's registers (lane = token row r + 32 h, as the MFMA leaves them).
 template <int PF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_tail_gemm_kernel(
-    const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
-    const float *__restrict__ gamma, const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int K, int xpacked) {
-    constexpr int N = 384, NT = 3, WAVES_N = 4, BM = 32;
-    __shared__ float red[2 * WAVES_N * BM];
+__device__ __forceinline__ void lt_gemm_slice(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32,
+                                              const float *__restrict__ bias, const bf16_t *__restrict__ res, int M, int K,
+                                              int xpacked, int wn, int m0, f32x16 (&acc)[3]) {
+    constexpr int N = 384, NT = 3;
     const int lane = threadIdx.x & 63;
-    const int wn = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, h = lane >> 5;
-    const int m0 = blockIdx.x * BM;
     const int ksteps = K / 16;                                   // a multiple of PF (launcher)
 
     // per-lane source addresses at k-step 0; per k-step the W pointer advances 12 KiB, the row pointer 1 KiB (packed) or 32 B
@@ -1709,7 +1710,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const char *wp = reinterpret_cast<const char *>(Wimg32) + (int64_t)(NT * wn) * 1024 + lane * 16;
     constexpr int WSTEP = (N / 32) * 1024;                       // fragment blocks of one k-step
 
-    f32x16 acc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -1756,8 +1756,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     wait_vmcnt<0>();
 
-    // ---- epilogue: gemm_bf16_kernel<.., WAVES_N = 4, ..>'s direct form with MT = 1, operation for operation
-    const int nbase = wn * 96 + 4 * h;
+    // ---- residual: gemm_bf16_kernel<.., WAVES_N = 4, ..>'s direct epilogue with MT = 1, operation for operation
     {
         const int64_t m = m0 + r;
         const int64_t mr = m < M ? m : M - 1;
@@ -1779,6 +1778,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 acc[i][4 * gq + 7] += __uint_as_float(c1 & 0xffff0000u);
             }
     }
+}
+
+// The LayerNorm part: statistics in the order (wave's 48 values, half-wave partner, waves 0..3) and the normalised bf16 rows.  All
+// four feature waves of the row block call it in one workgroup (red: its 2 x 4 x 32 floats of LDS).
+__device__ __forceinline__ void lt_layernorm(f32x16 (&acc)[3], float *red, const float *__restrict__ gamma,
+                                             const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int wn,
+                                             int m0) {
+    constexpr int N = 384, NT = 3, WAVES_N = 4, BM = 32;
+    const int lane = threadIdx.x & 63;
+    const int r = lane & 31, h = lane >> 5;
+    const int nbase = wn * 96 + 4 * h;
     float mean = 0.f, rstd = 0.f;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
@@ -1834,11 +1844,90 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
+template <int PF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_tail_gemm_kernel(
+    const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
+    const float *__restrict__ gamma, const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int K, int xpacked) {
+    __shared__ float red[2 * 4 * 32];
+    const int wn = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m0 = blockIdx.x * 32;
+    f32x16 acc[3];
+    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, wn, m0, acc);
+    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0);
+}
+
+// =====================================================================================================
+// ln_split: ln_tail with the 384 features of a row block split over S workgroups (S = 2: two feature waves each, S = 4: one),
+// for remainders of few blocks.  ln_tail's k loop is bound by the CU's L2 path — every workgroup streams ALL of W, 16 KiB per
+// k-step — on as many CUs as there are row blocks; with S slices per block, S times as many CUs stream 1/S of W each (at S = 4:
+// 3 KiB of W + 1 KiB of rows = 64 cycles against 96 of MFMA per k-step).  Each wave runs ln_tail's loop and residual add
+// unchanged and stores its accumulators as an fp32 register image (lane and register order kept); ln_split_finish_kernel then
+// reloads the four images of a row block into the registers of four waves and runs ln_tail's LayerNorm, so a row carries the
+// same bits as from every other form.
+// Image: [row block][wave wn][i * 4 + gq][lane] float4 = acc[i][4 gq .. 4 gq + 3] (48 KiB per row block, coalesced KiB stores).
+// =====================================================================================================
+constexpr int LS_MAX_BLOCKS = 256;   // ln_tail's limit of 8 192 rows: the image buffer's capacity (tsim_encoder_create)
+
+template <int PF, int S>
+__global__ __launch_bounds__(256 / S) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_split_gemm_kernel(
+    const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
+    float4 *__restrict__ img, int M, int K, int xpacked) {
+    const int blk = blockIdx.x / S, sl = blockIdx.x % S;
+    const int wn = __builtin_amdgcn_readfirstlane(sl * (4 / S) + (threadIdx.x >> 6));
+    const int m0 = blk * 32;
+    f32x16 acc[3];
+    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, wn, m0, acc);
+    float4 *dst = img + (int64_t)(blk * 4 + wn) * 12 * 64 + (threadIdx.x & 63);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+            dst[(i * 4 + gq) * 64] = make_float4(acc[i][4 * gq + 0], acc[i][4 * gq + 1], acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
+}
+
+__global__ __launch_bounds__(256) void ln_split_finish_kernel(const float4 *__restrict__ img, const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, float eps, bf16_t *__restrict__ out,
+                                                              int M) {
+    __shared__ float red[2 * 4 * 32];
+    const int wn = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m0 = blockIdx.x * 32;
+    const float4 *src = img + (int64_t)(blockIdx.x * 4 + wn) * 12 * 64 + (threadIdx.x & 63);
+    f32x16 acc[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const float4 v = src[(i * 4 + gq) * 64];
+            acc[i][4 * gq + 0] = v.x;
+            acc[i][4 * gq + 1] = v.y;
+            acc[i][4 * gq + 2] = v.z;
+            acc[i][4 * gq + 3] = v.w;
+        }
+    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0);
+}
+
+// The LayerNorm GEMM of width 384 for M <= 8 192 rows: ln_tail, or ln_split where blocks x slices still fit one round of the
+// chip's 256 CUs (img: LS_MAX_BLOCKS row blocks of image; null: ln_tail only)
 static int ln_tail_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
-                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked) {
+                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, float *img) {
     if (K % (16 * LT_PF) != 0) return fail(TSIM_EUNSUPPORTED, "ln_tail_gemm: K=%d", K);
-    hipLaunchKernelGGL(ln_tail_gemm_kernel<LT_PF>, dim3((unsigned)((M + 31) / 32)), dim3(256), 0, st, X, Wimg32, bias, res, gamma, beta,
-                       eps, out, M, K, xpacked ? 1 : 0);
+    const int nb = (M + 31) / 32;
+    const int S = !img || nb > LS_MAX_BLOCKS ? 1 : nb <= 64 ? 4 : nb <= 128 ? 2 : 1;
+    if (S == 1) {
+        hipLaunchKernelGGL(ln_tail_gemm_kernel<LT_PF>, dim3((unsigned)nb), dim3(256), 0, st, X, Wimg32, bias, res, gamma, beta, eps,
+                           out, M, K, xpacked ? 1 : 0);
+        TSIM_HIP_CHECK(hipGetLastError());
+        return TSIM_OK;
+    }
+    float4 *im = reinterpret_cast<float4 *>(img);
+    if (S == 4)
+        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 4>), dim3((unsigned)(nb * 4)), dim3(64), 0, st, X, Wimg32, bias, res, im, M, K,
+                           xpacked ? 1 : 0);
+    else
+        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 2>), dim3((unsigned)(nb * 2)), dim3(128), 0, st, X, Wimg32, bias, res, im, M,
+                           K, xpacked ? 1 : 0);
+    TSIM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(ln_split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, im, gamma, beta, eps, out, M);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
@@ -1877,7 +1966,8 @@ static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const 
 
 static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, const bf16_t *res,
                        const float *gamma, const float *beta, float eps, bf16_t *out, int M, int N, int K, float *ybuf,
-                       hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false) {
+                       hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false,
+                       float *lnimg = nullptr) {
     if (xpacked && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed operand layout is a hidden-384 form");
     if (ybuf && N >= 512 && N % 256 == 0 && gemm_pp_supported(N, K)) {
         // wide rows: a workgroup cannot own whole 768-feature rows at a 256-token tile, so the projection writes
@@ -1904,9 +1994,10 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                     X += (int64_t)m1 * K; res += (int64_t)m1 * N; out += (int64_t)m1 * N; M -= m1;
                     after_rows = true;
                 }
-                // few rows (a remainder, or a small batch): one round of 32-row workgroups that stream W straight into registers
-                if (M <= 256 * 32 && K % (16 * LT_PF) == 0)
-                    return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked);
+                // few rows (a remainder, or a small batch): one round of 32-row workgroups (or of 32-row x feature-slice
+                // workgroups) that stream W straight into registers
+                if (M <= LS_MAX_BLOCKS * 32 && K % (16 * LT_PF) == 0)
+                    return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked, lnimg);
             }
             // 128-token tiles, one workgroup per CU: mt tiles take ceil(mt/256) rounds and a nearly empty last round costs a full
             // one.  A small remainder is launched separately with 64-token tiles (2x more, 2x shorter workgroups).
@@ -2045,6 +2136,12 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
     if (H >= 512 && H % 256 == 0 && gemm_pp_supported(H, H)) {
         if ((rc = dev_alloc(e, Tp * H * 4, (void **)&e->ybuf))) return bail(rc);
         if (hipMemset(e->ybuf, 0, Tp * H * 4) != hipSuccess) return bail(fail(TSIM_EHIP, "hipMemset failed"));
+    }
+    if (!mx && H == 384 && F % 64 == 0) {   // ln_split's accumulator images: every row block a forward can hand to ln_tail_gemm
+        const size_t blocks = (Tp + 31) / 32 < (size_t)LS_MAX_BLOCKS ? (Tp + 31) / 32 : (size_t)LS_MAX_BLOCKS;   // (a forward has T <= max_tokens < Tp rows)
+        const size_t bytes = blocks * 4 * 12 * 64 * 16;
+        if ((rc = dev_alloc(e, bytes, (void **)&e->lnimg))) return bail(rc);
+        if (hipMemset(e->lnimg, 0, bytes) != hipSuccess) return bail(fail(TSIM_EHIP, "hipMemset failed"));
     }
     if ((size_t)cfg->max_seqs * H * 4 > Tp * 3 * H * 2 && (rc = dev_alloc(e, (size_t)cfg->max_seqs * H * 4, (void **)&e->head_x)))
         return bail(rc);
@@ -2216,11 +2313,11 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
                 if ((rc = res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, c.ln_eps, e->x0, e->aq, e->as, T, H, st))) return rc;
                 continue;
             }
-            if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32))) return rc;
+            if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg))) return rc;
             if (pk) {
                 if ((rc = gemm_xres2<EPI_GELU, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
             } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;
-            if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk))) return rc;
+            if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg))) return rc;
         }
         if (last_hidden_bf16)
             TSIM_HIP_CHECK(hipMemcpyAsync(last_hidden_bf16, e->x0, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
