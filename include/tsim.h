@@ -159,6 +159,58 @@ int tsim_dot_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f3
                         int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact range search: every corpus row whose score reaches a threshold (faiss `range_search`; what sentence-transformers'
+ * paraphrase_mining / community_detection and near-duplicate removal are built on).  Operands as for tsim_cosine_topk_ex /
+ * tsim_dot_topk_ex: unit (cosine) or scaled (inner product) half rows select, the float32 rows decide.  The float32 matrices
+ * are REQUIRED (NULL: TSIM_EINVAL; there is no unit-rows-only mode), for dot also ec_maxnorm and ec_rho_max.
+ * Definition.  Row r is a hit of query q iff s(q, r) >= tau compared in float32, s being exactly the float32 score the top-k
+ * entry of the same space returns for the pair (cosine: oracle/search_ref.exact_cosine; dot: float32 of the float64 lane-ordered
+ * sum).  tau is one float per call: NaN is TSIM_EINVAL, -inf returns every row (of non-NaN score), a tau above every score
+ * returns nothing.  The hits of a query are ordered by (score desc, index asc).  Nothing is ever truncated: the result is the
+ * complete set for any tau and any data.
+ * The result size depends on the data, so the call is split where the host has to allocate:
+ *   1. tsim_cosine_range_scan / tsim_dot_range_scan: threshold set-up -> ONE collect pass of the MFMA kernel over the corpus ->
+ *      exact re-score, filter and sort per query -> exact counting for the queries that need it.  Writes out_counts [Q] int64
+ *      (hits per query) and out_status [Q] int32 (may be NULL); its state stays in the workspace.
+ *   2. the caller makes lims [Q+1] int64, the exclusive prefix sum of out_counts (lims[0] = 0, lims[Q] = T), and allocates
+ *      out_scores [T] float32 and out_idx [T] int64;
+ *   3. tsim_range_fill with the SAME workspace (untouched in between), float32 matrices, Q, N, d and tau writes the hits of
+ *      query q to [lims[q], lims[q+1]) — the CSR layout of faiss — with out_idx = shard row + idx_offset.  A segment shorter
+ *      than the scan's count is never overrun.  It may be repeated (e.g. with another idx_offset).
+ * tsim_range_workspace_bytes(Q, N): the exact byte count (0 for Q <= 0 or N <= 0); it grows with Q * TSIM_RANGE_SLOT_CAP * 8 and
+ * not with N; callers slice large query sets.
+ * Guard (a proof, not an estimate).  eps_q = guard_eps(rho_q, rho_c, ld) bounds |m - s| for the query against EVERY row of the
+ * shard, m the MFMA score (the Cauchy-Schwarz + accumulation argument of tsim_cosine_topk_ex; rho_q measured from the query's
+ * two rows, rho_c = *ec_rho_max, cosine with NULL: the a-priori bound).  Cosine: a hit has s >= tau, hence m >= s - eps_q >=
+ * tau - eps_q > thr_q, where thr_q is a float STRICTLY below the real number tau - eps_q (the subtraction in float64, rounded
+ * to float32, stepped down until thr_q + eps_q < tau holds in float64); the collect pass appends every row with m > thr_q, so
+ * no hit is left uncollected.  Dot: m approximates q.c / (nq S) with |m - s / (nq S)| <= eps_q (nq = max(|q|, 1e-8), S the
+ * corpus scale); a hit has s >= tau, hence m >= tau / (nq S) - eps_q > thr_q, the float below that quotient minus eps_q minus
+ * 1e-15 of its magnitude (which covers the float64 roundings of the division and the subtraction).  When no finite thr_q is
+ * safe (tau = -inf, non-finite S, rows with NaN / inf that make rho 2, a zero query whose quotient leaves the float range) the
+ * query is not collected at all and goes to the exact pass.  The exact re-score then removes the rows of the band
+ * [tau - eps_q, tau) that were collected with the hits.
+ * Status per query: 1 = answered from the collected rows; 2 = more than TSIM_RANGE_SLOT_CAP rows were collected (or no finite
+ * threshold existed), or a re-scored row showed |m - s| > eps_q (operands that are not the images of the float32 rows), and
+ * the query was answered by an exact pass over the float32 rows of the whole shard with the arithmetic of the top-k
+ * brute-force pass: counted in the scan, written straight into the caller's segment and sorted there in the fill, so that a
+ * query that hits the whole shard needs no scratch of its own.  Status 0 is not used. */
+#define TSIM_RANGE_SLOT_CAP 2048
+#define TSIM_SPACE_COSINE 0
+#define TSIM_SPACE_DOT 1
+size_t tsim_range_workspace_bytes(int64_t Q, int64_t N);
+int tsim_cosine_range_scan(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_unit,
+                           const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld, float tau,
+                           int64_t *out_counts, int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream);
+int tsim_dot_range_scan(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_scaled,
+                        const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                        int d, int ld, float tau, int64_t *out_counts, int32_t *out_status, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int tsim_range_fill(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32, int64_t N,
+                    int d, float tau, const int64_t *lims, float *out_scores, int64_t *out_idx, int64_t idx_offset,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

@@ -19,5 +19,6 @@ int fail(int code, const char *fmt, ...) {
 }
 }  // namespace tsim
 
+// (the range-search entries were added WITHOUT a bump: nothing existing changed its signature or its results, and callers pin 104)
 extern "C" int tsim_version(void) { return 104; }
 extern "C" const char *tsim_last_error(void) { return tsim::g_last_error.c_str(); }

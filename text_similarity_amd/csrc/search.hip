@@ -1847,6 +1847,8 @@ static void launch_finalize(const TopkPlan &p, const float *part_s, const int *p
 }
 }  // namespace tsim
 
+#include "range_search.h"   // exact range search: kernels and entry points, on the helpers above
+
 extern "C" int tsim_cosine_topk_plan(int64_t Q, int64_t N, int ld, int k, int32_t plan[4]) {
     if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_MAX_K || !plan || tsim_pad_dim(ld) != ld)
         return fail(TSIM_EINVAL, "tsim_cosine_topk_plan: bad arguments (Q=%lld N=%lld ld=%d k=%d)", (long long)Q, (long long)N, ld, k);

@@ -1,6 +1,6 @@
 """GpuFlatIndex — an exact cosine index resident in HBM with the call surface the reference uses from
 ``hnswlib.Index(space='cosine')`` (/root/reference/src/pipeline/search_pipeline.py:105-169): ``init_index``,
-``add_items``, ``knn_query``, ``mark_deleted``, ``resize_index``, ``save_index`` / ``load_index``, ``get_current_count``,
+``add_items``, ``knn_query``, ``range_query`` (every row within a threshold; not in hnswlib), ``mark_deleted``, ``resize_index``, ``save_index`` / ``load_index``, ``get_current_count``,
 ``set_ef``.  Every query is a brute-force pass of the fused MFMA cosine + top-k kernel, so results are exact (hnswlib's are
 approximate) and ordered by (score desc, label-row asc).
 
@@ -129,6 +129,34 @@ class GpuFlatIndex:
                                    rho_c=self._rho)
         lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
         return lab, s
+
+    def range_search(self, data, threshold: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Every live row whose score against a query is >= ``threshold`` (cosine, or q.c for 'ip'): ``(lims int64 [Q+1], scores
+        float32 [T], labels int64 [T])`` on the device, faiss' ``range_search`` layout — the hits of query q are
+        ``[lims[q], lims[q+1])``, ordered by (score desc, row asc).  Exact and complete (:func:`ops.cosine_range`)."""
+        self._compact()
+        q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        qf = q.to(self.device, dtype=torch.float32).contiguous()
+        if self._n == 0:
+            return (torch.zeros((qf.shape[0] + 1,), dtype=torch.int64, device=self.device),
+                    torch.empty((0,), dtype=torch.float32, device=self.device),
+                    torch.empty((0,), dtype=torch.int64, device=self.device))
+        qn = ops.l2norm_rows(qf)
+        if self.space == "ip":
+            lims, s, i = ops.dot_range(qn, self._rows[:self._n], self.dim, threshold, eq_f32=qf, ec_f32=self._f32[:self._n],
+                                       rho_c=self._rho, scale_c=self._maxnorm)
+        else:
+            lims, s, i = ops.cosine_range(qn, self._rows[:self._n], self.dim, threshold, eq_f32=qf, ec_f32=self._f32[:self._n],
+                                          rho_c=self._rho)
+        return lims, s, self._labels[i]
+
+    def range_query(self, data, threshold: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """numpy form of :meth:`range_search` with ``knn_query``'s distance convention: ``(lims [Q+1], labels [T], distances [T]
+        = 1 - score)``, best first within each query."""
+        lims, scores, labels = self.range_search(data, threshold)
+        return lims.cpu().numpy(), labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
 
     # ------------------------------------------------------------------ persistence
     def save_index(self, path: str):

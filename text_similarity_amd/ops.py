@@ -6,6 +6,7 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -242,6 +243,143 @@ def dot_topk(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, k: int, eq_
     if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
         raise ValueError("dot_topk needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (dot_scaled_rows)")
     return _topk("dot_topk", eq_unit, ec_scaled, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out)
+
+
+# ------------------------------------------------------------------------------------------------- exact range search
+RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
+MAX_RANGE_QUERIES_PER_CALL = 4096       # the workspace holds RANGE_SLOT_CAP entries of 8 bytes per query: 64 MiB per call
+
+
+def _f32_below(f):
+    """csrc/search.hip float_below: the next float32 towards -inf of a finite f, stepping from +-0 to the smallest normal."""
+    f = np.float32(f)
+    if f == 0:
+        return np.float32(-1.17549435e-38)
+    b = f.view(np.int32)
+    return (b - np.int32(1) if f > 0 else b + np.int32(1)).view(np.float32)
+
+
+def range_collect_threshold(threshold, rho_q, rho_c, ld: int, nqs: Optional[float] = None):
+    """Host mirror of the range search's threshold set-up kernel (csrc/range_search.h range_setup_kernel) for ONE query:
+    ``(thr, eps)`` with ``eps`` = the float32 bound on |MFMA score - exact score| (csrc/common.h guard_eps) from the query's and
+    the corpus' residuals, and ``thr`` the collect threshold in the MFMA domain: every row whose MFMA score is strictly above it is
+    collected.  Cosine (``nqs`` None): a float32 strictly below ``threshold - eps``.  Inner product: ``nqs`` = max(|q|, 1e-8) * S
+    in float64, ``thr`` strictly below ``threshold / nqs - eps``.  ``thr`` is None when no finite threshold is safe (the kernel
+    then hands the query to the exact pass).  This is the executable statement of the guard: a row with exact score >=
+    threshold has an MFMA score >= threshold - eps > thr."""
+    f32 = np.float32
+    tau = f32(threshold)
+    rq, rc = float(f32(rho_q)), float(f32(rho_c))
+    acc = ld * 1.1920928955078125e-7 * (1.0 + rq) * (1.0 + rc)
+    eps = f32((rq + rc + rq * rc + acc + 2.384185791015625e-7) * (1.0 + 1e-6))
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if not (eps < f32(3.0e38)) or not (tau > f32(-3.0e38)):
+            return None, eps
+        if nqs is None:
+            thr = _f32_below(f32(float(tau) - float(eps)))
+            if float(thr) + float(eps) >= float(tau):
+                thr = _f32_below(thr)
+        else:
+            nqs = float(nqs)
+            if not (0.0 < nqs < float("inf")):
+                return None, eps
+            t = float(tau) / nqs
+            lo = t - float(eps) - (abs(t) + float(eps)) * 1e-15
+            if not (lo > -3.0e38):
+                return None, eps
+            thr = _f32_below(f32(lo))
+    return (thr if thr > f32(-3.4e38) else None), eps
+
+
+def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset, return_status):
+    _need_gpu(eq_unit, ec_half, eq_f32, ec_f32)
+    if eq_unit.dtype != UNIT_DTYPE or ec_half.dtype != UNIT_DTYPE:
+        raise ValueError(f"{what} expects float16 rows from l2norm_rows" + (" / dot_scaled_rows" if scale_c is not None else ""))
+    ld = pad_dim(d)
+    if eq_unit.shape[1] != ld or ec_half.shape[1] != ld or not eq_unit.is_contiguous() or not ec_half.is_contiguous():
+        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d})={ld}")
+    tau = float(threshold)
+    if tau != tau:
+        raise ValueError(f"{what}: the threshold is NaN")
+    Q, N = eq_unit.shape[0], ec_half.shape[0]
+    dev = eq_unit.device
+    for t, rows, name in ((eq_f32, Q, "eq_f32"), (ec_f32, N, "ec_f32")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.device != dev:
+            raise ValueError(f"{what}: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
+    if rho_c is not None:
+        _check_rho(rho_c, dev)
+    if scale_c is not None:
+        _check_rho(scale_c, dev)
+    lims = torch.zeros((Q + 1,), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    parts_s, parts_i = [], []
+    if Q > 0 and N > 0:
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            step = min(Q, MAX_RANGE_QUERIES_PER_CALL)
+            ws = _workspace(dev, L.tsim_range_workspace_bytes(step, N))
+            counts = torch.empty((Q,), dtype=torch.int64, device=dev)
+            st = _stream(eq_unit)
+            rho_p = rho_c.data_ptr() if rho_c is not None else 0
+            total = 0
+            for q0 in range(0, Q, step):
+                nq = min(step, Q - q0)
+                qf, ldq, ldc = eq_f32.data_ptr() + q0 * eq_f32.stride(0) * 4, eq_f32.stride(0), ec_f32.stride(0)
+                head = (eq_unit.data_ptr() + q0 * ld * 2, qf, ldq, nq, ec_half.data_ptr(), ec_f32.data_ptr(), ldc)
+                tail = (N, d, ld, tau, counts.data_ptr() + q0 * 8, status.data_ptr() + q0 * 4, ws.data_ptr(), ws.numel(), st)
+                if scale_c is None:
+                    rc = L.tsim_cosine_range_scan(*head, rho_p, *tail)
+                else:
+                    rc = L.tsim_dot_range_scan(*head, scale_c.data_ptr(), rho_p, *tail)
+                _lib.check(rc, what)
+                sl = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
+                torch.cumsum(counts[q0:q0 + nq], 0, out=sl[1:])
+                t_slice = int(sl[-1].item())       # the one host read: the fill's output is allocated from it
+                s = torch.empty((t_slice,), dtype=torch.float32, device=dev)
+                i = torch.empty((t_slice,), dtype=torch.int64, device=dev)
+                if t_slice:
+                    _lib.check(L.tsim_range_fill(space, qf, ldq, nq, ec_f32.data_ptr(), ldc, N, d, tau, sl.data_ptr(), s.data_ptr(),
+                                                 i.data_ptr(), idx_offset, ws.data_ptr(), ws.numel(), st), what)
+                lims[q0 + 1:q0 + nq + 1] = sl[1:] + total
+                total += t_slice
+                parts_s.append(s)
+                parts_i.append(i)
+    if len(parts_s) == 1:
+        scores, idx = parts_s[0], parts_i[0]
+    elif parts_s:
+        scores, idx = torch.cat(parts_s), torch.cat(parts_i)
+    else:
+        scores = torch.empty((0,), dtype=torch.float32, device=dev)
+        idx = torch.empty((0,), dtype=torch.int64, device=dev)
+    return (lims, scores, idx, status) if return_status else (lims, scores, idx)
+
+
+def cosine_range(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, threshold: float, eq_f32: torch.Tensor,
+                 ec_f32: torch.Tensor, rho_c: Optional[torch.Tensor] = None, idx_offset: int = 0, return_status: bool = False):
+    """Exact range search by cosine: EVERY corpus row whose score against a query is >= ``threshold`` (faiss ``range_search``),
+    the score being exactly what :func:`cosine_topk` returns for the pair with the float32 matrices given (which are required
+    here).  Returns ``(lims int64 [Q+1], scores float32 [T], idx int64 [T])`` on the device, the CSR layout of faiss: the hits
+    of query q are ``scores[lims[q]:lims[q+1]]`` / ``idx[...]`` (= corpus row + ``idx_offset``), ordered by (score desc, index
+    asc).  Nothing is truncated, whatever the threshold and the data: ``-inf`` returns every row.  One MFMA pass over the corpus
+    collects the candidates, an exact re-score decides; a query that collects more than RANGE_SLOT_CAP rows is answered by an
+    exact pass over the float32 rows instead (``return_status`` adds int32 [Q]: 1 = collected, 2 = exact pass; include/tsim.h).
+    The total T is read back once between the two halves of the call (the output is allocated from it); query sets above
+    MAX_RANGE_QUERIES_PER_CALL rows are processed in slices.  Q = 0 or N = 0: empty results, no launch."""
+    if eq_f32 is None or ec_f32 is None:
+        raise ValueError("cosine_range needs the float32 matrices eq_f32 and ec_f32")
+    return _range("cosine_range", _lib.SPACE_COSINE, eq_unit, ec_unit, d, threshold, eq_f32, ec_f32, rho_c, None, idx_offset,
+                  return_status)
+
+
+def dot_range(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, threshold: float, eq_f32: torch.Tensor,
+              ec_f32: torch.Tensor, rho_c: torch.Tensor, scale_c: torch.Tensor, idx_offset: int = 0, return_status: bool = False):
+    """:func:`cosine_range` by inner product: every row with float32(q.c) >= ``threshold``, the score of :func:`dot_topk`.
+    ``(ec_scaled, rho_c, scale_c)``: :func:`dot_scaled_rows` of ``ec_f32``; all are required.  A zero query scores 0 against
+    every row: all rows for a threshold <= 0, none above."""
+    if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
+        raise ValueError("dot_range needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (dot_scaled_rows)")
+    return _range("dot_range", _lib.SPACE_DOT, eq_unit, ec_scaled, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset,
+                  return_status)
 
 
 def packed_result_bytes(Q: int, k: int) -> int:

@@ -38,6 +38,15 @@ def resolve_score_function(score_function, model) -> str:
     return SCORE_FUNCTIONS[score_function]
 
 
+def _sort_columns(cols, order):
+    """Rows of equally long device columns sorted lexicographically by a chain of stable sorts: ``order`` = (column, descending)
+    pairs, LEAST significant key first."""
+    for k, desc in order:
+        o = torch.sort(cols[k], stable=True, descending=desc)[1]
+        cols = [c[o] for c in cols]
+    return cols
+
+
 class Pipeline:
     def __init__(self, params, model, name: Optional[str] = None):
         self.params = params
@@ -112,6 +121,67 @@ class SentenceMiningPipeline(SearchPipeline):
         if len(scores) == 1:
             return scores[0], idxs[0]
         return ops.topk_merge(scores, idxs, k)
+
+    def range_tensors(self, query_embeddings: torch.Tensor, threshold: float, corpus=None):
+        """Device-level range search: ``(lims int64 [Q+1], scores float32 [T], indices int64 [T])`` — EVERY corpus row whose
+        score (``score_function``) against a query is >= ``threshold``; the hits of query q are ``[lims[q], lims[q+1])``, ordered
+        by (score desc, index asc).  Exact and complete (:func:`ops.cosine_range` / :func:`ops.dot_range`).  The corpus goes
+        through in chunks of ``corpus_chunk_size``; a range result needs no merge, the per-chunk hits of a query are
+        concatenated and re-sorted on the device."""
+        corpus = self.corpus if corpus is None else corpus
+        n = len(corpus)
+        d = query_embeddings.shape[1]
+        dev = self.params.device
+        qf = query_embeddings.to(dev, dtype=torch.float32).contiguous()
+        qn = ops.l2norm_rows(qf)
+        Q = qf.shape[0]
+        parts = []
+        for start in range(0, n, self.corpus_chunk_size):
+            chunk = corpus[start:start + self.corpus_chunk_size]
+            if isinstance(chunk, list):
+                chunk = self.model.encode_text(chunk)
+            cf = chunk.to(dev, dtype=torch.float32).contiguous()
+            if self.score_function == "dot":
+                cn, rho, scale = ops.dot_scaled_rows(cf)
+                parts.append(ops.dot_range(qn, cn, d, threshold, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, idx_offset=start))
+            else:
+                cn, rho = ops.l2norm_rows(cf, return_rho=True)
+                parts.append(ops.cosine_range(qn, cn, d, threshold, eq_f32=qf, ec_f32=cf, rho_c=rho, idx_offset=start))
+        if len(parts) == 1:
+            return parts[0]
+        if not parts:
+            return (torch.zeros((Q + 1,), dtype=torch.int64, device=qf.device), torch.empty((0,), dtype=torch.float32, device=qf.device),
+                    torch.empty((0,), dtype=torch.int64, device=qf.device))
+        # query id of every hit, then one stable sort chain: index asc, score desc, query asc
+        qid = torch.cat([torch.repeat_interleave(torch.arange(Q, device=l.device), l[1:] - l[:-1]) for l, _, _ in parts])
+        s = torch.cat([p[1] for p in parts])
+        i = torch.cat([p[2] for p in parts])
+        qid, s, i = _sort_columns([qid, s, i], ((2, False), (1, True), (0, False)))
+        lims = torch.zeros((Q + 1,), dtype=torch.int64, device=s.device)
+        torch.cumsum(torch.bincount(qid, minlength=Q), 0, out=lims[1:])
+        return lims, s, i
+
+    def mine(self, queries, threshold: float) -> Dict[int, list]:
+        """``{query_idx: [(corpus_idx, text, score), ...]}``: every corpus entry scoring >= ``threshold`` against the query, best
+        first — sentence mining with a score floor.  ``queries``: texts or embeddings; the corpus is the pipeline's."""
+        query_embeddings = self.encode_corpus(documents=queries)
+        lims, scores, idx = self.range_tensors(query_embeddings, threshold)
+        lims, scores, idx = lims.cpu().tolist(), scores.cpu().tolist(), idx.cpu().tolist()
+        return {q: [(idx[t], self.corpus[idx[t]], scores[t]) for t in range(lims[q], lims[q + 1])]
+                for q in range(len(lims) - 1)}
+
+    def mine_pairs(self, threshold: float) -> List[tuple]:
+        """The corpus against itself: every unordered pair (i < j) scoring >= ``threshold``, each once, as ``[(score, i, j)]``
+        sorted by (score desc, i, j) — near-duplicate detection / paraphrase mining.  The i < j filter runs on the device on
+        the CSR arrays."""
+        emb = self.encode_corpus(documents=self.corpus)
+        lims, scores, idx = self.range_tensors(emb, threshold)
+        Q = lims.numel() - 1
+        qid = torch.repeat_interleave(torch.arange(Q, device=lims.device), lims[1:] - lims[:-1])
+        keep = qid < idx
+        qid, idx, scores = qid[keep], idx[keep], scores[keep]
+        qid, idx, scores = _sort_columns([qid, idx, scores], ((1, False), (0, False), (2, True)))
+        return list(zip(scores.cpu().tolist(), qid.cpu().tolist(), idx.cpu().tolist()))
 
     def _search(self, queries, corpus=None, max_num_results: int = 10, return_embeddings: bool = False
                 ) -> Dict[int, Union[list, torch.Tensor]]:

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot] [--spread]
-[--k K ...]
+[--k K ...] [--range TAU ... | --range-hits H ...]
 
 --score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
 one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --spread: corpus row norms spread
 log-uniformly over two decades (dot only; the default rows are Gaussian).  --k: the k values to time (default 10; up to 1024,
-k > 64 runs the _large entries); one line per (Q, k)."""
+k > 64 runs the _large entries); one line per (Q, k).
+--range TAU ...: time the exact range search (ops.cosine_range / ops.dot_range on the float32 rows) at these thresholds instead of
+top-k: ms per call (scan + the host read of the total + fill), mean hits per query and the status counts; one line per (Q, tau).
+--range-hits H ...: the same with tau derived from the normal tail so that about H of the N Gaussian rows pass per query (a cosine
+of Gaussian rows is ~ N(0, 1/d), an inner product ~ N(0, d)); the achieved mean is printed."""
 import argparse
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +27,8 @@ ap.add_argument("Q", nargs="*", type=int, default=[256, 1024, 4096, 16384])
 ap.add_argument("--score", choices=("cosine", "dot"), default="cosine")
 ap.add_argument("--spread", action="store_true")
 ap.add_argument("--k", nargs="+", type=int, default=[10])
+ap.add_argument("--range", nargs="+", type=float, default=[], dest="taus")
+ap.add_argument("--range-hits", nargs="+", type=float, default=[])
 a = ap.parse_args()
 N, d, Qs = a.N, a.d, a.Q
 dev = "cuda:0"
@@ -32,8 +39,40 @@ if a.spread:
 if a.score == "dot":
     corpus, rho, scale = ops.dot_scaled_rows(cf)
 else:
-    corpus = ops.l2norm_rows(cf)
-    del cf
+    corpus, rho = ops.l2norm_rows(cf, return_rho=True)
+    if not (a.taus or a.range_hits):
+        del cf
+taus = list(a.taus) + [statistics.NormalDist().inv_cdf(1.0 - h / N) * (d ** 0.5 if a.score == "dot" else d ** -0.5) for h in a.range_hits]
+
+
+def timed(run, iters):
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+for Q, tau in [(Q, tau) for Q in (Qs if taus else []) for tau in taus]:
+    qf = torch.randn((Q, d), generator=g, device=dev)
+    q = ops.l2norm_rows(qf)
+
+    def run():
+        if a.score == "dot":
+            return ops.dot_range(q, corpus, d, tau, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=True)
+        return ops.cosine_range(q, corpus, d, tau, eq_f32=qf, ec_f32=cf, rho_c=rho, return_status=True)
+    ms = timed(run, 5 if Q <= 4096 else 2)
+    lims, _, _, st = run()
+    print(json.dumps({"score": a.score, "range": True, "Q": Q, "N": N, "d": d, "tau": round(tau, 6), "ms": round(ms, 4),
+                      "mean_hits": round(int(lims[-1]) / Q, 2), "status_counts": torch.bincount(st.long(), minlength=3).tolist()}),
+          flush=True)
+if taus:
+    sys.exit(0)
 for Q, k in [(Q, k) for Q in Qs for k in a.k]:
     qf = torch.randn((Q, d), generator=g, device=dev)
     q = ops.l2norm_rows(qf)
