@@ -226,3 +226,29 @@ def test_meter_oracles_match_reference_fixture():
     corr, val = adjacent_ref.sts_correlations(g["sts_a"], g["sts_b"], g["sts_gold"])
     np.testing.assert_allclose(corr, g["sts_corr"], rtol=0, atol=2e-6)
     assert abs(val - float(g["sts_val"])) <= 2e-6 and float(g["sts_avg"]) == float(g["sts_val"])
+
+
+@pytest.mark.parametrize("preset", ["tiny-bert", "tiny-mpnet", "all-MiniLM-L6-v2", "all-mpnet-base-v2", "bert-base-uncased"])
+def test_probe_oracle_equals_encoder_ref(preset):
+    """oracle/encoder_probe.py (float64, packed tokens, every layer boundary) with no rounding and no defect is the same
+    function as oracle/encoder_ref.py: last hidden states of every live token of the golden batch within 2e-5 (the bound
+    of float32 against HF above), pooled rows within the bounds used against the goldens above."""
+    import torch
+    from oracle import encoder_probe
+    g = golden(f"encoder_{preset}.npz")
+    cfg, w = presets.PRESETS[preset], presets.synthetic_weights(preset)
+    if "input_ids" in g.files:
+        ids, mask = g["input_ids"], g["attention_mask"]
+        flat, cu, pos, cols = encoder_probe.pack_padded(cfg, ids, mask)
+        atol_pool = 1e-5
+    else:
+        flat, cu = g["flat_ids"].astype(np.int64), g["cu_seqlens"].astype(np.int64)
+        ids, mask = encoder_ref.pad_batch(flat, cu, range(cu.size - 1), cfg.pad_id)
+        pos = cols = None
+        atol_pool = 3e-5
+    with torch.no_grad():
+        ref = encoder_ref.encoder_forward(cfg, w, ids, mask).numpy()
+        hs = encoder_probe.probe_forward(cfg, w, flat, cu, pos=pos, cols=cols)
+    assert len(hs) == cfg.num_layers + 1 and all(h.shape == (flat.size, cfg.hidden) for h in hs)
+    np.testing.assert_allclose(hs[-1].numpy(), ref[mask.astype(bool)], rtol=0, atol=2e-5)
+    np.testing.assert_allclose(encoder_probe.mean_pool_packed(hs[-1], cu).numpy(), g["pooled"], rtol=0, atol=atol_pool)
