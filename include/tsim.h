@@ -315,7 +315,7 @@ void tsim_encoder_destroy(tsim_encoder *enc);
  * Outputs (either may be NULL): pooled_f32 [B, hidden] = masked mean-pool (A4), un-normalised like the
  * reference's encode_text; unit_f16 [B, ld_unit] = L2-normalised half rows ready for tsim_cosine_topk, with
  * unit_rho_max (device float, may be NULL) raised to their largest rounding residual exactly as tsim_l2norm_rows does;
- * last_hidden_bf16 [T, hidden] for tests. */
+ * last_hidden_bf16 [T, hidden] = the final hidden states of the packed tokens (token embeddings; tests read them too). */
 int tsim_encoder_forward(tsim_encoder *enc, const int32_t *tok_ids, const int32_t *tok_pos,
                          const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B,
                          int32_t max_len, float *pooled_f32, void *unit_f16, int ld_unit, float *unit_rho_max,
@@ -386,7 +386,39 @@ int tsim_encoder_forward_head(tsim_encoder *enc, const int32_t *tok_ids, const i
                               const tsim_sentence_head *head, float *emb_f32, void *unit_f16, int ld_unit,
                               float *unit_rho_max, void *last_hidden_bf16, void *stream);
 
-/* Kernels cannot raise HF's IndexError: a token id outside [0, vocab), a token type outside [0, n_types), a position row outside [0, max_pos) or a token whose
+/* ---------------------------------------------------------------------------------------------
+ * Word-in-context embeddings: WordEncoderModel.encode  /root/reference/src/models/word_encoder.py:46-50 with
+ * WordPoolingStrategy.forward  /root/reference/src/modules/modules.py:68-74, and GWSCModel's
+ * `torch.mean(embedded_1[i][w1_c1], dim=0)`  word_encoder.py:85-92 — the mean of the final hidden states over the token
+ * positions of a target word — on the device, behind the unchanged packed forward.
+ * Arguments: those of tsim_encoder_forward_ex (same meaning, same optional outputs: one call can return sentence and word
+ * embeddings), then the span table in CSR form and the span outputs:
+ *   span_seq [S] int32       the sequence (0 .. B-1) span s belongs to;
+ *   span_cu  [S+1] int32     span s lists span_tok[span_cu[s] .. span_cu[s+1]);
+ *   span_tok [n_span_tok] int32   token positions inside the sequence, 0-based, the first token ([CLS]) is 0.  A LIST, not a
+ *                            range: any order, gaps and repeats are legal, a repeated position counts as often as it is
+ *                            listed (as `embedded[i][positions]` does), a list may be longer than the sequence;
+ *   n_span_tok               the length of span_tok (= span_cu[S] of a well-formed table; what the kernel clamps offsets to);
+ *   span_out_f32 [S, hidden] (may be NULL) the means.  Fixed arithmetic, restated bit for bit on the host by
+ *                            tests/test_span_pool_gpu.py: each bf16 element widened to float32, float32 adds in list order
+ *                            starting from 0, ONE float32 division by the list length.  An EMPTY list gives a zero row
+ *                            (torch.mean of an empty selection is NaN);
+ *   span_unit_f16 [S, ld_span_unit] (may be NULL; hidden <= 768) exactly tsim_l2norm_rows(span rows, eps 1e-8), with
+ *                            span_rho_max (may be NULL) raised as it raises rho_max — the call runs that routine on the
+ *                            means.  Without span_out_f32 the means live in encoder scratch (S <= 1.5 x max_tokens then).
+ * Nothing faults on a bad table: a position outside [0, len(sequence)), a span_seq outside [0, B) and list offsets outside
+ * [0, n_span_tok] or out of order are clamped into range and computed anyway (a position listed for an EMPTY sequence adds
+ * zeros), and raise TSIM_ENC_ERR_SPAN in the flag word of tsim_encoder_error_flags.
+ * S == 0: tsim_encoder_forward_ex, bit for bit (the span arguments are not read).  S > 0 needs B > 0 and at least one span
+ * output, else TSIM_EINVAL. */
+int tsim_encoder_forward_spans(tsim_encoder *enc, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos,
+                               const int32_t *tok_col, const int32_t *cu_seqlens, int32_t T, int32_t B, int32_t max_len,
+                               float *pooled_f32, void *unit_f16, int ld_unit, float *unit_rho_max,
+                               void *last_hidden_bf16, float *logits_f32, const int32_t *span_seq, const int32_t *span_cu,
+                               const int32_t *span_tok, int32_t S, int32_t n_span_tok, float *span_out_f32,
+                               void *span_unit_f16, int ld_span_unit, float *span_rho_max, void *stream);
+
+/* Kernels cannot raise HF's IndexError: a token id outside [0, vocab), a token type outside [0, n_types), a position row outside [0, max_pos), a span-table entry out of range or a token whose
  * column is >= the max_len passed to tsim_encoder_forward is clamped / computed anyway and leaves a bit in a per-encoder
  * flag word.  This call copies the word to *flags_host, clears it and SYNCHRONISES `stream` (the only entry point that
  * does): 0 = every forward since the last call was clean.  The Python wrappers call it at the end of encode_text. */
@@ -394,6 +426,7 @@ int tsim_encoder_forward_head(tsim_encoder *enc, const int32_t *tok_ids, const i
 #define TSIM_ENC_ERR_POSITION 2
 #define TSIM_ENC_ERR_MAX_LEN 4
 #define TSIM_ENC_ERR_TOKEN_TYPE 8
+#define TSIM_ENC_ERR_SPAN 16   /* tsim_encoder_forward_spans: a position, sequence index or list offset of the span table */
 int tsim_encoder_error_flags(tsim_encoder *enc, int32_t *flags_host, void *stream);
 
 /* ---- tokenizer (host code, no GPU): BERT WordPiece for pure-ASCII sentences -------------------------------------------------

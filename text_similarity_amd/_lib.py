@@ -15,6 +15,7 @@ W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
 ACT_IDENTITY, ACT_TANH = 0, 1
 SPACE_COSINE, SPACE_DOT = 0, 1
+ENC_ERR_SPAN = 16                # include/tsim.h TSIM_ENC_ERR_SPAN
 RANGE_SLOT_CAP = 2048            # include/tsim.h TSIM_RANGE_SLOT_CAP
 
 
@@ -119,6 +120,10 @@ _SIGS = {
     "tsim_encoder_forward_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int32, C.POINTER(SentenceHeadC), C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsim_encoder_forward_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 DECLARED_SYMBOLS = tuple(_SIGS)

@@ -2404,3 +2404,5 @@ extern "C" int tsim_dense_rows(const float *x, int64_t B, int d_in, const float 
     TSIM_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "dense_rows: x and out must be 16-byte aligned");
     return dense_rows_launch(x, (int)B, d_in, w, b, d_out, act, normalize, out, nullptr, 0, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
+
+#include "span_pool.h"   // word-in-context embeddings: span_pool_kernel and tsim_encoder_forward_spans, behind the forward above

@@ -92,6 +92,21 @@ def _tokenize_library(tokenizer, docs: List[str], max_len: int, batch_size: int)
     return np.asarray(flat, dtype=np.int32), np.asarray(lens, dtype=np.int64)
 
 
+def _capacity_slices(enc: NativeEncoder, cu_h: np.ndarray):
+    """(s, e) ranges of the sequences of one packed chunk such that each range fits one forward of ``enc`` (max_seqs sequences,
+    max_tokens tokens); ``cu_h``: the chunk's offsets on the host."""
+    B = len(cu_h) - 1
+    s = 0
+    while s < B:
+        e = s + 1
+        while e < B and e - s < enc.max_seqs and cu_h[e + 1] - cu_h[s] <= enc.max_tokens:
+            e += 1
+        if cu_h[e] - cu_h[s] > enc.max_tokens:
+            raise ValueError("a single sequence exceeds the encoder token capacity")
+        yield s, e
+        s = e
+
+
 class _EncodeMixin:
     """encode / encode_text shared by both wrappers."""
 
@@ -129,48 +144,29 @@ class _EncodeMixin:
         enc: NativeEncoder = self.context_embedder
         if head is _RESOLVE:
             head = self._native_head(cu.device)
-        B = cu.numel() - 1
         outs, units = [], []
         cu_h = (cu.cpu().numpy() if cu_host is None else np.asarray(cu_host)).astype(np.int64)
-        s = 0
-        while s < B:
-            e = s + 1
-            while e < B and e - s < enc.max_seqs and cu_h[e + 1] - cu_h[s] <= enc.max_tokens:
-                e += 1
-            if cu_h[e] - cu_h[s] > enc.max_tokens:
-                raise ValueError("a single sequence exceeds the encoder token capacity")
+        for s, e in _capacity_slices(enc, cu_h):
             r = enc.forward_packed(flat_ids[cu_h[s]:cu_h[e]], cu[s:e + 1] - cu[s], pooled=True, unit=unit,
                                    max_len=int(np.diff(cu_h[s:e + 1]).max()), head=head)
             outs.append(r["pooled"])
             if unit:
                 units.append(r["unit"])
-            s = e
         width = head.width(enc.cfg.hidden) if head is not None else enc.cfg.hidden
         pooled = torch.cat(outs) if outs else torch.empty((0, width), device=cu.device)
         return (pooled, torch.cat(units)) if unit else pooled
 
-    def encode_text(self, documents: List[str], output_np: bool = False) -> Union[torch.Tensor, np.ndarray]:
-        """sentence_encoder.py:136-173: sort by character length, encode in batches, un-sort, stack.
-        Returns float32 [N, H] on params.device (or numpy when ``output_np``), un-normalised.
-        The host tokenizer is the end-to-end bottleneck of this path (SURVEY.md §8(f) N2), so it runs one chunk AHEAD on a
-        host thread: chunk i+1 is tokenised while the GPU encodes chunk i (kernel launches are asynchronous; fast
-        tokenizers release the GIL).  ``self.last_encode_stats`` holds the split of the wall time."""
+    def _sorted_chunks(self, documents: List[str], order: np.ndarray, t_tok: list):
+        """The batching of encode_text (sentence_encoder.py:136-173), shared by every text entry point: the documents in
+        ``order`` (ascending character length), cut into chunks, each tokenised without padding.  Yields (lo, flat ids int32,
+        lengths int64) per chunk; chunk i+1 is tokenised on a host thread while the caller works on chunk i.  ``t_tok[0]``
+        accumulates the tokenizer time."""
         import time
         from concurrent.futures import ThreadPoolExecutor
-        enc: NativeEncoder = self.context_embedder
-        dev = enc.device
         n = len(documents)
-        head = self._native_head(dev)
-        if n == 0:
-            out = torch.empty((0, head.width(enc.cfg.hidden) if head is not None else enc.cfg.hidden), dtype=torch.float32,
-                              device=dev)
-            return out.cpu().numpy() if output_np else out
-        t_start = time.perf_counter()
-        order = np.argsort([len(s) for s in documents], kind="stable")
         docs = [documents[i] for i in order]
         tok_batch = max(int(self.params.batch_size), 1) * 64
         chunk = max(tok_batch, int(getattr(self.params, "encode_chunk_sentences", 8192)))
-        t_tok = [0.0]
 
         def tokenize(lo):
             t0 = time.perf_counter()
@@ -178,13 +174,64 @@ class _EncodeMixin:
             t_tok[0] += time.perf_counter() - t0
             return r
 
-        parts = []
-        with ThreadPoolExecutor(max_workers=1) as pool, torch.no_grad():
+        with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(tokenize, 0)
             for lo in range(0, n, chunk):
                 flat, lens = fut.result()
                 if lo + chunk < n:
                     fut = pool.submit(tokenize, lo + chunk)
+                yield lo, flat, lens
+
+    def _token_embeddings(self, documents: List[str], output_np: bool):
+        """encode_text(output_value="token_embeddings"): the final hidden states of each sentence, [len_i, H] float32."""
+        enc: NativeEncoder = self.context_embedder
+        dev = enc.device
+        if len(documents) == 0:
+            return []
+        order = np.argsort([len(s) for s in documents], kind="stable")
+        out = [None] * len(documents)
+        with torch.no_grad():
+            for lo, flat, lens in self._sorted_chunks(documents, order, [0.0]):
+                cu = np.zeros(len(lens) + 1, dtype=np.int64)
+                np.cumsum(lens, out=cu[1:])
+                flat_d = torch.from_numpy(flat).to(dev, non_blocking=True)
+                cu_d = torch.from_numpy(cu.astype(np.int32)).to(dev, non_blocking=True)
+                for s, e in _capacity_slices(enc, cu):
+                    h = enc.forward_packed(flat_d[cu[s]:cu[e]], cu_d[s:e + 1] - cu_d[s], pooled=False, hidden=True,
+                                           max_len=int(lens[s:e].max()))["hidden"].float()
+                    for j, piece in enumerate(torch.split(h, [int(v) for v in lens[s:e]])):   # one slice per sentence
+                        out[order[lo + s + j]] = piece
+        enc.check()
+        return [t.cpu().numpy() for t in out] if output_np else out
+
+    def encode_text(self, documents: List[str], output_np: bool = False,
+                    output_value: str = "sentence_embedding") -> Union[torch.Tensor, np.ndarray, list]:
+        """sentence_encoder.py:136-173: sort by character length, encode in batches, un-sort, stack.
+        Returns float32 [N, H] on params.device (or numpy when ``output_np``), un-normalised.
+        ``output_value="token_embeddings"`` (the sentence-transformers name) returns instead a list of [len_i, H] float32
+        tensors in input order: the final hidden states of each sentence's tokens, special tokens included, no padding.
+        The host tokenizer is the end-to-end bottleneck of this path (SURVEY.md §8(f) N2), so it runs one chunk AHEAD on a
+        host thread: chunk i+1 is tokenised while the GPU encodes chunk i (kernel launches are asynchronous; fast
+        tokenizers release the GIL).  ``self.last_encode_stats`` holds the split of the wall time."""
+        import time
+        if output_value not in ("sentence_embedding", "token_embeddings"):
+            raise ValueError(f"output_value must be 'sentence_embedding' or 'token_embeddings', got {output_value!r}")
+        enc: NativeEncoder = self.context_embedder
+        dev = enc.device
+        n = len(documents)
+        if output_value == "token_embeddings":
+            return self._token_embeddings(documents, output_np)
+        head = self._native_head(dev)
+        if n == 0:
+            out = torch.empty((0, head.width(enc.cfg.hidden) if head is not None else enc.cfg.hidden), dtype=torch.float32,
+                              device=dev)
+            return out.cpu().numpy() if output_np else out
+        t_start = time.perf_counter()
+        order = np.argsort([len(s) for s in documents], kind="stable")
+        t_tok = [0.0]
+        parts = []
+        with torch.no_grad():
+            for _, flat, lens in self._sorted_chunks(documents, order, t_tok):
                 cu = np.zeros(len(lens) + 1, dtype=np.int64)
                 np.cumsum(lens, out=cu[1:])
                 flat_d = torch.from_numpy(flat).to(dev, non_blocking=True)

@@ -181,7 +181,8 @@ class NativeEncoder:
 
     # ------------------------------------------------------------------ input validation
     ERR_BITS = {1: "a token id outside [0, vocab_size)", 2: "a position id outside the position table",
-                4: "a sequence longer than the max_len passed to forward_packed", 8: "a token type id outside the type table"}
+                4: "a sequence longer than the max_len passed to forward_packed", 8: "a token type id outside the type table",
+                16: "a span position outside its sequence, or a span outside the batch"}
 
     @staticmethod
     def check_lengths(cfg: EncoderConfig, max_len: int) -> None:
@@ -238,14 +239,16 @@ class NativeEncoder:
     def forward_packed(self, flat_ids: torch.Tensor, cu: torch.Tensor, pos: Optional[torch.Tensor] = None,
                        cols: Optional[torch.Tensor] = None, max_len: Optional[int] = None, pooled: bool = True,
                        unit: bool = False, hidden: bool = False, rho: Optional[torch.Tensor] = None,
-                       types: Optional[torch.Tensor] = None, logits: bool = False, head: Optional[SentenceHead] = None):
+                       types: Optional[torch.Tensor] = None, logits: bool = False, head: Optional[SentenceHead] = None,
+                       spans=None):
         """flat_ids int32 [T], cu int32 [B+1] on the GPU.  Returns dict with 'pooled' f32 [B,H],
         'unit' float16 [B,pad_dim(H)] (L2-normalised rows for the search kernel), 'hidden' bf16 [T,H], 'logits' f32
         [B, num_labels] (the head of ``set_cls_head`` on each sequence's first token) as requested.
         ``rho``: a device float32 word raised to the largest rounding residual of the unit rows (ops.l2norm_rows).
         ``types``: int32 [T] token-type ids (BERT; None = all 0).
         ``head``: a :class:`SentenceHead` run in place of the mean pool: 'pooled' is then its final rows [B, head.width(H)] and
-        'unit' their unit rows (tsim_encoder_forward_head); not with ``logits``."""
+        'unit' their unit rows (tsim_encoder_forward_head); not with ``logits``.
+        ``spans``: what :meth:`forward_spans` passes down (the span table and which span outputs to make)."""
         ops._need_gpu(flat_ids, cu)
         flat_ids = flat_ids.to(torch.int32).contiguous()
         cu = cu.to(torch.int32).contiguous()
@@ -269,6 +272,8 @@ class NativeEncoder:
         self.check_lengths(self.cfg, max_len)
         if head is not None and logits:
             raise ValueError("a sentence head and logits are separate forwards")
+        if head is not None and spans is not None:
+            raise ValueError("a sentence head and spans are separate forwards")
         H = self.cfg.hidden
         W = head.width(H) if head is not None else H
         out = {}
@@ -277,6 +282,15 @@ class NativeEncoder:
         u = torch.empty((B, ops.pad_dim(W)), dtype=ops.UNIT_DTYPE, device=dev) if unit else None
         hd = torch.empty((T, H), dtype=torch.bfloat16, device=dev) if hidden else None
         lg = torch.empty((B, self.num_labels), dtype=torch.float32, device=dev) if logits else None
+        if spans is not None:
+            sseq, scu, stok, want_f32, want_unit, srho = spans
+            ops._need_gpu(sseq, scu, stok, flat_ids)
+            sseq, scu, stok = (t.to(torch.int32).contiguous() for t in (sseq, scu, stok))
+            S = sseq.numel()
+            if scu.numel() != S + 1:
+                raise ValueError(f"span_cu has {scu.numel()} entries for {S} spans (needs S + 1)")
+            sp = torch.empty((S, H), dtype=torch.float32, device=dev) if want_f32 else None
+            su = torch.empty((S, ops.pad_dim(H)), dtype=ops.UNIT_DTYPE, device=dev) if want_unit else None
         with torch.cuda.device(dev):
             if head is not None:
                 hc = head.c_struct(H)
@@ -288,6 +302,22 @@ class NativeEncoder:
                     p.data_ptr() if p is not None else None, u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
                     rho.data_ptr() if (rho is not None and u is not None) else None, hd.data_ptr() if hd is not None else None,
                     torch.cuda.current_stream(dev).cuda_stream), "encoder_forward_head")
+            elif spans is not None:
+                _lib.check(_lib.lib().tsim_encoder_forward_spans(
+                    self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
+                    cols.data_ptr() if cols is not None else None,
+                    cu.data_ptr(), T, B, int(max_len), p.data_ptr() if p is not None else None,
+                    u.data_ptr() if u is not None else None, u.shape[1] if u is not None else 0,
+                    rho.data_ptr() if (rho is not None and u is not None) else None,
+                    hd.data_ptr() if hd is not None else None, lg.data_ptr() if lg is not None else None,
+                    sseq.data_ptr(), scu.data_ptr(), stok.data_ptr() if stok.numel() else None, S, stok.numel(),
+                    sp.data_ptr() if sp is not None else None, su.data_ptr() if su is not None else None,
+                    su.shape[1] if su is not None else 0, srho.data_ptr() if (srho is not None and su is not None) else None,
+                    torch.cuda.current_stream(dev).cuda_stream), "encoder_forward_spans")
+                if want_f32:
+                    out["spans"] = sp
+                if want_unit:
+                    out["span_unit"] = su
             else:
                 _lib.check(_lib.lib().tsim_encoder_forward_ex(
                     self._h, flat_ids.data_ptr(), types.data_ptr() if types is not None else None, pos.data_ptr(),
@@ -307,6 +337,21 @@ class NativeEncoder:
         if logits:
             out["logits"] = lg
         return out
+
+    def forward_spans(self, flat_ids: torch.Tensor, cu: torch.Tensor, span_seq: torch.Tensor, span_cu: torch.Tensor,
+                      span_tok: torch.Tensor, span_out: bool = True, span_unit: bool = False,
+                      span_rho: Optional[torch.Tensor] = None, pooled: bool = False, **kw):
+        """The packed forward plus word-in-context embeddings (tsim_encoder_forward_spans): span ``s`` belongs to sequence
+        ``span_seq[s]`` and lists the token positions ``span_tok[span_cu[s]:span_cu[s+1]]`` inside it (0 = the first token,
+        [CLS]; any order, repeats count as often as listed), all int32 on the GPU (word_spans.span_table builds them).
+        Adds to the result of :meth:`forward_packed` (whose other arguments pass through ``kw``; no ``head``):
+        'spans' f32 [S, H] = the mean of the final hidden states over each list (an empty list gives a zero row) and
+        'span_unit' float16 [S, pad_dim(H)] = ops.l2norm_rows of those rows, with ``span_rho`` raised as it raises ``rho``.
+        An out-of-range position or sequence is clamped, computed anyway and reported by :meth:`check`."""
+        if span_rho is not None:
+            ops._check_rho(span_rho, flat_ids.device)
+        return self.forward_packed(flat_ids, cu, pooled=pooled, spans=(span_seq, span_cu, span_tok, bool(span_out),
+                                                                       bool(span_unit), span_rho), **kw)
 
     # ------------------------------------------------------------------ padded (HF-style) call
     @staticmethod

@@ -102,7 +102,9 @@ class NativeWordPiece:
             pre_a.ctypes.data if len(pre_a) else None, len(pre_a), suf_a.ctypes.data if len(suf_a) else None, len(suf_a),
             1 if norm.get("lowercase", True) else 0, int(model.get("max_input_chars_per_word", 100)),
             atext, aoff.ctypes.data, len(added), C.byref(h)), "tsim_wordpiece_create")
-        return cls(h, len(prefix_ids) + len(suffix_ids), tokenizer)
+        wp = cls(h, len(prefix_ids) + len(suffix_ids), tokenizer)
+        wp.n_prefix, wp.n_suffix = len(prefix_ids), len(suffix_ids)     # where the special ids sit (word_spans.special_layout)
+        return wp
 
     # ------------------------------------------------------------------------------------------------------------------
     def encode_ascii(self, docs: List[str], max_len: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
