@@ -40,7 +40,7 @@ __device__ __forceinline__ bool rs_before(unsigned long long a, unsigned long lo
     return sa > sb || (sa == sb && (uint32_t)(a >> 32) < (uint32_t)(b >> 32));
 }
 
-// sort e[0..n) by rs_before; n a power of two; a 256-thread workgroup (lk_sort on packed entries); barrier on return
+// sort e[0..n) by rs_before; n a power of two; a 256-thread workgroup (sl_sort on packed entries); barrier on return
 __device__ __forceinline__ void rs_sort(unsigned long long *e, int n) {
     for (int size = 2; size <= n; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
                     const unsigned long long in = slot[e < n ? e : g0];
                     const int row = (int)(in >> 32);
                     const int nvalid = n - g0 < 64 ? n - g0 : 64;
-                    const float es = lk_wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+                    const float es = wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
                     if (e < n) {
                         const float ms = __uint_as_float((uint32_t)in);
                         float err;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int
         for (int64_t g0 = r0 + wave * 64; g0 < r1; g0 += 256) {   // wave-uniform
             const int nvalid = r1 - g0 < 64 ? (int)(r1 - g0) : 64;
             const int row = (int)(g0 + (lane < nvalid ? lane : 0));
-            const float s = lk_wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+            const float s = wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
             const bool hit = lane < nvalid && s >= a.tau;
             const unsigned long long hits = __ballot(hit);
             if (hits == 0) continue;
@@ -236,7 +236,7 @@ constexpr int RS_SORT_T = 1024;
 __device__ __forceinline__ void rs_cmpx(float *s, int64_t *ix, int64_t i, int64_t j) {
     const float si = s[i], sj = s[j];
     const int64_t ii = ix[i], ij = ix[j];
-    if (key_before64(sj, ij, si, ii)) {
+    if (key_before(sj, ij, si, ii)) {
         s[i] = sj;
         s[j] = si;
         ix[i] = ij;

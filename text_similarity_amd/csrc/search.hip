@@ -9,6 +9,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -281,7 +282,8 @@ __device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const
     return __shfl(score, src, 64);
 }
 
-__device__ __forceinline__ bool key_before(float s1, int i1, float s2, int i2) {
+template <typename I>   // int row ids within a shard, int64_t ids across shards
+__device__ __forceinline__ bool key_before(float s1, I i1, float s2, I i2) {
     // true if (s1,i1) ranks strictly ahead of (s2,i2)
     return s1 > s2 || (s1 == s2 && i1 < i2);
 }
@@ -701,20 +703,19 @@ __device__ __forceinline__ void wg_select_topk(const float *sc, const int *ix, i
 }
 
 // =====================================================================================================
-// widen_finalize: one workgroup per FLAGGED query (slot).  Re-scores every entry the widening pass collected for it
-// (every row whose MFMA score exceeded the slot's threshold), selects the exact top-k and repeats the guard with the
-// threshold that was actually used and the errors seen on this larger sample.  An overflowed buffer or a failed guard
-// hands the query to the brute-force pass.
+// The k <= 64 forms of widen_finalize / bf_partial / bf_merge (further down: the sorted-list forms, which take any k): the
+// exact top-k by k rounds of wg_select_topk.  search_tail still sends k <= 64 here: the sorted-list kernels compute the same
+// bits, but their speed at k <= 64 has not been measured against these, and this is the serving path for k = 29 .. 64.
 // =====================================================================================================
 constexpr int COLL_CAP = 1024;   // entries per slot
 
 template <typename T, int SM>
-__global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long long *__restrict__ coll_buf,
-                                                             const int *__restrict__ coll_cnt, int64_t Q, int64_t N,
-                                                             const T *__restrict__ xq, int64_t ldq,
-                                                             const T *__restrict__ xc, int64_t ldc, int d, int k,
-                                                             float *__restrict__ out_s, int64_t *__restrict__ out_i,
-                                                             int64_t idx_offset, GuardArgs g) {
+__global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned long long *__restrict__ coll_buf,
+                                                                 const int *__restrict__ coll_cnt, int64_t Q, int64_t N,
+                                                                 const T *__restrict__ xq, int64_t ldq,
+                                                                 const T *__restrict__ xc, int64_t ldc, int d, int k,
+                                                                 float *__restrict__ out_s, int64_t *__restrict__ out_i,
+                                                                 int64_t idx_offset, GuardArgs g) {
     constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
     __shared__ float sc[COLL_CAP];
     __shared__ int ix[COLL_CAP];
@@ -779,20 +780,15 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
     }
 }
 
-// =====================================================================================================
-// Brute-force exact pass for the queries nothing else resolved: every row of the shard is scored exactly.
-//   bf_partial: workgroup (chunk c, slot u): rows of chunk c in blocks of BF_SB; a running exact top-k per chunk.
-//   bf_merge:   one workgroup per slot merges the NCH chunk lists and writes the query's final list.
-// HBM-bound (N*d*4 bytes per query); last resort, and the serving path for k > 28 on small shards.
-// =====================================================================================================
+// brute force, k <= 64: rows of a chunk in blocks of BF_SB, a running exact top-k per chunk; chunk lists pad with (-inf, -1)
 constexpr int BF_SB = 2048;
 constexpr int BF_MAXK = 64;
 
 template <typename T, bool COS>
-__global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, int rows_per_chunk,
-                                                         const T *__restrict__ xq, int64_t ldq,
-                                                         const T *__restrict__ xc, int64_t ldc, int d, int k,
-                                                         float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
+__global__ __launch_bounds__(256) void bf_partial_k64_kernel(int64_t Q, int64_t N, int rows_per_chunk,
+                                                             const T *__restrict__ xq, int64_t ldq,
+                                                             const T *__restrict__ xc, int64_t ldc, int d, int k,
+                                                             float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
     __shared__ float sc[BF_SB + BF_MAXK];
     __shared__ int ix[BF_SB + BF_MAXK];
     __shared__ float top_s[BF_MAXK];
@@ -842,9 +838,9 @@ __global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, i
     }
 }
 
-__global__ __launch_bounds__(256) void bf_merge_kernel(int64_t Q, int nch, int k, const float *__restrict__ bf_s,
-                                                       const int *__restrict__ bf_i, float *__restrict__ out_s,
-                                                       int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
+__global__ __launch_bounds__(256) void bf_merge_k64_kernel(int64_t Q, int nch, int k, const float *__restrict__ bf_s,
+                                                           const int *__restrict__ bf_i, float *__restrict__ out_s,
+                                                           int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
     __shared__ float red_s[4];
     __shared__ int red_i[4];
     int nu = g.ctl[CTL_NUNRES];
@@ -947,10 +943,6 @@ static void launch_thr_select(const float *bmax, int P2, int64_t Q, int KL, int 
 // =====================================================================================================
 // merge of sorted per-shard / per-chunk lists: [nlists, Q, k_in] -> [Q, k_out]; one wave per query.
 // =====================================================================================================
-__device__ __forceinline__ bool key_before64(float s1, int64_t i1, float s2, int64_t i2) {
-    return s1 > s2 || (s1 == s2 && i1 < i2);
-}
-
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict__ scores,
                                                          const int64_t *__restrict__ idx, int nlists,
                                                          int64_t Q, int k_in, int k_out,
@@ -971,7 +963,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
             const int64_t off = q * k_in + j;
             const float s = scores[(int64_t)l * lstride_s + off];
             const int64_t i = idx[(int64_t)l * lstride_i + off];
-            if (i >= 0 && key_before64(last_s, last_i, s, i) && key_before64(s, i, bs, bi)) {
+            if (i >= 0 && key_before(last_s, last_i, s, i) && key_before(s, i, bs, bi)) {
                 bs = s;
                 bi = i;
             }
@@ -980,7 +972,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
         for (int o = 32; o > 0; o >>= 1) {
             const float os = __shfl_xor(bs, o, 64);
             const int64_t oi = __shfl_xor(bi, o, 64);
-            if (key_before64(os, oi, bs, bi)) {
+            if (key_before(os, oi, bs, bi)) {
                 bs = os;
                 bi = oi;
             }
@@ -1001,36 +993,33 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
 }
 
 // =====================================================================================================
-// k > 64 (tsim_cosine_topk_large / tsim_dot_topk_large, tsim_topk_merge_strided with k_out > 64).  The threshold and collect
-// stages are those of the k > 28 path (flag_all_kernel); what changes is everything that held k entries: lists live in LDS
-// sorted by (score desc, index asc), new entries are sorted with a bitonic network and merged in by rank (each entry's place
-// in the other list by binary search), never selected one round at a time.  Padding is (-inf, PAD): it ranks behind every
-// real entry, a real entry with score -inf included; NaN scores become padding (the list kernels never select them either).
+// Sorted lists in LDS (sl_*): what the widening pass, the brute-force pass (any k up to 1 024) and tsim_topk_merge_strided
+// with k_out > 64 keep their entries in.  Lists are sorted by (score desc, index asc), new entries are sorted with a bitonic
+// network and merged in by rank (each entry's place in the other list by binary search), never selected one round at a time.
+// Padding is (-inf, PAD): it ranks behind every real entry, a real entry with score -inf included; NaN scores become padding
+// (the list kernels never select them either).
 // =====================================================================================================
-constexpr int LK_MAX_K = 1024;   // TSIM_TOPK_MAX_K
-constexpr int LK_NB = 1024;      // entries of one block merged into a running list
+constexpr int SL_MAX_K = 1024;   // TSIM_TOPK_MAX_K
+constexpr int SL_NB = 1024;      // entries of one block merged into a running list
 
 template <typename I>
-__device__ __forceinline__ I lk_pad();
+__device__ __forceinline__ I sl_pad();
 template <>
-__device__ __forceinline__ int lk_pad<int>() { return 0x7fffffff; }
+__device__ __forceinline__ int sl_pad<int>() { return 0x7fffffff; }
 template <>
-__device__ __forceinline__ int64_t lk_pad<int64_t>() { return INT64_MAX; }
-
-template <typename I>
-__device__ __forceinline__ bool lk_before(float s1, I i1, float s2, I i2) { return s1 > s2 || (s1 == s2 && i1 < i2); }
+__device__ __forceinline__ int64_t sl_pad<int64_t>() { return INT64_MAX; }
 
 // sort s/ix[0..n) by (score desc, index asc); n a power of two; a 256-thread workgroup; entries written before the call
 // must be behind a barrier, and the sorted list is behind one on return
 template <typename I>
-__device__ __forceinline__ void lk_sort(float *s, I *ix, int n) {
+__device__ __forceinline__ void sl_sort(float *s, I *ix, int n) {
     for (int size = 2; size <= n; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = threadIdx.x; t < n / 2; t += 256) {
                 const int i = 2 * t - (t & (stride - 1)), j = i + stride;
                 const float si = s[i], sj = s[j];
                 const I ii = ix[i], ij = ix[j];
-                if ((i & size) == 0 ? lk_before(sj, ij, si, ii) : lk_before(si, ii, sj, ij)) {
+                if ((i & size) == 0 ? key_before(sj, ij, si, ii) : key_before(si, ii, sj, ij)) {
                     s[i] = sj;
                     s[j] = si;
                     ix[i] = ij;
@@ -1043,11 +1032,11 @@ __device__ __forceinline__ void lk_sort(float *s, I *ix, int n) {
 
 // number of entries of the sorted list a[0..n) that rank before (s, i) (LE: before it or equal to it)
 template <typename I, bool LE>
-__device__ __forceinline__ int lk_count(const float *as, const I *ai, int n, float s, I i) {
+__device__ __forceinline__ int sl_count(const float *as, const I *ai, int n, float s, I i) {
     int lo = 0, hi = n;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        const bool p = LE ? !lk_before(s, i, as[mid], ai[mid]) : lk_before(as[mid], ai[mid], s, i);
+        const bool p = LE ? !key_before(s, i, as[mid], ai[mid]) : key_before(as[mid], ai[mid], s, i);
         lo = p ? mid + 1 : lo;
         hi = p ? hi : mid;
     }
@@ -1060,7 +1049,7 @@ __device__ __forceinline__ int lk_count(const float *as, const I *ai, int n, flo
 // DEDUP (tsim_topk_merge): an entry equal in (score, index) to the one before it in the merged order is dropped, and the
 // list is refilled with padding behind the survivors.  m_s / m_i: kp + nb entries of scratch; wsum: 4 ints.
 template <typename I, bool DEDUP>
-__device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *bs, const I *bi, int nb, float *m_s, I *m_i,
+__device__ __forceinline__ void sl_merge(float *ts, I *ti, int kp, const float *bs, const I *bi, int nb, float *m_s, I *m_i,
                                          int *wsum) {
     constexpr int R = 2048 / 256;
     float vs[R] = {};
@@ -1073,11 +1062,11 @@ __device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *
         if (t < kp) {
             vs[r] = ts[t];
             vi[r] = ti[t];
-            rk[r] = t + lk_count<I, false>(bs, bi, nb, vs[r], vi[r]);
+            rk[r] = t + sl_count<I, false>(bs, bi, nb, vs[r], vi[r]);
         } else if (t < kp + nb) {
             vs[r] = bs[t - kp];
             vi[r] = bi[t - kp];
-            if (vi[r] != lk_pad<I>()) rk[r] = t - kp + lk_count<I, true>(ts, ti, kp, vs[r], vi[r]);   // (padding: rank >= kp)
+            if (vi[r] != sl_pad<I>()) rk[r] = t - kp + sl_count<I, true>(ts, ti, kp, vs[r], vi[r]);   // (padding: rank >= kp)
         }
     }
     __syncthreads();
@@ -1093,7 +1082,7 @@ __device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *
         const int n = kp + nb;
         for (int t = threadIdx.x; t < n; t += 256) {   // block padding never got a rank: it is all alike
             m_s[t] = -INFINITY;
-            m_i[t] = lk_pad<I>();
+            m_i[t] = sl_pad<I>();
         }
         __syncthreads();
 #pragma unroll
@@ -1109,7 +1098,7 @@ __device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *
 #pragma unroll
         for (int e = 0; e < PER; ++e) {
             const int p = threadIdx.x * PER + e;
-            keep |= (p < n && m_i[p] != lk_pad<I>() && !(p > 0 && m_s[p] == m_s[p - 1] && m_i[p] == m_i[p - 1])) << e;
+            keep |= (p < n && m_i[p] != sl_pad<I>() && !(p > 0 && m_s[p] == m_s[p - 1] && m_i[p] == m_i[p - 1])) << e;
         }
         const int mine = __popc(keep);
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1140,7 +1129,7 @@ __device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *
         }
         for (int t = total + threadIdx.x; t < kp; t += 256) {
             ts[t] = -INFINITY;
-            ti[t] = lk_pad<I>();
+            ti[t] = sl_pad<I>();
         }
         __syncthreads();
     }
@@ -1148,8 +1137,8 @@ __device__ __forceinline__ void lk_merge(float *ts, I *ti, int kp, const float *
 
 // Append (s, i) to the block b (LDS counter *nb) when it ranks before the list's k-th entry (ws, wi); NaN is dropped.
 template <typename I>
-__device__ __forceinline__ void lk_offer(float *bs, I *bi, int *nb, float s, I i, float ws, I wi) {
-    if (s == s && lk_before(s, i, ws, wi)) {
+__device__ __forceinline__ void sl_offer(float *bs, I *bi, int *nb, float s, I i, float ws, I wi) {
+    if (s == s && key_before(s, i, ws, wi)) {
         const int p = atomicAdd(nb, 1);
         bs[p] = s;
         bi[p] = i;
@@ -1158,22 +1147,22 @@ __device__ __forceinline__ void lk_offer(float *bs, I *bi, int *nb, float s, I i
 
 // Sort the block (n entries, padded to a power of two) and merge it into the running list; workgroup-uniform n.
 template <typename I, bool DEDUP>
-__device__ __forceinline__ void lk_absorb(float *ts, I *ti, int kp, float *bs, I *bi, int n, float *m_s, I *m_i, int *wsum) {
+__device__ __forceinline__ void sl_absorb(float *ts, I *ti, int kp, float *bs, I *bi, int n, float *m_s, I *m_i, int *wsum) {
     int np = 1;
     while (np < n) np <<= 1;
     for (int t = n + threadIdx.x; t < np; t += 256) {
         bs[t] = -INFINITY;
-        bi[t] = lk_pad<I>();
+        bi[t] = sl_pad<I>();
     }
     __syncthreads();
-    lk_sort(bs, bi, np);
-    lk_merge<I, DEDUP>(ts, ti, kp, bs, bi, np, m_s, m_i, wsum);
+    sl_sort(bs, bi, np);
+    sl_merge<I, DEDUP>(ts, ti, kp, bs, bi, np, m_s, m_i, wsum);
 }
 
 // Exact scores of the rows held by lanes 0 .. nvalid-1 (my_i), eight at a time (exact_score_batch: the bits of exact_score).
 template <typename T, bool COS>
-__device__ __forceinline__ float lk_wave_scores(const ExactQuery<T> &q, const T *xc, int64_t ldc, int my_i, int nvalid, int d,
-                                                int lane) {
+__device__ __forceinline__ float wave_scores(const ExactQuery<T> &q, const T *xc, int64_t ldc, int my_i, int nvalid, int d,
+                                             int lane) {
     constexpr int NB = 8;
     float mine = 0.f;
     for (int t0 = 0; t0 < nvalid; t0 += NB) {
@@ -1183,16 +1172,19 @@ __device__ __forceinline__ float lk_wave_scores(const ExactQuery<T> &q, const T 
     return mine;
 }
 
-// widen_finalize for k > 64: one workgroup per flagged slot.  Every collected row (at most cap, a power of two >= 4k) is
-// re-scored exactly, the entries are sorted in LDS, the first k written; the guard is widen_finalize_kernel's.
-// Dynamic LDS: cap floats + cap ints.
+// =====================================================================================================
+// widen_finalize: one workgroup per FLAGGED query (slot).  Re-scores every entry the widening pass collected for it (every
+// row whose MFMA score exceeded the slot's threshold; at most cap, a power of two >= 4k), sorts the entries in LDS, writes the
+// first k and repeats the guard with the threshold that was actually used and the errors seen on this larger sample.  An
+// overflowed buffer or a failed guard hands the query to the brute-force pass.  Dynamic LDS: cap floats + cap ints.
+// =====================================================================================================
 template <typename T, int SM>
-__global__ __launch_bounds__(256) void widen_finalize_large_kernel(const unsigned long long *__restrict__ coll_buf,
-                                                                   const int *__restrict__ coll_cnt, int cap, int64_t Q,
-                                                                   const T *__restrict__ xq, int64_t ldq,
-                                                                   const T *__restrict__ xc, int64_t ldc, int d, int k,
-                                                                   float *__restrict__ out_s, int64_t *__restrict__ out_i,
-                                                                   int64_t idx_offset, GuardArgs g) {
+__global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long long *__restrict__ coll_buf,
+                                                             const int *__restrict__ coll_cnt, int cap, int64_t Q,
+                                                             const T *__restrict__ xq, int64_t ldq,
+                                                             const T *__restrict__ xc, int64_t ldc, int d, int k,
+                                                             float *__restrict__ out_s, int64_t *__restrict__ out_i,
+                                                             int64_t idx_offset, GuardArgs g) {
     constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *sc = reinterpret_cast<float *>(smem);
@@ -1221,7 +1213,7 @@ __global__ __launch_bounds__(256) void widen_finalize_large_kernel(const unsigne
                     const unsigned long long ent = coll_buf[(int64_t)slot * cap + (e < n ? e : g0)];
                     const int my_row = (int)(ent >> 32);
                     const int nvalid = n - g0 < 64 ? n - g0 : 64;
-                    const float es = lk_wave_scores<T, COS>(eqr, xc, ldc, my_row, nvalid, d, lane);
+                    const float es = wave_scores<T, COS>(eqr, xc, ldc, my_row, nvalid, d, lane);
                     if (e < n) {
                         const float ms = __uint_as_float((uint32_t)ent);
                         if constexpr (DOT) err = fmaxf(err, (float)fabs((double)ms - (double)es / nqs));
@@ -1238,13 +1230,16 @@ __global__ __launch_bounds__(256) void widen_finalize_large_kernel(const unsigne
             err = wave_max(err);
             if (lane == 0) s_err[wave] = err;
             __syncthreads();
-            lk_sort(sc, ix, np);
+            sl_sort(sc, ix, np);
             for (int t = threadIdx.x; t < k; t += 256) {
                 const int row = ix[t];
                 out_s[(int64_t)q * k + t] = row == 0x7fffffff ? -INFINITY : sc[t];
                 out_i[(int64_t)q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
             }
-            // the guard of widen_finalize_kernel, on the k-th entry
+            // guard again with the threshold the collection used: every row that was NOT collected has an MFMA score below
+            // it, hence an exact score below thr + eps.  COS: eps is the query's bound from the first pass (and it must hold on
+            // everything that was re-scored here, else the inputs are inconsistent -> brute force); unit rows only: the largest
+            // difference seen on this larger sample with half the safety factor of the first pass (not below 1).
             const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
             float eps;
             if constexpr (COS || DOT) {
@@ -1266,16 +1261,21 @@ __global__ __launch_bounds__(256) void widen_finalize_large_kernel(const unsigne
     }
 }
 
-// Brute force for k > 64.  bf_large_partial: workgroup (chunk c, slot u) scores the chunk's rows exactly in blocks of LK_NB and
-// keeps a running sorted list of kp >= k entries in LDS (only rows ahead of its k-th entry are sorted and merged in); writes
-// the first k, sorted, padding (-inf, INT_MAX) included.  bf_large_merge: one workgroup per slot merges the chunk lists.
+// =====================================================================================================
+// Brute-force exact pass for the queries nothing else resolved: every row of the shard is scored exactly.
+//   bf_partial: workgroup (chunk c, slot u) scores the chunk's rows in blocks of SL_NB and keeps a running sorted list of
+//               kp >= k entries in LDS (only rows ahead of its k-th entry are sorted and merged in); writes the first k,
+//               sorted, padding (-inf, INT_MAX) included.
+//   bf_merge:   one workgroup per slot merges the chunk lists and writes the query's final list.
+// HBM-bound (N*d*4 bytes per query); last resort, and the serving path for k > 28 on small shards.
+// =====================================================================================================
 template <typename T, bool COS>
-__global__ __launch_bounds__(256) void bf_large_partial_kernel(int64_t Q, int64_t N, int rows_per_chunk,
-                                                               const T *__restrict__ xq, int64_t ldq,
-                                                               const T *__restrict__ xc, int64_t ldc, int d, int k, int kp,
-                                                               float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
-    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB];
-    __shared__ int top_i[LK_MAX_K], blk_i[LK_NB];
+__global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, int rows_per_chunk,
+                                                         const T *__restrict__ xq, int64_t ldq,
+                                                         const T *__restrict__ xc, int64_t ldc, int d, int k, int kp,
+                                                         float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
+    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
+    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
     __shared__ int s_nb;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = gridDim.x, chunk = blockIdx.x;
@@ -1293,20 +1293,20 @@ __global__ __launch_bounds__(256) void bf_large_partial_kernel(int64_t Q, int64_
         }
         if (threadIdx.x == 0) s_nb = 0;
         __syncthreads();
-        for (int64_t b = r0; b < r1; b += LK_NB) {
-            const int nb = (int)(r1 - b < LK_NB ? r1 - b : LK_NB);
+        for (int64_t b = r0; b < r1; b += SL_NB) {
+            const int nb = (int)(r1 - b < SL_NB ? r1 - b : SL_NB);
             const float ws = top_s[k - 1];
             const int wi = top_i[k - 1];
             for (int g0 = wave * 64; g0 < nb; g0 += 256) {   // wave-uniform
                 const int e = g0 + lane;
                 const int nvalid = nb - g0 < 64 ? nb - g0 : 64;
                 const int row = (int)(b + (e < nb ? e : g0));
-                const float s = lk_wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
-                if (e < nb) lk_offer(blk_s, blk_i, &s_nb, s, row, ws, wi);
+                const float s = wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+                if (e < nb) sl_offer(blk_s, blk_i, &s_nb, s, row, ws, wi);
             }
             __syncthreads();
             const int n = s_nb;
-            if (n > 0) lk_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
+            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
             if (threadIdx.x == 0) s_nb = 0;
             __syncthreads();
         }
@@ -1318,11 +1318,11 @@ __global__ __launch_bounds__(256) void bf_large_partial_kernel(int64_t Q, int64_
     }
 }
 
-__global__ __launch_bounds__(256) void bf_large_merge_kernel(int64_t Q, int nch, int k, int kp, const float *__restrict__ bf_s,
-                                                             const int *__restrict__ bf_i, float *__restrict__ out_s,
-                                                             int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
-    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB];
-    __shared__ int top_i[LK_MAX_K], blk_i[LK_NB];
+__global__ __launch_bounds__(256) void bf_merge_kernel(int64_t Q, int nch, int k, int kp, const float *__restrict__ bf_s,
+                                                       const int *__restrict__ bf_i, float *__restrict__ out_s,
+                                                       int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
+    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
+    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
     __shared__ int s_nb;
     int nu = g.ctl[CTL_NUNRES];
     nu = nu < Q ? nu : (int)Q;
@@ -1339,11 +1339,11 @@ __global__ __launch_bounds__(256) void bf_large_merge_kernel(int64_t Q, int nch,
             const int wi = top_i[k - 1];
             for (int t = threadIdx.x; t < k; t += 256) {
                 const int64_t at = ((int64_t)u * nch + c) * k + t;
-                lk_offer(blk_s, blk_i, &s_nb, bf_s[at], bf_i[at], ws, wi);
+                sl_offer(blk_s, blk_i, &s_nb, bf_s[at], bf_i[at], ws, wi);
             }
             __syncthreads();
             const int n = s_nb;
-            if (n > 0) lk_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
+            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
             if (threadIdx.x == 0) s_nb = 0;
             __syncthreads();
         }
@@ -1357,14 +1357,14 @@ __global__ __launch_bounds__(256) void bf_large_merge_kernel(int64_t Q, int nch,
     }
 }
 
-// topk_merge for 64 < k_out <= 1024: one workgroup per query; the nlists * k_in entries pass in blocks of LK_NB through the
+// topk_merge for 64 < k_out <= 1024: one workgroup per query; the nlists * k_in entries pass in blocks of SL_NB through the
 // running list (kp >= k_out) with duplicates of (score, index) dropped.  Same output as topk_merge_kernel.
 __global__ __launch_bounds__(256) void topk_merge_large_kernel(const float *__restrict__ scores, const int64_t *__restrict__ idx,
                                                                int nlists, int64_t Q, int k_in, int k_out, int kp,
                                                                int64_t lstride_s, int64_t lstride_i, float *__restrict__ out_s,
                                                                int64_t *__restrict__ out_i) {
-    __shared__ float top_s[LK_MAX_K], blk_s[LK_NB], m_s[LK_MAX_K + LK_NB];
-    __shared__ int64_t top_i[LK_MAX_K], blk_i[LK_NB], m_i[LK_MAX_K + LK_NB];
+    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB], m_s[SL_MAX_K + SL_NB];
+    __shared__ int64_t top_i[SL_MAX_K], blk_i[SL_NB], m_i[SL_MAX_K + SL_NB];
     __shared__ int s_nb, wsum[4];
     const int64_t E = (int64_t)nlists * k_in;
     for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
@@ -1374,18 +1374,18 @@ __global__ __launch_bounds__(256) void topk_merge_large_kernel(const float *__re
         }
         if (threadIdx.x == 0) s_nb = 0;
         __syncthreads();
-        for (int64_t e0 = 0; e0 < E; e0 += LK_NB) {
+        for (int64_t e0 = 0; e0 < E; e0 += SL_NB) {
             const float ws = top_s[k_out - 1];
             const int64_t wi = top_i[k_out - 1];
-            for (int64_t e = e0 + threadIdx.x; e < E && e < e0 + LK_NB; e += 256) {
+            for (int64_t e = e0 + threadIdx.x; e < E && e < e0 + SL_NB; e += 256) {
                 const int l = (int)(e / k_in), j = (int)(e % k_in);
                 const int64_t off = q * k_in + j;
                 const int64_t i = idx[(int64_t)l * lstride_i + off];
-                if (i >= 0) lk_offer(blk_s, blk_i, &s_nb, scores[(int64_t)l * lstride_s + off], i, ws, wi);
+                if (i >= 0) sl_offer(blk_s, blk_i, &s_nb, scores[(int64_t)l * lstride_s + off], i, ws, wi);
             }
             __syncthreads();
             const int n = s_nb;
-            if (n > 0) lk_absorb<int64_t, true>(top_s, top_i, kp, blk_s, blk_i, n, m_s, m_i, wsum);
+            if (n > 0) sl_absorb<int64_t, true>(top_s, top_i, kp, blk_s, blk_i, n, m_s, m_i, wsum);
             if (threadIdx.x == 0) s_nb = 0;
             __syncthreads();
         }
@@ -1575,16 +1575,23 @@ extern "C" void tsim_time_next_topk(void *start_event, void *stop_event) {
 
 namespace tsim {
 constexpr int TOPK_MAX_LISTS = 28;   // largest k the list kernels (KL = 32) serve
-constexpr int TOPK_MAX_K = BF_MAXK;  // largest k of tsim_cosine_topk_ex / tsim_dot_topk_ex (widening / brute-force passes)
+constexpr int TOPK_MAX_K = 64;       // largest k of tsim_cosine_topk_ex / tsim_dot_topk_ex / tsim_cosine_topk_workspace_bytes
 constexpr int TOPK_LARGE_MAX_K = TSIM_TOPK_MAX_K;   // largest k of the _large entries
-static_assert(TOPK_LARGE_MAX_K == LK_MAX_K, "LDS lists of the k > 64 kernels");
+static_assert(TOPK_LARGE_MAX_K == SL_MAX_K, "LDS lists of the brute-force kernels");
+static_assert(TOPK_MAX_K == BF_MAXK && COLL_CAP == 1024, "the k <= 64 kernels: plan_workspace gives cap = 1 024 there");
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Workspace layout of one search call (byte offsets).
+// Workspace of one search call: byte offsets, and the sizes the widening and brute-force passes run with.
+//   part_s / part_i: partial lists of the list kernels; empty for k > 28.
+//   cap: collect-buffer entries per slot, the smallest power of two >= 4k and >= 1 024 (the bound of flag_all_kernel sits near
+//        rank 1.4 k on Gaussian rows, the 2 eps band adds a few hundred).  kp: LDS list length of the brute-force pass.
+//   bf_nch chunks of bf_rows rows in the brute-force pass: at most 64, of at least 256 rows; for k > 64 of at least SL_NB rows
+//        and no more than keep the chunk lists (Q x chunks x k entries of 8 B) within BF_BUDGET.
+constexpr size_t BF_BUDGET = (size_t)256 << 20;
 struct SearchWs {
     size_t part_s, part_i, gthr, bmax, ctl, flag_q, flag_thr, flag_eps, unres_q, coll_cnt, coll_buf, bf_s, bf_i, total;
-    int bf_nch, bf_rows;
+    int cap, kp, bf_nch, bf_rows;
 };
 
 static void plan_workspace(int64_t Q, int64_t N, int k, SearchWs *w) {
@@ -1602,53 +1609,22 @@ static void plan_workspace(int64_t Q, int64_t N, int k, SearchWs *w) {
             if (e > part) part = e;
         }
     }
-    int nch = (int)((N + 255) / 256);
-    w->bf_nch = nch < 64 ? (nch < 1 ? 1 : nch) : 64;
-    w->bf_rows = (int)((N + w->bf_nch - 1) / w->bf_nch);
+    w->cap = 1024;
+    while (w->cap < 4 * k) w->cap <<= 1;
+    w->kp = 64;
+    while (w->kp < k) w->kp <<= 1;
+    const bool large = k > TOPK_MAX_K;
+    const int64_t min_rows = large ? SL_NB : 256, within_budget = large ? (int64_t)(BF_BUDGET / ((size_t)Q * k * 8)) : 64;
+    const int64_t nch = std::max<int64_t>(1, std::min<int64_t>({64, (N + min_rows - 1) / min_rows, within_budget}));
+    w->bf_nch = (int)nch;
+    w->bf_rows = (int)((N + nch - 1) / nch);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
     w->part_s = take(part * 4);
     w->part_i = take(part * 4);
     w->gthr = take((size_t)Q * 4);
     w->bmax = take((size_t)Q * K1_PREPASS_MAX_P2 * 4);
-    w->ctl = take(CTL_WORDS * 4);
-    w->flag_q = take((size_t)Q * 4);
-    w->flag_thr = take((size_t)Q * 4);
-    w->flag_eps = take((size_t)Q * 4);
-    w->unres_q = take((size_t)Q * 4);
-    w->coll_cnt = take((size_t)Q * 4);
-    w->coll_buf = take((size_t)Q * COLL_CAP * 8);
-    w->bf_s = take((size_t)Q * w->bf_nch * k * 4);
-    w->bf_i = take((size_t)Q * w->bf_nch * k * 4);
-    w->total = o;
-}
-
-// Workspace of a k > 64 call.  cap: collect-buffer entries per slot, the smallest power of two >= 4k and >= 1 024 (the bound
-// of flag_all_kernel sits near rank 1.4 k on Gaussian rows, the 2 eps band adds a few hundred).  kp: LDS list length of the
-// brute-force pass.  Its chunk lists (Q x chunks x k entries of 8 B) are held to BFL_BUDGET by using fewer chunks.
-constexpr size_t BFL_BUDGET = (size_t)256 << 20;
-struct LargeWs {
-    size_t gthr, bmax, ctl, flag_q, flag_thr, flag_eps, unres_q, coll_cnt, coll_buf, bf_s, bf_i, total;
-    int cap, kp, bf_nch, bf_rows;
-};
-
-static void plan_workspace_large(int64_t Q, int64_t N, int k, LargeWs *w) {
-    w->cap = 1024;
-    while (w->cap < 4 * k) w->cap <<= 1;
-    w->kp = 64;
-    while (w->kp < k) w->kp <<= 1;
-    int64_t nch = (int64_t)(BFL_BUDGET / ((size_t)Q * k * 8));
-    const int64_t max_ch = (N + LK_NB - 1) / LK_NB;
-    if (nch > 64) nch = 64;
-    if (nch > max_ch) nch = max_ch;
-    if (nch < 1) nch = 1;
-    w->bf_nch = (int)nch;
-    w->bf_rows = (int)((N + nch - 1) / nch);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    w->gthr = take((size_t)Q * 4);
-    w->bmax = take((size_t)Q * K1_PREPASS_MAX_P2 * 4);
-    w->ctl = take(CTL_WORDS * 4);   // ctl .. coll_cnt contiguous: one memset
+    w->ctl = take(CTL_WORDS * 4);   // ctl .. coll_cnt contiguous: cleared together, coll_buf - ctl bytes
     w->flag_q = take((size_t)Q * 4);
     w->flag_thr = take((size_t)Q * 4);
     w->flag_eps = take((size_t)Q * 4);
@@ -1713,78 +1689,89 @@ static bool plan_two_phase(int64_t Q, int64_t N, int D, int k, TopkPlan *pa, Top
     return true;
 }
 
-template <typename T, int SM>
-static int search_tail(const SearchWs &w, char *ws, int64_t Q, int64_t N, const unit_t *eq, const unit_t *ec, int ld,
-                       const T *xq, int64_t ldq, const T *xc, int64_t ldc, int d, int k, float *out_s, int64_t *out_i,
-                       int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
-    // widening pass + its finalisation (workgroups leave at once when nothing was flagged) ...
-    if (run_collect) {
-        TopkPlan cp;
-        plan_collect(Q, N, ld, &cp);
-        K1Collect coll{};
-        coll.qcount = g.ctl + CTL_NFLAG;
-        coll.qmap = g.flag_q;
-        coll.buf = reinterpret_cast<unsigned long long *>(ws + w.coll_buf);
-        coll.cnt = reinterpret_cast<int *>(ws + w.coll_cnt);
-        coll.cap = COLL_CAP;
-        int rc = k1_launch_collect(cp, ld, eq, Q, ec, N, g.flag_thr, coll, st);
-        if (rc) return rc;
-        const unsigned wg = (unsigned)(Q < 2048 ? Q : 2048);
-        hipLaunchKernelGGL((widen_finalize_kernel<T, SM>), dim3(wg), dim3(256), 0, st, coll.buf, coll.cnt, Q, N, xq, ldq, xc,
-                           ldc, d, k, out_s, out_i, idx_offset, g);
-        TSIM_HIP_CHECK(hipGetLastError());
-    }
-    // ... and the brute-force pass for whatever is still unresolved
-    float *bf_s = reinterpret_cast<float *>(ws + w.bf_s);
-    int *bf_i = reinterpret_cast<int *>(ws + w.bf_i);
-    const unsigned us = (unsigned)(Q < 64 ? Q : 64);
-    // (brute force has no guard: DOT scores exactly like UNIT, on the float32 rows)
-    hipLaunchKernelGGL((bf_partial_kernel<T, SM == SM_COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, xq, ldq, xc, ldc, d, k,
-                       bf_s, bf_i, g);
-    TSIM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(bf_merge_kernel, dim3((unsigned)(Q < 1024 ? Q : 1024)), dim3(256), 0, st, Q, w.bf_nch, k, bf_s, bf_i,
-                       out_s, out_i, idx_offset, g);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
+// The operands of one search call, and the rows its exact scores are taken from: the float32 rows (SM_COS, SM_DOT) or the unit
+// rows themselves (SM_UNIT, d = ld).
+struct SearchOperands {
+    const unit_t *uq, *uc;
+    const float *q_f32, *c_f32;
+    int64_t ldq_f32, ldc_f32;
+    int d, ld;
+};
+template <typename T>
+struct ExactRows {
+    using row_t = T;
+    const T *xq;
+    int64_t ldq;
+    const T *xc;
+    int64_t ldc;
+    int d;
+};
+
+// The one place the runtime score mode becomes a compile-time one: f(ExactRows<T>, std::integral_constant<int, SM>).
+template <typename F>
+static void with_score_mode(int sm, const SearchOperands &o, F f) {
+    const ExactRows<float> rf{o.q_f32, o.ldq_f32, o.c_f32, o.ldc_f32, o.d};   // (null rows in SM_UNIT, where it is not used)
+    if (sm == SM_COS) f(rf, std::integral_constant<int, SM_COS>{});
+    else if (sm == SM_DOT) f(rf, std::integral_constant<int, SM_DOT>{});
+    else f(ExactRows<unit_t>{o.uq, o.ld, o.uc, o.ld, o.ld}, std::integral_constant<int, SM_UNIT>{});
 }
 
-// k > 64: collect with the call's capacity, re-score and sort per slot, then brute force for what is left (all launches leave at
-// once when there is nothing to do)
-template <typename T, int SM>
-static int search_tail_large(const LargeWs &w, char *ws, int64_t Q, int64_t N, const unit_t *eq, const unit_t *ec, int ld,
-                             const T *xq, int64_t ldq, const T *xc, int64_t ldc, int d, int k, float *out_s, int64_t *out_i,
-                             int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
+// Widening pass + its finalisation, then the brute-force pass for whatever is still unresolved (all launches leave at once
+// when there is nothing to do)
+static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N, const SearchOperands &o, int k, float *out_s,
+                       int64_t *out_i, int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
+    // k <= 64 keeps its arg-max kernels (same workspace: w.cap = COLL_CAP there) until the sorted-list ones, which give the same
+    // bits, have been measured against them at these k
+    const bool k64 = k <= TOPK_MAX_K;
     if (run_collect) {
         TopkPlan cp;
-        plan_collect(Q, N, ld, &cp);
+        plan_collect(Q, N, o.ld, &cp);
         K1Collect coll{};
         coll.qcount = g.ctl + CTL_NFLAG;
         coll.qmap = g.flag_q;
         coll.buf = reinterpret_cast<unsigned long long *>(ws + w.coll_buf);
         coll.cnt = reinterpret_cast<int *>(ws + w.coll_cnt);
         coll.cap = w.cap;
-        int rc = k1_launch_collect(cp, ld, eq, Q, ec, N, g.flag_thr, coll, st);
+        int rc = k1_launch_collect(cp, o.ld, o.uq, Q, o.uc, N, g.flag_thr, coll, st);
         if (rc) return rc;
         const unsigned wg = (unsigned)(Q < 2048 ? Q : 2048);
-        hipLaunchKernelGGL((widen_finalize_large_kernel<T, SM>), dim3(wg), dim3(256), (size_t)w.cap * 8, st, coll.buf, coll.cnt,
-                           w.cap, Q, xq, ldq, xc, ldc, d, k, out_s, out_i, idx_offset, g);
+        with_score_mode(sm, o, [&](auto x, auto smc) {
+            using T = typename decltype(x)::row_t;
+            constexpr int SM = decltype(smc)::value;
+            if (k64)
+                hipLaunchKernelGGL((widen_finalize_k64_kernel<T, SM>), dim3(wg), dim3(256), 0, st, coll.buf, coll.cnt, Q, N, x.xq,
+                                   x.ldq, x.xc, x.ldc, x.d, k, out_s, out_i, idx_offset, g);
+            else
+                hipLaunchKernelGGL((widen_finalize_kernel<T, SM>), dim3(wg), dim3(256), (size_t)w.cap * 8, st, coll.buf, coll.cnt,
+                                   w.cap, Q, x.xq, x.ldq, x.xc, x.ldc, x.d, k, out_s, out_i, idx_offset, g);
+        });
         TSIM_HIP_CHECK(hipGetLastError());
     }
     float *bf_s = reinterpret_cast<float *>(ws + w.bf_s);
     int *bf_i = reinterpret_cast<int *>(ws + w.bf_i);
     const unsigned us = (unsigned)(Q < 64 ? Q : 64);
-    hipLaunchKernelGGL((bf_large_partial_kernel<T, SM == SM_COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, xq, ldq,
-                       xc, ldc, d, k, w.kp, bf_s, bf_i, g);
+    // (brute force has no guard: DOT scores exactly like UNIT, on the float32 rows)
+    with_score_mode(sm, o, [&](auto x, auto smc) {
+        using T = typename decltype(x)::row_t;
+        constexpr bool COS = decltype(smc)::value == SM_COS;
+        if (k64)
+            hipLaunchKernelGGL((bf_partial_k64_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, x.xq, x.ldq,
+                               x.xc, x.ldc, x.d, k, bf_s, bf_i, g);
+        else
+            hipLaunchKernelGGL((bf_partial_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, x.xq, x.ldq,
+                               x.xc, x.ldc, x.d, k, w.kp, bf_s, bf_i, g);
+    });
     TSIM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(bf_large_merge_kernel, dim3((unsigned)(Q < 1024 ? Q : 1024)), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s,
-                       bf_i, out_s, out_i, idx_offset, g);
+    const unsigned mg = (unsigned)(Q < 1024 ? Q : 1024);
+    if (k64) hipLaunchKernelGGL(bf_merge_k64_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, bf_s, bf_i, out_s, out_i, idx_offset, g);
+    else hipLaunchKernelGGL(bf_merge_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s, bf_i, out_s, out_i, idx_offset, g);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-// GuardArgs of one call over the workspace words at the given offsets
-static GuardArgs make_guard(char *ws, size_t ctl, size_t flag_q, size_t flag_thr, size_t flag_eps, size_t unres_q, int ld,
-                            const float *ec_rho_max, const float *ec_maxnorm, int32_t *out_status) {
+// GuardArgs of one call over its workspace words
+static GuardArgs make_guard(char *ws, const SearchWs &w, int ld, const float *ec_rho_max, const float *ec_maxnorm,
+                            int32_t *out_status) {
     GuardArgs g;
     g.c1 = 4.0f;
     // unit rows only: float32 accumulation of ld exact products of unit rows, any order, rounding or truncation per step
@@ -1793,11 +1780,11 @@ static GuardArgs make_guard(char *ws, size_t ctl, size_t flag_q, size_t flag_thr
     g.rho_c_max = ec_rho_max;
     g.rho_c_default = rho_apriori(ld);
     g.ld = ld;
-    g.flag_eps = reinterpret_cast<float *>(ws + flag_eps);
-    g.ctl = reinterpret_cast<int *>(ws + ctl);
-    g.flag_q = reinterpret_cast<int *>(ws + flag_q);
-    g.flag_thr = reinterpret_cast<int *>(ws + flag_thr);
-    g.unres_q = reinterpret_cast<int *>(ws + unres_q);
+    g.flag_eps = reinterpret_cast<float *>(ws + w.flag_eps);
+    g.ctl = reinterpret_cast<int *>(ws + w.ctl);
+    g.flag_q = reinterpret_cast<int *>(ws + w.flag_q);
+    g.flag_thr = reinterpret_cast<int *>(ws + w.flag_thr);
+    g.unres_q = reinterpret_cast<int *>(ws + w.unres_q);
     g.status = out_status;
     g.c_maxnorm = ec_maxnorm;
     return g;
@@ -1806,44 +1793,47 @@ static GuardArgs make_guard(char *ws, size_t ctl, size_t flag_q, size_t flag_thr
 // k > 28: no list kernel.  Block maxima over the whole shard give a lower bound of the k-th best MFMA score; flag_all_kernel
 // turns it into every query's collection threshold (or hands every query to brute force: *ok = false, shard too small).
 // The control words must be cleared on the stream before.
-static int threshold_all(int sm, int64_t Q, int64_t N, int ld, int d, int k, const unit_t *uq, const unit_t *uc, const float *eq_f32,
-                         int64_t ldq_f32, float *bmax, int *gthr, const GuardArgs &g, bool *ok, hipStream_t st) {
+static int threshold_all(int sm, int64_t Q, int64_t N, const SearchOperands &o, int k, float *bmax, int *gthr, const GuardArgs &g,
+                         bool *ok, hipStream_t st) {
     TopkPlan fp;
-    *ok = plan_fullmax(Q, N, ld, k, &fp);
+    *ok = plan_fullmax(Q, N, o.ld, k, &fp);
     if (*ok) {
-        int rc0 = k1_launch_blockmax(fp, ld, uq, Q, uc, N, bmax, st);
+        int rc0 = k1_launch_blockmax(fp, o.ld, o.uq, Q, o.uc, N, bmax, st);
         if (rc0) return rc0;
         launch_thr_select(bmax, fp.P2, Q, k, gthr, st);
         TSIM_HIP_CHECK(hipGetLastError());
     }
-    if (sm == SM_COS)
-        hipLaunchKernelGGL(flag_all_kernel<SM_COS>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok, eq_f32, ldq_f32,
-                           uq, d, g);
-    else if (sm == SM_DOT)
-        hipLaunchKernelGGL(flag_all_kernel<SM_DOT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok, eq_f32, ldq_f32,
-                           uq, d, g);
-    else
-        hipLaunchKernelGGL(flag_all_kernel<SM_UNIT>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok,
-                           (const float *)nullptr, (int64_t)0, uq, d, g);
+    with_score_mode(sm, o, [&](auto, auto smc) {   // (SM_UNIT: the float32 query rows are null and not read)
+        hipLaunchKernelGGL(flag_all_kernel<decltype(smc)::value>, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, gthr, !*ok,
+                           o.q_f32, o.ldq_f32, o.uq, o.d, g);
+    });
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-template <int KL, typename T, int SM>
-static void launch_finalize(const TopkPlan &p, const float *part_s, const int *part_i, int64_t Q, int64_t N, const T *xq,
-                            int64_t ldq, const T *xc, int64_t ldc, int d, int k, const unit_t *uq, const int *gthr, float *out_s,
-                            int64_t *out_i, int64_t idx_offset, const GuardArgs &g, hipStream_t st) {
+// finalize of the list kernels' partial lists (p.KL = 16 or 32)
+static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, const int *part_i, int64_t Q, int64_t N,
+                            const SearchOperands &o, int k, const int *gthr, float *out_s, int64_t *out_i, int64_t idx_offset,
+                            const GuardArgs &g, hipStream_t st) {
     const dim3 grid((unsigned)((Q + 3) / 4));
-    constexpr int LBW = KL == 16 ? 8 : 4;   // (eight lists of 32 at a time spill)
-    if (Q <= 1024 && d <= 384)
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 16, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
-                           xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
-    else if (Q <= 1024)
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 8, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
-                           xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
-    else
-        hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 4, 4>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, xq, ldq,
-                           xc, ldc, d, k, uq, gthr, out_s, out_i, idx_offset, g);
+    auto launch = [&](auto x, auto smc, auto klc) {
+        using T = typename decltype(x)::row_t;
+        constexpr int SM = decltype(smc)::value, KL = decltype(klc)::value;
+        constexpr int LBW = KL == 16 ? 8 : 4;   // (eight lists of 32 at a time spill)
+        if (Q <= 1024 && x.d <= 384)
+            hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 16, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, x.xq,
+                               x.ldq, x.xc, x.ldc, x.d, k, o.uq, gthr, out_s, out_i, idx_offset, g);
+        else if (Q <= 1024)
+            hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 8, LBW>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, x.xq,
+                               x.ldq, x.xc, x.ldc, x.d, k, o.uq, gthr, out_s, out_i, idx_offset, g);
+        else
+            hipLaunchKernelGGL((cos_topk_finalize_kernel<KL, T, SM, 4, 4>), grid, dim3(256), 0, st, part_s, part_i, p.P2, Q, N, x.xq,
+                               x.ldq, x.xc, x.ldc, x.d, k, o.uq, gthr, out_s, out_i, idx_offset, g);
+    };
+    with_score_mode(sm, o, [&](auto x, auto smc) {
+        if (p.KL == 16) launch(x, smc, std::integral_constant<int, 16>{});
+        else launch(x, smc, std::integral_constant<int, 32>{});
+    });
 }
 }  // namespace tsim
 
@@ -1864,27 +1854,27 @@ extern "C" int tsim_cosine_topk_plan(int64_t Q, int64_t N, int ld, int k, int32_
 }
 
 extern "C" size_t tsim_cosine_topk_workspace_bytes(int64_t Q, int64_t N, int k) {
-    if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_MAX_K) return 0;
+    return k <= TOPK_MAX_K ? tsim_topk_large_workspace_bytes(Q, N, k) : 0;
+}
+
+extern "C" size_t tsim_topk_large_workspace_bytes(int64_t Q, int64_t N, int k) {
+    if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_LARGE_MAX_K) return 0;
     SearchWs w;
     plan_workspace(Q, N, k, &w);
     return w.total;
 }
 
-extern "C" size_t tsim_topk_large_workspace_bytes(int64_t Q, int64_t N, int k) {
-    if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_LARGE_MAX_K) return 0;
-    if (k <= TOPK_MAX_K) return tsim_cosine_topk_workspace_bytes(Q, N, k);
-    LargeWs w;
-    plan_workspace_large(Q, N, k, &w);
-    return w.total;
-}
-
-// One search call.  sm: SM_UNIT (no float32 matrices), SM_COS or SM_DOT (float32 matrices given; DOT also ec_maxnorm and
-// ec_rho_max, checked by tsim_dot_topk_ex).  `what` names the entry point in error messages.  kmax: the entry's largest k
-// (k > TOPK_MAX_K takes the k > 64 plan: tsim_cosine_topk_large / tsim_dot_topk_large).
-static int topk_search(int sm, const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
-                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d,
-                       int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
-                       void *workspace, size_t workspace_bytes, void *stream, int kmax = TOPK_MAX_K) {
+// One search call: validate, plan, [k <= 28: pre-pass, main pass, finalize | else: threshold_all], tail.  sm: SM_UNIT (no
+// float32 matrices), SM_COS or SM_DOT (float32 matrices given).  `what` names the entry point in error messages, kmax is its
+// largest k.
+static int topk_search(int sm, const char *what, int kmax, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q,
+                       const void *ec, const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
+                       int64_t N, int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
+                       int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+    if (sm == SM_DOT) {
+        TSIM_REQUIRE(eq_f32 && ec_f32, "%s: the float32 matrices are required", what);
+        TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "%s: the corpus rows' max-norm word and measured rho_max are required", what);
+    }
     TSIM_REQUIRE(eq && ec && out_scores && out_idx, "%s: null pointer", what);
     TSIM_REQUIRE(Q > 0 && N > 0, "%s: empty input Q=%lld N=%lld", what, (long long)Q, (long long)N);
     TSIM_REQUIRE(k >= 1 && k <= kmax, "%s: k=%d outside 1..%d", what, k, kmax);
@@ -1893,32 +1883,11 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
                  what, tsim_pad_dim(d), ld);
     TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "%s: embedding matrices must be 16-byte aligned", what);
     TSIM_REQUIRE((eq_f32 == nullptr) == (ec_f32 == nullptr), "%s: pass both float32 matrices or neither", what);
-    const bool cosf = eq_f32 != nullptr;   // (SM_COS or SM_DOT)
-    if (cosf) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
-                           (long long)ldc_f32, d);
+    if (eq_f32) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
+                             (long long)ldc_f32, d);
     hipStream_t st = as_stream(stream);
     const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
-    if (k > TOPK_MAX_K) {
-        LargeWs w;
-        plan_workspace_large(Q, N, k, &w);
-        if (!workspace || workspace_bytes < w.total)
-            return fail(TSIM_ENOMEM, "%s: workspace %zu B < %zu B", what, workspace_bytes, w.total);
-        char *ws = reinterpret_cast<char *>(workspace);
-        const GuardArgs g = make_guard(ws, w.ctl, w.flag_q, w.flag_thr, w.flag_eps, w.unres_q, ld, ec_rho_max, ec_maxnorm, out_status);
-        TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, w.coll_cnt + align256((size_t)Q * 4) - w.ctl, st));
-        bool ok = false;
-        int rc = threshold_all(sm, Q, N, ld, d, k, uq, uc, eq_f32, ldq_f32, reinterpret_cast<float *>(ws + w.bmax),
-                               reinterpret_cast<int *>(ws + w.gthr), g, &ok, st);
-        if (rc) return rc;
-        if (sm == SM_COS)
-            return search_tail_large<float, SM_COS>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores,
-                                                    out_idx, idx_offset, g, ok, st);
-        if (sm == SM_DOT)
-            return search_tail_large<float, SM_DOT>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores,
-                                                    out_idx, idx_offset, g, ok, st);
-        return search_tail_large<unit_t, SM_UNIT>(w, ws, Q, N, uq, uc, ld, uq, ld, uc, ld, ld, k, out_scores, out_idx, idx_offset,
-                                                  g, ok, st);
-    }
+    const SearchOperands o{uq, uc, eq_f32, ec_f32, ldq_f32, ldc_f32, d, ld};
     SearchWs w;
     plan_workspace(Q, N, k, &w);
     if (!workspace || workspace_bytes < w.total)
@@ -1928,11 +1897,10 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
     int *part_i = reinterpret_cast<int *>(ws + w.part_i);
     int *gthr = reinterpret_cast<int *>(ws + w.gthr);   // per-query shared threshold words, re-initialised every call
     float *bmax = reinterpret_cast<float *>(ws + w.bmax);
-    const GuardArgs g = make_guard(ws, w.ctl, w.flag_q, w.flag_thr, w.flag_eps, w.unres_q, ld, ec_rho_max, ec_maxnorm, out_status);
+    const GuardArgs g = make_guard(ws, w, ld, ec_rho_max, ec_maxnorm, out_status);
     // ctl .. coll_cnt are contiguous: one memset clears the control words and the per-slot counters — or the threshold kernel of
     // the pre-pass does (nothing in front of it touches them)
-    const size_t ctl_bytes = w.coll_cnt + align256((size_t)Q * 4) - w.ctl;
-    bool ctl_cleared = false;
+    const size_t ctl_bytes = w.coll_buf - w.ctl;
 
     bool run_collect = true;
     if (k <= TOPK_MAX_LISTS) {
@@ -1945,11 +1913,10 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
             if (rc0) return rc0;
             launch_thr_select(bmax, pp.P2, Q, p.KL, gthr, st, reinterpret_cast<int *>(ws + w.ctl), (int)(ctl_bytes / 4));
             TSIM_HIP_CHECK(hipGetLastError());
-            ctl_cleared = true;
         } else {
             TSIM_HIP_CHECK(hipMemsetAsync(gthr, 0x80, (size_t)Q * 4, st));
+            TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, ctl_bytes, st));
         }
-        if (!ctl_cleared) TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, ctl_bytes, st));
         hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
         g_ev_start = g_ev_stop = nullptr;
         if (ev0) TSIM_HIP_CHECK(hipEventRecord(ev0, st));
@@ -1978,74 +1945,49 @@ static int topk_search(int sm, const char *what, const void *eq, const float *eq
             if (rc) return rc;
         }
         if (ev1) TSIM_HIP_CHECK(hipEventRecord(ev1, st));
-        if (sm == SM_COS) {
-            if (p.KL == 16) launch_finalize<16, float, SM_COS>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k,
-                                                               uq, gthr, out_scores, out_idx, idx_offset, g, st);
-            else launch_finalize<32, float, SM_COS>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, uq, gthr,
-                                                    out_scores, out_idx, idx_offset, g, st);
-        } else if (sm == SM_DOT) {
-            if (p.KL == 16) launch_finalize<16, float, SM_DOT>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k,
-                                                               uq, gthr, out_scores, out_idx, idx_offset, g, st);
-            else launch_finalize<32, float, SM_DOT>(p, part_s, part_i, Q, N, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, uq, gthr,
-                                                    out_scores, out_idx, idx_offset, g, st);
-        } else {
-            if (p.KL == 16) launch_finalize<16, unit_t, SM_UNIT>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr,
-                                                                 out_scores, out_idx, idx_offset, g, st);
-            else launch_finalize<32, unit_t, SM_UNIT>(p, part_s, part_i, Q, N, uq, ld, uc, ld, ld, k, uq, gthr, out_scores,
-                                                      out_idx, idx_offset, g, st);
-        }
+        launch_finalize(sm, p, part_s, part_i, Q, N, o, k, gthr, out_scores, out_idx, idx_offset, g, st);
         TSIM_HIP_CHECK(hipGetLastError());
     } else {
         // k > 28: no list kernel.  Every row above (bound - margin) is collected and re-scored; widen_finalize's guard decides
         // whether that was enough.
         TSIM_HIP_CHECK(hipMemsetAsync(ws + w.ctl, 0, ctl_bytes, st));
-        int rc = threshold_all(sm, Q, N, ld, d, k, uq, uc, eq_f32, ldq_f32, bmax, gthr, g, &run_collect, st);
+        int rc = threshold_all(sm, Q, N, o, k, bmax, gthr, g, &run_collect, st);
         if (rc) return rc;
     }
-    if (sm == SM_COS)
-        return search_tail<float, SM_COS>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
-                                          idx_offset, g, run_collect, st);
-    if (sm == SM_DOT)
-        return search_tail<float, SM_DOT>(w, ws, Q, N, uq, uc, ld, eq_f32, ldq_f32, ec_f32, ldc_f32, d, k, out_scores, out_idx,
-                                          idx_offset, g, run_collect, st);
-    return search_tail<unit_t, SM_UNIT>(w, ws, Q, N, uq, uc, ld, uq, ld, uc, ld, ld, k, out_scores, out_idx, idx_offset, g,
-                                      run_collect, st);
+    return search_tail(sm, w, ws, Q, N, o, k, out_scores, out_idx, idx_offset, g, run_collect, st);
 }
 
 extern "C" int tsim_cosine_topk_ex(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                    const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld, int k,
                                    float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
                                    void *workspace, size_t workspace_bytes, void *stream) {
-    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N,
-                       d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
+    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", TOPK_MAX_K, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr,
+                       ec_rho_max, N, d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_dot_topk_ex(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                 const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
                                 int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
                                 void *workspace, size_t workspace_bytes, void *stream) {
-    TSIM_REQUIRE(eq_f32 && ec_f32, "dot_topk: the float32 matrices are required");
-    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "dot_topk: the corpus rows' max-norm word and measured rho_max are required");
-    return topk_search(SM_DOT, "dot_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, k,
-                       out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
+    return topk_search(SM_DOT, "dot_topk", TOPK_MAX_K, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld,
+                       k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_cosine_topk_large(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                       const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld,
                                       int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
                                       void *workspace, size_t workspace_bytes, void *stream) {
-    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N,
-                       d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream, TOPK_LARGE_MAX_K);
+    return topk_search(eq_f32 ? SM_COS : SM_UNIT, "cosine_topk", TOPK_LARGE_MAX_K, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32,
+                       nullptr, ec_rho_max, N, d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes,
+                       stream);
 }
 
 extern "C" int tsim_dot_topk_large(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                    const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
                                    int64_t N, int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
                                    int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
-    TSIM_REQUIRE(eq_f32 && ec_f32, "dot_topk: the float32 matrices are required");
-    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "dot_topk: the corpus rows' max-norm word and measured rho_max are required");
-    return topk_search(SM_DOT, "dot_topk", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, k,
-                       out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream, TOPK_LARGE_MAX_K);
+    return topk_search(SM_DOT, "dot_topk", TOPK_LARGE_MAX_K, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N,
+                       d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_cosine_topk(const void *eq, int64_t Q, const void *ec, int64_t N, int d, int ld, int k,
