@@ -247,12 +247,30 @@ def mining_search(query_emb: np.ndarray, corpus_emb: np.ndarray, k: int, chunk: 
 # (search_pipeline.py:77), and a float32 accumulation of the ld exact products in any order adds at most
 # ld 2^-23 (1 + rho_q)(1 + rho_c).
 # ---------------------------------------------------------------------------------------------------------------------
-def rho_rows(x: np.ndarray, eps: float = 1e-8) -> np.ndarray:
-    """[rows] float64: || half(u_r) - u_r ||_2, the rounding residual of each row's stored unit image."""
+HALF_MIN_NORMAL = 2.0 ** -14     # magnitudes below this are subnormal (or zero) as IEEE halves
+
+
+def flush_halves(h: np.ndarray) -> np.ndarray:
+    """Half values as an f16 MFMA that flushes subnormal inputs would read them: |h| < 2^-14 -> 0."""
+    return np.where(np.abs(h) < HALF_MIN_NORMAL, 0.0, h)
+
+
+def flush_safe_err(h: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """common.h flush_safe_err: the residual of one element v stored as the half h — h - v when the MFMA keeps subnormal
+    inputs, -v when it flushes them; for a subnormal (or zero) h the larger of the two in magnitude, so it covers both."""
+    e = h - v
+    return np.where(np.abs(h) < HALF_MIN_NORMAL, np.maximum(np.abs(e), np.abs(v)), e)
+
+
+def rho_rows(x: np.ndarray, eps: float = 1e-8, flush_safe: bool = False) -> np.ndarray:
+    """[rows] float64: || half(u_r) - u_r ||_2, the rounding residual of each row's stored unit image (what
+    l2norm_rows_kernel and query_rho<false> measure: the f16 MFMA keeps subnormal inputs).  flush_safe = True: every
+    subnormal element counts with flush_safe_err instead, so the residual also bounds a flushing MFMA."""
     u = l2_normalize_f64(x, eps)
     with np.errstate(over="ignore"):
         h = u.astype(np.float16).astype(np.float64)
-    return np.sqrt(((h - u) ** 2).sum(-1))
+    e = flush_safe_err(h, u) if flush_safe else h - u
+    return np.sqrt((e ** 2).sum(-1))
 
 
 def rho_apriori(ld: int) -> float:
@@ -268,11 +286,14 @@ def guard_eps(rho_q, rho_c, ld: int):
     return (rho_q + rho_c + rho_q * rho_c + acc + 2.0 ** -22) * (1.0 + 1e-6)
 
 
-def mfma_model_scores(q: np.ndarray, c: np.ndarray, order: str = "f64") -> np.ndarray:
+def mfma_model_scores(q: np.ndarray, c: np.ndarray, order: str = "f64", flush: bool = False) -> np.ndarray:
     """[Q,N] float32 model of the selection scores: inner products of the stored half unit rows.
     order = "f64": exact dot rounded once (the centre of every possible float32 accumulation);
-            "f32seq": float32 accumulation element by element (a worst-ish case for accumulation error)."""
+            "f32seq": float32 accumulation element by element (a worst-ish case for accumulation error).
+    flush = True: an MFMA that flushes subnormal half inputs — halves below 2^-14 in magnitude count as 0 on both operands."""
     uq, uc = unit_rows(q).astype(np.float64), unit_rows(c).astype(np.float64)
+    if flush:
+        uq, uc = flush_halves(uq), flush_halves(uc)
     if order == "f64":
         return (uq @ uc.T).astype(np.float32)
     acc = np.zeros((uq.shape[0], uc.shape[0]), dtype=np.float32)
@@ -281,13 +302,16 @@ def mfma_model_scores(q: np.ndarray, c: np.ndarray, order: str = "f64") -> np.nd
     return acc
 
 
-def guard_replay(q: np.ndarray, c: np.ndarray, k: int, KL: int, mode: str = "bound", rho_c=None, c1: float = 4.0):
+def guard_replay(q: np.ndarray, c: np.ndarray, k: int, KL: int, mode: str = "bound", rho_c=None, c1: float = 4.0,
+                 flush: bool = False, flush_safe: bool = False):
     """First pass of tsim_cosine_topk_ex on the CPU for ONE query row q [d]: the KL best rows by model MFMA score are
     re-scored exactly; returns (first-pass top-k indices, safe?, eps, cut, k-th exact score).
     mode = "bound": eps = guard_eps(rho_q, rho_c) (the shipped guard);  "sampled": eps = max(c1 x largest |MFMA - exact| seen on
-    the KL candidates, d 2^-24) — the round-2 heuristic, kept to show what the adversarial fixtures defeat."""
+    the KL candidates, d 2^-24) — the round-2 heuristic, kept to show what the adversarial fixtures defeat.
+    flush: the model MFMA flushes subnormal halves (mfma_model_scores);  flush_safe: rho_q and rho_c are the flush-safe
+    residuals (rho_rows).  The shipped guard is flush_safe = False; the hardware it is proven for is flush = False."""
     q = np.asarray(q, dtype=np.float32)[None, :]
-    m = mfma_model_scores(q, c)[0]
+    m = mfma_model_scores(q, c, flush=flush)[0]
     order = np.lexsort((np.arange(m.size), -m.astype(np.float64)))[:KL]
     ex = exact_cosine(q, c[order])[0]
     cut = float(m[order[-1]])
@@ -296,8 +320,69 @@ def guard_replay(q: np.ndarray, c: np.ndarray, k: int, KL: int, mode: str = "bou
     sk = float(ex[rank[k - 1]])
     ld = c.shape[1]
     if mode == "bound":
-        rc = float(rho_rows(c).max()) if rho_c is None else float(rho_c)
-        eps = float(guard_eps(rho_rows(q)[0], rc, ld))
+        rc = float(rho_rows(c, flush_safe=flush_safe).max()) if rho_c is None else float(rho_c)
+        eps = float(guard_eps(rho_rows(q, flush_safe=flush_safe)[0], rc, ld))
     else:
         eps = max(c1 * float(np.abs(m[order] - ex).max()), ld * 2.0 ** -24)
     return top, (cut + eps < sk), eps, cut, sk
+
+
+def guard_tau(target: float, eps: float) -> float:
+    """search.hip guard_tau: a float32 collection threshold with tau + eps < target (rows at or below it cannot reach target)."""
+    tau = np.nextafter(np.float32(float(target) - float(eps)), np.float32(-np.inf))
+    if float(tau) + float(eps) >= float(target):
+        tau = np.nextafter(tau, np.float32(-np.inf))
+    return float(tau)
+
+
+def fullmax_partition(rows: np.ndarray, N: int, k: int) -> np.ndarray:
+    """Partition index of corpus rows in the block-maxima pass that serves k > 28 at Q <= 128 queries (search.hip
+    plan_fullmax with one query block): chunks of ceil(N / max(512, k)) rows rounded up to 32, and inside a chunk the lane
+    halves — rows 4h .. 4h+3 of every group of eight belong to half h."""
+    nch = min(max(512, k), 1024)
+    rpc = -(-(-(-N // nch)) // 32) * 32
+    rows = np.asarray(rows)
+    return (rows // rpc) * 2 + (rows % 8) // 4
+
+
+def search_replay(q: np.ndarray, c: np.ndarray, k: int, KL=None, flush: bool = False, flush_safe: bool = False, rho_c=None,
+                  cap: int = 1024):
+    """The whole cosine top-k call on the CPU for ONE query row q [d] on model MFMA scores: (indices [k], status).
+    KL = 16 / 32: the list path (search.hip cos_topk_finalize: guard_replay, with the bound checked on the candidates), then
+    the widening pass with the collection threshold sk - eps;  KL = None: the k > 28 path (flag_all_kernel): threshold
+    B - 2 eps, B the k-th largest block maximum over fullmax_partition.  Then widen_finalize: every row with a model score
+    above the threshold is re-scored, the bound is checked on each, and the list stands when threshold + eps stays below
+    its k-th score; more than `cap` collected rows, a failed check or an unresolved list end in the exact pass (status 2).
+    flush / flush_safe as in guard_replay: which MFMA is modelled, and which residuals the guard is given."""
+    q = np.asarray(q, dtype=np.float32)[None, :]
+    N, ld = c.shape
+    m = mfma_model_scores(q, c, flush=flush)[0]
+    rc = float(rho_rows(c, flush_safe=flush_safe).max()) if rho_c is None else float(rho_c)
+    eps = float(np.float32(guard_eps(rho_rows(q, flush_safe=flush_safe)[0], rc, ld)))
+    ex = exact_cosine(q, c)[0]          # (the kernels compute only the entries they need; the values are the same)
+
+    def exact_list(rows):
+        return rows[np.lexsort((rows, -ex[rows].astype(np.float64)))][:k]
+
+    if KL is not None:
+        top, safe, _, cut, sk = guard_replay(q[0], c, k, KL, rho_c=rc, flush=flush, flush_safe=flush_safe)
+        cand = np.lexsort((np.arange(N), -m.astype(np.float64)))[:KL]
+        if not (np.abs(m[cand] - ex[cand]).max() <= eps):
+            return exact_list(np.arange(N)), 2
+        if N <= KL or cut + eps < sk:
+            return top, 0
+        thr = guard_tau(sk, eps)
+    else:
+        part = fullmax_partition(np.arange(N), N, k)
+        bmax = np.full(int(part.max()) + 1, -np.inf)
+        np.maximum.at(bmax, part, m.astype(np.float64))
+        if bmax.size < k:
+            return exact_list(np.arange(N)), 2
+        thr = guard_tau(float(np.sort(bmax)[::-1][k - 1]), float(np.float32(2.0 * eps * 1.000001)))
+    rows = np.nonzero(m > thr)[0]
+    if rows.size > cap or rows.size < k or not (np.abs(m[rows] - ex[rows]).max() <= eps):
+        return exact_list(np.arange(N)), 2
+    got = exact_list(rows)
+    if not (thr + eps < float(ex[got[k - 1]])):
+        return exact_list(np.arange(N)), 2
+    return got, 1

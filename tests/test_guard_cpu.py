@@ -1,16 +1,26 @@
 """CPU checks of the search's exactness guard (oracle/search_ref.guard_eps == csrc/common.h guard_eps): the BOUND it rests on
 holds on random, anisotropic and adversarially rounded rows, and the adversarial fixture of VERDICT r2 defeats a sampled-error
-guard while the bound-based guard flags it."""
-import numpy as np
+guard while the bound-based guard flags it.
 
-from adversary import adversarial_case, aligned_rounding_row
+Subnormal halves (last item): the cosine guard's residual rho = ||half(u) - u|| assumes that the f16 MFMA KEEPS
+subnormal half inputs.  The spiky cases of tests/adversary.py (unit rows with 767 subnormal halves) are replayed here on both
+models of the MFMA: kept — the bound holds and the replayed call returns the oracle's list; flushed with the shipped
+residuals — the bound fails and the replayed call returns a WRONG list (what tests/test_search_subnormal_gpu.py guards
+against on the hardware); flushed with the flush-safe residuals (common.h flush_safe_err, as the inner-product path
+measures them) — exact again."""
+import functools
+
+import numpy as np
+import pytest
+
+from adversary import adversarial_case, aligned_rounding_row, spiky_case, spiky_query_case
 from oracle import search_ref as sr
 
 
-def _max_violation(q, c, order):
-    m = sr.mfma_model_scores(q, c, order).astype(np.float64)
+def _max_violation(q, c, order, flush=False, flush_safe=False):
+    m = sr.mfma_model_scores(q, c, order, flush=flush).astype(np.float64)
     ex = sr.exact_cosine(q, c).astype(np.float64)
-    eps = sr.guard_eps(sr.rho_rows(q)[:, None], sr.rho_rows(c)[None, :], c.shape[1])
+    eps = sr.guard_eps(sr.rho_rows(q, flush_safe=flush_safe)[:, None], sr.rho_rows(c, flush_safe=flush_safe)[None, :], c.shape[1])
     return float((np.abs(m - ex) - eps).max()), float((np.abs(m - ex) / eps).max())
 
 
@@ -79,3 +89,76 @@ def test_duplicates_with_a_better_near_duplicate():
             m = sr.mfma_model_scores(q[None], c[[200, 3000]])[0]
             hit += int(ex[1] > ex[0] and m[1] < m[0])
         assert hit > 0      # the scenario does occur: the better row is ranked below the duplicates by the half rows
+
+
+# ---------------------------------------------------------------------------------------------------------- subnormal halves
+@functools.lru_cache(maxsize=None)
+def _spiky(k, KL):
+    q, c, info = spiky_case(d=768, k=k, KL=KL)
+    return q, c, info, sr.cosine_topk_f32(q[None], c, k)[1][0]
+
+
+@pytest.mark.parametrize("k,KL", [(10, 16), (20, 32), (100, None)])
+def test_spiky_row_kept_is_exact_flushed_is_wrong_flush_safe_is_exact(k, KL):
+    """d = 768, the smallest padded width at which the drop (t sum|q_j| ~ 1.5e-3) exceeds what the widening pass forgives."""
+    q, c, info, truth = _spiky(k, KL)
+    spiky = info["spiky"]
+    print(f"k={k} KL={KL}: exact {info['exact']:.6f} kept {info['kept']:.6f} flushed {info['flushed']:.6f} "
+          f"drop {info['drop']:.3e} eps {info['eps']:.3e} neighbours {info['neighbours']} over {info['span']:.3e}, "
+          f"flushed score {info['margin']:.3e} below (k-th score - 2 eps)")
+    assert truth[k - 1] == spiky and info["drop"] > 2.0 * info["eps"]
+    # kept model, shipped residuals: the replayed call returns the oracle's list, and the spiky row is why it had to widen
+    got, st = sr.search_replay(q, c, k, KL)
+    assert got.tolist() == truth.tolist() and st == 1
+    # flushed model, shipped residuals: the first pass misses the row, the widening threshold does not collect it, the
+    # re-check of the widened list passes: a flushing MFMA would return a wrong list with status 1
+    got, st = sr.search_replay(q, c, k, KL, flush=True)
+    assert spiky not in got and st == 1 and got.tolist() != truth.tolist()
+    mf = sr.mfma_model_scores(q[None], c, flush=True)[0]
+    if KL is not None:
+        top, safe, eps, cut, sk = sr.guard_replay(q, c, k, KL, flush=True)
+        assert spiky not in top and not safe
+        assert mf[spiky] < sr.guard_tau(sk, eps) and mf[spiky] < sk - 2.0 * eps
+    # flushed model, flush-safe residuals: the row is collected (or everything is: brute force) and the list is exact
+    got, st = sr.search_replay(q, c, k, KL, flush=True, flush_safe=True)
+    assert got.tolist() == truth.tolist() and st in (1, 2)
+    if KL is not None:
+        top, safe, eps, cut, sk = sr.guard_replay(q, c, k, KL, flush=True, flush_safe=True)
+        assert not safe and mf[spiky] > sr.guard_tau(sk, eps)
+
+
+def test_spiky_row_bound_on_every_pair():
+    q, c, info, _ = _spiky(10, 16)
+    for order in ("f64", "f32seq"):
+        assert _max_violation(q[None], c, order)[0] <= 0.0                                     # kept: the shipped bound holds
+        assert _max_violation(q[None], c, order, flush=True, flush_safe=True)[0] <= 0.0        # flushed: the flush-safe one
+        viol, ratio = _max_violation(q[None], c, order, flush=True)                            # flushed, shipped: it fails
+        assert viol > 0.0 and ratio > 2.0, (viol, ratio)
+    # the flush-safe residual of a Gaussian unit row at d = 768 is the shipped one to within a few percent: ~one subnormal
+    # element of at most 6.1e-5 in quadrature with ~2.3e-4
+    g = np.delete(np.arange(c.shape[0]), np.concatenate([info["slots"], [info["spiky"]]]))
+    kept, safe = sr.rho_rows(c[g]), sr.rho_rows(c[g], flush_safe=True)
+    assert (safe >= kept).all() and safe.max() <= np.sqrt(kept.max() ** 2 + 6 * sr.HALF_MIN_NORMAL ** 2)
+
+
+def test_spiky_query_bound_and_replay():
+    """Query-side: the spiky rows are the queries.  Query 0's best rows are all aligned with its signs: flushed, every
+    candidate misses the bound and the check on the candidates sends the query to brute force (status 2 — the signature
+    the GPU test records).  Query 1's aligned rows sit between unaligned neighbours: flushed, the candidates are honest
+    neighbours, the check passes and the list is wrong."""
+    q, c, info = spiky_query_case()
+    truth = sr.cosine_topk_f32(q, c, 10)[1]
+    print(f"eps {info['eps']}, drop of the aligned rows under the flushed model: query 0 {info['drop0']}, query 1 {info['drop1']}")
+    for order in ("f64", "f32seq"):
+        assert _max_violation(q, c, order)[0] <= 0.0
+        assert _max_violation(q, c, order, flush=True, flush_safe=True)[0] <= 0.0
+        assert _max_violation(q, c, order, flush=True)[1] > 2.0
+    for qi in (0, 1):
+        got, st = sr.search_replay(q[qi], c, 10, 16)
+        assert got.tolist() == truth[qi].tolist() and st in (0, 1)
+        got, st = sr.search_replay(q[qi], c, 10, 16, flush=True, flush_safe=True)
+        assert got.tolist() == truth[qi].tolist()
+    got, st = sr.search_replay(q[0], c, 10, 16, flush=True)
+    assert st == 2 and got.tolist() == truth[0].tolist()
+    got, st = sr.search_replay(q[1], c, 10, 16, flush=True)
+    assert st == 1 and got.tolist() != truth[1].tolist() and not set(info["aligned1"]) & set(got)

@@ -115,6 +115,12 @@ __device__ __forceinline__ float canonical_scale_f32(float x, double inv) { retu
 // float32 accumulation of ld products that are exact in float32 (11 x 11 significand bits): at most
 // ld * 2^-23 * |u^q| |u^c| for ANY summation order with rounding or truncation to float32 at every step.  One more 2^-22
 // covers the final rounding of the exact score to float32 and a tie on it.  Every constant is rounded UP.
+// ASSUMPTION, pinned: rho is the selection error of a row only if the f16 MFMA KEEPS subnormal half operands (|h| < 2^-14); one
+// that flushed them would err by |u| on such an element.  Measured on MI355X (gfx950): it keeps them, for A and for B.
+// tests/test_search_subnormal_gpu.py holds rows with 767 subnormal halves at d = 768 whose selection score a flush would lower by
+// 2.5 eps — out of the first pass and below the widening threshold (tests/test_guard_cpu.py replays that: a wrong list, status
+// 1) — and demands the oracle's lists; DESIGN.md section 7 has the numbers.  The inner-product path does not rest on this
+// (flush_safe_err below); should a part flush, l2norm_rows_kernel, query_rho<false> and rho_apriori take the same treatment.
 //   rho_round_up: float upper bound of a float64 residual norm; NaN / oversized values (rows with NaN or inf elements) are
 //                 clamped to 2, which sends every query that meets them to the brute-force pass.
 __device__ __forceinline__ float rho_round_up(double r) {

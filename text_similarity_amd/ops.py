@@ -77,9 +77,15 @@ def l2norm_rows(x: torch.Tensor, eps: float = 1e-8, rho: Optional[torch.Tensor] 
     if rho is not None:
         _check_rho(rho, x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().tsim_l2norm_rows(x.data_ptr(), dt, rows, d, x.stride(0), out.data_ptr(), ld, eps,
+        _lib.check(_lib.lib().tsim_l2norm_rows(x.data_ptr(), dt, rows, d, _row_stride(x), out.data_ptr(), ld, eps,
                                                rho.data_ptr() if rho is not None else 0, _stream(x)), "l2norm_rows")
     return (out, rho) if return_rho else out
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    """Elements between consecutive rows of a 2-D tensor with unit inner stride.  A tensor of one row may carry any stride(0)
+    (a [1, d] view made with ``x[None]`` in numpy has 0, and ``contiguous()`` keeps it); the kernels check ld >= d."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
 def _check_rho(rho, dev):
@@ -133,7 +139,7 @@ def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_statu
         for t, rows, name in ((eq_f32, Q, "eq_f32"), (ec_f32, N, "ec_f32")):
             if t.dtype != torch.float32 or t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.device != dev:
                 raise ValueError(f"{what}: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
-        qf, cf, ldq, ldc = eq_f32.data_ptr(), ec_f32.data_ptr(), eq_f32.stride(0), ec_f32.stride(0)
+        qf, cf, ldq, ldc = eq_f32.data_ptr(), ec_f32.data_ptr(), _row_stride(eq_f32), _row_stride(ec_f32)
     if rho_c is not None:
         _check_rho(rho_c, dev)
     if scale_c is not None:
@@ -187,7 +193,7 @@ def max_norm_rows(x: torch.Tensor, maxnorm: Optional[torch.Tensor] = None) -> to
     _check_rho(maxnorm, x.device)
     dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().tsim_max_norm_rows(x.data_ptr(), dt, x.shape[0], x.shape[1], x.stride(0), maxnorm.data_ptr(),
+        _lib.check(_lib.lib().tsim_max_norm_rows(x.data_ptr(), dt, x.shape[0], x.shape[1], _row_stride(x), maxnorm.data_ptr(),
                                                  _stream(x)), "max_norm_rows")
     return maxnorm
 
@@ -219,7 +225,7 @@ def dot_scaled_rows(x: torch.Tensor, maxnorm: Optional[torch.Tensor] = None, rho
     out = torch.empty((rows, ld), dtype=UNIT_DTYPE, device=x.device)
     dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().tsim_dot_scaled_rows(x.data_ptr(), dt, rows, d, x.stride(0), maxnorm.data_ptr(), out.data_ptr(), ld,
+        _lib.check(_lib.lib().tsim_dot_scaled_rows(x.data_ptr(), dt, rows, d, _row_stride(x), maxnorm.data_ptr(), out.data_ptr(), ld,
                                                    rho.data_ptr(), _stream(x)), "dot_scaled_rows")
     return out, rho, maxnorm
 
@@ -324,7 +330,8 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
             total = 0
             for q0 in range(0, Q, step):
                 nq = min(step, Q - q0)
-                qf, ldq, ldc = eq_f32.data_ptr() + q0 * eq_f32.stride(0) * 4, eq_f32.stride(0), ec_f32.stride(0)
+                ldq, ldc = _row_stride(eq_f32), _row_stride(ec_f32)
+                qf = eq_f32.data_ptr() + q0 * ldq * 4
                 head = (eq_unit.data_ptr() + q0 * ld * 2, qf, ldq, nq, ec_half.data_ptr(), ec_f32.data_ptr(), ldc)
                 tail = (N, d, ld, tau, counts.data_ptr() + q0 * 8, status.data_ptr() + q0 * 4, ws.data_ptr(), ws.numel(), st)
                 if scale_c is None:
