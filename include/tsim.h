@@ -166,8 +166,8 @@ int tsim_dot_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f3
  * are REQUIRED (NULL: TSIM_EINVAL; there is no unit-rows-only mode), for dot also ec_maxnorm and ec_rho_max.
  * Definition.  Row r is a hit of query q iff s(q, r) >= tau compared in float32, s being exactly the float32 score the top-k
  * entry of the same space returns for the pair (cosine: oracle/search_ref.exact_cosine; dot: float32 of the float64 lane-ordered
- * sum).  tau is one float per call: NaN is TSIM_EINVAL, -inf returns every row (of non-NaN score), a tau above every score
- * returns nothing.  The hits of a query are ordered by (score desc, index asc).  Nothing is ever truncated: the result is the
+ * sum).  tau is one float per call — NaN is TSIM_EINVAL, -inf returns every row (of non-NaN score), a tau above every score
+ * returns nothing — or, in the _tau entries below, one float per query.  The hits of a query are ordered by (score desc, index asc).  Nothing is ever truncated: the result is the
  * complete set for any tau and any data.
  * The result size depends on the data, so the call is split where the host has to allocate:
  *   1. tsim_cosine_range_scan / tsim_dot_range_scan: threshold set-up -> ONE collect pass of the MFMA kernel over the corpus ->
@@ -195,8 +195,27 @@ int tsim_dot_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f3
  * threshold existed), or a re-scored row showed |m - s| > eps_q (operands that are not the images of the float32 rows), and
  * the query was answered by an exact pass over the float32 rows of the whole shard with the arithmetic of the top-k
  * brute-force pass: counted in the scan, written straight into the caller's segment and sorted there in the fill, so that a
- * query that hits the whole shard needs no scratch of its own.  Status 0 is not used. */
+ * query that hits the whole shard needs no scratch of its own.  Status 0 is not used.
+ * Per-query thresholds.  tsim_cosine_range_scan_tau / tsim_dot_range_scan_tau / tsim_range_fill_tau are the three entries above
+ * with `float tau` replaced by `const float *tau_q`, a device pointer to float32 [Q] (NULL: TSIM_EINVAL): query q is answered
+ * exactly as by the scalar call with tau = tau_q[q] — same hits, scores, order and status rule, the same kernels reading
+ * tau_q[q] where they read tau.  -inf returns every row (of non-NaN score) through the exact pass, +inf or a value above every
+ * score nothing.  A NaN cannot be refused without reading the array; it is defined instead: that query has no hit and status 2
+ * (no finite collect threshold exists for it, and no score compares >= NaN).  The scan and the fill of one call must be given
+ * the SAME array, unchanged in between, as the scalar entries must be given the same tau.  The guard above is stated per query
+ * (eps_q, thr_q) and holds with tau_q[q] in the place of tau: no step of it relates one query's threshold to another's.
+ * Merging.  tsim_range_merge joins `nlists` (1 .. TSIM_RANGE_MERGE_MAX_LISTS) results of the same Q queries over DISJOINT row
+ * sets, already carrying global indices (idx_offset), into one: lims_in int64 [nlists, Q+1] holds ABSOLUTE offsets into
+ * scores_in / idx_in — segment q of list r is [lims_in[r][q], lims_in[r][q+1]), sorted by (score desc, index asc) as the fill
+ * leaves it; the lists may lie anywhere in the two buffers (e.g. padded to a common length by an all-gather).  The caller makes
+ * lims_out [Q+1], the exclusive prefix sum of the per-query totals over the lists, passes total = lims_out[Q] from the host (it
+ * sized out_scores / out_idx [total] with it) and gets segment q of the output = the union of the nlists segments ordered by
+ * (score desc, index asc).  Entries equal in score AND index (which disjoint shards do not produce) are ordered by list
+ * number: the output is always a permutation of the input.  Segments may have any length, also 0; a whole list may be empty;
+ * nlists = 1 is a copy; Q = 0 or total = 0 returns without a launch.  No workspace.  An output segment shorter than the lists'
+ * total for the query is never overrun. */
 #define TSIM_RANGE_SLOT_CAP 2048
+#define TSIM_RANGE_MERGE_MAX_LISTS 64
 #define TSIM_SPACE_COSINE 0
 #define TSIM_SPACE_DOT 1
 size_t tsim_range_workspace_bytes(int64_t Q, int64_t N);
@@ -210,6 +229,19 @@ int tsim_dot_range_scan(const void *eq_unit, const float *eq_f32, int64_t ldq_f3
 int tsim_range_fill(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32, int64_t N,
                     int d, float tau, const int64_t *lims, float *out_scores, int64_t *out_idx, int64_t idx_offset,
                     void *workspace, size_t workspace_bytes, void *stream);
+int tsim_cosine_range_scan_tau(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_unit,
+                               const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld,
+                               const float *tau_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int tsim_dot_range_scan_tau(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_scaled,
+                            const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                            int d, int ld, const float *tau_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int tsim_range_fill_tau(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
+                        int64_t N, int d, const float *tau_q, const int64_t *lims, float *out_scores, int64_t *out_idx,
+                        int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream);
+int tsim_range_merge(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                     const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream);
 
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are

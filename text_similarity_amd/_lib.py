@@ -17,6 +17,7 @@ ACT_IDENTITY, ACT_TANH = 0, 1
 SPACE_COSINE, SPACE_DOT = 0, 1
 ENC_ERR_SPAN = 16                # include/tsim.h TSIM_ENC_ERR_SPAN
 RANGE_SLOT_CAP = 2048            # include/tsim.h TSIM_RANGE_SLOT_CAP
+RANGE_MERGE_MAX_LISTS = 64       # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS
 
 
 class TsimError(RuntimeError):
@@ -84,6 +85,16 @@ _SIGS = {
                                       C.c_size_t, C.c_void_p]),
     "tsim_range_fill": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tsim_cosine_range_scan_tau": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+    "tsim_dot_range_scan_tau": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    "tsim_range_fill_tau": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tsim_range_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "tsim_cosine_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_time_next_topk": (None, [C.c_void_p, C.c_void_p]),

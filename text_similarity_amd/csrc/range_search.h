@@ -1,5 +1,5 @@
-// Exact range search (tsim_cosine_range_scan / tsim_dot_range_scan / tsim_range_fill): every corpus row whose exact score is
-// >= tau.  Included by search.hip behind the exact-score helpers, the guard helpers and plan_collect, which it uses as they are.
+// Exact range search (tsim_cosine_range_scan / tsim_dot_range_scan / tsim_range_fill and their _tau forms): every corpus row
+// whose exact score is >= tau, tau one float per call or one per query (tau_q[q]); tsim_range_merge joins per-shard results.  Included by search.hip behind the exact-score helpers, the guard helpers and plan_collect, which it uses as they are.
 //
 // Pipeline of one scan:   range_setup  ->  K1 in COLLECT mode (k1_launch_collect, unchanged)  ->  range_finalize  ->  range_bf<count>
 //          of one fill:   range_fill (status 1)  ->  range_bf<fill>  ->  range_bf_sort (status 2)
@@ -16,7 +16,8 @@ enum { RCTL_QCOUNT = 0, RCTL_NUNRES = 1, RCTL_WORDS = 4 };
 enum { RST_COLLECTED = 1, RST_EXACT = 2 };   // out_status values (include/tsim.h)
 
 struct RangeArgs {
-    float tau;
+    float tau;                // the threshold of every query when tau_q is null
+    const float *tau_q;       // device [Q], or null: the threshold of query q (the _tau entries)
     int ld;
     const float *rho_c_max;   // device, or null (cosine: the a-priori bound)
     float rho_c_default;
@@ -32,6 +33,10 @@ struct RangeArgs {
     unsigned long long *cursor;   // [Q] fill: entries of a status-2 query written so far
     unsigned long long *buf;      // [Q][RS_CAP] score bits | (uint64)(shard row) << 32
 };
+
+// The threshold of query q.  Every kernel compares against this one value, so a query of a _tau call is answered exactly as by
+// the scalar call with tau = tau_q[q]; a NaN there fails every comparison below (no finite collect threshold: status 2, no hit).
+__device__ __forceinline__ float rs_tau(const RangeArgs &a, int64_t q) { return a.tau_q ? a.tau_q[q] : a.tau; }
 
 // entry order (score desc, row asc); RS_PAD = (-inf, row 2^32 - 1) ranks behind every real entry (rows are < 2^31)
 constexpr unsigned long long RS_PAD = 0xffffffffff800000ull;
@@ -79,9 +84,10 @@ __global__ __launch_bounds__(256) void range_setup_kernel(int64_t Q, const float
     exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);   // norm = max(|q|, 1e-8): the scale the unit row was made with
     const float rho_c = a.rho_c_max ? *a.rho_c_max : a.rho_c_default;
     const float eps = guard_eps(query_rho<DOT>(eqr, uq + q * a.ld, d, lane), rho_c, a.ld);
+    const float tau = rs_tau(a, q);
     float thr;
-    if constexpr (DOT) thr = guard_tau_dot(a.tau, eps, eqr.norm * dot_scale(*a.c_maxnorm));
-    else thr = guard_tau(a.tau, eps);
+    if constexpr (DOT) thr = guard_tau_dot(tau, eps, eqr.norm * dot_scale(*a.c_maxnorm));
+    else thr = guard_tau(tau, eps);
     const bool everything = !(thr > -3.4e38f);
     if (lane != 0) return;
     a.gthr[q] = float_to_ordered(everything ? INFINITY : thr);
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
             exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);
             double nqs = 1.0;
             if constexpr (DOT) nqs = eqr.norm * dot_scale(*a.c_maxnorm);
-            const float eps = a.eps[q];
+            const float eps = a.eps[q], tau = rs_tau(a, q);
             unsigned long long *slot = a.buf + q * RS_CAP;
             bool bad = false;
             int mine = 0;
@@ -141,7 +147,7 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
                         if constexpr (DOT) err = (float)fabs((double)ms - (double)es / nqs);
                         else err = fabsf(ms - es);
                         if (!(err <= eps)) bad = true;
-                        if (es >= a.tau) {
+                        if (es >= tau) {
                             v = (unsigned long long)__float_as_uint(es) | ((unsigned long long)(uint32_t)row << 32);
                             ++mine;
                         }
@@ -193,6 +199,7 @@ __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int
     const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
     for (int u = blockIdx.y; u < nu; u += gridDim.y) {
         const int q = a.unres_q[u];
+        const float tau = rs_tau(a, q);
         ExactQuery<float> eqr;
         exact_load_query<float, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
         int64_t seg0 = 0, seglen = 0;
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int
             const int nvalid = r1 - g0 < 64 ? (int)(r1 - g0) : 64;
             const int row = (int)(g0 + (lane < nvalid ? lane : 0));
             const float s = wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
-            const bool hit = lane < nvalid && s >= a.tau;
+            const bool hit = lane < nvalid && s >= tau;
             const unsigned long long hits = __ballot(hit);
             if (hits == 0) continue;
             if constexpr (FILL) {
@@ -348,9 +355,10 @@ static void plan_workspace_range(int64_t Q, RangeWs *w) {
     w->total = o;
 }
 
-static RangeArgs make_range_args(const RangeWs &w, char *ws, float tau, int ld, const float *ec_rho_max, const float *ec_maxnorm) {
+static RangeArgs make_range_args(const RangeWs &w, char *ws, float tau, const float *tau_q, int ld, const float *ec_rho_max, const float *ec_maxnorm) {
     RangeArgs a;
     a.tau = tau;
+    a.tau_q = tau_q;
     a.ld = ld;
     a.rho_c_max = ec_rho_max;
     a.rho_c_default = rho_apriori(ld);
@@ -377,8 +385,9 @@ static void plan_range_bf(int64_t N, int *nch, int *rows) {
 }
 
 static int range_check_shapes(const char *what, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
-                              int64_t N, int d, float tau, const void *workspace, size_t workspace_bytes, RangeWs *w) {
-    TSIM_REQUIRE(tau == tau, "%s: the threshold is NaN", what);
+                              int64_t N, int d, float tau, const float *tau_q, const void *workspace, size_t workspace_bytes,
+                              RangeWs *w) {
+    TSIM_REQUIRE(tau_q || tau == tau, "%s: the threshold is NaN", what);   // (a NaN in tau_q[q]: query q has no hit, status 2)
     TSIM_REQUIRE(eq_f32 && ec_f32, "%s: the float32 matrices are required (there is no unit-rows-only range search)", what);
     TSIM_REQUIRE(Q > 0 && N > 0, "%s: empty input Q=%lld N=%lld", what, (long long)Q, (long long)N);
     TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: shard too large for 32-bit row ids", what);
@@ -392,16 +401,17 @@ static int range_check_shapes(const char *what, const float *eq_f32, int64_t ldq
 
 static int range_scan(int sm, const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d, int ld,
-                      float tau, int64_t *out_counts, int32_t *out_status, void *workspace, size_t workspace_bytes, void *stream) {
+                      float tau, const float *tau_q, int64_t *out_counts, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                      void *stream) {
     RangeWs w;
-    int rc = range_check_shapes(what, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, workspace, workspace_bytes, &w);
+    int rc = range_check_shapes(what, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, tau_q, workspace, workspace_bytes, &w);
     if (rc) return rc;
     TSIM_REQUIRE(eq && ec && out_counts, "%s: null pointer", what);
     TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "%s: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)", what, tsim_pad_dim(d), ld);
     TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "%s: embedding matrices must be 16-byte aligned", what);
     hipStream_t st = as_stream(stream);
     const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
-    const RangeArgs a = make_range_args(w, reinterpret_cast<char *>(workspace), tau, ld, ec_rho_max, ec_maxnorm);
+    const RangeArgs a = make_range_args(w, reinterpret_cast<char *>(workspace), tau, tau_q, ld, ec_rho_max, ec_maxnorm);
     const dim3 qgrid((unsigned)((Q + 3) / 4));
     if (sm == SM_DOT) hipLaunchKernelGGL(range_setup_kernel<SM_DOT>, qgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, uq, d, a);
     else hipLaunchKernelGGL(range_setup_kernel<SM_COS>, qgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, uq, d, a);
@@ -436,6 +446,74 @@ static int range_scan(int sm, const char *what, const void *eq, const float *eq_
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
+
+// =====================================================================================================
+// tsim_range_merge: R CSR results of the same Q queries over disjoint row sets (global indices; every segment sorted by
+// (score desc, index asc)) -> one CSR result in the same order.  Merge by rank: an entry's place in its query's output segment
+// is its offset within its own segment plus, for every other list, the number of that list's entries of the query that rank
+// ahead of it, found by binary search (entries equal in score AND index rank by list number, so the result is a permutation of
+// the input whatever the data).  No scratch, no LDS, no dependence on a segment's length; every output slot is written exactly
+// once, by the thread of the entry that belongs there, so the result is deterministic.
+// Work is cut by ENTRY, not by query: thread t of the launch takes entry p of the query-major enumeration of all input entries
+// (query q holds the positions [lims_out[q], lims_out[q+1]), its lists one after the other), so one query that returns whole
+// shards spreads over the chip like 4 096 queries of a hundred hits.  Finding (q, list) costs log2 Q + R cached reads, small
+// against the R binary searches.  Whatever the data, a write lands inside the entry's own output segment: the place is < the sum
+// of the R segment lengths, and it is checked against the segment lims_out gives.
+// =====================================================================================================
+constexpr int RM_PER = 4;   // entries per thread
+
+__global__ __launch_bounds__(256) void range_merge_kernel(int R, int64_t Q, const int64_t *__restrict__ lims_in,
+                                                          const float *__restrict__ s_in, const int64_t *__restrict__ i_in,
+                                                          const int64_t *__restrict__ lims_out, float *__restrict__ out_s,
+                                                          int64_t *__restrict__ out_i, int64_t total) {
+    for (int k = 0; k < RM_PER; ++k) {
+        const int64_t p = ((int64_t)blockIdx.x * RM_PER + k) * 256 + threadIdx.x;
+        if (p >= total) return;
+        int64_t lo = 0, hi = Q;   // the query whose output segment holds position p: the first q with lims_out[q + 1] > p
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (lims_out[mid + 1] > p) hi = mid;
+            else lo = mid + 1;
+        }
+        if (lo >= Q) return;      // (total beyond lims_out[Q])
+        const int64_t q = lo, seg0 = lims_out[q], seglen = lims_out[q + 1] - seg0;
+        int64_t o = p - seg0;     // position among the query's input entries, list after list
+        if (o < 0) continue;
+        int r = 0;
+        int64_t b0 = 0;
+        for (; r < R; ++r) {
+            b0 = lims_in[r * (Q + 1) + q];
+            const int64_t len = lims_in[r * (Q + 1) + q + 1] - b0;
+            if (o < len) break;
+            if (len > 0) o -= len;
+        }
+        if (r == R) continue;     // (lims_out counts more entries than the lists hold)
+        const float s = s_in[b0 + o];
+        const int64_t i = i_in[b0 + o];
+        int64_t pos = o;
+        for (int r2 = 0; r2 < R; ++r2) {
+            if (r2 == r) continue;
+            const int64_t b = lims_in[r2 * (Q + 1) + q];
+            int64_t l = 0, h = lims_in[r2 * (Q + 1) + q + 1] - b;
+            while (l < h) {       // entries of list r2 ahead of (s, i): strictly ahead, and the equal one too when r2 < r
+                const int64_t mid = (l + h) >> 1;
+                const float ms = s_in[b + mid];
+                bool ahead = ms > s;
+                if (ms == s) {    // (the index is read on a tie of the score only)
+                    const int64_t mi = i_in[b + mid];
+                    ahead = mi < i || (mi == i && r2 < r);
+                }
+                if (ahead) l = mid + 1;
+                else h = mid;
+            }
+            pos += l;
+        }
+        if (pos < seglen) {
+            out_s[seg0 + pos] = s;
+            out_i[seg0 + pos] = i;
+        }
+    }
+}
 }  // namespace tsim
 
 extern "C" size_t tsim_range_workspace_bytes(int64_t Q, int64_t N) {
@@ -445,38 +523,64 @@ extern "C" size_t tsim_range_workspace_bytes(int64_t Q, int64_t N) {
     return w.total;
 }
 
+extern "C" int tsim_cosine_range_scan_tau(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                          const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld,
+                                          const float *tau_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                                          size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(tau_q, "cosine_range_scan_tau: null threshold array");
+    return tsim::range_scan(tsim::SM_COS, "cosine_range_scan_tau", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N,
+                            d, ld, 0.f, tau_q, out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
 extern "C" int tsim_cosine_range_scan(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                       const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld,
                                       float tau, int64_t *out_counts, int32_t *out_status, void *workspace, size_t workspace_bytes,
                                       void *stream) {
     return tsim::range_scan(tsim::SM_COS, "cosine_range_scan", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, nullptr, ec_rho_max, N, d,
-                            ld, tau, out_counts, out_status, workspace, workspace_bytes, stream);
+                            ld, tau, nullptr, out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
+static int dot_range_scan(const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                          const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d, int ld,
+                          float tau, const float *tau_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+    using namespace tsim;
+    TSIM_REQUIRE(tau_q || tau == tau, "%s: the threshold is NaN", what);
+    TSIM_REQUIRE(eq_f32 && ec_f32, "%s: the float32 matrices are required", what);
+    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "%s: the corpus rows' max-norm word and measured rho_max are required", what);
+    return range_scan(SM_DOT, what, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, tau, tau_q,
+                      out_counts, out_status, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_dot_range_scan(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
                                    const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
                                    int d, int ld, float tau, int64_t *out_counts, int32_t *out_status, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    using namespace tsim;
-    TSIM_REQUIRE(tau == tau, "dot_range_scan: the threshold is NaN");
-    TSIM_REQUIRE(eq_f32 && ec_f32, "dot_range_scan: the float32 matrices are required");
-    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "dot_range_scan: the corpus rows' max-norm word and measured rho_max are required");
-    return range_scan(SM_DOT, "dot_range_scan", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, tau,
-                      out_counts, out_status, workspace, workspace_bytes, stream);
+    return dot_range_scan("dot_range_scan", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, tau, nullptr,
+                          out_counts, out_status, workspace, workspace_bytes, stream);
 }
 
-extern "C" int tsim_range_fill(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
-                               int64_t N, int d, float tau, const int64_t *lims, float *out_scores, int64_t *out_idx,
-                               int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" int tsim_dot_range_scan_tau(const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
+                                       int64_t N, int d, int ld, const float *tau_q, int64_t *out_counts, int32_t *out_status,
+                                       void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(tau_q, "dot_range_scan_tau: null threshold array");
+    return dot_range_scan("dot_range_scan_tau", eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, 0.f,
+                          tau_q, out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
+static int range_fill(const char *what, int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32,
+                      int64_t ldc_f32, int64_t N, int d, float tau, const float *tau_q, const int64_t *lims, float *out_scores,
+                      int64_t *out_idx, int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
     using namespace tsim;
-    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT, "range_fill: unknown space %d", space);
+    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT, "%s: unknown space %d", what, space);
     RangeWs w;
-    int rc = range_check_shapes("range_fill", eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, workspace, workspace_bytes, &w);
+    int rc = range_check_shapes(what, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, tau_q, workspace, workspace_bytes, &w);
     if (rc) return rc;
     // out_scores / out_idx may be null when the scan reported no hit at all (lims[Q] == 0): nothing is written then
-    TSIM_REQUIRE(lims, "range_fill: null pointer");
+    TSIM_REQUIRE(lims, "%s: null pointer", what);
     hipStream_t st = as_stream(stream);
-    const RangeArgs a = make_range_args(w, reinterpret_cast<char *>(workspace), tau, 0, nullptr, nullptr);
+    const RangeArgs a = make_range_args(w, reinterpret_cast<char *>(workspace), tau, tau_q, 0, nullptr, nullptr);
     TSIM_HIP_CHECK(hipMemsetAsync(a.cursor, 0, (size_t)Q * 8, st));
     hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, Q, lims, out_scores, out_idx, idx_offset, a);
     TSIM_HIP_CHECK(hipGetLastError());
@@ -491,6 +595,38 @@ extern "C" int tsim_range_fill(int space, const float *eq_f32, int64_t ldq_f32, 
                            (int64_t *)nullptr, lims, out_scores, out_idx, idx_offset, a);
     TSIM_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(range_bf_sort_kernel, dim3((unsigned)(Q < 256 ? Q : 256)), dim3(RS_SORT_T), 0, st, Q, lims, out_scores, out_idx, a);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+extern "C" int tsim_range_fill(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
+                               int64_t N, int d, float tau, const int64_t *lims, float *out_scores, int64_t *out_idx,
+                               int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+    return range_fill("range_fill", space, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, nullptr, lims, out_scores, out_idx,
+                      idx_offset, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_range_fill_tau(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
+                                   int64_t N, int d, const float *tau_q, const int64_t *lims, float *out_scores, int64_t *out_idx,
+                                   int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(tau_q, "range_fill_tau: null threshold array");
+    return range_fill("range_fill_tau", space, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, 0.f, tau_q, lims, out_scores, out_idx,
+                      idx_offset, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_range_merge(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                                const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream) {
+    using namespace tsim;
+    TSIM_REQUIRE(nlists >= 1 && nlists <= TSIM_RANGE_MERGE_MAX_LISTS, "range_merge: %d lists (1 .. %d)", nlists,
+                 TSIM_RANGE_MERGE_MAX_LISTS);
+    TSIM_REQUIRE(Q >= 0 && total >= 0, "range_merge: bad shape Q=%lld total=%lld", (long long)Q, (long long)total);
+    TSIM_REQUIRE(Q < (1ll << 31) - 512 && total < (1ll << 33), "range_merge: Q=%lld total=%lld too large for one launch", (long long)Q,
+                 (long long)total);
+    if (Q == 0 || total == 0) return TSIM_OK;
+    TSIM_REQUIRE(lims_in && scores_in && idx_in && lims_out && out_scores && out_idx, "range_merge: null pointer");
+    const int64_t per = 256 * (int64_t)RM_PER;
+    hipLaunchKernelGGL(range_merge_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, as_stream(stream), nlists, Q,
+                       lims_in, scores_in, idx_in, lims_out, out_scores, out_idx, total);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }

@@ -16,7 +16,11 @@ rows with exact scores, so the result is bit-identical to a single-GPU search ov
 ``submit`` / ``finish`` split a search at the first exchange: ``submit`` starts the query all-gather of batch i+1 on a side
 stream while the local search of batch i still runs on the main stream; ``search`` = ``finish(submit)``.
 
-``local_search`` / ``merge`` are injectable so that the collective choreography can be exercised on CPU ranks
+``range_search`` is the same choreography for the exact range search (every row at or above a threshold, one float or one per
+query): CSR results of variable length, so the per-rank ``lims`` travel first and the payloads are padded to the largest rank
+total; ``ops.range_merge`` joins them on the device.
+
+``local_search`` / ``merge`` (and ``local_range`` / ``range_merge``) are injectable so that the collective choreography can be exercised on CPU ranks
 (gloo) with the oracle standing in for the kernels — in tests only; the defaults are the HIP ops and raise without
 a GPU.
 """
@@ -52,6 +56,16 @@ def _hip_merge(scores: torch.Tensor, idx: torch.Tensor, k: int):
     return ops.topk_merge(scores, idx, k)
 
 
+def _hip_local_range(q_f32, c_unit, c_f32, d, threshold, offset, rho_c=None):
+    from .. import ops
+    return ops.cosine_range(ops.l2norm_rows(q_f32), c_unit, d, threshold, eq_f32=q_f32, ec_f32=c_f32, rho_c=rho_c, idx_offset=offset)
+
+
+def _hip_range_merge(results, total):
+    from .. import ops
+    return ops.range_merge(results, total=total)
+
+
 def shard_bounds(n_total: int, world: int, rank: int) -> Tuple[int, int]:
     """Block partition of n_total rows: rank r owns [lo, hi)."""
     base, rem = divmod(n_total, world)
@@ -70,7 +84,8 @@ class ShardedCorpusSearch:
     def __init__(self, corpus_unit_local: torch.Tensor, d: int, row_offset: int,
                  group: Optional[dist.ProcessGroup] = None,
                  local_search: Callable = _hip_local_search, merge: Callable = _hip_merge,
-                 corpus_f32_local: Optional[torch.Tensor] = None, corpus_rho: Optional[torch.Tensor] = None):
+                 corpus_f32_local: Optional[torch.Tensor] = None, corpus_rho: Optional[torch.Tensor] = None,
+                 local_range: Callable = _hip_local_range, range_merge: Callable = _hip_range_merge):
         """``corpus_f32_local`` [n_r, d] float32: the embeddings (scores are then the reference's cosines of float32 rows and
         queries are passed as float32 embeddings); without it queries are unit float16 rows and scores their inner products.
         ``corpus_rho``: the shard's rounding-residual maximum from ``ops.l2norm_rows(..., return_rho=True)`` (tightens the
@@ -83,6 +98,8 @@ class ShardedCorpusSearch:
         self.group = group
         self.local_search = local_search
         self.merge = merge
+        self.local_range = local_range
+        self.range_merge = range_merge
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if self.world > 1 else 0
         self._comm_stream = None
@@ -189,3 +206,74 @@ class ShardedCorpusSearch:
             prev = t
         if prev is not None:
             yield self.finish(prev, k)
+
+    # ------------------------------------------------------------------ range search
+    def range_search(self, q_local: torch.Tensor, threshold, counts: Optional[Sequence[int]] = None
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Exact range search by cosine over the sharded corpus: every rank passes its slice of the query batch (float32
+        embeddings) and gets ``(lims int64 [Q+1], scores float32 [T], global indices int64 [T])`` for ALL queries (rank-major
+        order, as :meth:`search`) — bit for bit what ``ops.cosine_range`` returns on one GPU over the concatenated corpus.
+        ``threshold``: a float (the same on every rank), or a tensor [Q_local] with one threshold per local query, which is
+        gathered with the queries.  ``counts`` as in :meth:`submit`; the padding queries get the threshold +inf and no hits.
+        Needs ``corpus_f32_local`` (there is no unit-rows-only range search).  Cosine only: a shard holds unit rows, not the
+        scaled rows and max-norm word of the inner-product space.
+        Exchanges: the queries (with their thresholds), the per-rank ``lims`` (from which every rank reads the totals on the
+        host), then scores and indices padded to the largest rank total — skipped when no rank has a hit."""
+        if self.corpus_f32 is None:
+            raise ValueError("range_search needs the shard's float32 rows (corpus_f32_local)")
+        if q_local.dtype != torch.float32 or q_local.dim() != 2:
+            raise ValueError("range_search takes float32 query embeddings [Q_local, d]")
+        ql = q_local.shape[0]
+        per_query = isinstance(threshold, torch.Tensor) and threshold.dim() > 0
+        if per_query and (threshold.dim() != 1 or threshold.shape[0] != ql):
+            raise ValueError(f"a per-query threshold must have shape [{ql}] (one per local query), got {tuple(threshold.shape)}")
+        hip = self.local_range is _hip_local_range
+        extra = (self.corpus_rho,) if hip else ()
+        if self.world == 1:
+            return self.local_range(q_local, self.corpus, self.corpus_f32, self.d, threshold, self.row_offset, *extra)
+        qmax = ql
+        if counts is not None:
+            counts = [int(c) for c in counts]
+            if len(counts) != self.world or counts[self.rank] != ql:
+                raise ValueError(f"counts {counts} do not describe {self.world} ranks with {ql} local rows")
+            qmax = max(counts)
+            if all(c == qmax for c in counts):
+                counts = None
+        dev = q_local.device
+        if per_query or counts is not None:
+            # the thresholds travel as one more float32 column of the query rows; padding rows are zero queries with +inf
+            ext = torch.zeros((qmax, q_local.shape[1] + 1), dtype=torch.float32, device=dev)
+            ext[:ql, :-1] = q_local
+            ext[:, -1] = float("inf")
+            ext[:ql, -1] = threshold.to(device=dev, dtype=torch.float32) if per_query else float(threshold)
+            g = self.gather_queries(ext)
+            q_all, threshold = g[:, :-1].contiguous(), g[:, -1].contiguous()
+        else:
+            q_all = self.gather_queries(q_local)
+        Q = q_all.shape[0]
+        lims, s, i = self.local_range(q_all, self.corpus, self.corpus_f32, self.d, threshold, self.row_offset, *extra)
+        lims_all = torch.empty((self.world, Q + 1), dtype=torch.int64, device=dev)
+        self._all_gather(lims_all.view(-1), lims.contiguous())
+        totals = [int(t) for t in lims_all[:, -1].tolist()]           # the host read: payload and output sizes
+        tmax = max(totals)
+        if tmax == 0:
+            out = (torch.zeros((Q + 1,), dtype=torch.int64, device=dev), s[:0], i[:0])
+        else:
+            s_pad = torch.zeros((tmax,), dtype=torch.float32, device=dev)
+            i_pad = torch.zeros((tmax,), dtype=torch.int64, device=dev)
+            s_pad[:totals[self.rank]] = s
+            i_pad[:totals[self.rank]] = i
+            s_all = torch.empty((self.world, tmax), dtype=torch.float32, device=dev)
+            i_all = torch.empty((self.world, tmax), dtype=torch.int64, device=dev)
+            self._all_gather(s_all.view(-1), s_pad)
+            self._all_gather(i_all.view(-1), i_pad)
+            out = self.range_merge([(lims_all[r], s_all[r], i_all[r]) for r in range(self.world)], sum(totals))
+        if counts is None:
+            return out
+        # uneven batch: the padding queries have no hits, so only their (empty) segments leave lims
+        lims = out[0]
+        n = lims[1:] - lims[:-1]
+        keep = torch.cat([n[r * qmax:r * qmax + c] for r, c in enumerate(counts)])
+        lims = torch.zeros((keep.numel() + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(keep, 0, out=lims[1:])
+        return lims, out[1], out[2]

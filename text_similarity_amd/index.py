@@ -130,16 +130,18 @@ class GpuFlatIndex:
         lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
         return lab, s
 
-    def range_search(self, data, threshold: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def range_search(self, data, threshold) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Every live row whose score against a query is >= ``threshold`` (cosine, or q.c for 'ip'): ``(lims int64 [Q+1], scores
         float32 [T], labels int64 [T])`` on the device, faiss' ``range_search`` layout — the hits of query q are
-        ``[lims[q], lims[q+1])``, ordered by (score desc, row asc).  Exact and complete (:func:`ops.cosine_range`)."""
+        ``[lims[q], lims[q+1])``, ordered by (score desc, row asc).  Exact and complete (:func:`ops.cosine_range`).
+        ``threshold``: a float, or an array / tensor [Q] with one threshold per query (a wrong length is a ValueError)."""
         self._compact()
         q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
         if q.dim() == 1:
             q = q.unsqueeze(0)
         qf = q.to(self.device, dtype=torch.float32).contiguous()
         if self._n == 0:
+            ops._threshold_array("range_search", threshold, qf.shape[0], self.device)      # (the length check of the ops)
             return (torch.zeros((qf.shape[0] + 1,), dtype=torch.int64, device=self.device),
                     torch.empty((0,), dtype=torch.float32, device=self.device),
                     torch.empty((0,), dtype=torch.int64, device=self.device))
@@ -152,7 +154,7 @@ class GpuFlatIndex:
                                           rho_c=self._rho)
         return lims, s, self._labels[i]
 
-    def range_query(self, data, threshold: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def range_query(self, data, threshold) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """numpy form of :meth:`range_search` with ``knn_query``'s distance convention: ``(lims [Q+1], labels [T], distances [T]
         = 1 - score)``, best first within each query."""
         lims, scores, labels = self.range_search(data, threshold)

@@ -253,6 +253,7 @@ def dot_topk(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, k: int, eq_
 
 # ------------------------------------------------------------------------------------------------- exact range search
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
+RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins
 MAX_RANGE_QUERIES_PER_CALL = 4096       # the workspace holds RANGE_SLOT_CAP entries of 8 bytes per query: 64 MiB per call
 
 
@@ -297,6 +298,20 @@ def range_collect_threshold(threshold, rho_q, rho_c, ld: int, nqs: Optional[floa
     return (thr if thr > f32(-3.4e38) else None), eps
 
 
+def _threshold_array(what, threshold, Q: int, dev):
+    """None for one threshold per call (a number or a 0-dim tensor / array); else the per-query thresholds as contiguous float32 [Q] on ``dev``.  Another dtype or device is converted; another length is
+    a ValueError."""
+    if isinstance(threshold, (np.ndarray, list, tuple)):
+        threshold = torch.as_tensor(np.asarray(threshold))
+    if not isinstance(threshold, torch.Tensor) or threshold.dim() == 0:
+        return None
+    if threshold.dim() != 1 or threshold.shape[0] != Q:
+        raise ValueError(f"{what}: a per-query threshold must have shape [{Q}] (one per query), got {tuple(threshold.shape)}")
+    if threshold.is_complex() or threshold.dtype == torch.bool:
+        raise ValueError(f"{what}: a per-query threshold must be real-valued, got {threshold.dtype}")
+    return threshold.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
 def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset, return_status):
     _need_gpu(eq_unit, ec_half, eq_f32, ec_f32)
     if eq_unit.dtype != UNIT_DTYPE or ec_half.dtype != UNIT_DTYPE:
@@ -304,11 +319,13 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
     ld = pad_dim(d)
     if eq_unit.shape[1] != ld or ec_half.shape[1] != ld or not eq_unit.is_contiguous() or not ec_half.is_contiguous():
         raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d})={ld}")
-    tau = float(threshold)
-    if tau != tau:
-        raise ValueError(f"{what}: the threshold is NaN")
     Q, N = eq_unit.shape[0], ec_half.shape[0]
     dev = eq_unit.device
+    tau_q = _threshold_array(what, threshold, Q, dev)
+    if tau_q is None:
+        tau = float(threshold)
+        if tau != tau:
+            raise ValueError(f"{what}: the threshold is NaN")
     for t, rows, name in ((eq_f32, Q, "eq_f32"), (ec_f32, N, "ec_f32")):
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.device != dev:
             raise ValueError(f"{what}: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
@@ -333,11 +350,13 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
                 ldq, ldc = _row_stride(eq_f32), _row_stride(ec_f32)
                 qf = eq_f32.data_ptr() + q0 * ldq * 4
                 head = (eq_unit.data_ptr() + q0 * ld * 2, qf, ldq, nq, ec_half.data_ptr(), ec_f32.data_ptr(), ldc)
-                tail = (N, d, ld, tau, counts.data_ptr() + q0 * 8, status.data_ptr() + q0 * 4, ws.data_ptr(), ws.numel(), st)
+                # (a threshold array is sliced with the queries; the _tau entries are the scalar ones reading tau_q[q])
+                tau_arg = tau if tau_q is None else tau_q.data_ptr() + q0 * 4
+                tail = (N, d, ld, tau_arg, counts.data_ptr() + q0 * 8, status.data_ptr() + q0 * 4, ws.data_ptr(), ws.numel(), st)
                 if scale_c is None:
-                    rc = L.tsim_cosine_range_scan(*head, rho_p, *tail)
+                    rc = (L.tsim_cosine_range_scan if tau_q is None else L.tsim_cosine_range_scan_tau)(*head, rho_p, *tail)
                 else:
-                    rc = L.tsim_dot_range_scan(*head, scale_c.data_ptr(), rho_p, *tail)
+                    rc = (L.tsim_dot_range_scan if tau_q is None else L.tsim_dot_range_scan_tau)(*head, scale_c.data_ptr(), rho_p, *tail)
                 _lib.check(rc, what)
                 sl = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
                 torch.cumsum(counts[q0:q0 + nq], 0, out=sl[1:])
@@ -345,8 +364,9 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
                 s = torch.empty((t_slice,), dtype=torch.float32, device=dev)
                 i = torch.empty((t_slice,), dtype=torch.int64, device=dev)
                 if t_slice:
-                    _lib.check(L.tsim_range_fill(space, qf, ldq, nq, ec_f32.data_ptr(), ldc, N, d, tau, sl.data_ptr(), s.data_ptr(),
-                                                 i.data_ptr(), idx_offset, ws.data_ptr(), ws.numel(), st), what)
+                    fill = L.tsim_range_fill if tau_q is None else L.tsim_range_fill_tau
+                    _lib.check(fill(space, qf, ldq, nq, ec_f32.data_ptr(), ldc, N, d, tau_arg, sl.data_ptr(), s.data_ptr(),
+                                    i.data_ptr(), idx_offset, ws.data_ptr(), ws.numel(), st), what)
                 lims[q0 + 1:q0 + nq + 1] = sl[1:] + total
                 total += t_slice
                 parts_s.append(s)
@@ -361,7 +381,7 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
     return (lims, scores, idx, status) if return_status else (lims, scores, idx)
 
 
-def cosine_range(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, threshold: float, eq_f32: torch.Tensor,
+def cosine_range(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, threshold, eq_f32: torch.Tensor,
                  ec_f32: torch.Tensor, rho_c: Optional[torch.Tensor] = None, idx_offset: int = 0, return_status: bool = False):
     """Exact range search by cosine: EVERY corpus row whose score against a query is >= ``threshold`` (faiss ``range_search``),
     the score being exactly what :func:`cosine_topk` returns for the pair with the float32 matrices given (which are required
@@ -371,14 +391,18 @@ def cosine_range(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, threshold
     collects the candidates, an exact re-score decides; a query that collects more than RANGE_SLOT_CAP rows is answered by an
     exact pass over the float32 rows instead (``return_status`` adds int32 [Q]: 1 = collected, 2 = exact pass; include/tsim.h).
     The total T is read back once between the two halves of the call (the output is allocated from it); query sets above
-    MAX_RANGE_QUERIES_PER_CALL rows are processed in slices.  Q = 0 or N = 0: empty results, no launch."""
+    MAX_RANGE_QUERIES_PER_CALL rows are processed in slices.  Q = 0 or N = 0: empty results, no launch.
+    ``threshold`` may also be a tensor (or array) [Q], one threshold per query (converted to float32 on the queries' device; a
+    wrong length is a ValueError): query q is answered exactly as by the call with the float ``threshold[q]``, in the same single
+    pass over the corpus.  ``-inf`` there returns every row, ``+inf`` none; a NaN there — which a float argument refuses — gives
+    that query no hit and status 2."""
     if eq_f32 is None or ec_f32 is None:
         raise ValueError("cosine_range needs the float32 matrices eq_f32 and ec_f32")
     return _range("cosine_range", _lib.SPACE_COSINE, eq_unit, ec_unit, d, threshold, eq_f32, ec_f32, rho_c, None, idx_offset,
                   return_status)
 
 
-def dot_range(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, threshold: float, eq_f32: torch.Tensor,
+def dot_range(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, threshold, eq_f32: torch.Tensor,
               ec_f32: torch.Tensor, rho_c: torch.Tensor, scale_c: torch.Tensor, idx_offset: int = 0, return_status: bool = False):
     """:func:`cosine_range` by inner product: every row with float32(q.c) >= ``threshold``, the score of :func:`dot_topk`.
     ``(ec_scaled, rho_c, scale_c)``: :func:`dot_scaled_rows` of ``ec_f32``; all are required.  A zero query scores 0 against
@@ -387,6 +411,49 @@ def dot_range(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, threshold:
         raise ValueError("dot_range needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (dot_scaled_rows)")
     return _range("dot_range", _lib.SPACE_DOT, eq_unit, ec_scaled, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset,
                   return_status)
+
+
+def range_merge(results, total: Optional[int] = None):
+    """Merge range results of the SAME queries over disjoint row sets (corpus shards or chunks searched with their own
+    ``idx_offset``): ``results`` is a sequence of ``(lims [Q+1], scores [T_r], idx [T_r])`` as :func:`cosine_range` returns them
+    (a payload may be longer than ``lims[-1]``, e.g. padded for an exchange; the excess is ignored), the return value one such
+    triple whose segment q is the union of the lists' segments ordered by (score desc, index asc) — what one range search over
+    the concatenated rows returns, bit for bit.  One kernel (tsim_range_merge): each entry finds its place by binary search in
+    the other lists' segments, so segments may be of any length.  1 <= len(results) <= 64; one list comes back as a copy.
+    ``total``: the number of entries over all lists when the caller knows it on the host (the sum of ``lims[-1]``); without it
+    the total is read back once."""
+    results = [tuple(r) for r in results]
+    R = len(results)
+    if not 1 <= R <= _lib.RANGE_MERGE_MAX_LISTS:
+        raise ValueError(f"range_merge takes 1 to {_lib.RANGE_MERGE_MAX_LISTS} results, got {R}")
+    _need_gpu(*[t for r in results for t in r])
+    Q = results[0][0].numel() - 1
+    for lims, s, i in results:
+        if lims.dtype != torch.int64 or lims.dim() != 1 or lims.numel() != Q + 1 or Q < 0:
+            raise ValueError("range_merge: every lims must be int64 [Q+1] for one Q")
+        if s.dtype != torch.float32 or i.dtype != torch.int64 or s.dim() != 1 or s.shape != i.shape:
+            raise ValueError("range_merge: scores float32 [T] and idx int64 [T] of one length per result")
+    dev = results[0][0].device
+    base, bases = 0, []
+    for _, s, _ in results:
+        bases.append(base)
+        base += s.numel()
+    # absolute offsets of every segment in the concatenated payloads, and the output's prefix sum
+    lims_in = torch.stack([r[0] for r in results]) + torch.tensor(bases, dtype=torch.int64, device=dev)[:, None]
+    lims_out = torch.zeros((Q + 1,), dtype=torch.int64, device=dev)
+    if Q > 0:
+        torch.cumsum((lims_in[:, 1:] - lims_in[:, :-1]).sum(0), 0, out=lims_out[1:])
+    T = int(lims_out[-1].item()) if total is None else int(total)
+    out_s = torch.empty((T,), dtype=torch.float32, device=dev)
+    out_i = torch.empty((T,), dtype=torch.int64, device=dev)
+    if Q > 0 and T > 0:
+        s_in = (results[0][1] if R == 1 else torch.cat([r[1] for r in results])).contiguous()
+        i_in = (results[0][2] if R == 1 else torch.cat([r[2] for r in results])).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().tsim_range_merge(lims_in.data_ptr(), s_in.data_ptr(), i_in.data_ptr(), R, Q,
+                                                   lims_out.data_ptr(), T, out_s.data_ptr(), out_i.data_ptr(), _stream(out_s)),
+                       "range_merge")
+    return lims_out, out_s, out_i
 
 
 def packed_result_bytes(Q: int, k: int) -> int:

@@ -122,12 +122,12 @@ class SentenceMiningPipeline(SearchPipeline):
             return scores[0], idxs[0]
         return ops.topk_merge(scores, idxs, k)
 
-    def range_tensors(self, query_embeddings: torch.Tensor, threshold: float, corpus=None):
+    def range_tensors(self, query_embeddings: torch.Tensor, threshold, corpus=None):
         """Device-level range search: ``(lims int64 [Q+1], scores float32 [T], indices int64 [T])`` — EVERY corpus row whose
         score (``score_function``) against a query is >= ``threshold``; the hits of query q are ``[lims[q], lims[q+1])``, ordered
         by (score desc, index asc).  Exact and complete (:func:`ops.cosine_range` / :func:`ops.dot_range`).  The corpus goes
-        through in chunks of ``corpus_chunk_size``; a range result needs no merge, the per-chunk hits of a query are
-        concatenated and re-sorted on the device."""
+        through in chunks of ``corpus_chunk_size``; the per-chunk results, sorted already, are merged on the device
+        (:func:`ops.range_merge`).  ``threshold``: a float, or an array / tensor [Q] with one threshold per query."""
         corpus = self.corpus if corpus is None else corpus
         n = len(corpus)
         d = query_embeddings.shape[1]
@@ -135,6 +135,9 @@ class SentenceMiningPipeline(SearchPipeline):
         qf = query_embeddings.to(dev, dtype=torch.float32).contiguous()
         qn = ops.l2norm_rows(qf)
         Q = qf.shape[0]
+        tau_q = ops._threshold_array("range_tensors", threshold, Q, qf.device)    # converted once, not per chunk
+        if tau_q is not None:
+            threshold = tau_q
         parts = []
         for start in range(0, n, self.corpus_chunk_size):
             chunk = corpus[start:start + self.corpus_chunk_size]
@@ -152,18 +155,16 @@ class SentenceMiningPipeline(SearchPipeline):
         if not parts:
             return (torch.zeros((Q + 1,), dtype=torch.int64, device=qf.device), torch.empty((0,), dtype=torch.float32, device=qf.device),
                     torch.empty((0,), dtype=torch.int64, device=qf.device))
-        # query id of every hit, then one stable sort chain: index asc, score desc, query asc
-        qid = torch.cat([torch.repeat_interleave(torch.arange(Q, device=l.device), l[1:] - l[:-1]) for l, _, _ in parts])
-        s = torch.cat([p[1] for p in parts])
-        i = torch.cat([p[2] for p in parts])
-        qid, s, i = _sort_columns([qid, s, i], ((2, False), (1, True), (0, False)))
-        lims = torch.zeros((Q + 1,), dtype=torch.int64, device=s.device)
-        torch.cumsum(torch.bincount(qid, minlength=Q), 0, out=lims[1:])
-        return lims, s, i
+        out = None
+        for r0 in range(0, len(parts), ops.RANGE_MERGE_MAX_LISTS - 1):      # (more chunks than one merge takes: fold them in)
+            group = ([out] if out is not None else []) + parts[r0:r0 + ops.RANGE_MERGE_MAX_LISTS - 1]
+            out = ops.range_merge(group, total=sum(p[1].numel() for p in group))   # (the payloads of the ops are exactly lims[-1] long)
+        return out
 
-    def mine(self, queries, threshold: float) -> Dict[int, list]:
+    def mine(self, queries, threshold) -> Dict[int, list]:
         """``{query_idx: [(corpus_idx, text, score), ...]}``: every corpus entry scoring >= ``threshold`` against the query, best
-        first — sentence mining with a score floor.  ``queries``: texts or embeddings; the corpus is the pipeline's."""
+        first — sentence mining with a score floor.  ``queries``: texts or embeddings; the corpus is the pipeline's.
+        ``threshold``: a float, or one floor per query (array / tensor [Q])."""
         query_embeddings = self.encode_corpus(documents=queries)
         lims, scores, idx = self.range_tensors(query_embeddings, threshold)
         lims, scores, idx = lims.cpu().tolist(), scores.cpu().tolist(), idx.cpu().tolist()

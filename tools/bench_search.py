@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot] [--spread]
-[--k K ...] [--range TAU ... | --range-hits H ...]
+[--k K ...] [--range TAU ... | --range-hits H ...] [--tau-array] [--range-merge R Q HITS]
 
 --score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
 one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --spread: corpus row norms spread
@@ -9,7 +9,9 @@ k > 64 runs the _large entries); one line per (Q, k).
 --range TAU ...: time the exact range search (ops.cosine_range / ops.dot_range on the float32 rows) at these thresholds instead of
 top-k: ms per call (scan + the host read of the total + fill), mean hits per query and the status counts; one line per (Q, tau).
 --range-hits H ...: the same with tau derived from the normal tail so that about H of the N Gaussian rows pass per query (a cosine
-of Gaussian rows is ~ N(0, 1/d), an inner product ~ N(0, d)); the achieved mean is printed."""
+of Gaussian rows is ~ N(0, 1/d), an inner product ~ N(0, d)); the achieved mean is printed.
+--tau-array: pass the threshold of a range run as a per-query tensor [Q] holding that one value (the _tau entries) instead of a float.
+--range-merge R Q HITS: time ops.range_merge alone on R synthetic lists of Q queries x HITS sorted entries each (no corpus is made)."""
 import argparse
 import json
 import os
@@ -29,20 +31,12 @@ ap.add_argument("--spread", action="store_true")
 ap.add_argument("--k", nargs="+", type=int, default=[10])
 ap.add_argument("--range", nargs="+", type=float, default=[], dest="taus")
 ap.add_argument("--range-hits", nargs="+", type=float, default=[])
+ap.add_argument("--tau-array", action="store_true")
+ap.add_argument("--range-merge", nargs=3, type=int, default=None, metavar=("R", "Q", "HITS"))
 a = ap.parse_args()
 N, d, Qs = a.N, a.d, a.Q
 dev = "cuda:0"
 g = torch.Generator(device=dev).manual_seed(4321)
-cf = torch.randn((N, d), generator=g, device=dev)
-if a.spread:
-    cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
-if a.score == "dot":
-    corpus, rho, scale = ops.dot_scaled_rows(cf)
-else:
-    corpus, rho = ops.l2norm_rows(cf, return_rho=True)
-    if not (a.taus or a.range_hits):
-        del cf
-taus = list(a.taus) + [statistics.NormalDist().inv_cdf(1.0 - h / N) * (d ** 0.5 if a.score == "dot" else d ** -0.5) for h in a.range_hits]
 
 
 def timed(run, iters):
@@ -58,17 +52,46 @@ def timed(run, iters):
     return e0.elapsed_time(e1) / iters
 
 
+if a.range_merge:
+    R, Q, H = a.range_merge
+    lims = torch.arange(Q + 1, device=dev, dtype=torch.int64) * H
+    lists = []
+    for r in range(R):      # list r holds the indices = r mod R; scores sorted descending within each query
+        sc = torch.rand((Q, H), generator=g, device=dev).sort(dim=1, descending=True).values.reshape(-1)
+        ix = torch.arange(H, device=dev, dtype=torch.int64).repeat(Q) * R + r
+        lists.append((lims, sc, ix))
+    ms = timed(lambda: ops.range_merge(lists, total=R * Q * H), 5)
+    ms_read = timed(lambda: ops.range_merge(lists), 5)
+    ml, msc, mi = ops.range_merge(lists)
+    srt = msc.view(Q, R * H)
+    assert int(ml[-1]) == R * Q * H and bool((srt[:, 1:] <= srt[:, :-1]).all())
+    print(json.dumps({"range_merge": True, "R": R, "Q": Q, "hits_per_list": H, "entries": R * Q * H, "ms_total_given": round(ms, 4),
+                      "ms_total_read_back": round(ms_read, 4)}), flush=True)
+    sys.exit(0)
+cf = torch.randn((N, d), generator=g, device=dev)
+if a.spread:
+    cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
+if a.score == "dot":
+    corpus, rho, scale = ops.dot_scaled_rows(cf)
+else:
+    corpus, rho = ops.l2norm_rows(cf, return_rho=True)
+    if not (a.taus or a.range_hits):
+        del cf
+taus = list(a.taus) + [statistics.NormalDist().inv_cdf(1.0 - h / N) * (d ** 0.5 if a.score == "dot" else d ** -0.5) for h in a.range_hits]
+
+
 for Q, tau in [(Q, tau) for Q in (Qs if taus else []) for tau in taus]:
     qf = torch.randn((Q, d), generator=g, device=dev)
     q = ops.l2norm_rows(qf)
+    thr = torch.full((Q,), tau, dtype=torch.float32, device=dev) if a.tau_array else tau
 
     def run():
         if a.score == "dot":
-            return ops.dot_range(q, corpus, d, tau, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=True)
-        return ops.cosine_range(q, corpus, d, tau, eq_f32=qf, ec_f32=cf, rho_c=rho, return_status=True)
+            return ops.dot_range(q, corpus, d, thr, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=True)
+        return ops.cosine_range(q, corpus, d, thr, eq_f32=qf, ec_f32=cf, rho_c=rho, return_status=True)
     ms = timed(run, 5 if Q <= 4096 else 2)
     lims, _, _, st = run()
-    print(json.dumps({"score": a.score, "range": True, "Q": Q, "N": N, "d": d, "tau": round(tau, 6), "ms": round(ms, 4),
+    print(json.dumps({"score": a.score, "range": True, "tau_array": a.tau_array, "Q": Q, "N": N, "d": d, "tau": round(tau, 6), "ms": round(ms, 4),
                       "mean_hits": round(int(lims[-1]) / Q, 2), "status_counts": torch.bincount(st.long(), minlength=3).tolist()}),
           flush=True)
 if taus:
