@@ -135,6 +135,67 @@ int tsim_dot_topk_ex(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, 
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact Euclidean search: top-k by squared L2 distance of the float32 rows (the default space of hnswlib and faiss).
+ *
+ * The idea.  argmin_c |q - c|^2 = argmax_c (q.c - |c|^2 / 2): an inner product of vectors one element longer, so the MFMA
+ * selection pass of the other spaces runs unchanged.  A = tsim_dot_scale(word), word the corpus' max-norm word
+ * (tsim_max_norm_rows), S = 2 A.
+ *   corpus row   c' = (c, -|c|^2 / (2A)):  |c'| <= A sqrt(1.25) < S, stored as half(c' / S) — no second max pass;
+ *   query row    q' = (q, A):  stored as the unit row half(q' / nq'), nq' = sqrt(|q|^2 + A^2) >= A > 0;
+ *   MFMA score   m ~ q'.c' / (nq' S) = (q.c - |c|^2 / 2) / nqs = (|q|^2 - dist^2) / (2 nqs),  nqs = nq' S, dist^2 = |q - c|^2:
+ *                for a fixed query it falls as dist^2 grows.  A (not 1) in the extra column balances the two parts: the
+ *                guard's window in dist^2 is about 1e-3 |q| |c| whatever the overall scale of the embeddings.
+ * The half operands are ld = tsim_pad_dim(d + 1) wide, so d <= 767 (d = 384 runs the 512-wide kernel).
+ * tsim_l2_rows writes out[r, :d] = half(x[r] / S), out[r, d] = half(-|x_r|^2 / (2 A S)) with |x_r|^2 the float64 sum in the
+ * canonical order of tsim_l2norm_rows, zeros up to ld_out (>= d + 1, else TSIM_EINVAL), and raises rho_max (may be NULL) to the
+ * flush-safe residual of the d + 1 elements as tsim_dot_scaled_rows does.  A non-finite word gives zero rows and rho 2.
+ * tsim_l2_query_rows writes the augmented unit rows: float64 throughout, one rounding to half per element; a non-finite nq'
+ * gives a zero row.  Both words must be the ones the search is given: rows made before the word grew must be made again. */
+int tsim_l2_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm, void *out_f16,
+                 int ld_out, float *rho_max, void *stream);
+int tsim_l2_query_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm, void *out_f16,
+                       int ld_out, void *stream);
+/* Top-k by distance: out_scores[q, j] = float32(sum_j (q_j - c_j)^2) of the float32 rows, ASCENDING, ties to the lower index;
+ * padding +inf / -1.  Canonical evaluation (restated in numpy by tests/test_l2_search_*.py): diff = (double)q_j - (double)c_j;
+ * lane l adds diff * diff for j = l, l + 64, ... with the multiply and the add rounded separately (no fused multiply-add: diff^2
+ * is not exact in float64); the xor butterfly 32 .. 1; one rounding to float32.  eq_aug / ec_aug: tsim_l2_query_rows /
+ * tsim_l2_rows of eq_f32 / ec_f32 under ec_maxnorm, ec_rho_max the residual word of tsim_l2_rows; all four are REQUIRED, and
+ * ld == tsim_pad_dim(d + 1) (else TSIM_EINVAL).  tsim_l2_topk_ex: 1 <= k <= 64; tsim_l2_topk_large: 1 <= k <= TSIM_TOPK_MAX_K
+ * (below).  Workspace functions, out_status, idx_offset and stream as for the dot entries.
+ * Guard (a proof, as for dot).  |q' / nq'| = 1 and |c' / S| <= 1, so the Cauchy-Schwarz argument of tsim_cosine_topk_ex gives
+ * |m - (|q|^2 - dist^2) / (2 nqs)| <= eps_q = guard_eps(rho_q, rho_c, ld), rho_q measured flush-safe over the d + 1 elements of the
+ * query's two rows, rho_c = *ec_rho_max.  The guard works with the query's float64 |q|^2 and nqs; 1e-13 in MFMA units and 1e-14
+ * relative cover every float64 rounding (of |q|^2, nq', the definitions of the stored elements, the canonical dist^2) on the
+ * safe side.
+ *   Lower bound.  A row with m <= cut has (|q|^2 - dist^2) / (2 nqs) <= cut + eps_q, i.e. dist^2 >= |q|^2 - 2 nqs (cut + eps_q).
+ *   The ulp.  Distances are compared after rounding to float32.  The 2^-22 term of guard_eps is in MFMA units: it does NOT cover
+ *   that rounding when |q| >> A (a float32 ulp of dist^2 ~ |q|^2 is (|q| / A) 2^-24 in MFMA units).  So the k-th distance dk
+ *   carries one float32 ulp: up(dk) = dk (1 + 2^-23) + 2^-149 (rounded up) lies above every real number that rounds to a float32
+ *   <= dk.  The first pass stands (status 0) when the lower bound of every row outside the candidates exceeds up(dk): such a row
+ *   rounds to a distance > dk and cannot enter the list, not even through a tie.
+ *   Collection.  A row whose float32 distance is <= dk has dist^2 <= up(dk), hence m >= (|q|^2 - up(dk)) / (2 nqs) - eps_q > tau,
+ *   tau one float below that value: every such row is collected (status 1), and the guard is repeated with the threshold that
+ *   was used.  For k > 28 the block-maxima threshold B - 2 eps_q is widened by the same ulp, (nq' / A) 2^-24 in MFMA units.
+ *   Brute force (status 2) takes over as for cosine, and whenever nqs or |q|^2 is not finite.
+ * Known, not fixed: a corpus clustered far from the origin (radius << 0.05 |c|) puts every row inside the window, and every
+ * query lands in brute force — exact but slow; centring the corpus is the remedy and is left to the caller.
+ * Internally the lists hold -dist^2 (negation is exact), so sorting, merging and the tie rule are those of the other spaces;
+ * the last kernel of the call flips the sign. */
+/* Introspection (host only, no launch): the guard's three conversions as the kernels evaluate them, for a CPU replay of the
+ * proof.  m: an MFMA score (a cut or a threshold), eps: eps_q, nqs = nq' S, qq = |q|^2, dk: a float32 k-th squared distance.
+ * out[0] = up(dk); out[1] = the lower bound of dist^2 of any row with MFMA score <= m; out[2] = the real number the collection
+ * threshold tau is taken one float below (-inf: no finite threshold is safe, everything is collected). */
+int tsim_l2_guard_host(float m, float eps, double nqs, double qq, float dk, double out[3]);
+int tsim_l2_topk_ex(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                    const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                    int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int tsim_l2_topk_large(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                       int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Top-k for k up to TSIM_TOPK_MAX_K: the per-query `torch.topk` of /root/reference/src/pipeline/search_pipeline.py:78 and
  * hnswlib's `knn_query` (search_pipeline.py:138) take any k; retrieve-then-rerank and
  * recall@100 / recall@1000 evaluations ask for 100 to 1 000 candidates per query.

@@ -29,6 +29,14 @@ template <>
 __device__ __forceinline__ float load_as_f32<bf16_t>(const bf16_t *p) { return bf16_to_f32(*p); }
 template <>
 __device__ __forceinline__ float load_as_f32<unit_t>(const unit_t *p) { return (float)*p; }
+// A float32 element of rows that are compared by Euclidean distance (tsim_l2_topk_ex): the exact-score routines below take
+// squared differences of such rows where they take products of plain float rows.  The row type carries the metric, so the
+// kernels of the other spaces keep their template arguments — and their code objects — as they were.
+struct l2_f32 { float x; };
+template <>
+__device__ __forceinline__ float load_as_f32<l2_f32>(const l2_f32 *p) { return p->x; }
+template <typename T>
+constexpr bool is_l2_rows = std::is_same_v<T, l2_f32>;
 
 // rho_max (optional): the largest rounding residual rho_r = || half(u_r) - u_r ||_2 of the rows written, u_r = the exact unit
 // row x_r / max(|x_r|, eps) — the quantity the search's exactness guard is built on (guard_eps below).  Accumulated with an
@@ -121,6 +129,82 @@ __global__ __launch_bounds__(256) void dot_scaled_rows_kernel(const T *__restric
 }
 
 // =====================================================================================================
+// Operands of the Euclidean search (tsim_l2_topk_ex): rows one element longer, so that the MFMA's inner product ranks by
+// distance (include/tsim.h).  A = dot_scale(*maxnorm), S = 2 A.  One wave per row like the kernels above.
+//   l2_rows:       corpus row (c, -|c|^2 / (2A)) / S: |.| <= sqrt(1.25) / 2 < 1.  |c|^2 is the canonical float64 sum of
+//                  l2norm_rows; 1 / S and 1 / (4 A^2) are powers of two, so every element is rounded once, to half.  rho_max as
+//                  in dot_scaled_rows (flush-safe, over the d + 1 elements); a non-finite word gives zero rows and rho = 2.
+//   l2_query_rows: query row (q, A) / nq', nq' = sqrt(|q|^2 + A^2) in float64, each element rounded once to half; a non-finite
+//                  nq' gives a zero row (the search then answers the query by brute force).
+// =====================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void l2_rows_kernel(const T *__restrict__ x, int64_t rows, int d, int64_t ld_in,
+                                                      const float *__restrict__ maxnorm, unit_t *__restrict__ out, int ld_out,
+                                                      float *__restrict__ rho_max) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double A = dot_scale(*maxnorm);
+    const bool finite = A < INFINITY;
+    const double inv = finite ? 0.5 / A : 0.0;   // 1 / S
+    const T *xr = x + row * ld_in;
+    double ss = 0.0;
+    for (int j = lane; j < d; j += 64) {
+        const double v = (double)load_as_f32<T>(xr + j);
+        ss = fma(v, v, ss);
+    }
+    const double extra = finite ? -(wave_sum_f64(ss) * (inv * inv)) : 0.0;   // -|c|^2 / (2 A S)
+    unit_t *o = out + row * (int64_t)ld_out;
+    double r2 = 0.0;
+    for (int j = lane; j < ld_out; j += 64) {
+        unit_t hv = (unit_t)0;
+        if (j <= d && finite) {
+            const double v = j < d ? (double)load_as_f32<T>(xr + j) * inv : extra;
+            hv = f64_to_f16(v);
+            const double e = flush_safe_err((double)(float)hv, v);
+            r2 = fma(e, e, r2);
+        }
+        o[j] = hv;
+    }
+    if (rho_max) {
+        const float rho = finite ? rho_round_up(sqrt(wave_sum_f64(r2))) : 2.f;
+        if (lane == 0) rho_publish(rho_max, rho);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void l2_query_rows_kernel(const T *__restrict__ x, int64_t rows, int d, int64_t ld_in,
+                                                            const float *__restrict__ maxnorm, unit_t *__restrict__ out,
+                                                            int ld_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const double A = dot_scale(*maxnorm);
+    const T *xr = x + row * ld_in;
+    double ss = 0.0;
+    for (int j = lane; j < d; j += 64) {
+        const double v = (double)load_as_f32<T>(xr + j);
+        ss = fma(v, v, ss);
+    }
+    const double nq = sqrt(wave_sum_f64(ss) + A * A);   // >= A > 0
+    const bool finite = nq < INFINITY;
+    const double inv = finite ? 1.0 / nq : 0.0;
+    unit_t *o = out + row * (int64_t)ld_out;
+    for (int j = lane; j < ld_out; j += 64) {
+        unit_t hv = (unit_t)0;
+        if (j <= d && finite) hv = f64_to_f16((j < d ? (double)load_as_f32<T>(xr + j) : A) * inv);
+        o[j] = hv;
+    }
+}
+
+// out_scores of an L2 call hold -dist^2 until the last kernel of the call: negation is exact, so the lists, merges and the
+// (score desc, index asc) order of every kernel in between serve distances unchanged.  -(-inf) = +inf is the padding.
+__global__ __launch_bounds__(256) void l2_negate_scores_kernel(float *__restrict__ s, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) s[i] = -s[i];
+}
+
+// =====================================================================================================
 // Exact scores.  Two definitions, both evaluated in float64 in ONE canonical order and rounded once to float32, so that
 // GPU and oracle agree bit for bit (oracle/search_ref._lane_sum): lane l accumulates the products of elements j = l,
 // l + 64, ... in that order (fma of an exact product == multiply + add), then an xor butterfly 32, 16, .., 1.
@@ -129,14 +213,19 @@ __global__ __launch_bounds__(256) void dot_scaled_rows_kernel(const T *__restric
 //                (oracle/search_ref.exact_cosine);
 //   COS = false (unit rows as stored): the inner product of the stored unit rows (oracle/search_ref.canonical_scores).
 // MFMA scores only SELECT candidates; every score that is returned or compared for the final order is one of these.
+// A third, for rows of l2_f32 (tsim_l2_topk_ex): -(squared Euclidean distance).  Lane l adds (q_j - c_j)^2 for j = l, l + 64, ...
+// with the difference, the square and the sum each rounded to float64 on its own (the square of a float64 difference is not
+// exact, so a fused multiply-add would not be restatable in numpy), the same butterfly, one rounding to float32, then the sign.
 // =====================================================================================================
 constexpr int XS_MAXI = 12;   // 64 * 12 = 768 elements per row at most
 constexpr double XS_EPS = (double)1e-8f;
+// what exact_load_query leaves in ExactQuery::norm (`false` / `true` of the cosine and inner-product callers: NONE / COS)
+enum { NORM_NONE = 0, NORM_COS = 1, NORM_SQ = 2 };
 
 template <typename T>
 struct ExactQuery {
     double v[XS_MAXI];   // this lane's elements j = lane + 64 i of the query row (0 beyond d)
-    double norm;         // COS: max(|q|, eps)
+    double norm;         // NORM_COS: max(|q|, eps);  NORM_SQ (L2): |q|^2
 };
 
 // This lane's elements j = lane + 64 i, i < NI, of a row as float64 (0 beyond d).  BRANCH-FREE: the address of an element past
@@ -155,7 +244,7 @@ __device__ __forceinline__ void row_elems_f64(double (&c)[NI], const T *row, int
     for (int i = 0; i < NI; ++i) c[i] = lane + 64 * i < d ? (double)x[i] : 0.0;
 }
 
-template <typename T, bool COS, int NI>
+template <typename T, int NORM, int NI>
 __device__ __forceinline__ void exact_load_query_ni(ExactQuery<T> &q, const T *row, int d, int lane) {
     double c[NI];
     row_elems_f64<T, NI>(c, row, d, lane);
@@ -166,14 +255,15 @@ __device__ __forceinline__ void exact_load_query_ni(ExactQuery<T> &q, const T *r
         ss = fma(q.v[i], q.v[i], ss);   // (+0 beyond d: the sum is that of the elements below d, in their order)
     }
     q.norm = 1.0;
-    if constexpr (COS) q.norm = fmax(sqrt(wave_sum_f64(ss)), XS_EPS);
+    if constexpr (NORM == NORM_COS) q.norm = fmax(sqrt(wave_sum_f64(ss)), XS_EPS);
+    if constexpr (NORM == NORM_SQ) q.norm = wave_sum_f64(ss);
 }
-template <typename T, bool COS>
+template <typename T, int NORM>
 __device__ __forceinline__ void exact_load_query(ExactQuery<T> &q, const T *row, int d, int lane) {
-    if (d <= 64 * (XS_MAXI / 2)) exact_load_query_ni<T, COS, XS_MAXI / 2>(q, row, d, lane);   // wave-uniform
-    else exact_load_query_ni<T, COS, XS_MAXI>(q, row, d, lane);
+    if (d <= 64 * (XS_MAXI / 2)) exact_load_query_ni<T, NORM, XS_MAXI / 2>(q, row, d, lane);   // wave-uniform
+    else exact_load_query_ni<T, NORM, XS_MAXI>(q, row, d, lane);
 }
-// the norm exact_load_query<T, true> sets, from the elements already held (the same fma chain: the +0 terms change nothing)
+// the norm exact_load_query<T, NORM_COS> sets, from the elements already held (the same fma chain: the +0 terms change nothing)
 template <typename T>
 __device__ __forceinline__ double exact_query_norm(const ExactQuery<T> &q) {
     double ss = 0.0;
@@ -181,8 +271,25 @@ __device__ __forceinline__ double exact_query_norm(const ExactQuery<T> &q) {
     for (int i = 0; i < XS_MAXI; ++i) ss = fma(q.v[i], q.v[i], ss);
     return fmax(sqrt(wave_sum_f64(ss)), XS_EPS);
 }
+// |q|^2 as exact_load_query<T, NORM_SQ> sets it, from the elements already held
+template <typename T>
+__device__ __forceinline__ double exact_query_sumsq(const ExactQuery<T> &q) {
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < XS_MAXI; ++i) ss = fma(q.v[i], q.v[i], ss);
+    return wave_sum_f64(ss);
+}
 
-// per-lane partial sums of the query against one row: dot (and |row|^2 for COS)
+// acc + diff * diff with the product and the sum each rounded to float64 on its own.  Contraction is switched off for this
+// block: under hipcc's default (fp-contract=fast) a product and a sum fuse into v_fma / v_fmac_f64, and the __dmul_rn /
+// __dadd_rn of this ROCm's headers are a plain `*` and `+` that fuse just the same.
+__device__ __forceinline__ double add_square_unfused(double acc, double diff) {
+#pragma clang fp contract(off)
+    const double sq = diff * diff;
+    return acc + sq;
+}
+
+// per-lane partial sums of the query against one row: dot (and |row|^2 for COS); L2: the squared differences in `dot`
 template <typename T, bool COS, int NI>
 __device__ __forceinline__ void exact_partials(const ExactQuery<T> &q, const T *row, int d, int lane, double &dot, double &cc) {
     double c[NI];
@@ -191,7 +298,12 @@ __device__ __forceinline__ void exact_partials(const ExactQuery<T> &q, const T *
     cc = 0.0;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        dot = fma(q.v[i], c[i], dot);
+        if constexpr (is_l2_rows<T>) {
+            const double diff = q.v[i] - c[i];   // (0 - 0 beyond d: the sum is that of the elements below d)
+            dot = add_square_unfused(dot, diff);
+        } else {
+            dot = fma(q.v[i], c[i], dot);
+        }
         if constexpr (COS) cc = fma(c[i], c[i], cc);
     }
 }
@@ -207,6 +319,7 @@ __device__ __forceinline__ float exact_score(const ExactQuery<T> &q, const T *ro
         const double nc = fmax(sqrt(wave_sum_f64(cc)), XS_EPS);
         return (float)(dot / (q.norm * nc));
     }
+    if constexpr (is_l2_rows<T>) return -(float)dot;
     return (float)dot;
 }
 
@@ -274,6 +387,8 @@ __device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const
         const double other = __shfl_xor(acc[0], 1 << SH, 64);          // even v (dot) lanes receive cc
         const double nc = fmax(sqrt(other), XS_EPS);
         score = (float)(acc[0] / (q.norm * nc));
+    } else if constexpr (is_l2_rows<T>) {
+        score = -(float)acc[0];
     } else {
         score = (float)acc[0];
     }
@@ -303,7 +418,11 @@ enum { ST_PASS1 = 0, ST_WIDENED = 1, ST_BRUTE = 2 };
 //            query operand the unit row of q, so the MFMA score approximates q.c / (nq S), nq = max(|q|, 1e-8) (the scale
 //            the unit row was made with): monotone in q.c for a fixed query, and bounded by guard_eps exactly as for COS.
 //            Exact scores live in the other domain; dot_bound_up / guard_tau_dot convert with nqs = nq S.
-enum { SM_UNIT = 0, SM_COS = 1, SM_DOT = 2 };
+//   SM_L2:   squared Euclidean distance of the float32 rows (tsim_l2_topk_ex).  Operands: l2_rows / l2_query_rows, one element
+//            longer than the rows, so the MFMA score approximates (|q|^2 - dist^2) / (2 nqs), nqs = nq' S: falling in dist^2 for
+//            a fixed query and bounded by guard_eps like the others (|q' / nq'| = 1, |c' / S| <= 1).  Exact scores are -dist^2;
+//            l2_bound_low / guard_tau_l2 convert.
+enum { SM_UNIT = 0, SM_COS = 1, SM_DOT = 2, SM_L2 = 3 };
 
 struct GuardArgs {
     // COS (float32 rows given): eps = guard_eps(rho_q, rho_c, ld) — a BOUND on |MFMA score - exact score| for the query against
@@ -322,7 +441,7 @@ struct GuardArgs {
     float *flag_eps;   // [Q] per slot: the query's eps (COS)
     int *unres_q;      // [Q] queries left to the brute-force pass, compact
     int *status;       // [Q] or null
-    const float *c_maxnorm;   // SM_DOT: the corpus rows' max-norm word (device), S = dot_scale(*c_maxnorm)
+    const float *c_maxnorm;   // SM_DOT: the corpus rows' max-norm word (device), S = dot_scale(*c_maxnorm); SM_L2: A = that, S = 2 A
 };
 
 // rho of a query row: || stored half row - exact unit row ||_2 from the float32 row already held in `q` (all 64 lanes take part).
@@ -343,6 +462,25 @@ __device__ __forceinline__ float query_rho(const ExactQuery<float> &q, const uni
         }
     };
     if (d <= 64 * (XS_MAXI / 2)) body(std::integral_constant<int, XS_MAXI / 2>{});   // wave-uniform
+    else body(std::integral_constant<int, XS_MAXI>{});
+    return rho_round_up(sqrt(wave_sum_f64(r2)));
+}
+// SM_L2: rho of an augmented query row (q, A) / nq against its stored half row, over the d + 1 elements, flush-safe.
+template <typename T>
+__device__ __forceinline__ float query_rho_l2(const ExactQuery<T> &q, const unit_t *urow, int d, double A, double nq, int lane) {
+    double r2 = 0.0;
+    const double inv = 1.0 / nq;
+    auto body = [&](auto nic) __attribute__((always_inline)) {
+        constexpr int NI = decltype(nic)::value;
+        double u[NI];
+        row_elems_f64<unit_t, NI>(u, urow, d + 1, lane);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const double e = flush_safe_err(u[i], (lane + 64 * i == d ? A : q.v[i]) * inv);   // (0 against 0 beyond d)
+            r2 = fma(e, e, r2);
+        }
+    };
+    if (d + 1 <= 64 * (XS_MAXI / 2)) body(std::integral_constant<int, XS_MAXI / 2>{});   // wave-uniform
     else body(std::integral_constant<int, XS_MAXI>{});
     return rho_round_up(sqrt(wave_sum_f64(r2)));
 }
@@ -369,6 +507,40 @@ __device__ __forceinline__ float guard_tau_dot(float sk, float eps, double nqs) 
     const double lo = t - (double)eps - (fabs(t) + (double)eps) * 1e-15;
     if (!(lo > -3.0e38)) return -3.4028234e38f;
     return float_below((float)lo);   // (float)lo is within one float of lo: one step down is below it
+}
+
+// SM_L2 conversions (proof: include/tsim.h tsim_l2_topk_ex).  qq = |q|^2 and nqs = nq' S in float64; dk = a float32 squared
+// distance (the k-th of a list).  The MFMA score m of a row obeys |m - (|q|^2 - dist^2) / (2 nqs)| <= eps; 1e-13 in MFMA units and
+// 1e-14 relative cover every float64 rounding on the way (qq, nq', the stored operands' definitions, the canonical dist^2).
+//   l2_dist_up:   above every float64 distance that can round to a float32 <= dk: dk plus one float32 ulp of it (the 2^-22 of
+//                 guard_eps is in MFMA units and does not cover that rounding when |q| >> A);
+//   l2_bound_low: a lower bound of dist^2 of any row whose MFMA score is <= m;
+//   guard_tau_l2: every row whose float32 distance could be <= dk has an MFMA score > tau.
+// (host and device: tsim_l2_guard_host evaluates the same three functions for the CPU replay of the guard)
+__host__ __device__ inline double l2_dist_up(float dk) { return (double)dk * (1.0 + 1.1921e-7) + 1e-44; }
+__host__ __device__ inline double l2_bound_low(float m, float eps, double nqs, double qq) {
+    const double b = ((double)m + (double)eps + 1e-13) * 2.0 * nqs;
+    return qq - b - (qq + fabs(b)) * 1e-14;
+}
+// the real number guard_tau_l2 steps below; -inf when no finite threshold is safe
+__host__ __device__ inline double l2_tau_lo(float dk, float eps, double nqs, double qq) {
+    if (!(eps < 3.0e38f) || !(dk < 3.0e38f) || !(nqs > 0.0 && nqs < INFINITY) || !(qq < INFINITY)) return -INFINITY;
+    const double up = l2_dist_up(dk);
+    const double t = (qq - up - (qq + up) * 1e-14) / (2.0 * nqs);
+    const double lo = t - (double)eps - 1e-13 - (fabs(t) + (double)eps) * 1e-15;
+    return lo > -3.0e38 ? lo : -INFINITY;
+}
+__device__ __forceinline__ float guard_tau_l2(float dk, float eps, double nqs, double qq) {
+    const double lo = l2_tau_lo(dk, eps, nqs, qq);
+    if (!(lo > -3.0e38)) return -3.4028234e38f;
+    return float_below((float)lo);   // (float)lo is within one float of lo: one step down is below it
+}
+__device__ __forceinline__ double l2_nqs(double qq, double A) { return sqrt(qq + A * A) * 2.0 * A; }   // nq' S
+// |MFMA score - its exact counterpart| net of the float32 rounding of the distance (es = -dist^2 as stored): what the
+// consistency checks compare with eps
+__device__ __forceinline__ float l2_err(float ms, float es, double nqs, double qq) {
+    const double inv = 0.5 / nqs;
+    return (float)(fabs((double)ms - (qq + (double)es) * inv) + (double)es * 6.0e-8 * inv);
 }
 
 // The KL best entries of a query's partial lists by (MFMA score desc, index asc): lane t < KL returns the t-th
@@ -547,7 +719,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
                                                                 float *__restrict__ out_s,
                                                                 int64_t *__restrict__ out_i,
                                                                 int64_t idx_offset, GuardArgs g) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
+    static_assert(L2 == is_l2_rows<T>, "SM_L2 scores rows of l2_f32");
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
@@ -571,7 +744,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
 
     // 2. exact re-score: the wave works on one candidate at a time (coalesced row reads)
     ExactQuery<T> eqr;
-    exact_load_query<T, COS>(eqr, xq + q * ldq, d, lane);   // (DOT: the norm is taken in the guard, not held across the loop)
+    exact_load_query<T, COS>(eqr, xq + q * ldq, d, lane);   // (DOT, L2: the norm is taken in the guard, not held across the loop)
     float cs = -INFINITY;
 #pragma unroll 1
     for (int t0 = 0; t0 < nvalid; t0 += NB) {   // NB candidates per step: their row reads overlap, their wave sums share shuffles
@@ -622,6 +795,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
             const double inv_nqs = 1.0 / nqs;   // (a consistency check, not the proof: one reciprocal, no per-lane division)
             const float derr = wave_max(lane < nvalid ? (float)fabs((double)my_s - (double)cs * inv_nqs) : 0.f);
             if (!(derr <= eps)) eps = INFINITY;   // (as for COS: the rows are not the images of the float32 rows)
+        } else if constexpr (L2) {
+            const double A = dot_scale(*g.c_maxnorm);
+            eqr.norm = exact_query_sumsq(eqr);   // |q|^2
+            const double nq = sqrt(eqr.norm + A * A);   // nq' of l2_query_rows_kernel, the same bits
+            nqs = l2_nqs(eqr.norm, A);
+            eps = guard_eps(query_rho_l2(eqr, uq + q * g.ld, d, A, nq, lane), *g.rho_c_max, g.ld);
+            const float derr = wave_max(lane < nvalid ? l2_err(my_s, cs, nqs, eqr.norm) : 0.f);
+            if (!(derr <= eps) || !(nqs < INFINITY) || !(eqr.norm < INFINITY)) eps = INFINITY;   // (non-finite: brute force)
         } else {
             eps = fmaxf(g.c1 * err, g.floor);
         }
@@ -632,6 +813,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
         if constexpr (DOT) {
             safe = kth != 0 && dot_bound_up(cut, eps, nqs) < (double)sk;
             tau = guard_tau_dot(sk, eps, nqs);
+        } else if constexpr (L2) {   // (sk = -(k-th distance); no k-th entry: +inf, everything is collected)
+            safe = kth != 0 && l2_bound_low(cut, eps, nqs, eqr.norm) > l2_dist_up(-sk);
+            tau = guard_tau_l2(-sk, eps, nqs, eqr.norm);
         } else {
             safe = kth != 0 && (double)cut + (double)eps < (double)sk;
             tau = guard_tau(sk, eps);   // rows at or below tau cannot reach sk
@@ -716,7 +900,8 @@ __global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned 
                                                                  const T *__restrict__ xc, int64_t ldc, int d, int k,
                                                                  float *__restrict__ out_s, int64_t *__restrict__ out_i,
                                                                  int64_t idx_offset, GuardArgs g) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
+    static_assert(L2 == is_l2_rows<T>, "SM_L2 scores rows of l2_f32");
     __shared__ float sc[COLL_CAP];
     __shared__ int ix[COLL_CAP];
     __shared__ float red_s[4];
@@ -733,15 +918,17 @@ __global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned 
         bool resolved = cnt <= COLL_CAP;
         if (resolved) {   // workgroup-uniform
             ExactQuery<T> eqr;
-            exact_load_query<T, COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
+            exact_load_query<T, L2 ? NORM_SQ : COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
             double nqs = 1.0;
             if constexpr (DOT) nqs = eqr.norm * dot_scale(*g.c_maxnorm);
+            if constexpr (L2) nqs = l2_nqs(eqr.norm, dot_scale(*g.c_maxnorm));
             float err = 0.f;
             for (int e = wave; e < n; e += 4) {
                 const unsigned long long ent = coll_buf[(int64_t)slot * COLL_CAP + e];
                 const int row = (int)(ent >> 32);
                 const float s = exact_score<T, COS>(eqr, xc + (int64_t)row * ldc, d, lane);
                 if constexpr (DOT) err = fmaxf(err, (float)fabs((double)__uint_as_float((uint32_t)ent) - (double)s / nqs));
+                else if constexpr (L2) err = fmaxf(err, l2_err(__uint_as_float((uint32_t)ent), s, nqs, eqr.norm));
                 else err = fmaxf(err, fabsf(__uint_as_float((uint32_t)ent) - s));
                 if (lane == 0) {
                     sc[e] = s;
@@ -762,7 +949,7 @@ __global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned 
             // difference seen on this larger sample with half the safety factor of the first pass (not below 1).
             const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
             float eps;
-            if constexpr (COS || DOT) {
+            if constexpr (COS || DOT || L2) {
                 eps = g.flag_eps[slot];
                 if (!(errmax <= eps)) eps = INFINITY;
             } else {
@@ -770,6 +957,7 @@ __global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned 
             }
             const float thr = ordered_to_float(g.flag_thr[slot]);
             if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)s_top[k - 1];
+            else if constexpr (L2) resolved = n >= k && l2_bound_low(thr, eps, nqs, eqr.norm) > l2_dist_up(-s_top[k - 1]);
             else resolved = n >= k && (double)thr + (double)eps < (double)s_top[k - 1];
         }
         if (threadIdx.x == 0) {
@@ -861,16 +1049,31 @@ __global__ __launch_bounds__(256) void bf_merge_k64_kernel(int64_t Q, int nch, i
 // so the k-th best EXACT score is >= B - eps and every row of the exact top-k has an MFMA score >= B - 2 eps: that is the
 // collection threshold.  One wave per query (COS, DOT: the query's rho comes from its two rows).  DOT: the argument holds with
 // the exact scores taken in the MFMA domain (q.c / (nq S), a monotone map), so the threshold needs no conversion here.
+// L2: the same in the domain (|q|^2 - dist^2) / (2 nqs), except that distances are ranked after their rounding to float32: a row
+// of the top-k may lie one float32 ulp of a distance behind the k rows above B - eps, in MFMA units at most dist^2 2^-23 /
+// (2 nqs) <= (nq' / A) 2^-24 (dist^2 <= 2 nq'^2): `margin` widens the band by that.  The threshold is a choice, not the proof:
+// widen_finalize's guard decides with the threshold that was used.
 template <int SM>
 __global__ __launch_bounds__(256) void flag_all_kernel(int64_t Q, const int *__restrict__ gthr, bool all_brute,
                                                        const float *__restrict__ xq, int64_t ldq, const unit_t *__restrict__ uq,
                                                        int d, GuardArgs g) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q == 0 && lane == 0) g.ctl[all_brute ? CTL_NUNRES : CTL_NFLAG] = (int)Q;
     if (q >= Q) return;
     float eps = g.floor;
+    float margin = 0.f;
+    (void)margin;
+    if constexpr (L2) {
+        if (!all_brute) {
+            ExactQuery<float> eqr;
+            exact_load_query<float, NORM_SQ>(eqr, xq + q * ldq, d, lane);
+            const double A = dot_scale(*g.c_maxnorm), nq = sqrt(eqr.norm + A * A);
+            eps = guard_eps(query_rho_l2(eqr, uq + q * g.ld, d, A, nq, lane), *g.rho_c_max, g.ld);
+            margin = (float)(nq / A * 6.0e-8);
+        }
+    }
     if constexpr (COS || DOT) {
         if (!all_brute) {
             ExactQuery<float> eqr;
@@ -884,7 +1087,8 @@ __global__ __launch_bounds__(256) void flag_all_kernel(int64_t Q, const int *__r
     } else {
         g.flag_q[q] = (int)q;
         const int key = gthr[q];
-        g.flag_thr[q] = key <= K1_GTHR_INIT ? key : float_to_ordered(guard_tau(ordered_to_float(key), 2.f * eps * 1.000001f));
+        if constexpr (L2) g.flag_thr[q] = key <= K1_GTHR_INIT ? key : float_to_ordered(guard_tau(ordered_to_float(key), 2.f * eps * 1.000001f + margin));
+        else g.flag_thr[q] = key <= K1_GTHR_INIT ? key : float_to_ordered(guard_tau(ordered_to_float(key), 2.f * eps * 1.000001f));
         g.flag_eps[q] = eps;
     }
     if (g.status) g.status[q] = all_brute ? ST_BRUTE : ST_WIDENED;
@@ -1185,7 +1389,8 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
                                                              const T *__restrict__ xc, int64_t ldc, int d, int k,
                                                              float *__restrict__ out_s, int64_t *__restrict__ out_i,
                                                              int64_t idx_offset, GuardArgs g) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
+    static_assert(L2 == is_l2_rows<T>, "SM_L2 scores rows of l2_f32");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *sc = reinterpret_cast<float *>(smem);
     int *ix = reinterpret_cast<int *>(sc + cap);
@@ -1201,9 +1406,10 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             int np = 64;
             while (np < n || np < k) np <<= 1;   // <= cap (a power of two >= 4k)
             ExactQuery<T> eqr;
-            exact_load_query<T, COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
+            exact_load_query<T, L2 ? NORM_SQ : COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
             double nqs = 1.0;
             if constexpr (DOT) nqs = eqr.norm * dot_scale(*g.c_maxnorm);
+            if constexpr (L2) nqs = l2_nqs(eqr.norm, dot_scale(*g.c_maxnorm));
             float err = 0.f;
             for (int g0 = wave * 64; g0 < np; g0 += 256) {   // wave-uniform
                 const int e = g0 + lane;
@@ -1217,6 +1423,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
                     if (e < n) {
                         const float ms = __uint_as_float((uint32_t)ent);
                         if constexpr (DOT) err = fmaxf(err, (float)fabs((double)ms - (double)es / nqs));
+                        else if constexpr (L2) err = fmaxf(err, l2_err(ms, es, nqs, eqr.norm));
                         else err = fmaxf(err, fabsf(ms - es));
                         if (es == es) {
                             s = es;
@@ -1242,7 +1449,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             // difference seen on this larger sample with half the safety factor of the first pass (not below 1).
             const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
             float eps;
-            if constexpr (COS || DOT) {
+            if constexpr (COS || DOT || L2) {
                 eps = g.flag_eps[slot];
                 if (!(errmax <= eps)) eps = INFINITY;
             } else {
@@ -1251,6 +1458,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             const float thr = ordered_to_float(g.flag_thr[slot]);
             const float sk = ix[k - 1] == 0x7fffffff ? -INFINITY : sc[k - 1];
             if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)sk;
+            else if constexpr (L2) resolved = n >= k && l2_bound_low(thr, eps, nqs, eqr.norm) > l2_dist_up(-sk);
             else resolved = n >= k && (double)thr + (double)eps < (double)sk;
         }
         if (threadIdx.x == 0) {
@@ -1566,6 +1774,28 @@ extern "C" int tsim_dot_scaled_rows(const void *x, int x_dtype, int64_t rows, in
 
 extern "C" double tsim_dot_scale(float maxnorm) { return dot_scale(maxnorm); }
 
+extern "C" int tsim_l2_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm, void *out_f16,
+                            int ld_out, float *rho_max, void *stream) {
+    TSIM_REQUIRE(x && maxnorm && out_f16, "l2_rows: null pointer");
+    TSIM_REQUIRE(ld_out >= d + 1, "l2_rows: ld_out=%d < d+1=%d", ld_out, d + 1);
+    return dot_prep_launch("l2_rows", x, x_dtype, rows, d, ld_in, [&](dim3 grid, auto xt) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+        hipLaunchKernelGGL(l2_rows_kernel<T>, grid, dim3(256), 0, as_stream(stream), xt, rows, d, ld_in, maxnorm,
+                           (unit_t *)out_f16, ld_out, rho_max);
+    });
+}
+
+extern "C" int tsim_l2_query_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *maxnorm,
+                                  void *out_f16, int ld_out, void *stream) {
+    TSIM_REQUIRE(x && maxnorm && out_f16, "l2_query_rows: null pointer");
+    TSIM_REQUIRE(ld_out >= d + 1, "l2_query_rows: ld_out=%d < d+1=%d", ld_out, d + 1);
+    return dot_prep_launch("l2_query_rows", x, x_dtype, rows, d, ld_in, [&](dim3 grid, auto xt) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+        hipLaunchKernelGGL(l2_query_rows_kernel<T>, grid, dim3(256), 0, as_stream(stream), xt, rows, d, ld_in, maxnorm,
+                           (unit_t *)out_f16, ld_out);
+    });
+}
+
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
 
 extern "C" void tsim_time_next_topk(void *start_event, void *stop_event) {
@@ -1713,6 +1943,11 @@ static void with_score_mode(int sm, const SearchOperands &o, F f) {
     const ExactRows<float> rf{o.q_f32, o.ldq_f32, o.c_f32, o.ldc_f32, o.d};   // (null rows in SM_UNIT, where it is not used)
     if (sm == SM_COS) f(rf, std::integral_constant<int, SM_COS>{});
     else if (sm == SM_DOT) f(rf, std::integral_constant<int, SM_DOT>{});
+    else if (sm == SM_L2)   // (the float32 rows read through l2_f32, a struct of one float: the same layout, and the kernels only
+                            // ever load from them; the type is what keeps the other spaces' instantiations as they were)
+        f(ExactRows<l2_f32>{reinterpret_cast<const l2_f32 *>(o.q_f32), o.ldq_f32, reinterpret_cast<const l2_f32 *>(o.c_f32), o.ldc_f32,
+                            o.d},
+          std::integral_constant<int, SM_L2>{});
     else f(ExactRows<unit_t>{o.uq, o.ld, o.uc, o.ld, o.ld}, std::integral_constant<int, SM_UNIT>{});
 }
 
@@ -1750,7 +1985,7 @@ static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N
     float *bf_s = reinterpret_cast<float *>(ws + w.bf_s);
     int *bf_i = reinterpret_cast<int *>(ws + w.bf_i);
     const unsigned us = (unsigned)(Q < 64 ? Q : 64);
-    // (brute force has no guard: DOT scores exactly like UNIT, on the float32 rows)
+    // (brute force has no guard: DOT scores exactly like UNIT, on the float32 rows; L2 by its row type)
     with_score_mode(sm, o, [&](auto x, auto smc) {
         using T = typename decltype(x)::row_t;
         constexpr bool COS = decltype(smc)::value == SM_COS;
@@ -1766,6 +2001,11 @@ static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N
     if (k64) hipLaunchKernelGGL(bf_merge_k64_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, bf_s, bf_i, out_s, out_i, idx_offset, g);
     else hipLaunchKernelGGL(bf_merge_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s, bf_i, out_s, out_i, idx_offset, g);
     TSIM_HIP_CHECK(hipGetLastError());
+    if (sm == SM_L2) {   // every kernel above wrote -dist^2 (and -inf padding)
+        const int64_t n = Q * k;
+        hipLaunchKernelGGL(l2_negate_scores_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out_s, n);
+        TSIM_HIP_CHECK(hipGetLastError());
+    }
     return TSIM_OK;
 }
 
@@ -1865,13 +2105,14 @@ extern "C" size_t tsim_topk_large_workspace_bytes(int64_t Q, int64_t N, int k) {
 }
 
 // One search call: validate, plan, [k <= 28: pre-pass, main pass, finalize | else: threshold_all], tail.  sm: SM_UNIT (no
-// float32 matrices), SM_COS or SM_DOT (float32 matrices given).  `what` names the entry point in error messages, kmax is its
+// float32 matrices), SM_COS, SM_DOT or SM_L2 (float32 matrices given).  `what` names the entry point in error messages, kmax is its
 // largest k.
 static int topk_search(int sm, const char *what, int kmax, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q,
                        const void *ec, const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
                        int64_t N, int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
                        int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
-    if (sm == SM_DOT) {
+    const int dw = d + (sm == SM_L2);   // width of the half operands (L2: one element longer than the rows)
+    if (sm == SM_DOT || sm == SM_L2) {
         TSIM_REQUIRE(eq_f32 && ec_f32, "%s: the float32 matrices are required", what);
         TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "%s: the corpus rows' max-norm word and measured rho_max are required", what);
     }
@@ -1879,8 +2120,8 @@ static int topk_search(int sm, const char *what, int kmax, const void *eq, const
     TSIM_REQUIRE(Q > 0 && N > 0, "%s: empty input Q=%lld N=%lld", what, (long long)Q, (long long)N);
     TSIM_REQUIRE(k >= 1 && k <= kmax, "%s: k=%d outside 1..%d", what, k, kmax);
     TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: shard too large for 32-bit row ids", what);
-    TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "%s: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)",
-                 what, tsim_pad_dim(d), ld);
+    TSIM_REQUIRE((sm != SM_L2 || d > 0) && ld == tsim_pad_dim(dw) && ld > 0, "%s: rows must be padded to tsim_pad_dim(%d)=%d (got ld=%d)",
+                 what, dw, tsim_pad_dim(dw), ld);
     TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "%s: embedding matrices must be 16-byte aligned", what);
     TSIM_REQUIRE((eq_f32 == nullptr) == (ec_f32 == nullptr), "%s: pass both float32 matrices or neither", what);
     if (eq_f32) TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
@@ -1988,6 +2229,30 @@ extern "C" int tsim_dot_topk_large(const void *eq, const float *eq_f32, int64_t 
                                    int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
     return topk_search(SM_DOT, "dot_topk", TOPK_LARGE_MAX_K, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N,
                        d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_l2_guard_host(float m, float eps, double nqs, double qq, float dk, double out[3]) {
+    TSIM_REQUIRE(out, "l2_guard_host: null pointer");
+    out[0] = l2_dist_up(dk);
+    out[1] = l2_bound_low(m, eps, nqs, qq);
+    out[2] = l2_tau_lo(dk, eps, nqs, qq);
+    return TSIM_OK;
+}
+
+extern "C" int tsim_l2_topk_ex(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                               const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                               int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status, int64_t idx_offset,
+                               void *workspace, size_t workspace_bytes, void *stream) {
+    return topk_search(SM_L2, "l2_topk", TOPK_MAX_K, eq_aug, eq_f32, ldq_f32, Q, ec_aug, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max,
+                       N, d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_l2_topk_large(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                                  const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
+                                  int64_t N, int d, int ld, int k, float *out_scores, int64_t *out_idx, int32_t *out_status,
+                                  int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
+    return topk_search(SM_L2, "l2_topk", TOPK_LARGE_MAX_K, eq_aug, eq_f32, ldq_f32, Q, ec_aug, ec_f32, ldc_f32, ec_maxnorm,
+                       ec_rho_max, N, d, ld, k, out_scores, out_idx, out_status, idx_offset, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tsim_cosine_topk(const void *eq, int64_t Q, const void *ec, int64_t N, int d, int ld, int k,

@@ -16,6 +16,12 @@ index holds bf16 unit rows only, which then ARE the float32 rows).  k <= 1024, d
 (:func:`ops.dot_scaled_rows`), and an ``add_items`` batch that raises S re-derives all of them.  Rows with a non-finite
 element are refused there.  The file records the space; a file without it is a cosine index, and loading a file of the
 other space raises ``ValueError``.
+
+``space='euclidean'`` ranks by Euclidean distance (hnswlib's and faiss' default space; ``knn_query`` returns SQUARED distances,
+ascending, hnswlib's l2 convention; ``search`` pads with -1 / +inf): the half rows are one element wider than the float32 rows
+(:func:`ops.l2_rows`), so d <= 767, and they follow the 'ip' rules — one power of two from the largest row norm, re-derived
+when a batch raises it, non-finite rows refused.  ``range_search`` is not implemented in this space.  The name ``'l2'`` stays
+refused, as it was before this space existed (callers test for that).
 """
 from __future__ import annotations
 
@@ -30,13 +36,14 @@ from . import ops
 
 
 class GpuFlatIndex:
-    SPACES = ("cosine", "ip")
+    SPACES = ("cosine", "ip", "euclidean")
 
     def __init__(self, space: str = "cosine", dim: int = 0, device: Optional[torch.device] = None):
         if space not in self.SPACES:
             raise ValueError(f"GpuFlatIndex implements the spaces {self.SPACES}, not {space!r}")
         self.space = space
         self.dim = int(dim)
+        self._check_dim()
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self._rows: Optional[torch.Tensor] = None      # [capacity, ld] float16 unit rows
         self._f32: Optional[torch.Tensor] = None       # [capacity, d] float32 rows as given
@@ -70,6 +77,7 @@ class GpuFlatIndex:
             x = x.unsqueeze(0)
         if self.dim == 0:
             self.dim = int(x.shape[1])
+            self._check_dim()
         if x.shape[1] != self.dim:
             raise ValueError(f"expected width {self.dim}, got {x.shape[1]}")
         n = x.shape[0]
@@ -81,7 +89,7 @@ class GpuFlatIndex:
         xf = x.to(self.device, dtype=torch.float32).contiguous()
         if self._rho is None:
             self._rho = ops.new_rho(self.device)
-        if self.space == "ip":
+        if self.space in ("ip", "euclidean"):
             unit = self._ip_rows(xf)
         else:
             unit = ops.l2norm_rows(xf, rho=self._rho)   # the word only grows: deleted rows leave the bound conservative
@@ -103,25 +111,32 @@ class GpuFlatIndex:
         self._n_dead += k
 
     def knn_query(self, data, k: int = 1) -> Tuple[np.ndarray, np.ndarray]:
-        """(labels [Q,k] int64, distances [Q,k] float32 = 1 - cosine, or 1 - q.c for 'ip'), best first — hnswlib's return
-        convention."""
+        """(labels [Q,k] int64, distances [Q,k] float32 = 1 - cosine, 1 - q.c for 'ip', or the squared distance for 'euclidean'),
+        best first — hnswlib's return convention."""
         labels, scores = self.search(data, k)
+        if self.space == "euclidean":
+            return labels.cpu().numpy(), scores.cpu().numpy()
         return labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
 
     # ------------------------------------------------------------------ device-level API
     def search(self, data, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(labels [Q,k] int64, scores [Q,k] float32) on the device; -1 / -inf pad when fewer than k live rows."""
+        """(labels [Q,k] int64, scores [Q,k] float32) on the device; -1 / -inf pad when fewer than k live rows.  'euclidean': the
+        scores are squared distances, ascending, padded with +inf."""
         self._compact()
         q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
         if q.dim() == 1:
             q = q.unsqueeze(0)
         qf = q.to(self.device, dtype=torch.float32).contiguous()
-        qn = ops.l2norm_rows(qf)
+        euclid = self.space == "euclidean"
+        qn = None if euclid else ops.l2norm_rows(qf)     # (euclidean: the query rows need the corpus' word, below)
         if self._n == 0:
             Q = q.shape[0]
             return (torch.full((Q, k), -1, dtype=torch.int64, device=self.device),
-                    torch.full((Q, k), float("-inf"), device=self.device))
-        if self.space == "ip":
+                    torch.full((Q, k), float("inf" if euclid else "-inf"), device=self.device))
+        if euclid:
+            s, i = ops.l2_topk(ops.l2_query_rows(qf, self._maxnorm), self._rows[:self._n], self.dim, k, eq_f32=qf,
+                               ec_f32=self._f32[:self._n], rho_c=self._rho, scale_c=self._maxnorm)
+        elif self.space == "ip":
             s, i = ops.dot_topk(qn, self._rows[:self._n], self.dim, k, eq_f32=qf, ec_f32=self._f32[:self._n], rho_c=self._rho,
                                 scale_c=self._maxnorm)
         else:
@@ -135,6 +150,8 @@ class GpuFlatIndex:
         float32 [T], labels int64 [T])`` on the device, faiss' ``range_search`` layout — the hits of query q are
         ``[lims[q], lims[q+1])``, ordered by (score desc, row asc).  Exact and complete (:func:`ops.cosine_range`).
         ``threshold``: a float, or an array / tensor [Q] with one threshold per query (a wrong length is a ValueError)."""
+        if self.space == "euclidean":
+            raise NotImplementedError("range_search is not implemented in the 'euclidean' space")
         self._compact()
         q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
         if q.dim() == 1:
@@ -192,19 +209,25 @@ class GpuFlatIndex:
         if n:
             xf = torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
             self._f32[:n] = xf
-            self._rows[:n] = self._ip_rows(xf) if self.space == "ip" else ops.l2norm_rows(xf, rho=self._rho)
+            self._rows[:n] = self._ip_rows(xf) if self.space in ("ip", "euclidean") else ops.l2norm_rows(xf, rho=self._rho)
         if n:
             self._labels[:n] = torch.from_numpy(labels).to(self.device)
             self._n = n
 
     # ------------------------------------------------------------------ internals
+    def _check_dim(self):
+        if self.space == "euclidean" and self.dim > ops.L2_MAX_DIM:
+            raise ValueError(f"the 'euclidean' space takes rows of width <= {ops.L2_MAX_DIM}, not {self.dim}")
+
     def _ip_rows(self, xf: torch.Tensor) -> torch.Tensor:
-        """Half rows of a new batch for the 'ip' space.  The batch's max norm (read back: one synchronisation per batch) joins
-        the index's word; when that raises S, every stored row is re-derived under the new S with a fresh residual word."""
+        """Half rows of a new batch for the 'ip' and 'euclidean' spaces.  The batch's max norm (read back: one synchronisation per
+        batch) joins the index's word; when that raises S, every stored row is re-derived under the new S with a fresh residual
+        word."""
+        rows_fn = ops.l2_rows if self.space == "euclidean" else ops.dot_scaled_rows
         batch = float(ops.max_norm_rows(xf).item())
         if not math.isfinite(batch):
             raise ValueError("add_items: rows with non-finite elements (or norms beyond the float32 range) cannot be indexed "
-                             "in the 'ip' space")
+                             f"in the {self.space!r} space")
         old = 0.0 if self._maxnorm is None else float(self._maxnorm.item())
         if self._maxnorm is None:
             self._maxnorm = ops.new_rho(self.device)
@@ -212,8 +235,8 @@ class GpuFlatIndex:
             self._maxnorm.fill_(batch)
             if self._n and ops.dot_scale(batch) != ops.dot_scale(old):
                 self._rho.zero_()
-                self._rows[:self._n] = ops.dot_scaled_rows(self._f32[:self._n], self._maxnorm, self._rho)[0]
-        return ops.dot_scaled_rows(xf, self._maxnorm, self._rho)[0]
+                self._rows[:self._n] = rows_fn(self._f32[:self._n], self._maxnorm, self._rho)[0]
+        return rows_fn(xf, self._maxnorm, self._rho)[0]
 
     def _reserve(self, n: int):
         if self.dim == 0:
@@ -222,7 +245,7 @@ class GpuFlatIndex:
         if n <= cap:
             return
         new_cap = max(n, 2 * cap, 1024)
-        ld = ops.pad_dim(self.dim)
+        ld = ops.pad_dim(self.dim + 1 if self.space == "euclidean" else self.dim)
         rows = torch.zeros((new_cap, ld), dtype=ops.UNIT_DTYPE, device=self.device)
         f32 = torch.zeros((new_cap, self.dim), dtype=torch.float32, device=self.device)
         if self._f32 is not None and self._n:

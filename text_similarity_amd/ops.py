@@ -118,14 +118,16 @@ def cosine_topk(eq_unit: torch.Tensor, ec_unit: torch.Tensor, d: int, k: int, id
     return _topk("cosine_topk", eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, None, out)
 
 
-def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out):
-    """cosine_topk (scale_c is None) and dot_topk (scale_c = the corpus rows' max-norm word)."""
+def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out, l2=False):
+    """cosine_topk (scale_c is None), dot_topk (scale_c = the corpus rows' max-norm word) and l2_topk (the same word; the half
+    rows are one element wider than the float32 rows)."""
     _need_gpu(eq_unit, ec_unit)
     if eq_unit.dtype != UNIT_DTYPE or ec_unit.dtype != UNIT_DTYPE:
-        raise ValueError(f"{what} expects float16 rows from l2norm_rows" + (" / dot_scaled_rows" if scale_c is not None else ""))
-    ld = pad_dim(d)
+        raise ValueError(f"{what} expects float16 rows from " + ("l2_query_rows / l2_rows" if l2 else "l2norm_rows" +
+                         (" / dot_scaled_rows" if scale_c is not None else "")))
+    ld = pad_dim(d + 1 if l2 else d)
     if eq_unit.shape[1] != ld or ec_unit.shape[1] != ld or not eq_unit.is_contiguous() or not ec_unit.is_contiguous():
-        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d})={ld}")
+        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d + 1 if l2 else d})={ld}")
     if (eq_f32 is None) != (ec_f32 is None):
         raise ValueError(f"{what}: pass both float32 matrices or neither")
     Q, N = eq_unit.shape[0], ec_unit.shape[0]
@@ -176,6 +178,8 @@ def _topk(what, eq_unit, ec_unit, d, k, idx_offset, eq_f32, ec_f32, return_statu
             rho_p = rho_c.data_ptr() if rho_c is not None else 0
             if scale_c is None:
                 rc = (L.tsim_cosine_topk_large if large else L.tsim_cosine_topk_ex)(*qargs, rho_p, *rest)
+            elif l2:
+                rc = (L.tsim_l2_topk_large if large else L.tsim_l2_topk_ex)(*qargs, scale_c.data_ptr(), rho_p, *rest)
             else:
                 rc = (L.tsim_dot_topk_large if large else L.tsim_dot_topk_ex)(*qargs, scale_c.data_ptr(), rho_p, *rest)
             _lib.check(rc, what)
@@ -249,6 +253,67 @@ def dot_topk(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, k: int, eq_
     if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
         raise ValueError("dot_topk needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (dot_scaled_rows)")
     return _topk("dot_topk", eq_unit, ec_scaled, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out)
+
+
+# ------------------------------------------------------------------------------------------------- exact Euclidean search
+L2_MAX_DIM = 767                # the half operands are one element wider than the rows: pad_dim(d + 1) <= 768
+
+
+def _l2_dim(d: int, what: str) -> int:
+    if d > L2_MAX_DIM:
+        raise ValueError(f"{what}: embedding width {d} > {L2_MAX_DIM} is not supported (the half rows are d + 1 wide)")
+    return pad_dim(d + 1)
+
+
+def l2_rows(x: torch.Tensor, maxnorm: Optional[torch.Tensor] = None, rho: Optional[torch.Tensor] = None):
+    """Corpus operand of :func:`l2_topk`: [rows, d] float32/bf16 -> ``(rows, rho, maxnorm)``.  ``rows`` = half((x, -|x|^2 / (2A))
+    / 2A) zero-padded to [rows, pad_dim(d + 1)], A = :func:`dot_scale` of the max-norm word ``maxnorm``; ``rho`` raised to the
+    rows' largest flush-safe residual.  ``maxnorm`` / ``rho`` None or given: as in :func:`dot_scaled_rows`.  d <= 767."""
+    _need_gpu(x)
+    x = _rows_operand(x, "l2_rows")
+    rows, d = x.shape
+    ld = _l2_dim(d, "l2_rows")
+    if maxnorm is None:
+        maxnorm = max_norm_rows(x)
+    _check_rho(maxnorm, x.device)
+    if rho is None:
+        rho = new_rho(x.device)
+    _check_rho(rho, x.device)
+    out = torch.empty((rows, ld), dtype=UNIT_DTYPE, device=x.device)
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().tsim_l2_rows(x.data_ptr(), dt, rows, d, _row_stride(x), maxnorm.data_ptr(), out.data_ptr(), ld,
+                                           rho.data_ptr(), _stream(x)), "l2_rows")
+    return out, rho, maxnorm
+
+
+def l2_query_rows(x: torch.Tensor, maxnorm: torch.Tensor) -> torch.Tensor:
+    """Query operand of :func:`l2_topk`: [rows, d] float32/bf16 -> half((x, A) / sqrt(|x|^2 + A^2)) zero-padded to
+    [rows, pad_dim(d + 1)], A = :func:`dot_scale` of the CORPUS' max-norm word ``maxnorm`` (the one :func:`l2_rows` used)."""
+    _need_gpu(x)
+    x = _rows_operand(x, "l2_query_rows")
+    rows, d = x.shape
+    ld = _l2_dim(d, "l2_query_rows")
+    _check_rho(maxnorm, x.device)
+    out = torch.empty((rows, ld), dtype=UNIT_DTYPE, device=x.device)
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().tsim_l2_query_rows(x.data_ptr(), dt, rows, d, _row_stride(x), maxnorm.data_ptr(), out.data_ptr(), ld,
+                                                 _stream(x)), "l2_query_rows")
+    return out
+
+
+def l2_topk(eq_aug: torch.Tensor, ec_aug: torch.Tensor, d: int, k: int, eq_f32: torch.Tensor, ec_f32: torch.Tensor,
+            rho_c: torch.Tensor, scale_c: torch.Tensor, idx_offset: int = 0, return_status: bool = False,
+            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Exact top-k by Euclidean distance (the 'l2' space of hnswlib and faiss): scores [Q,k] = float32 SQUARED distances of the
+    float32 rows (canonical float64 evaluation, include/tsim.h tsim_l2_topk_ex), ascending, ties to the lower index; idx [Q,k]
+    i64; padding +inf / -1.  ``eq_aug``: :func:`l2_query_rows` of ``eq_f32`` under ``scale_c``; ``(ec_aug, rho_c, scale_c)``:
+    :func:`l2_rows` of ``ec_f32``.  All are required; the rest as :func:`cosine_topk`.  d <= 767."""
+    if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
+        raise ValueError("l2_topk needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (l2_rows)")
+    _l2_dim(d, "l2_topk")
+    return _topk("l2_topk", eq_aug, ec_aug, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out, l2=True)
 
 
 # ------------------------------------------------------------------------------------------------- exact range search

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot] [--spread]
+"""Quick timing of the search on the GPU box: python tools/bench_search.py [N] [d] [Q ...] [--score cosine|dot|l2] [--spread]
 [--k K ...] [--range TAU ... | --range-hits H ...] [--tau-array] [--range-merge R Q HITS]
 
 --score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
-one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --spread: corpus row norms spread
-log-uniformly over two decades (dot only; the default rows are Gaussian).  --k: the k values to time (default 10; up to 1024,
+one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --score l2: tsim_l2_topk_ex (squared
+Euclidean distance; half rows one element wider, l2_rows / l2_query_rows; top-k only).  --prep: also time the corpus row
+preparation (dot_scaled_rows / l2_rows) and print it.  --spread: corpus row norms spread
+log-uniformly over two decades (dot and l2; the default rows are Gaussian).  --k: the k values to time (default 10; up to 1024,
 k > 64 runs the _large entries); one line per (Q, k).
 --range TAU ...: time the exact range search (ops.cosine_range / ops.dot_range on the float32 rows) at these thresholds instead of
 top-k: ms per call (scan + the host read of the total + fill), mean hits per query and the status counts; one line per (Q, tau).
@@ -26,7 +28,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("N", nargs="?", type=int, default=1_000_000)
 ap.add_argument("d", nargs="?", type=int, default=384)
 ap.add_argument("Q", nargs="*", type=int, default=[256, 1024, 4096, 16384])
-ap.add_argument("--score", choices=("cosine", "dot"), default="cosine")
+ap.add_argument("--score", choices=("cosine", "dot", "l2"), default="cosine")
+ap.add_argument("--prep", action="store_true")
 ap.add_argument("--spread", action="store_true")
 ap.add_argument("--k", nargs="+", type=int, default=[10])
 ap.add_argument("--range", nargs="+", type=float, default=[], dest="taus")
@@ -71,8 +74,14 @@ if a.range_merge:
 cf = torch.randn((N, d), generator=g, device=dev)
 if a.spread:
     cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
-if a.score == "dot":
-    corpus, rho, scale = ops.dot_scaled_rows(cf)
+if a.score == "l2" and (a.taus or a.range_hits):
+    sys.exit("--score l2 has no range search")
+if a.score in ("dot", "l2"):
+    rows_fn = ops.dot_scaled_rows if a.score == "dot" else ops.l2_rows
+    corpus, rho, scale = rows_fn(cf)
+    if a.prep:
+        print(json.dumps({"score": a.score, "prep": rows_fn.__name__, "N": N, "d": d,
+                          "ms": round(timed(lambda: rows_fn(cf, scale), 5), 4)}), flush=True)
 else:
     corpus, rho = ops.l2norm_rows(cf, return_rho=True)
     if not (a.taus or a.range_hits):
@@ -98,8 +107,11 @@ if taus:
     sys.exit(0)
 for Q, k in [(Q, k) for Q in Qs for k in a.k]:
     qf = torch.randn((Q, d), generator=g, device=dev)
-    q = ops.l2norm_rows(qf)
-    if a.score == "dot":
+    q = ops.l2_query_rows(qf, scale) if a.score == "l2" else ops.l2norm_rows(qf)
+    if a.score == "l2":
+        def run(status=False):
+            return ops.l2_topk(q, corpus, d, k, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=status)
+    elif a.score == "dot":
         def run(status=False):
             return ops.dot_topk(q, corpus, d, k, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=status)
     else:

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of the fused cosine top-k against the oracle (bit-exact indices and scores), in both modes: unit rows
 only (canonical scores) and the reference's cosine of float32 rows (tsim_cosine_topk_ex); every fourth case takes k up to 64.
+Cases of width <= 767 also run the Euclidean search (tsim_l2_topk_ex) against the canonical squared distances of tests/l2_cases.py.
 Usage: python tools/fuzz_search.py [cases] [seed].  Not part of the pytest suite (minutes of CPU oracle time)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np, torch
+from l2_cases import l2_topk_ref
 from oracle import search_ref
 from text_similarity_amd import ops
 
@@ -45,6 +48,13 @@ for c in range(cases):
     fs, fi = search_ref.cosine_topk_f32(q[qs], x, kk)
     ok2 = np.array_equal(i2.cpu().numpy()[qs], fi) and np.array_equal(s2.cpu().numpy()[qs], fs) and int(st.max()) <= 2
     ok = ok and ok2
+    if d <= ops.L2_MAX_DIM:      # Euclidean: squared distances ascending, ties to the lower index
+        cn, rho, scale = ops.l2_rows(xt)
+        s3, i3, st3 = ops.l2_topk(ops.l2_query_rows(qt, scale), cn, d, kk, eq_f32=qt, ec_f32=xt, rho_c=rho, scale_c=scale,
+                                  return_status=True)
+        torch.cuda.synchronize()
+        ls, li = l2_topk_ref(q[qs], x, kk)
+        ok = ok and np.array_equal(i3.cpu().numpy()[qs], li) and np.array_equal(s3.cpu().numpy()[qs], ls) and int(st3.max()) <= 2
     bad += not ok
     print(f"case {c:3d} d={d:3d} Q={Q:4d} N={N:6d} k={kk:2d} {kind:6s} {'ok' if ok else 'MISMATCH'}  ({time.time() - t0:.0f} s)", flush=True)
 print(f"fuzz_search: {cases - bad}/{cases} cases bit-exact")
