@@ -274,11 +274,31 @@ int tsim_dot_topk_large(const void *eq_unit, const float *eq_f32, int64_t ldq_f3
  * (score desc, index asc).  Entries equal in score AND index (which disjoint shards do not produce) are ordered by list
  * number: the output is always a permutation of the input.  Segments may have any length, also 0; a whole list may be empty;
  * nlists = 1 is a copy; Q = 0 or total = 0 returns without a launch.  No workspace.  An output segment shorter than the lists'
- * total for the query is never overrun. */
+ * total for the query is never overrun.
+ * Euclidean space.  tsim_l2_range_scan / tsim_l2_range_scan_tau: every row within a SQUARED radius (faiss' L2 convention for
+ * range_search).  Row r is a hit of query q iff float32(dist^2(q, r)) <= radius, dist^2 being exactly the float32 value
+ * tsim_l2_topk_ex returns for the pair.  The comparison is <=, the counterpart of >= in the other spaces; faiss compares with <,
+ * so a row AT the radius is a hit here and not there (pass the float32 below the radius for faiss' set).  Operands and limits
+ * are those of tsim_l2_topk_ex: eq_aug / ec_aug from tsim_l2_query_rows / tsim_l2_rows, ld == tsim_pad_dim(d + 1), d <= 767,
+ * ec_maxnorm and ec_rho_max REQUIRED; the argument order is that of the dot entries, the radius (one float, NaN: TSIM_EINVAL, or
+ * radius_q, device float32 [Q]) in the threshold's place.  The fill is tsim_range_fill / tsim_range_fill_tau with space =
+ * TSIM_SPACE_L2 and the same radius; it writes squared distances, each segment ordered by (distance asc, index asc).
+ * radius < 0: no hit; 0: exactly the rows equal to the query; +inf: every row (of non-NaN distance) through the exact pass,
+ * status 2; NaN in radius_q: no hit, status 2.  Status as above.
+ * Guard.  A hit has float32 dist^2 <= r, so its float64 dist^2 < up(r) = l2_dist_up(r) (tsim_l2_topk_ex, "The ulp").  By
+ * |m - (|q|^2 - dist^2) / (2 nqs)| <= eps_q its MFMA score is m > (|q|^2 - up(r)) / (2 nqs) - eps_q > thr_q = guard_tau_l2(r,
+ * eps_q, nqs, |q|^2), the threshold the widening pass of the top-k uses with r in the place of the k-th distance: the row is
+ * collected.  The re-score drops the rows of the band that came with the hits.  Internally every list holds -dist^2 (a hit is
+ * -dist^2 >= -r, the same comparison); the last kernel of the fill flips the sign.
+ * Known, not fixed: a corpus whose norms spread over decades, or one clustered far from the origin, puts every row inside the
+ * window; such queries overflow the slot and end in status 2 — exact but slow.
+ * tsim_range_merge_asc: tsim_range_merge for segments sorted by (score asc, index asc) — the squared distances of the
+ * Euclidean entries; same arguments, limits and tie rule. */
 #define TSIM_RANGE_SLOT_CAP 2048
 #define TSIM_RANGE_MERGE_MAX_LISTS 64
 #define TSIM_SPACE_COSINE 0
 #define TSIM_SPACE_DOT 1
+#define TSIM_SPACE_L2 2
 size_t tsim_range_workspace_bytes(int64_t Q, int64_t N);
 int tsim_cosine_range_scan(const void *eq_unit, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_unit,
                            const float *ec_f32, int64_t ldc_f32, const float *ec_rho_max, int64_t N, int d, int ld, float tau,
@@ -303,6 +323,16 @@ int tsim_range_fill_tau(int space, const float *eq_f32, int64_t ldq_f32, int64_t
                         int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream);
 int tsim_range_merge(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
                      const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream);
+int tsim_l2_range_scan(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                       const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                       int d, int ld, float radius, int64_t *out_counts, int32_t *out_status, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int tsim_l2_range_scan_tau(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                           const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                           int d, int ld, const float *radius_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int tsim_range_merge_asc(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                         const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream);
 
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are

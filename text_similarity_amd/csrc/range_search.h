@@ -1,11 +1,15 @@
-// Exact range search (tsim_cosine_range_scan / tsim_dot_range_scan / tsim_range_fill and their _tau forms): every corpus row
-// whose exact score is >= tau, tau one float per call or one per query (tau_q[q]); tsim_range_merge joins per-shard results.  Included by search.hip behind the exact-score helpers, the guard helpers and plan_collect, which it uses as they are.
+// Exact range search (tsim_cosine_range_scan / tsim_dot_range_scan / tsim_l2_range_scan / tsim_range_fill and their _tau forms): every corpus row
+// whose exact score is >= tau (Euclidean: whose squared distance is <= the radius, which travels in tau / tau_q), tau one float per call or one per query (tau_q[q]); tsim_range_merge joins per-shard results.  Included by search.hip behind the exact-score helpers, the guard helpers and plan_collect, which it uses as they are.
 //
 // Pipeline of one scan:   range_setup  ->  K1 in COLLECT mode (k1_launch_collect, unchanged)  ->  range_finalize  ->  range_bf<count>
 //          of one fill:   range_fill (status 1)  ->  range_bf<fill>  ->  range_bf_sort (status 2)
 // The guard is simpler than top-k's: there is no k-th competitor, only the fixed tau.  A row with exact score s >= tau has an MFMA
 // score m >= s - eps_q >= tau - eps_q (guard_eps bounds |m - s|), so collecting every row with m strictly above a threshold placed
 // below tau - eps_q misses no hit; the exact re-score then drops the few rows of the band [tau - eps_q, tau) that came with them.
+// SM_L2: the operands are the augmented rows of the Euclidean top-k (l2_rows / l2_query_rows, ld = pad_dim(d + 1)), the exact
+// scores are -dist^2 (rows of l2_f32) in every list until range_fill_negate flips the sign of the output, and the threshold is
+// guard_tau_l2(r, eps_q, nqs, |q|^2): every row whose float32 distance could be <= r has an MFMA score above it.  A hit is
+// es >= -r, which on es = -dist^2 is exactly dist^2 <= r (false for NaN, true for r = 0 against -0).
 #pragma once
 
 namespace tsim {
@@ -16,12 +20,12 @@ enum { RCTL_QCOUNT = 0, RCTL_NUNRES = 1, RCTL_WORDS = 4 };
 enum { RST_COLLECTED = 1, RST_EXACT = 2 };   // out_status values (include/tsim.h)
 
 struct RangeArgs {
-    float tau;                // the threshold of every query when tau_q is null
+    float tau;                // the threshold of every query when tau_q is null (SM_L2: the squared radius)
     const float *tau_q;       // device [Q], or null: the threshold of query q (the _tau entries)
     int ld;
     const float *rho_c_max;   // device, or null (cosine: the a-priori bound)
     float rho_c_default;
-    const float *c_maxnorm;   // SM_DOT: the corpus rows' max-norm word
+    const float *c_maxnorm;   // SM_DOT: the corpus rows' max-norm word; SM_L2: the same word (A = dot_scale of it)
     int *ctl;                 // RCTL_* words
     int *gthr;                // [Q] collect threshold of slot q as an ordered int (k1_topk.h float_to_ordered)
     int *qmap;                // [Q] identity: slot q = query q
@@ -37,6 +41,9 @@ struct RangeArgs {
 // The threshold of query q.  Every kernel compares against this one value, so a query of a _tau call is answered exactly as by
 // the scalar call with tau = tau_q[q]; a NaN there fails every comparison below (no finite collect threshold: status 2, no hit).
 __device__ __forceinline__ float rs_tau(const RangeArgs &a, int64_t q) { return a.tau_q ? a.tau_q[q] : a.tau; }
+// the value exact scores are compared with (>=): tau; rows of l2_f32 score -dist^2, so the radius changes sign (exactly)
+template <bool L2>
+__device__ __forceinline__ float rs_cut(const RangeArgs &a, int64_t q) { return L2 ? -rs_tau(a, q) : rs_tau(a, q); }
 
 // entry order (score desc, row asc); RS_PAD = (-inf, row 2^32 - 1) ranks behind every real entry (rows are < 2^31)
 constexpr unsigned long long RS_PAD = 0xffffffffff800000ull;
@@ -67,12 +74,14 @@ __device__ __forceinline__ void rs_sort(unsigned long long *e, int n) {
 // tau / (nq S) - eps_q with the conversion slack on the safe side).  Both return "collect everything" (-FLT_MAX) when no finite
 // threshold is safe: tau = -inf, a non-finite S, eps_q = inf, a zero query with tau <= 0 whose quotient leaves the float range.
 // Such a query would overflow any buffer: it is handed to the exact pass at once (status 2) and its slot collects nothing.
+// SM_L2: rho_q over the d + 1 elements of the augmented row, the threshold guard_tau_l2 of the radius (no finite one for
+// r = +inf, NaN, a non-finite |q|^2 or nqs).
 // Writes everything k1_launch_collect reads: gthr, the identity qmap, qcount = Q, zeroed counters.
 // =====================================================================================================
 template <int SM>
 __global__ __launch_bounds__(256) void range_setup_kernel(int64_t Q, const float *__restrict__ xq, int64_t ldq,
                                                           const unit_t *__restrict__ uq, int d, RangeArgs a) {
-    constexpr bool DOT = SM == SM_DOT;
+    constexpr bool DOT = SM == SM_DOT, L2 = SM == SM_L2;
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -80,14 +89,23 @@ __global__ __launch_bounds__(256) void range_setup_kernel(int64_t Q, const float
         a.ctl[RCTL_NUNRES] = 0;
     }
     if (q >= Q) return;
-    ExactQuery<float> eqr;
-    exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);   // norm = max(|q|, 1e-8): the scale the unit row was made with
-    const float rho_c = a.rho_c_max ? *a.rho_c_max : a.rho_c_default;
-    const float eps = guard_eps(query_rho<DOT>(eqr, uq + q * a.ld, d, lane), rho_c, a.ld);
-    const float tau = rs_tau(a, q);
-    float thr;
-    if constexpr (DOT) thr = guard_tau_dot(tau, eps, eqr.norm * dot_scale(*a.c_maxnorm));
-    else thr = guard_tau(tau, eps);
+    float eps, thr;
+    if constexpr (L2) {
+        ExactQuery<l2_f32> eqr;
+        exact_load_query<l2_f32, NORM_SQ>(eqr, reinterpret_cast<const l2_f32 *>(xq) + q * ldq, d, lane);   // norm = |q|^2
+        const double A = dot_scale(*a.c_maxnorm);
+        const double nq = sqrt(eqr.norm + A * A);   // nq' of l2_query_rows_kernel, the same bits
+        eps = guard_eps(query_rho_l2(eqr, uq + q * a.ld, d, A, nq, lane), *a.rho_c_max, a.ld);
+        thr = guard_tau_l2(rs_tau(a, q), eps, l2_nqs(eqr.norm, A), eqr.norm);   // (the radius)
+    } else {
+        ExactQuery<float> eqr;
+        exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);   // norm = max(|q|, 1e-8): the scale the unit row was made with
+        const float rho_c = a.rho_c_max ? *a.rho_c_max : a.rho_c_default;
+        eps = guard_eps(query_rho<DOT>(eqr, uq + q * a.ld, d, lane), rho_c, a.ld);
+        const float tau = rs_tau(a, q);
+        if constexpr (DOT) thr = guard_tau_dot(tau, eps, eqr.norm * dot_scale(*a.c_maxnorm));
+        else thr = guard_tau(tau, eps);
+    }
     const bool everything = !(thr > -3.4e38f);
     if (lane != 0) return;
     a.gthr[q] = float_to_ordered(everything ? INFINITY : thr);
@@ -109,7 +127,9 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
                                                              const float *__restrict__ xc, int64_t ldc, int d,
                                                              int64_t *__restrict__ out_counts, int32_t *__restrict__ out_status,
                                                              RangeArgs a) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT;
+    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
+    using T = std::conditional_t<L2, l2_f32, float>;   // (l2_f32: a struct of one float, the layout of the float32 rows)
+    const T *tq = reinterpret_cast<const T *>(xq), *tc = reinterpret_cast<const T *>(xc);
     __shared__ unsigned long long ent[RS_CAP];
     __shared__ int s_keep, s_bad;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -125,11 +145,12 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
             __syncthreads();
             int np = 64;
             while (np < n) np <<= 1;   // <= RS_CAP
-            ExactQuery<float> eqr;
-            exact_load_query<float, true>(eqr, xq + q * ldq, d, lane);
+            ExactQuery<T> eqr;
+            exact_load_query<T, L2 ? NORM_SQ : NORM_COS>(eqr, tq + q * ldq, d, lane);
             double nqs = 1.0;
             if constexpr (DOT) nqs = eqr.norm * dot_scale(*a.c_maxnorm);
-            const float eps = a.eps[q], tau = rs_tau(a, q);
+            if constexpr (L2) nqs = l2_nqs(eqr.norm, dot_scale(*a.c_maxnorm));
+            const float eps = a.eps[q], tau = rs_cut<L2>(a, q);
             unsigned long long *slot = a.buf + q * RS_CAP;
             bool bad = false;
             int mine = 0;
@@ -140,11 +161,12 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
                     const unsigned long long in = slot[e < n ? e : g0];
                     const int row = (int)(in >> 32);
                     const int nvalid = n - g0 < 64 ? n - g0 : 64;
-                    const float es = wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+                    const float es = wave_scores<T, COS>(eqr, tc, ldc, row, nvalid, d, lane);
                     if (e < n) {
                         const float ms = __uint_as_float((uint32_t)in);
                         float err;
                         if constexpr (DOT) err = (float)fabs((double)ms - (double)es / nqs);
+                        else if constexpr (L2) err = l2_err(ms, es, nqs, eqr.norm);
                         else err = fabsf(ms - es);
                         if (!(err <= eps)) bad = true;
                         if (es >= tau) {
@@ -179,6 +201,7 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
 
 // =====================================================================================================
 // Exact pass for status-2 queries: every row of the shard scored with the arithmetic of bf_partial_kernel (exact_score's bits).
+//   (T = l2_f32: the rows scored as -dist^2 against -radius; COS is false then)
 //   range_bf_kernel<COS, FILL = false>: workgroup (chunk c, slot u) counts the chunk's hits of query unres_q[u] into out_counts;
 //   range_bf_kernel<COS, FILL = true>:  the same pass writes each hit straight into the query's segment [lims[q], lims[q+1]) of
 //                                       the output (no per-query scratch: a query may hit the whole shard), in arrival order;
@@ -186,12 +209,14 @@ __global__ __launch_bounds__(256) void range_finalize_kernel(int64_t Q, const fl
 // =====================================================================================================
 constexpr int RS_BF_MAXCH = 256;
 
-template <bool COS, bool FILL>
+template <bool COS, bool FILL, typename T = float>
 __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int rows_per_chunk, const float *__restrict__ xq,
                                                        int64_t ldq, const float *__restrict__ xc, int64_t ldc, int d,
                                                        int64_t *__restrict__ out_counts, const int64_t *__restrict__ lims,
                                                        float *__restrict__ out_s, int64_t *__restrict__ out_i, int64_t idx_offset,
                                                        RangeArgs a) {
+    static_assert(!(COS && is_l2_rows<T>), "rows of l2_f32 have no cosine");
+    const T *tq = reinterpret_cast<const T *>(xq), *tc = reinterpret_cast<const T *>(xc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int nu = a.ctl[RCTL_NUNRES];
     nu = nu < Q ? nu : (int)Q;
@@ -199,9 +224,9 @@ __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int
     const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
     for (int u = blockIdx.y; u < nu; u += gridDim.y) {
         const int q = a.unres_q[u];
-        const float tau = rs_tau(a, q);
-        ExactQuery<float> eqr;
-        exact_load_query<float, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
+        const float tau = rs_cut<is_l2_rows<T>>(a, q);
+        ExactQuery<T> eqr;
+        exact_load_query<T, COS>(eqr, tq + (int64_t)q * ldq, d, lane);
         int64_t seg0 = 0, seglen = 0;
         if constexpr (FILL) {
             seg0 = lims[q];
@@ -211,7 +236,7 @@ __global__ __launch_bounds__(256) void range_bf_kernel(int64_t Q, int64_t N, int
         for (int64_t g0 = r0 + wave * 64; g0 < r1; g0 += 256) {   // wave-uniform
             const int nvalid = r1 - g0 < 64 ? (int)(r1 - g0) : 64;
             const int row = (int)(g0 + (lane < nvalid ? lane : 0));
-            const float s = wave_scores<float, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+            const float s = wave_scores<T, COS>(eqr, tc, ldc, row, nvalid, d, lane);
             const bool hit = lane < nvalid && s >= tau;
             const unsigned long long hits = __ballot(hit);
             if (hits == 0) continue;
@@ -334,6 +359,13 @@ __global__ __launch_bounds__(256) void range_fill_kernel(int64_t Q, const int64_
     }
 }
 
+// SM_L2, the last kernel of a fill: the segments hold -dist^2 in (score desc, index asc) order; the sign flip (exact) leaves
+// squared distances in (distance asc, index asc) order.  The host does not know T = lims[Q]: the kernel reads it.
+__global__ __launch_bounds__(256) void range_fill_negate_kernel(float *__restrict__ out_s, const int64_t *__restrict__ total) {
+    const int64_t n = *total;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out_s[i] = -out_s[i];
+}
+
 // Workspace layout of one range scan + fill (byte offsets)
 struct RangeWs {
     size_t ctl, gthr, qmap, cnt, eps, status, nhit, unres_q, cursor, buf, total;
@@ -407,13 +439,15 @@ static int range_scan(int sm, const char *what, const void *eq, const float *eq_
     int rc = range_check_shapes(what, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, tau_q, workspace, workspace_bytes, &w);
     if (rc) return rc;
     TSIM_REQUIRE(eq && ec && out_counts, "%s: null pointer", what);
-    TSIM_REQUIRE(ld == tsim_pad_dim(d) && ld > 0, "%s: rows must be padded to tsim_pad_dim(d)=%d (got ld=%d)", what, tsim_pad_dim(d), ld);
+    const int dw = d + (sm == SM_L2);   // width of the half operands (L2: one element longer than the rows)
+    TSIM_REQUIRE(ld == tsim_pad_dim(dw) && ld > 0, "%s: rows must be padded to tsim_pad_dim(%d)=%d (got ld=%d)", what, dw, tsim_pad_dim(dw), ld);
     TSIM_REQUIRE((((uintptr_t)eq | (uintptr_t)ec) & 15) == 0, "%s: embedding matrices must be 16-byte aligned", what);
     hipStream_t st = as_stream(stream);
     const unit_t *uq = (const unit_t *)eq, *uc = (const unit_t *)ec;
     const RangeArgs a = make_range_args(w, reinterpret_cast<char *>(workspace), tau, tau_q, ld, ec_rho_max, ec_maxnorm);
     const dim3 qgrid((unsigned)((Q + 3) / 4));
     if (sm == SM_DOT) hipLaunchKernelGGL(range_setup_kernel<SM_DOT>, qgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, uq, d, a);
+    else if (sm == SM_L2) hipLaunchKernelGGL(range_setup_kernel<SM_L2>, qgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, uq, d, a);
     else hipLaunchKernelGGL(range_setup_kernel<SM_COS>, qgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, uq, d, a);
     TSIM_HIP_CHECK(hipGetLastError());
     TopkPlan cp;
@@ -430,6 +464,9 @@ static int range_scan(int sm, const char *what, const void *eq, const float *eq_
     if (sm == SM_DOT)
         hipLaunchKernelGGL(range_finalize_kernel<SM_DOT>, fgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, ec_f32, ldc_f32, d, out_counts,
                            out_status, a);
+    else if (sm == SM_L2)
+        hipLaunchKernelGGL(range_finalize_kernel<SM_L2>, fgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, ec_f32, ldc_f32, d, out_counts,
+                           out_status, a);
     else
         hipLaunchKernelGGL(range_finalize_kernel<SM_COS>, fgrid, dim3(256), 0, st, Q, eq_f32, ldq_f32, ec_f32, ldc_f32, d, out_counts,
                            out_status, a);
@@ -440,6 +477,9 @@ static int range_scan(int sm, const char *what, const void *eq, const float *eq_
     if (sm == SM_DOT)
         hipLaunchKernelGGL((range_bf_kernel<false, false>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32, d,
                            out_counts, (const int64_t *)nullptr, (float *)nullptr, (int64_t *)nullptr, (int64_t)0, a);
+    else if (sm == SM_L2)
+        hipLaunchKernelGGL((range_bf_kernel<false, false, l2_f32>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32,
+                           d, out_counts, (const int64_t *)nullptr, (float *)nullptr, (int64_t *)nullptr, (int64_t)0, a);
     else
         hipLaunchKernelGGL((range_bf_kernel<true, false>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32, d,
                            out_counts, (const int64_t *)nullptr, (float *)nullptr, (int64_t *)nullptr, (int64_t)0, a);
@@ -459,9 +499,11 @@ static int range_scan(int sm, const char *what, const void *eq, const float *eq_
 // shards spreads over the chip like 4 096 queries of a hundred hits.  Finding (q, list) costs log2 Q + R cached reads, small
 // against the R binary searches.  Whatever the data, a write lands inside the entry's own output segment: the place is < the sum
 // of the R segment lengths, and it is checked against the segment lims_out gives.
+// ASC (tsim_range_merge_asc): the segments are sorted by (score asc, index asc) — squared distances — and so is the output.
 // =====================================================================================================
 constexpr int RM_PER = 4;   // entries per thread
 
+template <bool ASC>
 __global__ __launch_bounds__(256) void range_merge_kernel(int R, int64_t Q, const int64_t *__restrict__ lims_in,
                                                           const float *__restrict__ s_in, const int64_t *__restrict__ i_in,
                                                           const int64_t *__restrict__ lims_out, float *__restrict__ out_s,
@@ -498,7 +540,7 @@ __global__ __launch_bounds__(256) void range_merge_kernel(int R, int64_t Q, cons
             while (l < h) {       // entries of list r2 ahead of (s, i): strictly ahead, and the equal one too when r2 < r
                 const int64_t mid = (l + h) >> 1;
                 const float ms = s_in[b + mid];
-                bool ahead = ms > s;
+                bool ahead = ASC ? ms < s : ms > s;
                 if (ms == s) {    // (the index is read on a tie of the score only)
                     const int64_t mi = i_in[b + mid];
                     ahead = mi < i || (mi == i && r2 < r);
@@ -569,11 +611,42 @@ extern "C" int tsim_dot_range_scan_tau(const void *eq, const float *eq_f32, int6
                           tau_q, out_counts, out_status, workspace, workspace_bytes, stream);
 }
 
+static int l2_range_scan(const char *what, const void *eq, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec,
+                         const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N, int d, int ld,
+                         float radius, const float *radius_q, int64_t *out_counts, int32_t *out_status, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+    using namespace tsim;
+    TSIM_REQUIRE(radius_q || radius == radius, "%s: the radius is NaN", what);
+    TSIM_REQUIRE(eq_f32 && ec_f32, "%s: the float32 matrices are required", what);
+    TSIM_REQUIRE(ec_maxnorm && ec_rho_max, "%s: the corpus rows' max-norm word and measured rho_max are required", what);
+    TSIM_REQUIRE(d > 0 && d < 64 * XS_MAXI, "%s: d=%d (1 .. %d: the half rows are d + 1 wide)", what, d, 64 * XS_MAXI - 1);
+    return range_scan(SM_L2, what, eq, eq_f32, ldq_f32, Q, ec, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, radius, radius_q,
+                      out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_l2_range_scan(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                                  const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max, int64_t N,
+                                  int d, int ld, float radius, int64_t *out_counts, int32_t *out_status, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    return l2_range_scan("l2_range_scan", eq_aug, eq_f32, ldq_f32, Q, ec_aug, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, radius,
+                         nullptr, out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_l2_range_scan_tau(const void *eq_aug, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_aug,
+                                      const float *ec_f32, int64_t ldc_f32, const float *ec_maxnorm, const float *ec_rho_max,
+                                      int64_t N, int d, int ld, const float *radius_q, int64_t *out_counts, int32_t *out_status,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(radius_q, "l2_range_scan_tau: null radius array");
+    return l2_range_scan("l2_range_scan_tau", eq_aug, eq_f32, ldq_f32, Q, ec_aug, ec_f32, ldc_f32, ec_maxnorm, ec_rho_max, N, d, ld, 0.f,
+                         radius_q, out_counts, out_status, workspace, workspace_bytes, stream);
+}
+
 static int range_fill(const char *what, int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32,
                       int64_t ldc_f32, int64_t N, int d, float tau, const float *tau_q, const int64_t *lims, float *out_scores,
                       int64_t *out_idx, int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream) {
     using namespace tsim;
-    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT, "%s: unknown space %d", what, space);
+    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT || space == TSIM_SPACE_L2, "%s: unknown space %d", what, space);
+    TSIM_REQUIRE(space != TSIM_SPACE_L2 || d < 64 * XS_MAXI, "%s: d=%d (the Euclidean space takes d <= %d)", what, d, 64 * XS_MAXI - 1);
     RangeWs w;
     int rc = range_check_shapes(what, eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, tau, tau_q, workspace, workspace_bytes, &w);
     if (rc) return rc;
@@ -590,12 +663,19 @@ static int range_fill(const char *what, int space, const float *eq_f32, int64_t 
     if (space == TSIM_SPACE_DOT)
         hipLaunchKernelGGL((range_bf_kernel<false, true>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32, d,
                            (int64_t *)nullptr, lims, out_scores, out_idx, idx_offset, a);
+    else if (space == TSIM_SPACE_L2)
+        hipLaunchKernelGGL((range_bf_kernel<false, true, l2_f32>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32, d,
+                           (int64_t *)nullptr, lims, out_scores, out_idx, idx_offset, a);
     else
         hipLaunchKernelGGL((range_bf_kernel<true, true>), bgrid, dim3(256), 0, st, Q, N, rows, eq_f32, ldq_f32, ec_f32, ldc_f32, d,
                            (int64_t *)nullptr, lims, out_scores, out_idx, idx_offset, a);
     TSIM_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(range_bf_sort_kernel, dim3((unsigned)(Q < 256 ? Q : 256)), dim3(RS_SORT_T), 0, st, Q, lims, out_scores, out_idx, a);
     TSIM_HIP_CHECK(hipGetLastError());
+    if (space == TSIM_SPACE_L2) {   // every kernel above wrote -dist^2
+        hipLaunchKernelGGL(range_fill_negate_kernel, dim3(1024), dim3(256), 0, st, out_scores, lims + Q);
+        TSIM_HIP_CHECK(hipGetLastError());
+    }
     return TSIM_OK;
 }
 
@@ -614,19 +694,30 @@ extern "C" int tsim_range_fill_tau(int space, const float *eq_f32, int64_t ldq_f
                       idx_offset, workspace, workspace_bytes, stream);
 }
 
-extern "C" int tsim_range_merge(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
-                                const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream) {
+template <bool ASC>
+static int range_merge(const char *what, const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                       const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream) {
     using namespace tsim;
-    TSIM_REQUIRE(nlists >= 1 && nlists <= TSIM_RANGE_MERGE_MAX_LISTS, "range_merge: %d lists (1 .. %d)", nlists,
+    TSIM_REQUIRE(nlists >= 1 && nlists <= TSIM_RANGE_MERGE_MAX_LISTS, "%s: %d lists (1 .. %d)", what, nlists,
                  TSIM_RANGE_MERGE_MAX_LISTS);
-    TSIM_REQUIRE(Q >= 0 && total >= 0, "range_merge: bad shape Q=%lld total=%lld", (long long)Q, (long long)total);
-    TSIM_REQUIRE(Q < (1ll << 31) - 512 && total < (1ll << 33), "range_merge: Q=%lld total=%lld too large for one launch", (long long)Q,
+    TSIM_REQUIRE(Q >= 0 && total >= 0, "%s: bad shape Q=%lld total=%lld", what, (long long)Q, (long long)total);
+    TSIM_REQUIRE(Q < (1ll << 31) - 512 && total < (1ll << 33), "%s: Q=%lld total=%lld too large for one launch", what, (long long)Q,
                  (long long)total);
     if (Q == 0 || total == 0) return TSIM_OK;
-    TSIM_REQUIRE(lims_in && scores_in && idx_in && lims_out && out_scores && out_idx, "range_merge: null pointer");
+    TSIM_REQUIRE(lims_in && scores_in && idx_in && lims_out && out_scores && out_idx, "%s: null pointer", what);
     const int64_t per = 256 * (int64_t)RM_PER;
-    hipLaunchKernelGGL(range_merge_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, as_stream(stream), nlists, Q,
+    hipLaunchKernelGGL(range_merge_kernel<ASC>, dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, as_stream(stream), nlists, Q,
                        lims_in, scores_in, idx_in, lims_out, out_scores, out_idx, total);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
+}
+
+extern "C" int tsim_range_merge(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                                const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream) {
+    return range_merge<false>("range_merge", lims_in, scores_in, idx_in, nlists, Q, lims_out, total, out_scores, out_idx, stream);
+}
+
+extern "C" int tsim_range_merge_asc(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
+                                    const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream) {
+    return range_merge<true>("range_merge_asc", lims_in, scores_in, idx_in, nlists, Q, lims_out, total, out_scores, out_idx, stream);
 }

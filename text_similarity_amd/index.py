@@ -20,8 +20,9 @@ other space raises ``ValueError``.
 ``space='euclidean'`` ranks by Euclidean distance (hnswlib's and faiss' default space; ``knn_query`` returns SQUARED distances,
 ascending, hnswlib's l2 convention; ``search`` pads with -1 / +inf): the half rows are one element wider than the float32 rows
 (:func:`ops.l2_rows`), so d <= 767, and they follow the 'ip' rules — one power of two from the largest row norm, re-derived
-when a batch raises it, non-finite rows refused.  ``range_search`` is not implemented in this space.  The name ``'l2'`` stays
-refused, as it was before this space existed (callers test for that).
+when a batch raises it, non-finite rows refused.  ``radius_search`` / ``radius_query`` return every row within a SQUARED radius
+(faiss' ``range_search`` in this space); ``range_search`` means "score >= threshold" and stays undefined here.  The name
+``'l2'`` stays refused, as it was before this space existed (callers test for that).
 """
 from __future__ import annotations
 
@@ -151,7 +152,8 @@ class GpuFlatIndex:
         ``[lims[q], lims[q+1])``, ordered by (score desc, row asc).  Exact and complete (:func:`ops.cosine_range`).
         ``threshold``: a float, or an array / tensor [Q] with one threshold per query (a wrong length is a ValueError)."""
         if self.space == "euclidean":
-            raise NotImplementedError("range_search is not implemented in the 'euclidean' space")
+            raise NotImplementedError("range_search (score >= threshold) is not defined in the 'euclidean' space: "
+                                      "radius_search returns every row within a squared distance")
         self._compact()
         q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
         if q.dim() == 1:
@@ -176,6 +178,33 @@ class GpuFlatIndex:
         = 1 - score)``, best first within each query."""
         lims, scores, labels = self.range_search(data, threshold)
         return lims.cpu().numpy(), labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
+
+    def radius_search(self, data, radius) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """'euclidean' only: every live row whose SQUARED distance to a query is <= ``radius`` (faiss' L2 ``range_search``, which
+        compares with ``<``): ``(lims int64 [Q+1], dist2 float32 [T], labels int64 [T])`` on the device, the hits of query q in
+        ``[lims[q], lims[q+1])`` ordered by (distance asc, row asc).  Exact and complete (:func:`ops.l2_range`).  ``radius``: a
+        float, or an array / tensor [Q] with one radius per query (a wrong length is a ValueError)."""
+        if self.space != "euclidean":
+            raise ValueError(f"radius_search is defined in the 'euclidean' space, not {self.space!r} (range_search takes a score)")
+        self._compact()
+        q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        qf = q.to(self.device, dtype=torch.float32).contiguous()
+        if self._n == 0:
+            ops._threshold_array("radius_search", radius, qf.shape[0], self.device)      # (the length check of the ops)
+            return (torch.zeros((qf.shape[0] + 1,), dtype=torch.int64, device=self.device),
+                    torch.empty((0,), dtype=torch.float32, device=self.device),
+                    torch.empty((0,), dtype=torch.int64, device=self.device))
+        lims, s, i = ops.l2_range(ops.l2_query_rows(qf, self._maxnorm), self._rows[:self._n], self.dim, radius, eq_f32=qf,
+                                  ec_f32=self._f32[:self._n], rho_c=self._rho, scale_c=self._maxnorm)
+        return lims, s, self._labels[i]
+
+    def radius_query(self, data, radius) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """numpy form of :meth:`radius_search` with ``knn_query``'s convention for this space: ``(lims [Q+1], labels [T],
+        distances [T])``, the squared distances themselves, nearest first within each query."""
+        lims, dist2, labels = self.radius_search(data, radius)
+        return lims.cpu().numpy(), labels.cpu().numpy(), dist2.cpu().numpy()
 
     # ------------------------------------------------------------------ persistence
     def save_index(self, path: str):

@@ -378,19 +378,24 @@ def _threshold_array(what, threshold, Q: int, dev):
 
 
 def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset, return_status):
+    """cosine_range (scale_c is None), dot_range and l2_range (space SPACE_L2: the half rows are one element wider than the
+    float32 rows, the threshold is the squared radius and the scores that come back are squared distances)."""
     _need_gpu(eq_unit, ec_half, eq_f32, ec_f32)
+    l2 = space == _lib.SPACE_L2
     if eq_unit.dtype != UNIT_DTYPE or ec_half.dtype != UNIT_DTYPE:
-        raise ValueError(f"{what} expects float16 rows from l2norm_rows" + (" / dot_scaled_rows" if scale_c is not None else ""))
-    ld = pad_dim(d)
+        raise ValueError(f"{what} expects float16 rows from " + ("l2_query_rows / l2_rows" if l2 else "l2norm_rows" +
+                         (" / dot_scaled_rows" if scale_c is not None else "")))
+    dw = d + 1 if l2 else d
+    ld = pad_dim(dw)
     if eq_unit.shape[1] != ld or ec_half.shape[1] != ld or not eq_unit.is_contiguous() or not ec_half.is_contiguous():
-        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({d})={ld}")
+        raise ValueError(f"{what}: rows must be contiguous with stride pad_dim({dw})={ld}")
     Q, N = eq_unit.shape[0], ec_half.shape[0]
     dev = eq_unit.device
     tau_q = _threshold_array(what, threshold, Q, dev)
     if tau_q is None:
         tau = float(threshold)
         if tau != tau:
-            raise ValueError(f"{what}: the threshold is NaN")
+            raise ValueError(f"{what}: the {'radius' if l2 else 'threshold'} is NaN")
     for t, rows, name in ((eq_f32, Q, "eq_f32"), (ec_f32, N, "ec_f32")):
         if t.dtype != torch.float32 or t.dim() != 2 or t.shape != (rows, d) or t.stride(1) != 1 or t.device != dev:
             raise ValueError(f"{what}: {name} must be float32 [{rows}, {d}] with unit inner stride on {dev}")
@@ -420,6 +425,8 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
                 tail = (N, d, ld, tau_arg, counts.data_ptr() + q0 * 8, status.data_ptr() + q0 * 4, ws.data_ptr(), ws.numel(), st)
                 if scale_c is None:
                     rc = (L.tsim_cosine_range_scan if tau_q is None else L.tsim_cosine_range_scan_tau)(*head, rho_p, *tail)
+                elif l2:
+                    rc = (L.tsim_l2_range_scan if tau_q is None else L.tsim_l2_range_scan_tau)(*head, scale_c.data_ptr(), rho_p, *tail)
                 else:
                     rc = (L.tsim_dot_range_scan if tau_q is None else L.tsim_dot_range_scan_tau)(*head, scale_c.data_ptr(), rho_p, *tail)
                 _lib.check(rc, what)
@@ -478,7 +485,27 @@ def dot_range(eq_unit: torch.Tensor, ec_scaled: torch.Tensor, d: int, threshold,
                   return_status)
 
 
-def range_merge(results, total: Optional[int] = None):
+def l2_range(eq_aug: torch.Tensor, ec_aug: torch.Tensor, d: int, threshold, eq_f32: torch.Tensor, ec_f32: torch.Tensor,
+             rho_c: torch.Tensor, scale_c: torch.Tensor, idx_offset: int = 0, return_status: bool = False):
+    """Exact range search by Euclidean distance: EVERY corpus row whose SQUARED distance to a query is <= ``threshold`` (the
+    radius of faiss' ``range_search`` in the L2 space, which is on the squared distance too), the distance being exactly the
+    float32 value :func:`l2_topk` returns for the pair.  Returns ``(lims int64 [Q+1], dist2 float32 [T], idx int64 [T])`` in the
+    CSR layout of :func:`cosine_range`, every segment ordered by (distance asc, index asc); ``return_status`` adds int32 [Q] with
+    the same meaning.  The comparison is ``<=`` (the counterpart of ``>=`` in the other spaces); faiss compares with ``<``, so a
+    row AT the radius is a hit here and not there.  ``eq_aug``: :func:`l2_query_rows` of ``eq_f32`` under ``scale_c``;
+    ``(ec_aug, rho_c, scale_c)``: :func:`l2_rows` of ``ec_f32``; all are required; d <= 767.
+    ``threshold``: a float, or a tensor / array [Q], under the rules of :func:`cosine_range`.  A negative radius hits nothing, 0
+    exactly the rows equal to the query, ``+inf`` every row (through the exact pass, status 2); a NaN in an array gives that query
+    no hit and status 2.  Nothing is truncated.  Known: a corpus whose norms spread over decades (or one clustered far from the
+    origin) puts every row inside the guard's window; such queries end in the exact pass — exact but slow."""
+    if eq_f32 is None or ec_f32 is None or rho_c is None or scale_c is None:
+        raise ValueError("l2_range needs eq_f32, ec_f32 and the corpus rows' rho_c and scale_c (l2_rows)")
+    _l2_dim(d, "l2_range")
+    return _range("l2_range", _lib.SPACE_L2, eq_aug, ec_aug, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset,
+                  return_status)
+
+
+def range_merge(results, total: Optional[int] = None, ascending: bool = False):
     """Merge range results of the SAME queries over disjoint row sets (corpus shards or chunks searched with their own
     ``idx_offset``): ``results`` is a sequence of ``(lims [Q+1], scores [T_r], idx [T_r])`` as :func:`cosine_range` returns them
     (a payload may be longer than ``lims[-1]``, e.g. padded for an exchange; the excess is ignored), the return value one such
@@ -486,7 +513,8 @@ def range_merge(results, total: Optional[int] = None):
     the concatenated rows returns, bit for bit.  One kernel (tsim_range_merge): each entry finds its place by binary search in
     the other lists' segments, so segments may be of any length.  1 <= len(results) <= 64; one list comes back as a copy.
     ``total``: the number of entries over all lists when the caller knows it on the host (the sum of ``lims[-1]``); without it
-    the total is read back once."""
+    the total is read back once.  ``ascending``: the segments are ordered by (score asc, index asc) — the squared distances of
+    :func:`l2_range` — and so is the result (tsim_range_merge_asc)."""
     results = [tuple(r) for r in results]
     R = len(results)
     if not 1 <= R <= _lib.RANGE_MERGE_MAX_LISTS:
@@ -515,8 +543,9 @@ def range_merge(results, total: Optional[int] = None):
         s_in = (results[0][1] if R == 1 else torch.cat([r[1] for r in results])).contiguous()
         i_in = (results[0][2] if R == 1 else torch.cat([r[2] for r in results])).contiguous()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().tsim_range_merge(lims_in.data_ptr(), s_in.data_ptr(), i_in.data_ptr(), R, Q,
-                                                   lims_out.data_ptr(), T, out_s.data_ptr(), out_i.data_ptr(), _stream(out_s)),
+            merge = _lib.lib().tsim_range_merge_asc if ascending else _lib.lib().tsim_range_merge
+            _lib.check(merge(lims_in.data_ptr(), s_in.data_ptr(), i_in.data_ptr(), R, Q,
+                             lims_out.data_ptr(), T, out_s.data_ptr(), out_i.data_ptr(), _stream(out_s)),
                        "range_merge")
     return lims_out, out_s, out_i
 

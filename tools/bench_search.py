@@ -4,15 +4,18 @@
 
 --score cosine (default): tsim_cosine_topk on unit rows.  --score dot: tsim_dot_topk_ex on the float32 rows (corpus scaled by
 one power of two, dot_scaled_rows), which also reports the per-pass status counts.  --score l2: tsim_l2_topk_ex (squared
-Euclidean distance; half rows one element wider, l2_rows / l2_query_rows; top-k only).  --prep: also time the corpus row
+Euclidean distance; half rows one element wider, l2_rows / l2_query_rows).  --prep: also time the corpus row
 preparation (dot_scaled_rows / l2_rows) and print it.  --spread: corpus row norms spread
 log-uniformly over two decades (dot and l2; the default rows are Gaussian).  --k: the k values to time (default 10; up to 1024,
 k > 64 runs the _large entries); one line per (Q, k).
---range TAU ...: time the exact range search (ops.cosine_range / ops.dot_range on the float32 rows) at these thresholds instead of
-top-k: ms per call (scan + the host read of the total + fill), mean hits per query and the status counts; one line per (Q, tau).
+--range TAU ...: time the exact range search (ops.cosine_range / ops.dot_range / ops.l2_range on the float32 rows) at these
+thresholds (l2: squared radii) instead of top-k: ms per call (scan + the host read of the total + fill), mean hits per query and the status counts; one line per (Q, tau).
 --range-hits H ...: the same with tau derived from the normal tail so that about H of the N Gaussian rows pass per query (a cosine
-of Gaussian rows is ~ N(0, 1/d), an inner product ~ N(0, d)); the achieved mean is printed.
+of Gaussian rows is ~ N(0, 1/d), an inner product ~ N(0, d)); the achieved mean is printed.  --score l2: the radius is the
+median over a sample of 64 queries of their H-th smallest squared distance (ops.l2_topk over the whole corpus).
 --tau-array: pass the threshold of a range run as a per-query tensor [Q] holding that one value (the _tau entries) instead of a float.
+With --score l2 --range-hits the tensor holds every query's OWN H-th smallest squared distance instead (one radius hits very
+different numbers of rows for queries of different norm: dist^2 ~ |q|^2 + |c|^2), so every query has H hits.
 --range-merge R Q HITS: time ops.range_merge alone on R synthetic lists of Q queries x HITS sorted entries each (no corpus is made)."""
 import argparse
 import json
@@ -74,8 +77,6 @@ if a.range_merge:
 cf = torch.randn((N, d), generator=g, device=dev)
 if a.spread:
     cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
-if a.score == "l2" and (a.taus or a.range_hits):
-    sys.exit("--score l2 has no range search")
 if a.score in ("dot", "l2"):
     rows_fn = ops.dot_scaled_rows if a.score == "dot" else ops.l2_rows
     corpus, rho, scale = rows_fn(cf)
@@ -86,15 +87,30 @@ else:
     corpus, rho = ops.l2norm_rows(cf, return_rho=True)
     if not (a.taus or a.range_hits):
         del cf
-taus = list(a.taus) + [statistics.NormalDist().inv_cdf(1.0 - h / N) * (d ** 0.5 if a.score == "dot" else d ** -0.5) for h in a.range_hits]
+own_k = {}     # l2 --range-hits: the H behind a derived radius
+if a.score == "l2":
+    taus = list(a.taus)
+    if a.range_hits:
+        sf = torch.randn((64, d), generator=torch.Generator(device=dev).manual_seed(99), device=dev)
+        for h in a.range_hits:
+            kh = max(1, min(int(round(h)), ops.MAX_K, N))
+            kth = ops.l2_topk(ops.l2_query_rows(sf, scale), corpus, d, kh, eq_f32=sf, ec_f32=cf, rho_c=rho, scale_c=scale)[0][:, kh - 1]
+            taus.append(float(kth.median()))
+            own_k[taus[-1]] = kh
+else:
+    taus = list(a.taus) + [statistics.NormalDist().inv_cdf(1.0 - h / N) * (d ** 0.5 if a.score == "dot" else d ** -0.5) for h in a.range_hits]
 
 
 for Q, tau in [(Q, tau) for Q in (Qs if taus else []) for tau in taus]:
     qf = torch.randn((Q, d), generator=g, device=dev)
-    q = ops.l2norm_rows(qf)
+    q = ops.l2_query_rows(qf, scale) if a.score == "l2" else ops.l2norm_rows(qf)
     thr = torch.full((Q,), tau, dtype=torch.float32, device=dev) if a.tau_array else tau
+    if a.tau_array and tau in own_k:
+        thr = ops.l2_topk(q, corpus, d, own_k[tau], eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale)[0][:, own_k[tau] - 1].contiguous()
 
     def run():
+        if a.score == "l2":
+            return ops.l2_range(q, corpus, d, thr, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=True)
         if a.score == "dot":
             return ops.dot_range(q, corpus, d, thr, eq_f32=qf, ec_f32=cf, rho_c=rho, scale_c=scale, return_status=True)
         return ops.cosine_range(q, corpus, d, thr, eq_f32=qf, ec_f32=cf, rho_c=rho, return_status=True)
