@@ -38,6 +38,9 @@ extern "C" {
 
 #define TSIM_ARCH_BERT 0
 #define TSIM_ARCH_MPNET 1
+/* the BERT graph with MPNet's position rule: rows pad_id+1 .. pad_id+len, one token-type row added to every token
+ * (HF RobertaModel, XLMRobertaModel, CamembertModel).  DistilBERT is TSIM_ARCH_BERT with type_emb == NULL. */
+#define TSIM_ARCH_ROBERTA 2
 
 int tsim_version(void);
 const char *tsim_last_error(void);
@@ -402,9 +405,9 @@ int tsim_gemm_mxfp8(const void *xq, const void *xs, const void *wq, const void *
                     int M, int N, int K, void *stream);
 
 typedef struct tsim_encoder_config {
-    int32_t arch;          /* TSIM_ARCH_BERT | TSIM_ARCH_MPNET */
+    int32_t arch;          /* TSIM_ARCH_BERT | TSIM_ARCH_MPNET | TSIM_ARCH_ROBERTA */
     int32_t num_layers, hidden, heads, ffn, vocab, max_pos;
-    int32_t pad_id;        /* MPNet: position ids skip tokens equal to pad_id */
+    int32_t pad_id;        /* MPNet, RoBERTa: position ids skip tokens equal to pad_id */
     int32_t rel_buckets;   /* MPNet relative-position buckets (32) */
     float ln_eps;
     int32_t max_tokens;    /* capacity of the activation workspace, in packed tokens per call */
@@ -420,7 +423,7 @@ typedef struct tsim_layer_weights_host {
 } tsim_layer_weights_host;
 
 typedef struct tsim_encoder_weights_host {
-    const float *word_emb, *pos_emb, *type_emb /* row 0 (tsim_encoder_set_token_types: all rows); NULL for MPNet */,
+    const float *word_emb, *pos_emb, *type_emb /* row 0 (tsim_encoder_set_token_types: all rows); NULL for MPNet and DistilBERT */,
         *emb_ln_g, *emb_ln_b;
     const float *rel_bias;
     const tsim_layer_weights_host *layers;
@@ -433,8 +436,8 @@ void tsim_encoder_destroy(tsim_encoder *enc);
 /* Forward on PACKED tokens (no padding work): token t of sequence b lives at cu_seqlens[b] <= t <
  * cu_seqlens[b+1]; tok_ids/tok_pos int32 [T] (tok_pos = position-embedding row, tok_col = column of the
  * token in the padded batch, used for MPNet's relative bias; pass tok_col = NULL to use tok_pos).
- * max_len = the longest sequence of the batch (sizes the attention grid); max_len (+ pad_id + 1 for MPNet, whose position
- * rows start there) must not exceed max_pos, else TSIM_EINVAL.
+ * max_len = the longest sequence of the batch (sizes the attention grid); max_len (+ pad_id + 1 for MPNet and RoBERTa, whose
+ * position rows start there) must not exceed max_pos, else TSIM_EINVAL.
  * Outputs (either may be NULL): pooled_f32 [B, hidden] = masked mean-pool (A4), un-normalised like the
  * reference's encode_text; unit_f16 [B, ld_unit] = L2-normalised half rows ready for tsim_cosine_topk, with
  * unit_rho_max (device float, may be NULL) raised to their largest rounding residual exactly as tsim_l2norm_rows does;
@@ -459,6 +462,11 @@ int tsim_encoder_set_token_types(tsim_encoder *enc, const float *type_emb_host, 
  * reads a zero CLS row. */
 int tsim_encoder_set_cls_head(tsim_encoder *enc, const float *pool_w_host, const float *pool_b_host,
                               const float *cls_w_host, const float *cls_b_host, int32_t num_labels);
+/* The same head with the activation between its two layers chosen: act = TSIM_ACT_TANH (tsim_encoder_set_cls_head; also HF
+ * RobertaClassificationHead: classifier.dense, tanh, classifier.out_proj) or TSIM_ACT_RELU (HF
+ * DistilBertForSequenceClassification: pre_classifier, ReLU, classifier).  hidden <= 1024. */
+int tsim_encoder_set_cls_head_act(tsim_encoder *enc, const float *pool_w_host, const float *pool_b_host,
+                                  const float *cls_w_host, const float *cls_b_host, int32_t num_labels, int32_t act);
 /* tsim_encoder_forward plus tok_type int32 [T] (token-type row of each token; NULL = all 0, bit-identical to
  * tsim_encoder_forward) and logits_f32 [B, num_labels] (NULL = no head).  logits_f32 without a head, or tok_type without a
  * type table: TSIM_EINVAL.  A type id outside [0, n_types) is clamped and raises TSIM_ENC_ERR_TOKEN_TYPE. */
@@ -491,6 +499,7 @@ int tsim_encoder_forward_ex(tsim_encoder *enc, const int32_t *tok_ids, const int
 #define TSIM_POOL_MEAN_SQRT_LEN 3
 #define TSIM_ACT_IDENTITY 0
 #define TSIM_ACT_TANH 1
+#define TSIM_ACT_RELU 2 /* classification heads only (tsim_encoder_set_cls_head_act); a Dense refuses it */
 typedef struct tsim_sentence_head {
     int32_t pool_mode;               /* TSIM_POOL_* */
     int32_t d_out;                   /* 0 = no Dense */

@@ -10,10 +10,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSIM_LIB") or os.path.join(_HERE, "libtsim.so")   # TSIM_LIB: a variant build (build.py TSIM_BUILD_TAG)
 
 TSIM_F32, TSIM_BF16 = 0, 1
-ARCH_BERT, ARCH_MPNET = 0, 1
+ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
 W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
-ACT_IDENTITY, ACT_TANH = 0, 1
+ACT_IDENTITY, ACT_TANH, ACT_RELU = 0, 1, 2
 SPACE_COSINE, SPACE_DOT, SPACE_L2 = 0, 1, 2
 ENC_ERR_SPAN = 16                # include/tsim.h TSIM_ENC_ERR_SPAN
 RANGE_SLOT_CAP = 2048            # include/tsim.h TSIM_RANGE_SLOT_CAP
@@ -144,6 +144,7 @@ _SIGS = {
                                        C.c_void_p]),
     "tsim_encoder_set_token_types": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "tsim_encoder_set_cls_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "tsim_encoder_set_cls_head_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "tsim_encoder_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),

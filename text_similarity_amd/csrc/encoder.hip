@@ -1,4 +1,4 @@
-// Transformer encoder forward for gfx950 (MI355X) on PACKED tokens: BERT and MPNet families.
+// Transformer encoder forward for gfx950 (MI355X) on PACKED tokens: BERT (DistilBERT, RoBERTa / XLM-R / CamemBERT) and MPNet families.
 //
 // Replaces `context_embedder(**features)[0]` + mean-pool of the reference
 // (/root/reference/src/models/sentence_encoder.py:33-38; layer arithmetic as stated in
@@ -1281,6 +1281,7 @@ __global__ __launch_bounds__(256) void pool_packed_kernel(const bf16_t *__restri
 // =====================================================================================================
 constexpr int CLS_ROWS = 8;
 constexpr int CLS_MAX_H = 768;
+constexpr int CLS_WIDE_H = 1024;   // hidden-1024 encoders: an instance of their own (the launch bound fixes the register budget)
 constexpr int CLS_MAX_LABELS = 32;
 
 __global__ __launch_bounds__(CLS_MAX_H) void cls_head_kernel(const bf16_t *__restrict__ x, const int32_t *__restrict__ cu,
@@ -1322,6 +1323,64 @@ __global__ __launch_bounds__(CLS_MAX_H) void cls_head_kernel(const bf16_t *__res
     const float bj = bp[j];
 #pragma unroll
     for (int r = 0; r < CLS_ROWS; ++r) ps[r][j] = tanhf(acc[r] + bj);
+    __syncthreads();
+    const int lane = j & 63, wave = j >> 6, n_waves = H >> 6;
+    const int n_out = CLS_ROWS * n_labels;
+    for (int o = wave; o < n_out; o += n_waves) {   // wave-uniform
+        const int r = o / n_labels, c = o - r * n_labels;
+        const int b = b0 + r;
+        if (b >= B) break;   // o grows with r: every later output of this wave is past B as well
+        float s = 0.f;
+        for (int i = lane; i < H; i += 64) s = fmaf(wc[(int64_t)c * H + i], ps[r][i], s);
+        s = wave_sum(s);
+        if (lane == 0) logits[(int64_t)b * n_labels + c] = s + bc[c];
+    }
+}
+
+// The same head for hidden 1024 (1 024 threads; MAXH sits in the launch bound) and for the ReLU between the two layers
+// (ACT = TSIM_ACT_RELU, DistilBERT's pre_classifier; TSIM_ACT_TANH also serves RoBERTa's classifier.dense).  A copy, not a
+// shared body: the instance above keeps its instructions (through a shared inline body hipcc schedules its index arithmetic
+// differently).
+template <int MAXH, int ACT>
+__global__ __launch_bounds__(MAXH) void cls_head_wide_kernel(const bf16_t *__restrict__ x, const int32_t *__restrict__ cu,
+                                                             int B, int H, const float *__restrict__ wpT,
+                                                             const float *__restrict__ bp, const float *__restrict__ wc,
+                                                             const float *__restrict__ bc, int n_labels,
+                                                             float *__restrict__ logits) {
+    __shared__ __attribute__((aligned(16))) float xs[MAXH][CLS_ROWS];   // CLS rows, [feature][row]
+    __shared__ float ps[CLS_ROWS][MAXH];                               // pooled rows
+    const int j = threadIdx.x;   // blockDim.x == H
+    const int b0 = blockIdx.x * CLS_ROWS;
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) {
+        const int b = b0 + r;
+        float v = 0.f;
+        if (b < B) {
+            const int t0 = cu[b];
+            if (cu[b + 1] > t0) v = bf16_to_f32(x[(int64_t)t0 * H + j]);
+        }
+        xs[j][r] = v;
+    }
+    __syncthreads();
+    float acc[CLS_ROWS];
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += 8) {   // H % 64 == 0
+        float w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[u] = wpT[(int64_t)(k0 + u) * H + j];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float4 lo = *reinterpret_cast<const float4 *>(&xs[k0 + u][0]);
+            const float4 hi = *reinterpret_cast<const float4 *>(&xs[k0 + u][4]);
+            const float xv[CLS_ROWS] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int r = 0; r < CLS_ROWS; ++r) acc[r] = fmaf(w[u], xv[r], acc[r]);
+        }
+    }
+    const float bj = bp[j];
+#pragma unroll
+    for (int r = 0; r < CLS_ROWS; ++r) ps[r][j] = ACT == TSIM_ACT_RELU ? fmaxf(acc[r] + bj, 0.f) : tanhf(acc[r] + bj);
     __syncthreads();
     const int lane = j & 63, wave = j >> 6, n_waves = H >> 6;
     const int n_out = CLS_ROWS * n_labels;
@@ -1516,6 +1575,7 @@ struct tsim_encoder {
     // sequence-classification head (tsim_encoder_set_cls_head), float32: W_p transposed [in][out], b_p, W_c [labels][H], b_c
     float *head_wpT = nullptr, *head_bp = nullptr, *head_wc = nullptr, *head_bc = nullptr;
     int n_labels = 0;
+    int head_act = TSIM_ACT_TANH;   // TSIM_ACT_TANH | TSIM_ACT_RELU (tsim_encoder_set_cls_head_act)
     struct Layer {
         bf16_t *wqkv, *wo, *w1, *w2;
         bf16_t *pqkv = nullptr, *po = nullptr;     // tile-major copies for the ping-pong GEMM (QKV and O-projection)
@@ -2034,12 +2094,12 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
                                    tsim_encoder **out) {
     TSIM_REQUIRE(cfg && w && out, "encoder_create: null pointer");
     const int H = cfg->hidden, F = cfg->ffn, L = cfg->num_layers;
-    TSIM_REQUIRE(H == 64 || H == 384 || H == 768, "encoder_create: hidden=%d unsupported (64, 384, 768)", H);
+    TSIM_REQUIRE(H == 64 || H == 384 || H == 768 || H == 1024, "encoder_create: hidden=%d unsupported (64, 384, 768, 1024)", H);
     TSIM_REQUIRE(cfg->heads > 0 && H % cfg->heads == 0, "encoder_create: heads=%d does not divide hidden=%d", cfg->heads, H);
     const int dh = H / cfg->heads;
     TSIM_REQUIRE(dh == 16 || dh == 32 || dh == 64, "encoder_create: head_dim=%d unsupported (16, 32, 64)", dh);
     TSIM_REQUIRE(F % 64 == 0 && L > 0 && cfg->max_tokens > 0 && cfg->max_seqs > 0, "encoder_create: bad ffn/layers/capacity");
-    TSIM_REQUIRE(cfg->arch == TSIM_ARCH_BERT || cfg->arch == TSIM_ARCH_MPNET, "encoder_create: unknown arch");
+    TSIM_REQUIRE(cfg->arch == TSIM_ARCH_BERT || cfg->arch == TSIM_ARCH_MPNET || cfg->arch == TSIM_ARCH_ROBERTA, "encoder_create: unknown arch");
     TSIM_REQUIRE(w->word_emb && w->pos_emb && w->emb_ln_g && w->emb_ln_b && w->layers, "encoder_create: missing weights");
     TSIM_REQUIRE(cfg->arch != TSIM_ARCH_MPNET || w->rel_bias, "encoder_create: MPNet needs rel_bias");
     const bool mx = cfg->weight_dtype == TSIM_W_MXFP8;
@@ -2200,7 +2260,7 @@ extern "C" void tsim_encoder_destroy(tsim_encoder *e) {
 
 extern "C" int tsim_encoder_set_token_types(tsim_encoder *e, const float *type_emb_host, int32_t n_types) {
     TSIM_REQUIRE(e && type_emb_host, "encoder_set_token_types: null pointer");
-    TSIM_REQUIRE(e->cfg.arch == TSIM_ARCH_BERT, "encoder_set_token_types: BERT only (MPNet has no token-type table)");
+    TSIM_REQUIRE(e->cfg.arch != TSIM_ARCH_MPNET, "encoder_set_token_types: BERT only (MPNet has no token-type table)");
     TSIM_REQUIRE(n_types >= 1, "encoder_set_token_types: n_types=%d < 1", n_types);
     float *tab = nullptr;
     if (int rc = upload_f32(e, type_emb_host, (size_t)n_types * e->cfg.hidden, &tab)) return rc;
@@ -2211,12 +2271,18 @@ extern "C" int tsim_encoder_set_token_types(tsim_encoder *e, const float *type_e
 
 extern "C" int tsim_encoder_set_cls_head(tsim_encoder *e, const float *pool_w_host, const float *pool_b_host,
                                          const float *cls_w_host, const float *cls_b_host, int32_t num_labels) {
+    return tsim_encoder_set_cls_head_act(e, pool_w_host, pool_b_host, cls_w_host, cls_b_host, num_labels, TSIM_ACT_TANH);
+}
+
+extern "C" int tsim_encoder_set_cls_head_act(tsim_encoder *e, const float *pool_w_host, const float *pool_b_host,
+                                             const float *cls_w_host, const float *cls_b_host, int32_t num_labels, int32_t act) {
     TSIM_REQUIRE(e && pool_w_host && pool_b_host && cls_w_host && cls_b_host, "encoder_set_cls_head: null pointer");
-    TSIM_REQUIRE(e->cfg.arch == TSIM_ARCH_BERT, "encoder_set_cls_head: BERT only");
+    TSIM_REQUIRE(e->cfg.arch != TSIM_ARCH_MPNET, "encoder_set_cls_head: BERT only");
+    TSIM_REQUIRE(act == TSIM_ACT_TANH || act == TSIM_ACT_RELU, "encoder_set_cls_head: activation %d (TSIM_ACT_TANH, TSIM_ACT_RELU)", act);
     TSIM_REQUIRE(num_labels >= 1 && num_labels <= CLS_MAX_LABELS, "encoder_set_cls_head: num_labels=%d outside [1, %d]", num_labels,
                  CLS_MAX_LABELS);
     const int H = e->cfg.hidden;
-    TSIM_REQUIRE(H % 64 == 0 && H <= CLS_MAX_H, "encoder_set_cls_head: hidden=%d unsupported", H);
+    TSIM_REQUIRE(H % 64 == 0 && H <= CLS_WIDE_H, "encoder_set_cls_head: hidden=%d unsupported", H);
     std::vector<float> wT((size_t)H * H);
     for (int o = 0; o < H; ++o)
         for (int k = 0; k < H; ++k) wT[(size_t)k * H + o] = pool_w_host[(size_t)o * H + k];
@@ -2226,6 +2292,7 @@ extern "C" int tsim_encoder_set_cls_head(tsim_encoder *e, const float *pool_w_ho
     if ((rc = upload_f32(e, cls_w_host, (size_t)num_labels * H, &e->head_wc))) return rc;
     if ((rc = upload_f32(e, cls_b_host, num_labels, &e->head_bc))) return rc;
     e->n_labels = num_labels;
+    e->head_act = act;
     return TSIM_OK;
 }
 
@@ -2248,12 +2315,13 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
                  "(tsim_encoder_set_cls_head)");
     TSIM_REQUIRE(T >= 0 && B >= 0 && T <= e->cfg.max_tokens && B <= e->cfg.max_seqs,
                  "encoder_forward: T=%d B=%d exceed capacity (%d tokens, %d sequences)", T, B, e->cfg.max_tokens, e->cfg.max_seqs);
-    // position rows: BERT uses 0 .. len-1, MPNet pad_id+1 .. pad_id+len (modeling_mpnet create_position_ids_from_input_ids)
-    const int pos_span = max_len + (e->cfg.arch == TSIM_ARCH_MPNET ? e->cfg.pad_id + 1 : 0);
+    // position rows: BERT uses 0 .. len-1, MPNet and RoBERTa pad_id+1 .. pad_id+len (create_position_ids_from_input_ids)
+    const int pos_span = max_len + (e->cfg.arch != TSIM_ARCH_BERT ? e->cfg.pad_id + 1 : 0);
     TSIM_REQUIRE(max_len >= 0 && pos_span <= e->cfg.max_pos,
                  "encoder_forward: sequences of %d tokens need position rows up to %d, the table has %d", max_len, pos_span - 1,
                  e->cfg.max_pos);
     TSIM_REQUIRE(!unit_bf16 || ld_unit >= e->cfg.hidden, "encoder_forward: ld_unit < hidden");
+    TSIM_REQUIRE(!unit_bf16 || e->cfg.hidden <= 768, "encoder_forward: unit rows need a width <= 768 (got %d)", e->cfg.hidden);
     if (B == 0) return TSIM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const tsim_encoder_config &c = e->cfg;
@@ -2264,12 +2332,12 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
         const unsigned g = (unsigned)((T + 3) / 4);
         // column of a token inside its sequence: tok_col when given (MPNet), else tok_pos (BERT: position == column)
         const int32_t *colp = tok_col ? tok_col : tok_pos;
-        const int col_limit = tok_col || c.arch == TSIM_ARCH_BERT ? max_len : c.max_pos;   // MPNet without tok_col: pos is not a column
+        const int col_limit = tok_col || c.arch == TSIM_ARCH_BERT ? max_len : c.max_pos;   // MPNet / RoBERTa without tok_col: pos is not a column
 #define EMBED(V) hipLaunchKernelGGL(embed_ln_kernel<V>, dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, nullptr, 0)
 #define EMBED_T(V) hipLaunchKernelGGL((embed_ln_kernel<V, true>), dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, tok_type, e->n_types)
         if (tok_type) {
-            if (H == 64) EMBED_T(1); else if (H == 384) EMBED_T(6); else EMBED_T(12);
-        } else if (H == 64) EMBED(1); else if (H == 384) EMBED(6); else EMBED(12);
+            if (H == 64) EMBED_T(1); else if (H == 384) EMBED_T(6); else if (H == 768) EMBED_T(12); else EMBED_T(16);
+        } else if (H == 64) EMBED(1); else if (H == 384) EMBED(6); else if (H == 768) EMBED(12); else EMBED(16);
 #undef EMBED_T
 #undef EMBED
         TSIM_HIP_CHECK(hipGetLastError());
@@ -2334,8 +2402,17 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
         TSIM_HIP_CHECK(hipGetLastError());
     }
     if (logits_f32) {   // CLS rows straight from the final hidden state (x0); sequences without tokens read zeros
-        hipLaunchKernelGGL(cls_head_kernel, dim3((unsigned)((B + CLS_ROWS - 1) / CLS_ROWS)), dim3((unsigned)H), 0, st, e->x0, cu_seqlens,
-                           B, H, e->head_wpT, e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32);
+        const dim3 cgrid((unsigned)((B + CLS_ROWS - 1) / CLS_ROWS)), cblock((unsigned)H);
+#define CLS_WIDE(MAXH, ACT)                                                                                       \
+    hipLaunchKernelGGL((cls_head_wide_kernel<MAXH, ACT>), cgrid, cblock, 0, st, e->x0, cu_seqlens, B, H, e->head_wpT, \
+                       e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32)
+        if (e->head_act == TSIM_ACT_RELU) {
+            if (H <= CLS_MAX_H) CLS_WIDE(CLS_MAX_H, TSIM_ACT_RELU); else CLS_WIDE(CLS_WIDE_H, TSIM_ACT_RELU);
+        } else if (H <= CLS_MAX_H) {
+            hipLaunchKernelGGL(cls_head_kernel, cgrid, cblock, 0, st, e->x0, cu_seqlens,
+                               B, H, e->head_wpT, e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32);
+        } else CLS_WIDE(CLS_WIDE_H, TSIM_ACT_TANH);
+#undef CLS_WIDE
         TSIM_HIP_CHECK(hipGetLastError());
     }
     return TSIM_OK;

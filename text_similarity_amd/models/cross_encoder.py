@@ -12,6 +12,12 @@ Pairs are tokenised as the library would tokenise them (``tokenizer(list_a, list
 ``[CLS] a [SEP] b [SEP]``, token types 0 then 1, ``longest_first`` truncation) without tokenising Q x k pairs: every
 unique string goes once, untruncated, through the single-sentence path (``_tokenize_packed``: native WordPiece for ASCII, the
 library for the rest), and the pairs are assembled from those ids in numpy (``PairTokenizer``).  BERT only: MPNet has no token types.
+
+The BERT graph also carries ``DistilBertForSequenceClassification`` (``pre_classifier``, ReLU, ``classifier``) and
+``RobertaForSequenceClassification`` / ``XLMRobertaForSequenceClassification`` / ``CamembertForSequenceClassification``
+(``classifier.dense``, tanh, ``classifier.out_proj``): the same two-layer head on the first token's row.  These models have no
+row for token type 1, so no type ids are sent; a tokenizer whose pair template is not BERT's (BPE and SentencePiece
+tokenizers: ``<s> a </s></s> b </s>``) encodes the pairs itself (``LibraryPairTokenizer``).
 """
 from __future__ import annotations
 
@@ -29,6 +35,14 @@ from .sentence_encoder import _tokenize_packed
 
 _ACTIVATIONS = {"Sigmoid": torch.nn.Sigmoid, "Identity": torch.nn.Identity}
 _HEAD = ("pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias")
+_ROBERTA_HEAD = ("classifier.dense.weight", "classifier.dense.bias", "classifier.out_proj.weight", "classifier.out_proj.bias")
+_DISTIL_HEAD = ("pre_classifier.weight", "pre_classifier.bias", "classifier.weight", "classifier.bias")
+# HF model_type -> (the architecture a checkpoint must name, its head tensors [first layer w, b, second layer w, b], activation)
+_SEQ_CLS = {"bert": ("BertForSequenceClassification", _HEAD, "tanh"),
+            "distilbert": ("DistilBertForSequenceClassification", _DISTIL_HEAD, "relu"),
+            "roberta": ("RobertaForSequenceClassification", _ROBERTA_HEAD, "tanh"),
+            "xlm-roberta": ("XLMRobertaForSequenceClassification", _ROBERTA_HEAD, "tanh"),
+            "camembert": ("CamembertForSequenceClassification", _ROBERTA_HEAD, "tanh")}
 
 
 def longest_first(la: np.ndarray, lb: np.ndarray, budget: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -55,6 +69,10 @@ def _spans(starts: np.ndarray, counts: np.ndarray) -> np.ndarray:
     return np.repeat(np.asarray(starts, np.int64) - excl, counts) + np.arange(n, dtype=np.int64)
 
 
+class PairTemplateError(ValueError):
+    """The tokenizer's single-sentence or pair template is not BERT's (no [CLS] / [SEP], or another arrangement)."""
+
+
 class PairTokenizer:
     """(query, text) pairs -> packed ids, token types and lengths, equal to the library's pair encoding.
     Built from a BERT tokenizer; raises ValueError when the tokenizer's single / pair templates are not BERT's
@@ -63,7 +81,8 @@ class PairTokenizer:
     NO_TRUNCATION = 1 << 30
     PROBE = ("the first segment of a probe pair", "and the second, somewhat longer, segment of the same probe pair")
 
-    def __init__(self, tokenizer, max_length: int, batch_size: int = 2048):
+    def __init__(self, tokenizer, max_length: int, batch_size: int = 2048, typed: bool = True):
+        """``typed`` False: the model has no row for token type 1 (DistilBERT), so the library's type ids are not compared."""
         self.tokenizer = tokenizer
         self.max_length = int(max_length)
         self.batch_size = int(batch_size)
@@ -71,14 +90,14 @@ class PairTokenizer:
             raise ValueError(f"max_length={max_length}: a pair needs 3 special tokens and at least one text token")
         self.cls_id, self.sep_id = tokenizer.cls_token_id, tokenizer.sep_token_id
         if self.cls_id is None or self.sep_id is None:
-            raise ValueError("the tokenizer has no [CLS] / [SEP] tokens: not a BERT tokenizer")
+            raise PairTemplateError("the tokenizer has no [CLS] / [SEP] tokens: not a BERT tokenizer")
         for L in (self.max_length, 9):   # once without truncation (for short probes), once through longest_first
             ref = tokenizer([self.PROBE[0]], [self.PROBE[1]], truncation=True, max_length=L)
             ids, types, lens = self(([self.PROBE[0], self.PROBE[1]],), max_length=L)
-            if list(ids) != list(ref["input_ids"][0]) or list(types) != list(ref.get("token_type_ids", [[None]])[0]):
-                raise ValueError("the tokenizer's pair template is not BERT's [CLS] a [SEP] b [SEP] with token types 0 / 1 "
-                                 f"(library: {ref['input_ids'][0]} types {ref.get('token_type_ids')}; assembled: {list(ids)} "
-                                 f"types {list(types)})")
+            if list(ids) != list(ref["input_ids"][0]) or (typed and list(types) != list(ref.get("token_type_ids", [[None]])[0])):
+                raise PairTemplateError("the tokenizer's pair template is not BERT's [CLS] a [SEP] b [SEP] with token types 0 / 1 "
+                                        f"(library: {ref['input_ids'][0]} types {ref.get('token_type_ids')}; assembled: "
+                                        f"{list(ids)} types {list(types)})")
 
     def _segments(self, docs: List[str]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Each string once through the single-sentence path, specials stripped -> (flat ids, start, length).  Not
@@ -89,7 +108,7 @@ class PairTokenizer:
         np.cumsum(lens, out=cu[1:])
         if len(docs) and not ((flat[cu[:-1]] == self.cls_id).all() and (flat[cu[1:] - 1] == self.sep_id).all()
                               and (lens >= 2).all()):
-            raise ValueError("the tokenizer's single-sentence template is not BERT's [CLS] x [SEP]")
+            raise PairTemplateError("the tokenizer's single-sentence template is not BERT's [CLS] x [SEP]")
         return flat, cu[:-1] + 1, lens - 2
 
     def __call__(self, pairs: Sequence[Sequence[str]], max_length: Optional[int] = None
@@ -123,6 +142,33 @@ class PairTokenizer:
         return ids, types, lens
 
 
+class LibraryPairTokenizer:
+    """Pairs through the library tokenizer's own pair template, for tokenizers that are not BERT's (BPE, SentencePiece):
+    ``tokenizer(list_a, list_b, truncation=True, max_length=L)``.  Same result layout as :class:`PairTokenizer`; the token types
+    are all 0 (the models served have one token-type row or none)."""
+
+    def __init__(self, tokenizer, max_length: int, batch_size: int = 2048):
+        self.tokenizer, self.max_length, self.batch_size = tokenizer, int(max_length), int(batch_size)
+
+    def __call__(self, pairs: Sequence[Sequence[str]], max_length: Optional[int] = None
+                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        L = self.max_length if max_length is None else int(max_length)
+        flat: List[int] = []
+        lens: List[int] = []
+        for i, p in enumerate(pairs):
+            if len(p) != 2:
+                raise ValueError(f"pair {i} has {len(p)} texts; a cross-encoder scores [query, text] pairs")
+        for s in range(0, len(pairs), self.batch_size):
+            chunk = pairs[s:s + self.batch_size]
+            enc = self.tokenizer([p[0] for p in chunk], [p[1] for p in chunk], truncation=True, max_length=L, padding=False,
+                                 return_attention_mask=False, return_token_type_ids=False)
+            for ids in enc["input_ids"]:
+                flat.extend(ids)
+                lens.append(len(ids))
+        ids = np.asarray(flat, np.int32)
+        return ids, np.zeros(len(ids), np.int32), np.asarray(lens, np.int64)
+
+
 def _read_hf_config(path: str) -> dict:
     with open(os.path.join(path, "config.json")) as f:
         return json.load(f)
@@ -132,28 +178,31 @@ class CrossEncoder:
     def __init__(self, path_or_preset: str, num_labels: Optional[int] = None, max_length: Optional[int] = None,
                  device=None, default_activation_function=None, *, tokenizer=None, max_tokens: int = 65536,
                  max_seqs: int = 8192):
-        """``path_or_preset``: a LOCAL HF directory of a ``BertForSequenceClassification`` (config.json, model.safetensors
-        or pytorch_model.bin, tokenizer files), or a preset name of ``presets.PRESETS`` (BERT family) with ``tokenizer=``
+        """``path_or_preset``: a LOCAL HF directory of a ``BertForSequenceClassification`` or of its DistilBERT / RoBERTa /
+        XLM-R / CamemBERT counterpart (config.json, model.safetensors
+        or pytorch_model.bin, tokenizer files), or a preset name of ``presets.PRESETS`` (BERT graph) with ``tokenizer=``
         and synthetic weights (``synthetic_weights`` + ``synthetic_head_weights``; ``num_labels`` default 1).
-        ``max_length`` defaults to the tokenizer's ``model_max_length`` capped at the position table.
+        ``max_length`` defaults to the tokenizer's ``model_max_length`` and is capped at what the position table holds.
         ``max_tokens`` / ``max_seqs``: capacity of one encoder forward; ``predict`` splits larger inputs."""
         act_name = None
         if os.path.isdir(path_or_preset):
             from ..weights import load_hf_dir
             d = _read_hf_config(path_or_preset)
-            if d.get("model_type", "bert") != "bert":
+            if d.get("model_type", "bert") not in _SEQ_CLS:
                 raise ValueError(f"model_type {d.get('model_type')!r}: the cross-encoder supports BERT only "
                                  "(MPNet has no token types and a different pair template)")
-            if "BertForSequenceClassification" not in (d.get("architectures") or []):
+            want, head, head_act = _SEQ_CLS[d.get("model_type", "bert")]
+            if want not in (d.get("architectures") or []):
                 raise ValueError(f"architectures {d.get('architectures')}: a cross-encoder checkpoint is a "
-                                 "BertForSequenceClassification")
+                                 + ("BertForSequenceClassification" if want == _SEQ_CLS["bert"][0] else
+                                    f"{want} (the BertForSequenceClassification of {d['model_type']})"))
             n_ckpt = len(d["id2label"]) if d.get("id2label") else int(d.get("num_labels", 2))
             if num_labels is not None and int(num_labels) != n_ckpt:
                 raise ValueError(f"num_labels={num_labels}, the checkpoint has {n_ckpt}")
             num_labels = n_ckpt
             act_name = d.get("sbert_ce_default_activation_function")
             cfg, w = load_hf_dir(path_or_preset)
-            missing = [k for k in _HEAD if k not in w]
+            missing = [k for k in head if k not in w]
             if missing:
                 raise KeyError(f"{path_or_preset}: missing head weights {missing}")
             if tokenizer is None:
@@ -166,8 +215,9 @@ class CrossEncoder:
             if tokenizer is None:
                 raise ValueError("a preset needs tokenizer=: presets carry no vocabulary")
             num_labels = 1 if num_labels is None else int(num_labels)
+            want, head, head_act = _SEQ_CLS[cfg.source_type]
             w = synthetic_weights(path_or_preset)
-            w.update(synthetic_head_weights(path_or_preset, num_labels))
+            w.update(zip(head, synthetic_head_weights(path_or_preset, num_labels).values()))   # (drawn under BERT's names)
         else:
             raise ValueError(f"{path_or_preset!r} is neither a local directory nor a preset ({', '.join(PRESETS)})")
         self.config = cfg
@@ -175,7 +225,7 @@ class CrossEncoder:
         self.tokenizer = tokenizer
         if max_length is None:
             max_length = int(getattr(tokenizer, "model_max_length", cfg.max_pos) or cfg.max_pos)
-        self.max_length = min(int(max_length), cfg.max_pos)
+        self.max_length = min(int(max_length), cfg.max_pos - cfg.first_pos)   # (a 514-row RoBERTa table holds 512 tokens)
         if default_activation_function is not None:
             self.default_activation_function = default_activation_function
         elif act_name is not None:
@@ -185,12 +235,18 @@ class CrossEncoder:
             self.default_activation_function = _ACTIVATIONS[cls_name]()
         else:
             self.default_activation_function = torch.nn.Sigmoid() if self.num_labels == 1 else torch.nn.Identity()
-        self.pair_tokenizer = PairTokenizer(tokenizer, self.max_length)
+        typed = cfg.source_type == "bert"   # the others have no row for token type 1: no type ids are sent
+        try:
+            self.pair_tokenizer = PairTokenizer(tokenizer, self.max_length, typed=typed)
+        except PairTemplateError:
+            if typed:
+                raise
+            self.pair_tokenizer = LibraryPairTokenizer(tokenizer, self.max_length)
         enc_dev = torch.device(device) if device is not None else None
         if enc_dev is not None and enc_dev.type != "cuda":
             enc_dev = None
         self.model = NativeEncoder(cfg, w, max_tokens=max_tokens, max_seqs=max_seqs, device=enc_dev)
-        self.model.set_cls_head(*(w[k] for k in _HEAD))
+        self.model.set_cls_head(*(w[k] for k in head), act=head_act)
         self.device = self.model.device
         self.last_predict_stats: dict = {}
 
@@ -214,7 +270,7 @@ class CrossEncoder:
             if cu_h[e] - cu_h[s] > enc.max_tokens:
                 raise ValueError("a single pair exceeds the encoder token capacity")
             t0, t1 = int(cu_h[s]), int(cu_h[e])
-            r = enc.forward_packed(flat[t0:t1], cu[s:e + 1] - cu[s], types=types[t0:t1], pooled=False, logits=True,
+            r = enc.forward_packed(flat[t0:t1], cu[s:e + 1] - cu[s], types=types[t0:t1] if enc.n_types else None, pooled=False, logits=True,
                                    max_len=int(np.diff(cu_h[s:e + 1]).max()))
             outs.append(r["logits"])
             s = e

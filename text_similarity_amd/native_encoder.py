@@ -92,7 +92,7 @@ class NativeEncoder:
         self.config = SimpleNamespace(hidden_size=cfg.hidden, dim=cfg.hidden, num_hidden_layers=cfg.num_layers,
                                       num_attention_heads=cfg.heads, intermediate_size=cfg.ffn,
                                       vocab_size=cfg.vocab, max_position_embeddings=cfg.max_pos,
-                                      model_type=cfg.arch)
+                                      model_type=cfg.source_type)
         w = {k: _f32(v) for k, v in weights.items() if not k.endswith("position_ids")}
         keep = []
         layers = (_lib.LayerWeightsC * cfg.num_layers)()
@@ -113,14 +113,18 @@ class NativeEncoder:
         ew = _lib.EncoderWeightsC()
         ew.word_emb = _ptr(w["embeddings.word_embeddings.weight"])
         ew.pos_emb = _ptr(w["embeddings.position_embeddings.weight"])
-        if cfg.arch == "bert":
+        if cfg.arch == "bert" and cfg.type_vocab > 0:   # (DistilBERT has none; RoBERTa's single row is added to every token)
             ew.type_emb = _ptr(w["embeddings.token_type_embeddings.weight"])
         ew.emb_ln_g = _ptr(w["embeddings.LayerNorm.weight"])
         ew.emb_ln_b = _ptr(w["embeddings.LayerNorm.bias"])
         if cfg.arch == "mpnet":
             ew.rel_bias = _ptr(w["encoder.relative_attention_bias.weight"])
         ew.layers = layers
-        cc = _lib.EncoderConfigC(arch=_lib.ARCH_BERT if cfg.arch == "bert" else _lib.ARCH_MPNET,
+        if cfg.arch not in ("bert", "mpnet") or cfg.pos_offset not in (0, cfg.pad_id + 1) or (cfg.pos_offset and cfg.arch != "bert"):
+            raise ValueError(f"arch {cfg.arch!r} with pos_offset {cfg.pos_offset} (pad_id {cfg.pad_id}): position rows start "
+                             "at 0 (BERT, DistilBERT) or at pad_id + 1 (MPNet, RoBERTa family)")
+        arch = _lib.ARCH_MPNET if cfg.arch == "mpnet" else _lib.ARCH_ROBERTA if cfg.pos_offset else _lib.ARCH_BERT
+        cc = _lib.EncoderConfigC(arch=arch,
                                  num_layers=cfg.num_layers, hidden=cfg.hidden, heads=cfg.heads, ffn=cfg.ffn,
                                  vocab=cfg.vocab, max_pos=cfg.max_pos, pad_id=cfg.pad_id,
                                  rel_buckets=cfg.rel_buckets, ln_eps=cfg.ln_eps, max_tokens=self.max_tokens,
@@ -132,24 +136,32 @@ class NativeEncoder:
         self._h = handle
         self.n_types = 0
         self.num_labels = 0
-        if cfg.arch == "bert":   # the whole token-type table: sentence pairs use row 1 (untyped forwards keep adding row 0)
+        if cfg.source_type == "bert":   # the whole token-type table: sentence pairs use row 1 (untyped forwards keep adding row 0)
             tt = w["embeddings.token_type_embeddings.weight"]
             with torch.cuda.device(self.device):
                 _lib.check(_lib.lib().tsim_encoder_set_token_types(handle, _ptr(tt), tt.shape[0]), "encoder_set_token_types")
             self.n_types = int(tt.shape[0])
         self._weights_host = w  # float32 source weights: what save_pretrained writes (the handle holds bf16 / fp8 copies)
 
-    def set_cls_head(self, pool_w, pool_b, cls_w, cls_b) -> None:
+    def set_cls_head(self, pool_w, pool_b, cls_w, cls_b, act="tanh") -> None:
         """HF BertForSequenceClassification head: ``bert.pooler.dense`` (pool_w [H,H], pool_b [H]) and ``classifier``
-        (cls_w [num_labels,H], cls_b [num_labels]), float32, 1 <= num_labels <= 32.  BERT only."""
+        (cls_w [num_labels,H], cls_b [num_labels]), float32, 1 <= num_labels <= 32.  BERT only (its graph: not MPNet).
+        ``act``: 'tanh', or 'relu' for DistilBertForSequenceClassification's ``pre_classifier`` / ``classifier``; the RoBERTa
+        family's ``classifier.dense`` / ``classifier.out_proj`` is the tanh form."""
+        if act not in ("tanh", "relu"):
+            raise ValueError(f"classification-head activation {act!r} (tanh, relu)")
         pw, pb, cw, cb = (_f32(a) for a in (pool_w, pool_b, cls_w, cls_b))
         H = self.cfg.hidden
         n = cw.shape[0] if cw.ndim == 2 else 0
         if pw.shape != (H, H) or pb.shape != (H,) or cw.shape != (n, H) or cb.shape != (n,):
             raise ValueError(f"head shapes {pw.shape} {pb.shape} {cw.shape} {cb.shape} do not fit hidden={H}")
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().tsim_encoder_set_cls_head(self._h, _ptr(pw), _ptr(pb), _ptr(cw), _ptr(cb), n),
-                       "encoder_set_cls_head")
+            if act == "tanh":
+                _lib.check(_lib.lib().tsim_encoder_set_cls_head(self._h, _ptr(pw), _ptr(pb), _ptr(cw), _ptr(cb), n),
+                           "encoder_set_cls_head")
+            else:
+                _lib.check(_lib.lib().tsim_encoder_set_cls_head_act(self._h, _ptr(pw), _ptr(pb), _ptr(cw), _ptr(cb), n,
+                                                                    _lib.ACT_RELU), "encoder_set_cls_head")
         self.num_labels = n
 
     # ------------------------------------------------------------------ constructors
@@ -186,12 +198,12 @@ class NativeEncoder:
 
     @staticmethod
     def check_lengths(cfg: EncoderConfig, max_len: int) -> None:
-        """HF raises IndexError when a sequence needs a position row the table does not have: BERT rows 0..len-1, MPNet
-        rows pad_id+1..pad_id+len (max_pos 514 holds 512 tokens).  Raised here, before any launch."""
-        need = int(max_len) + (cfg.pad_id + 1 if cfg.arch == "mpnet" else 0)
+        """HF raises IndexError when a sequence needs a position row the table does not have: BERT rows 0..len-1, MPNet and
+        the RoBERTa family rows pad_id+1..pad_id+len (max_pos 514 holds 512 tokens).  Raised here, before any launch."""
+        need = int(max_len) + cfg.first_pos
         if need > cfg.max_pos:
             raise ValueError(f"sequences of {max_len} tokens need position rows up to {need - 1}; "
-                             f"{cfg.arch} table has {cfg.max_pos} (max {cfg.max_pos - need + int(max_len)} tokens)")
+                             f"{cfg.source_type} table has {cfg.max_pos} (max {cfg.max_pos - need + int(max_len)} tokens)")
 
     def check(self) -> None:
         """Raise if any forward since the last check saw an out-of-range token id / type id / position id or a sequence longer than
@@ -218,14 +230,15 @@ class NativeEncoder:
     def positions(self, flat_ids: torch.Tensor, cu: torch.Tensor, cols: Optional[torch.Tensor] = None
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
         """(position-embedding rows, padded-batch columns) for packed tokens.
-        BERT: row = column (bert_of_theseus.py:199-200).  MPNet: cumsum(ids != pad) * (ids != pad) + pad over the
-        tokens present (mpnet create_position_ids_from_input_ids)."""
+        BERT, DistilBERT: row = column (bert_of_theseus.py:199-200).  MPNet and the RoBERTa family: cumsum(ids != pad) *
+        (ids != pad) + pad over the tokens present (create_position_ids_from_input_ids), i.e. pad + 1 + column unless the
+        pad id occurs inside a sequence."""
         T = flat_ids.numel()
         seq_of = torch.repeat_interleave(torch.arange(cu.numel() - 1, device=cu.device), (cu[1:] - cu[:-1]).long(),
                                          output_size=T)
         if cols is None:
             cols = torch.arange(T, device=cu.device, dtype=torch.int32) - cu[seq_of.long()].to(torch.int32)
-        if self.cfg.arch == "bert":
+        if self.cfg.first_pos == 0:
             return cols.to(torch.int32), cols.to(torch.int32)
         ne = (flat_ids != self.cfg.pad_id).to(torch.int32)
         csum = torch.cumsum(ne, 0, dtype=torch.int32)
@@ -261,7 +274,7 @@ class NativeEncoder:
         if types is not None:
             ops._need_gpu(types)
             if self.n_types == 0:
-                raise ValueError(f"token type ids need a token-type table; {self.cfg.arch} has none")
+                raise ValueError(f"token type ids need a token-type table; {self.cfg.source_type} has none")
             types = types.to(torch.int32).contiguous()
             if types.numel() != T:
                 raise ValueError(f"types has {types.numel()} entries for {T} tokens")
@@ -369,7 +382,8 @@ class NativeEncoder:
         """HF AutoModel contract used by the wrappers: returns (last_hidden_state [B,S,H] float32,).
         Positions whose mask is 0 come back as zeros (the reference never reads them: the pooler multiplies
         by the mask, modules.py:165).  ``token_type_ids`` [B,S] (BERT) selects the token-type row of each token; None or
-        all zeros is the untyped forward."""
+        all zeros is the untyped forward; an architecture without a row for a non-zero id (MPNet, DistilBERT, the RoBERTa
+        family) refuses it."""
         ops._need_gpu(input_ids)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
@@ -381,12 +395,12 @@ class NativeEncoder:
                 raise ValueError(f"token_type_ids shape {tuple(token_type_ids.shape)} != input_ids shape {(B, S)}")
             ops._need_gpu(token_type_ids)
             types = token_type_ids[attention_mask.bool()].to(torch.int32)
-            if self.cfg.arch != "bert" and bool((types != 0).any()):
-                raise ValueError(f"{self.cfg.arch} has no token-type table: token_type_ids must be None or all zeros")
+            if self.n_types == 0 and bool((types != 0).any()):   # (RoBERTa's one row is row 0, added to every token)
+                raise ValueError(f"{self.cfg.source_type} has no token-type table: token_type_ids must be None or all zeros")
             if self.n_types == 0:
                 types = None
-        if self.cfg.arch == "mpnet":
-            # position ids come from input_ids over the WHOLE padded row (masked non-pad tokens count too)
+        if self.cfg.first_pos:
+            # MPNet, RoBERTa family: position ids come from input_ids over the WHOLE padded row (masked non-pad tokens count too)
             ne = (input_ids != self.cfg.pad_id).to(torch.int32)
             pos_full = torch.cumsum(ne, 1, dtype=torch.int32) * ne + self.cfg.pad_id
             pos = pos_full[attention_mask.bool()].to(torch.int32)

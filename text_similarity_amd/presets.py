@@ -24,7 +24,14 @@ _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 class EncoderConfig:
     """Shape of one encoder.  ``arch`` is "bert" (absolute positions, token-type 0 row added,
     /root/reference/src/models/bert_of_theseus.py:185-211) or "mpnet" (RoBERTa-style position ids,
-    one relative-position bias table shared by all layers; transformers mpnet/modeling_mpnet.py)."""
+    one relative-position bias table shared by all layers; transformers mpnet/modeling_mpnet.py).
+
+    Other source architectures run on the "bert" graph and say so in ``model_type`` (the HF ``model_type`` the weights came from
+    and are saved as; "" = the same as ``arch``):
+    "distilbert" has no token-type table (``type_vocab`` 0); "roberta", "xlm-roberta" and "camembert" add their single
+    token-type row to every token (``type_vocab`` 1) and read position row ``pos_offset + column`` with
+    ``pos_offset = pad_id + 1``, the rule of MPNet (a 514-row table holds 512 tokens).  Held in memory, every "bert"-graph
+    model uses BertModel's tensor names (``weights.load_hf_dir`` renames, ``weights.save_hf_dir`` names them back)."""
     arch: str
     num_layers: int
     hidden: int
@@ -36,6 +43,17 @@ class EncoderConfig:
     type_vocab: int = 2
     pad_id: int = 0
     rel_buckets: int = 32
+    pos_offset: int = 0
+    model_type: str = ""
+
+    @property
+    def source_type(self) -> str:
+        return self.model_type or self.arch
+
+    @property
+    def first_pos(self) -> int:
+        """Position row of a sequence's first token: 0 for BERT and DistilBERT, pad_id + 1 for MPNet and the RoBERTa family."""
+        return self.pad_id + 1 if self.arch == "mpnet" else self.pos_offset
 
     @property
     def head_dim(self) -> int:
@@ -53,6 +71,18 @@ PRESETS: Dict[str, EncoderConfig] = {
     # small shapes for golden fixtures / unit tests
     "tiny-bert": EncoderConfig("bert", 2, 64, 4, 128, 1000, 64, 1e-12),
     "tiny-mpnet": EncoderConfig("mpnet", 2, 64, 4, 128, 1000, 66, 1e-5, type_vocab=0, pad_id=1),
+    # source architectures on the BERT graph (tiny-bert / tiny-mpnet shapes, then public model-card shapes)
+    "tiny-distilbert": EncoderConfig("bert", 2, 64, 4, 128, 1000, 64, 1e-12, type_vocab=0, model_type="distilbert"),
+    "tiny-roberta": EncoderConfig("bert", 2, 64, 4, 128, 1000, 66, 1e-5, type_vocab=1, pad_id=1, pos_offset=2,
+                                  model_type="roberta"),
+    "distilbert-base-multilingual-cased": EncoderConfig("bert", 6, 768, 12, 3072, 119547, 512, 1e-12, type_vocab=0,
+                                                        model_type="distilbert"),
+    "xlm-roberta-base": EncoderConfig("bert", 12, 768, 12, 3072, 250002, 514, 1e-5, type_vocab=1, pad_id=1, pos_offset=2,
+                                      model_type="xlm-roberta"),
+    # hidden 1024 (head_dim 64): pooled float32 rows, heads, spans and logits; unit rows stay capped at 768
+    "bert-large": EncoderConfig("bert", 24, 1024, 16, 4096, 30522, 512, 1e-12),
+    "xlm-roberta-large": EncoderConfig("bert", 24, 1024, 16, 4096, 250002, 514, 1e-5, type_vocab=1, pad_id=1, pos_offset=2,
+                                       model_type="xlm-roberta"),
 }
 
 
@@ -110,12 +140,46 @@ def to_bf16_bits(x: np.ndarray) -> np.ndarray:
 
 
 # --------------------------------------------------------------------------- weights
-def weight_names(cfg: EncoderConfig) -> List[tuple]:
-    """(name, shape, kind) for every tensor of the encoder, HF naming."""
+_DISTIL_LAYER = {   # DistilBertModel module inside transformer.layer.N -> BertModel module inside encoder.layer.N
+    "attention.q_lin": "attention.self.query", "attention.k_lin": "attention.self.key",
+    "attention.v_lin": "attention.self.value", "attention.out_lin": "attention.output.dense",
+    "sa_layer_norm": "attention.output.LayerNorm", "ffn.lin1": "intermediate.dense", "ffn.lin2": "output.dense",
+    "output_layer_norm": "output.LayerNorm"}
+
+
+def _rename_layer(name: str, src: str, dst: str, table: Dict[str, str]) -> str:
+    if not name.startswith(src):
+        return name
+    n, _, rest = name[len(src):].partition(".")
+    module, _, leaf = rest.rpartition(".")
+    return f"{dst}{n}.{table.get(module, module)}.{leaf}"
+
+
+def bert_name(model_type: str, name: str) -> str:
+    """Tensor name of a source architecture's HF state_dict (prefix already stripped) -> the BertModel name held in memory
+    (weights.load_hf_dir; only DistilBertModel's differ)."""
+    if model_type == "distilbert":
+        return _rename_layer(name, "transformer.layer.", "encoder.layer.", _DISTIL_LAYER)
+    return name
+
+
+def source_name(model_type: str, name: str) -> str:
+    """The inverse of :func:`bert_name` (weights.save_hf_dir)."""
+    if model_type == "distilbert":
+        return _rename_layer(name, "encoder.layer.", "transformer.layer.", {v: k for k, v in _DISTIL_LAYER.items()})
+    return name
+
+
+def weight_names(cfg: EncoderConfig, source: bool = False) -> List[tuple]:
+    """(name, shape, kind) for every tensor of the encoder: the names held in memory (BertModel's for every "bert"-graph
+    model, MPNetModel's for MPNet), or with ``source`` the HF state_dict names of the source architecture
+    (``cfg.model_type``: DistilBertModel's differ)."""
+    if source:
+        return [(source_name(cfg.source_type, n), shp, kind) for n, shp, kind in weight_names(cfg)]
     H, F = cfg.hidden, cfg.ffn
     out = [("embeddings.word_embeddings.weight", (cfg.vocab, H), "w"),
            ("embeddings.position_embeddings.weight", (cfg.max_pos, H), "w")]
-    if cfg.arch == "bert":
+    if cfg.arch == "bert" and cfg.type_vocab > 0:
         out.append(("embeddings.token_type_embeddings.weight", (cfg.type_vocab, H), "w"))
     out += [("embeddings.LayerNorm.weight", (H,), "g"), ("embeddings.LayerNorm.bias", (H,), "b")]
     for l in range(cfg.num_layers):

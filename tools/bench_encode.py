@@ -37,11 +37,14 @@ if span_mode:
     span_bytes = int(span_tok.size * cfg.hidden * 2 + span_seq.size * cfg.hidden * 4)
 
 
+units = cfg.hidden <= 768   # unit rows stop at the search width: a hidden-1024 preset is timed with its float32 rows alone
+
+
 def forward():
     if span_mode:
-        return enc.forward_spans(fd, cd, *tabs, span_unit=True, pooled=True, unit=True, pos=pos, cols=cols,
+        return enc.forward_spans(fd, cd, *tabs, span_unit=units, pooled=True, unit=units, pos=pos, cols=cols,
                                  max_len=int(np.diff(cu).max()))
-    return enc.forward_packed(fd, cd, pos, cols, int(np.diff(cu).max()), pooled=True, unit=True, head=head)
+    return enc.forward_packed(fd, cd, pos, cols, int(np.diff(cu).max()), pooled=True, unit=units, head=head)
 
 
 if head_name and not span_mode:

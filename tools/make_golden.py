@@ -137,6 +137,44 @@ def g1_tiny():
              last_hidden_state=hidden.numpy(), pooled=pooled.numpy(), weights_crc=weights_crc(w))
 
 
+# ------------------------------------------------------------------ G1a tiny DistilBERT / RoBERTa (source architectures on the BERT graph)
+def g1_arch():
+    """tests/golden/encoder_tiny-distilbert.npz and encoder_tiny-roberta.npz: HF's own DistilBertModel / RobertaModel, loaded
+    with the presets' synthetic weights under their own state_dict names, through the reference's
+    OnnxSentenceTransformerWrapper; keys and input batch of the tiny-bert fixture (every id >= 5, so no RoBERTa pad id occurs
+    and masked tokens count towards the positions as HF counts them)."""
+    from transformers import DistilBertConfig, DistilBertModel, RobertaConfig, RobertaModel
+    for preset in ("tiny-distilbert", "tiny-roberta"):
+        cfg = presets.PRESETS[preset]
+        w = presets.synthetic_weights(preset)
+        if cfg.model_type == "distilbert":
+            m = DistilBertModel(DistilBertConfig(vocab_size=cfg.vocab, dim=cfg.hidden, n_layers=cfg.num_layers, n_heads=cfg.heads,
+                                                 hidden_dim=cfg.ffn, max_position_embeddings=cfg.max_pos, activation="gelu",
+                                                 pad_token_id=cfg.pad_id, dropout=0.0, attention_dropout=0.0))
+        else:
+            m = RobertaModel(RobertaConfig(vocab_size=cfg.vocab, hidden_size=cfg.hidden, num_hidden_layers=cfg.num_layers,
+                                           num_attention_heads=cfg.heads, intermediate_size=cfg.ffn,
+                                           max_position_embeddings=cfg.max_pos, layer_norm_eps=cfg.ln_eps,
+                                           type_vocab_size=cfg.type_vocab, pad_token_id=cfg.pad_id, hidden_act="gelu"),
+                             add_pooling_layer=False)
+        sd = {presets.source_name(cfg.model_type, k): torch.from_numpy(v.copy()) for k, v in w.items()}
+        missing, unexpected = m.load_state_dict(sd, strict=False)
+        missing = [k for k in missing if "position_ids" not in k and "token_type_ids" not in k]
+        assert not missing and not unexpected, (missing, unexpected)
+        m.eval()
+        params, wrap = ref_wrapper(m, preset)
+        g = np.load(os.path.join(OUT, "encoder_tiny-bert.npz"))
+        ids, mask = g["input_ids"], g["attention_mask"]
+        assert ids.max() < cfg.vocab and (ids != cfg.pad_id).all()
+        tid, tmask = torch.from_numpy(ids), torch.from_numpy(mask)
+        hidden = m(input_ids=tid, attention_mask=tmask)[0]
+        pooled = wrap.forward(tid, tmask)
+        pooled2 = AvgPoolingStrategy(params).forward(hidden, EmbeddingsFeatures(tid, tmask))
+        assert torch.equal(pooled, pooled2)
+        save(f"encoder_{preset}.npz", input_ids=ids, attention_mask=mask,
+             last_hidden_state=hidden.numpy(), pooled=pooled.numpy(), weights_crc=weights_crc(w))
+
+
 # ------------------------------------------------------------------ G2 preset-shape encoders (32 pooled rows)
 def g2_presets():
     for preset in ("all-MiniLM-L6-v2", "all-mpnet-base-v2", "bert-base-uncased"):
@@ -331,7 +369,7 @@ def g8_kmeans():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
+    which = sys.argv[1:] or ["g1", "g1a", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
     for g in which:
-        {"g1": g1_tiny, "g2": g2_presets, "g3": g3_pool, "g4": g4_cos, "g5": g5_topk, "g6": g6_e2e, "g7": g7_meters,
+        {"g1": g1_tiny, "g1a": g1_arch, "g2": g2_presets, "g3": g3_pool, "g4": g4_cos, "g5": g5_topk, "g6": g6_e2e, "g7": g7_meters,
          "g8": g8_kmeans}[g]()
