@@ -337,6 +337,56 @@ int tsim_l2_range_scan_tau(const void *eq_aug, const float *eq_f32, int64_t ldq_
 int tsim_range_merge_asc(const int64_t *lims_in, const float *scores_in, const int64_t *idx_in, int nlists, int64_t Q,
                          const int64_t *lims_out, int64_t total, float *out_scores, int64_t *out_idx, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact filtered search: the best k of each query among the rows of a LIST (hnswlib's `knn_query(filter=...)`, faiss'
+ * `SearchParameters(sel=IDSelectorBatch(ids))`, and the re-scoring of someone else's candidates: a lexical first stage, the
+ * senses of a lemma, the [Q, m] index output of an earlier search).  Float32 rows only: eq_f32 [Q, d], ec_f32 [N, d], row strides
+ * ldq_f32 / ldc_f32 >= d elements.  No half rows, no rho, no max-norm word: nothing is selected by MFMA, every listed row is
+ * scored exactly.
+ * Scores are those of the top-k entries of the same space, bit for bit: tsim_cosine_list_topk the reference's cosine of the
+ * float32 rows (tsim_cosine_topk_ex with float32 matrices), tsim_dot_list_topk float32(q . c) (tsim_dot_topk_ex),
+ * tsim_l2_list_topk the squared distance (tsim_l2_topk_ex; -dist^2 inside, the sign flipped by the last kernel).  A list that holds
+ * every row once returns what those entries return.
+ * Lists.  cand [T]: row numbers, cand_dtype TSIM_I32 or TSIM_I64.  Either lims != NULL and shared == 0: int64 [Q+1], query q owns
+ * cand[lims[q] .. lims[q+1]) (CSR, as tsim_range_fill writes it); or lims == NULL and shared == 1: every query owns cand[0 .. T),
+ * no CSR replicated.  Both or neither: TSIM_EINVAL.  T == 0 is legal (cand may be NULL then).
+ *   - a negative entry is padding and is skipped: the -1 padded [Q, m] out_idx of an earlier search can be passed as it is
+ *     (lims[q] = q m);
+ *   - an entry >= N is never dereferenced; it is skipped and sets TSIM_LIST_ST_ROW in out_status[q];
+ *   - lims are expected non-decreasing within [0, T].  They are replaced by their running maximum clamped to [0, T] before
+ *     anything reads them: a decreasing pair gives an EMPTY list, a pair pointing outside [0, T] an in-range one, and every
+ *     query one of whose two words was changed gets TSIM_LIST_ST_LIMS;
+ *   - lists are expected to hold distinct rows.  A row listed twice is scored twice and returned twice, in adjacent
+ *     positions (equal score, equal index); callers that cannot promise distinct rows remove duplicates first (ops does).
+ * Output.  out_scores [Q, k] float32, out_idx [Q, k] int64 = row + idx_offset, ordered by (score desc, row asc), Euclidean by
+ * (dist^2 asc, row asc); 1 <= k <= TSIM_TOPK_MAX_K; a list with fewer than k usable entries (a row of NaN score is not usable)
+ * is padded with -inf / -1 (Euclidean +inf / -1).  out_status [Q] int32 (may be NULL): 0 or the TSIM_LIST_ST_* bits.
+ * Limits: 1 <= d <= 768 (Euclidean <= 767, as tsim_l2_topk_ex), N < 2^31 - 64.
+ * Work.  cand is cut into slices of TSIM_LIST_SLICE entries; one workgroup scores the part of one query's list inside one slice
+ * (shared lists: inside a chunk of slices) and keeps the running sorted list of the brute-force pass; one workgroup per query
+ * merges.  The host never learns the list lengths: the grid and tsim_list_topk_workspace_bytes(Q, T, k) — pure host, 0 for Q <= 0,
+ * T < 0 or k outside 1..TSIM_TOPK_MAX_K, non-decreasing in each argument, the same for both forms — depend on (Q, T, k) alone, and
+ * no call reads device memory back.  CSR needs (Q + ceil(T / TSIM_LIST_SLICE)) k 8 B, whatever the lengths; callers slice large
+ * query sets. */
+#define TSIM_I32 2 /* int32 row numbers */
+#define TSIM_I64 3 /* int64 row numbers */
+#define TSIM_LIST_SLICE 1024
+#define TSIM_LIST_ST_ROW 1  /* the list held an entry >= N */
+#define TSIM_LIST_ST_LIMS 2 /* the query's lims pair was decreasing or outside [0, T] */
+size_t tsim_list_topk_workspace_bytes(int64_t Q, int64_t T, int k);
+int tsim_cosine_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32, int64_t N, int d,
+                          const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k, float *out_scores,
+                          int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                          void *stream);
+int tsim_dot_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32, int64_t N, int d,
+                       const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k, float *out_scores,
+                       int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                       void *stream);
+int tsim_l2_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32, int64_t N, int d,
+                      const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k, float *out_scores,
+                      int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

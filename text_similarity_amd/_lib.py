@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSIM_LIB") or os.path.join(_HERE, "libtsim.so")   # TSIM_LIB: a variant build (build.py TSIM_BUILD_TAG)
 
 TSIM_F32, TSIM_BF16 = 0, 1
+TSIM_I32, TSIM_I64 = 2, 3        # index dtypes of the candidate lists (tsim_*_list_topk)
+LIST_ST_ROW, LIST_ST_LIMS = 1, 2  # include/tsim.h TSIM_LIST_ST_*
 ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
 W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
@@ -114,6 +116,11 @@ _SIGS = {
                                          C.c_size_t, C.c_void_p]),
     "tsim_range_merge_asc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "tsim_list_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    **{name: (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64,
+                        C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                        C.c_void_p])
+       for name in ("tsim_cosine_list_topk", "tsim_dot_list_topk", "tsim_l2_list_topk")},
     "tsim_cosine_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_time_next_topk": (None, [C.c_void_p, C.c_void_p]),

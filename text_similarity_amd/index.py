@@ -111,24 +111,31 @@ class GpuFlatIndex:
         self._dead[:self._n] |= hit
         self._n_dead += k
 
-    def knn_query(self, data, k: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    def knn_query(self, data, k: int = 1, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """(labels [Q,k] int64, distances [Q,k] float32 = 1 - cosine, 1 - q.c for 'ip', or the squared distance for 'euclidean'),
-        best first — hnswlib's return convention."""
-        labels, scores = self.search(data, k)
+        best first — hnswlib's return convention.  ``filter``: see :meth:`search` (hnswlib's ``filter=callable`` among its forms)."""
+        labels, scores = self.search(data, k, filter=filter)
         if self.space == "euclidean":
             return labels.cpu().numpy(), scores.cpu().numpy()
         return labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
 
     # ------------------------------------------------------------------ device-level API
-    def search(self, data, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, data, k: int, filter=None, filter_plan: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(labels [Q,k] int64, scores [Q,k] float32) on the device; -1 / -inf pad when fewer than k live rows.  'euclidean': the
-        scores are squared distances, ascending, padded with +inf."""
+        scores are squared distances, ascending, padded with +inf.
+        ``filter`` restricts the search to the rows it allows — exact, same scores and tie rule (row asc) as the unfiltered call:
+        a 1-D int array / tensor of allowed labels (faiss ``IDSelectorBatch``); a callable ``label -> bool`` (hnswlib's form,
+        evaluated on the host over the live labels); a ``list`` of Q label arrays, or a ``tuple`` ``(lims [Q+1], labels)``, for
+        one allow-list per query.  Unknown labels are ignored, deleted rows never match, fewer than k matches pad.
+        ``filter_plan``: ``"list"`` or ``"compact"`` forces the regime of a shared allow-list (:meth:`filter_plan` chooses)."""
         self._compact()
         q = torch.as_tensor(np.asarray(data) if not isinstance(data, torch.Tensor) else data)
         if q.dim() == 1:
             q = q.unsqueeze(0)
         qf = q.to(self.device, dtype=torch.float32).contiguous()
         euclid = self.space == "euclidean"
+        if filter is not None:
+            return self._search_filtered(qf, int(k), filter, filter_plan)
         qn = None if euclid else ops.l2norm_rows(qf)     # (euclidean: the query rows need the corpus' word, below)
         if self._n == 0:
             Q = q.shape[0]
@@ -143,6 +150,93 @@ class GpuFlatIndex:
         else:
             s, i = ops.cosine_topk(qn, self._rows[:self._n], self.dim, k, eq_f32=qf, ec_f32=self._f32[:self._n],
                                    rho_c=self._rho)
+        lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
+        return lab, s
+
+    # The byte model of :meth:`filter_plan`: what the compact regime costs before its search reads a row (two gathers, the
+    # queries' unit rows, the launches of the ordinary search), in bytes of the list kernel's traffic.  Set from the table in
+    # DESIGN.md §7 (MI355X, N = 1 M, d = 384, k = 10; ms per call list / compact): Q = 16: n = 10 k 0.93 / 0.91, 100 k 1.32 / 1.66,
+    # 500 k 3.56 / 1.46; Q = 256: 10 k 1.34 / 0.88, 100 k 6.79 / 1.37; Q = 4 096: 10 k 9.44 / 0.96.  The list regime still wins
+    # at Q n d 4 = 2.5e9 B and has lost at 3.9e9 B: the crossover lies between, about 0.6 ms of the list kernel's 5 TB/s.
+    FILTER_COMPACT_FIXED_BYTES = 3 << 30
+
+    def filter_plan(self, Q: int, n_allowed: int) -> str:
+        """``"list"`` or ``"compact"``: the regime :meth:`search` takes for ONE allow-list of ``n_allowed`` rows shared by ``Q``
+        queries.  Pure host arithmetic on a byte model: the list kernel (:func:`ops.cosine_list_topk`) reads Q n d 4 bytes — every
+        query gathers every allowed float32 row; the compact regime reads and writes the allowed half and float32 rows once,
+        2 n (2 ld + 4 d) bytes, runs the space's ordinary MFMA search on the temporary, whose traffic does not grow with Q, and
+        pays a fixed cost.  Monotone: more queries or more rows never turn "compact" back into "list"."""
+        d = self.dim or 384
+        ld = ops.pad_dim(d + 1 if self.space == "euclidean" else d)
+        Q, n = int(Q), int(n_allowed)
+        return "list" if Q * n * d * 4 <= self.FILTER_COMPACT_FIXED_BYTES + 2 * n * (2 * ld + 4 * d) else "compact"
+
+    def _filter_rows(self, filt, Q: int):
+        """rows (device int64) and lims (None: one list for all queries) of a filter; per-query lists carry -1 for labels the
+        index does not hold."""
+        n = self._n
+        labels = self._labels[:n]
+        if callable(filt):
+            lab = labels.cpu().numpy()
+            keep = np.fromiter((bool(filt(int(x))) for x in lab), dtype=bool, count=lab.shape[0])
+            return torch.from_numpy(np.flatnonzero(keep)).to(self.device), None
+        lims = None
+        if isinstance(filt, tuple):
+            if len(filt) != 2:
+                raise ValueError("filter: a tuple is (lims [Q+1], labels)")
+            lims = torch.as_tensor(np.asarray(filt[0]) if not isinstance(filt[0], torch.Tensor) else filt[0])
+            lims = lims.to(self.device, dtype=torch.int64)
+            if lims.shape != (Q + 1,):
+                raise ValueError(f"filter: lims must have {Q + 1} entries for {Q} queries")
+            filt = filt[1]
+        elif isinstance(filt, list) and len(filt) and np.ndim(filt[0]) > 0:
+            if len(filt) != Q:
+                raise ValueError(f"filter: {len(filt)} allow-lists for {Q} queries")
+            parts = [np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, dtype=np.int64).reshape(-1) for p in filt]
+            lims = torch.from_numpy(np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)).to(self.device)
+            filt = np.concatenate(parts) if parts else np.zeros((0,), np.int64)
+        lab = torch.as_tensor(np.asarray(filt) if not isinstance(filt, torch.Tensor) else filt)
+        if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+            raise ValueError("filter: expected a 1-D integer array of labels, a callable, a list of Q label arrays or (lims, labels)")
+        lab = lab.to(self.device, dtype=torch.int64)
+        if lims is None:
+            return torch.isin(labels, lab).nonzero(as_tuple=False).squeeze(1), None      # ascending rows
+        if n == 0 or lab.numel() == 0:
+            return torch.full_like(lab, -1), lims
+        sl, order = torch.sort(labels)
+        pos = torch.searchsorted(sl, lab).clamp(max=n - 1)
+        return torch.where(sl[pos] == lab, order[pos], torch.full_like(lab, -1)), lims
+
+    def _search_filtered(self, qf: torch.Tensor, k: int, filt, plan: Optional[str]):
+        if plan not in (None, "list", "compact"):
+            raise ValueError(f"filter_plan must be 'list' or 'compact', not {plan!r}")
+        Q = qf.shape[0]
+        euclid = self.space == "euclidean"
+        pad = (torch.full((Q, k), -1, dtype=torch.int64, device=self.device),
+               torch.full((Q, k), float("inf" if euclid else "-inf"), device=self.device))
+        if self._n == 0 or Q == 0:
+            return pad
+        rows, lims = self._filter_rows(filt, Q)
+        if lims is None and rows.numel() == 0:
+            return pad
+        n = self._n
+        if lims is not None or (plan or self.filter_plan(Q, rows.numel())) == "list":
+            fn = ops.l2_list_topk if euclid else ops.dot_list_topk if self.space == "ip" else ops.cosine_list_topk
+            # (a shared list comes from nonzero(): distinct and ascending already)
+            s, i = fn(qf, self._f32[:n], rows, lims, k=k, assume_unique=lims is None)
+        else:
+            # compact: the allowed rows, in row order, as a temporary index; positions in it map back through `rows`, and
+            # because the gather keeps the order, (score, position) ranks exactly as (score, row) does
+            half, f32 = self._rows[:n].index_select(0, rows), self._f32[:n].index_select(0, rows)
+            if euclid:
+                s, i = ops.l2_topk(ops.l2_query_rows(qf, self._maxnorm), half, self.dim, k, eq_f32=qf, ec_f32=f32, rho_c=self._rho,
+                                   scale_c=self._maxnorm)
+            elif self.space == "ip":
+                s, i = ops.dot_topk(ops.l2norm_rows(qf), half, self.dim, k, eq_f32=qf, ec_f32=f32, rho_c=self._rho,
+                                    scale_c=self._maxnorm)
+            else:
+                s, i = ops.cosine_topk(ops.l2norm_rows(qf), half, self.dim, k, eq_f32=qf, ec_f32=f32, rho_c=self._rho)
+            i = torch.where(i >= 0, rows[i.clamp(min=0)], torch.full_like(i, -1))
         lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
         return lab, s
 

@@ -316,6 +316,141 @@ def l2_topk(eq_aug: torch.Tensor, ec_aug: torch.Tensor, d: int, k: int, eq_f32: 
     return _topk("l2_topk", eq_aug, ec_aug, d, k, idx_offset, eq_f32, ec_f32, return_status, rho_c, scale_c, out, l2=True)
 
 
+# ------------------------------------------------------------------------------------------------- exact search within lists
+LIST_SLICE = 1024               # include/tsim.h TSIM_LIST_SLICE
+LIST_ST_ROW, LIST_ST_LIMS = _lib.LIST_ST_ROW, _lib.LIST_ST_LIMS
+LIST_MAX_WORKSPACE = 256 << 20  # csrc/search.hip BF_BUDGET
+
+
+def _list_operands(what, cand, lims, Q, N, dev, assume_unique):
+    """(cand 1-D int32/int64 contiguous, lims int64 [Q+1] or None, extra status int32 [Q] or None) on the device.  A 2-D ``cand``
+    gets its implicit lims; unless ``assume_unique``, negatives and repeats inside a list are removed (torch plumbing: one sort
+    of the keys query * (N + 1) + min(row, N), so every entry >= N survives as ONE entry N and still raises its status bit) and
+    the lims are rebuilt from the per-query counts — the bit of a bad lims pair is computed here then, from the same rule as the
+    kernel's (running maximum, clamped)."""
+    _need_gpu(cand)
+    if cand.device != dev:
+        raise ValueError(f"{what}: cand on {cand.device}, rows on {dev}")
+    if cand.dtype not in (torch.int32, torch.int64):
+        if cand.dtype.is_floating_point or cand.dtype == torch.bool:
+            raise ValueError(f"{what}: cand must hold integers, not {cand.dtype}")
+        cand = cand.long()
+    if cand.dim() == 2:
+        if lims is not None:
+            raise ValueError(f"{what}: a 2-D cand [Q, m] carries its own lists; pass lims with a 1-D cand")
+        if cand.shape[0] != Q:
+            raise ValueError(f"{what}: cand has {cand.shape[0]} rows for {Q} queries")
+        m = cand.shape[1]
+        lims = torch.arange(Q + 1, dtype=torch.int64, device=dev) * m
+        cand = cand.reshape(-1)
+    elif cand.dim() != 1:
+        raise ValueError(f"{what}: cand must be 1-D (with lims: CSR; without: one shared list) or 2-D [Q, m]")
+    elif lims is not None:
+        lims = torch.as_tensor(lims).to(dev, dtype=torch.int64).contiguous()
+        if lims.shape != (Q + 1,):
+            raise ValueError(f"{what}: lims must be int64 [{Q + 1}], got {tuple(lims.shape)}")
+    cand = cand.contiguous()
+    if assume_unique:
+        return cand, lims, None
+    T = cand.numel()
+    if lims is None:
+        c = cand[cand >= 0]
+        return torch.unique(c.clamp(max=N)), None, None
+    clean = torch.cummax(lims, 0).values.clamp(0, T)
+    bad = ((clean[:-1] != lims[:-1]) | (clean[1:] != lims[1:])).to(torch.int32) * LIST_ST_LIMS
+    pos = torch.arange(T, dtype=torch.int64, device=dev)
+    qid = torch.searchsorted(clean[1:].contiguous(), pos, right=True)          # the query owning position p (Q: none)
+    keep = (cand >= 0) & (qid < Q) & (pos >= clean[:-1][qid.clamp(max=Q - 1)])
+    key = torch.unique(qid[keep] * (N + 1) + cand[keep].long().clamp(max=N))
+    counts = torch.bincount(torch.div(key, N + 1, rounding_mode="floor"), minlength=Q)
+    new_lims = torch.zeros((Q + 1,), dtype=torch.int64, device=dev)
+    new_lims[1:] = torch.cumsum(counts, 0)
+    return (key % (N + 1)).contiguous(), new_lims, bad
+
+
+def _list_topk(what, fn_name, eq_f32, ec_f32, cand, lims, k, idx_offset, return_status, assume_unique):
+    _need_gpu(eq_f32, ec_f32)
+    dev = eq_f32.device
+    for t, name in ((eq_f32, "eq_f32"), (ec_f32, "ec_f32")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be float32 [rows, d] with unit inner stride")
+    Q, d = eq_f32.shape
+    N = ec_f32.shape[0]
+    if ec_f32.shape[1] != d:
+        raise ValueError(f"{what}: query rows are {d} wide, corpus rows {ec_f32.shape[1]}")
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    if not isinstance(cand, torch.Tensor):
+        raise _lib.TsimError(f"{what}: cand must be a CUDA/ROCm tensor, got {type(cand).__name__}")
+    cand, lims, extra = _list_operands(what, cand, lims, Q, N, dev, assume_unique)
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q == 0:
+        return (scores, idx, status) if return_status else (scores, idx)
+    if N == 0:
+        raise ValueError(f"{what}: empty corpus")
+    L = _lib.lib()
+    T = cand.numel()
+    dt = _lib.TSIM_I32 if cand.dtype == torch.int32 else _lib.TSIM_I64
+    ldq, ldc = _row_stride(eq_f32), _row_stride(ec_f32)
+    with torch.cuda.device(dev):
+        # queries per call: the workspace stays within what the full search of the same queries asks for (or within the budget
+        # of its brute-force lists, which the list kernels' own chunk lists are sized by)
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_list_topk_workspace_bytes(step, T, k)
+        while step > 1 and nbytes > max(L.tsim_topk_large_workspace_bytes(step, N, k), LIST_MAX_WORKSPACE):
+            step = (step + 1) // 2
+            nbytes = L.tsim_list_topk_workspace_bytes(step, T, k)
+        ws = _workspace(dev, nbytes)
+        fn = getattr(L, fn_name)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = fn(eq_f32.data_ptr() + q0 * ldq * 4, ldq, nq, ec_f32.data_ptr(), ldc, N, d, cand.data_ptr() if T else 0, dt, T,
+                    lims.data_ptr() + q0 * 8 if lims is not None else 0, int(lims is None), k, scores.data_ptr() + q0 * k * 4,
+                    idx.data_ptr() + q0 * k * 8, idx_offset, status.data_ptr() + q0 * 4 if return_status else 0, ws.data_ptr(),
+                    ws.numel(), _stream(eq_f32))
+            _lib.check(rc, what)
+    if return_status and extra is not None:
+        status |= extra
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
+def cosine_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor, lims: Optional[torch.Tensor] = None,
+                     k: int = 10, idx_offset: int = 0, return_status: bool = False, assume_unique: bool = False):
+    """Exact top-k of every query WITHIN ITS OWN LIST of corpus rows: scores [Q,k] f32 and idx [Q,k] i64 ordered by (score desc,
+    row asc), padded with -inf / -1 where a list has fewer than k usable rows.  Float32 rows only (``eq_f32`` [Q,d], ``ec_f32``
+    [N,d]; strided row views are fine): nothing is selected by MFMA, every listed row is scored with the exact cosine of
+    :func:`cosine_topk`'s float32 mode — a list that holds every row returns the same bits.
+    ``cand``: 1-D with ``lims=None`` — ONE list shared by all queries; 1-D with ``lims`` int64 [Q+1] — CSR, query q owns
+    ``cand[lims[q]:lims[q+1]]``; 2-D [Q, m] — fixed-width lists (the ``idx`` of an earlier search can be passed as it is).
+    int32 or int64.  Negative entries are padding.  Entries >= N are skipped and set status bit ``LIST_ST_ROW``; a lims pair
+    that is decreasing or outside [0, len(cand)] is clamped (include/tsim.h) and sets ``LIST_ST_LIMS``; ``return_status`` adds
+    the int32 [Q] status.  Rows repeated inside a list are removed first (a device sort; the lists come out sorted by row)
+    unless ``assume_unique=True``, which passes the lists to the kernel untouched — a row listed twice is then returned twice,
+    adjacent.  CPU tensors raise ``TsimError``."""
+    return _list_topk("cosine_list_topk", "tsim_cosine_list_topk", eq_f32, ec_f32, cand, lims, k, idx_offset, return_status,
+                      assume_unique)
+
+
+def dot_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor, lims: Optional[torch.Tensor] = None,
+                  k: int = 10, idx_offset: int = 0, return_status: bool = False, assume_unique: bool = False):
+    """:func:`cosine_list_topk` by inner product: scores = float32(q.c) as :func:`dot_topk` returns them."""
+    return _list_topk("dot_list_topk", "tsim_dot_list_topk", eq_f32, ec_f32, cand, lims, k, idx_offset, return_status,
+                      assume_unique)
+
+
+def l2_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor, lims: Optional[torch.Tensor] = None,
+                 k: int = 10, idx_offset: int = 0, return_status: bool = False, assume_unique: bool = False):
+    """:func:`cosine_list_topk` by Euclidean distance: SQUARED distances as :func:`l2_topk` returns them, ascending, ties to the
+    lower row, padded with +inf / -1.  d <= 767, as there."""
+    if eq_f32.dim() == 2:
+        _l2_dim(eq_f32.shape[1], "l2_list_topk")
+    return _list_topk("l2_list_topk", "tsim_l2_list_topk", eq_f32, ec_f32, cand, lims, k, idx_offset, return_status,
+                      assume_unique)
+
+
 # ------------------------------------------------------------------------------------------------- exact range search
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins

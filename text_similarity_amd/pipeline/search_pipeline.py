@@ -86,19 +86,28 @@ class SentenceMiningPipeline(SearchPipeline):
         self.last_scores = None      # [Q,k] float32 of the last search (the reference only prints indices)
         self.last_indices = None
 
-    def search_tensors(self, query_embeddings: torch.Tensor, corpus=None, max_num_results: int = 10):
+    def search_tensors(self, query_embeddings: torch.Tensor, corpus=None, max_num_results: int = 10, candidates=None):
         """Device-level search: returns (scores [Q,k] f32, indices [Q,k] i64) over the whole corpus.  Scores are the
         reference's ``F.cosine_similarity`` of the float32 embeddings (search_pipeline.py:76-77) and the order is exact for
         them: half-precision unit rows feed the MFMA kernel for candidate selection only.  With ``score_function='dot'`` the
         scores are the inner products of the float32 embeddings (each chunk scaled by its own power of two for the MFMA
-        pass; results do not depend on the chunking).  1 <= max_num_results <= 1024, width <= 768."""
+        pass; results do not depend on the chunking).  1 <= max_num_results <= 1024, width <= 768.
+        ``candidates`` restricts every query to its own corpus positions — re-scoring a first stage's candidates: a list of Q
+        position lists, a ``[Q, m]`` tensor (-1 = padding) or ONE 1-D list shared by all queries.  Same scores, same order
+        (:func:`ops.cosine_list_topk` / :func:`ops.dot_list_topk`); positions index the WHOLE corpus, so it is embedded in one
+        piece and ``corpus_chunk_size`` does not apply."""
         corpus = self.corpus if corpus is None else corpus
         n = len(corpus)
         d = query_embeddings.shape[1]
         qf = query_embeddings.to(self.params.device, dtype=torch.float32).contiguous()
-        qn = ops.l2norm_rows(qf)
         k = min(max_num_results, len(query_embeddings)) if self.reference_k_clamp else max_num_results
         k = max(1, min(k, n))
+        if candidates is not None:
+            cf = (self.model.encode_text(corpus) if isinstance(corpus, list) else corpus).to(self.params.device, dtype=torch.float32)
+            cand, lims = self._candidate_lists(candidates, qf.shape[0])
+            fn = ops.dot_list_topk if self.score_function == "dot" else ops.cosine_list_topk
+            return fn(qf, cf.contiguous(), cand, lims, k=k)
+        qn = ops.l2norm_rows(qf)
         scores, idxs = [], []
         for start in range(0, n, self.corpus_chunk_size):
             chunk = corpus[start:start + self.corpus_chunk_size]
@@ -121,6 +130,20 @@ class SentenceMiningPipeline(SearchPipeline):
         if len(scores) == 1:
             return scores[0], idxs[0]
         return ops.topk_merge(scores, idxs, k)
+
+    def _candidate_lists(self, candidates, Q: int):
+        """(cand, lims) on the device for the three forms ``search_tensors`` takes."""
+        dev = self.params.device
+        if isinstance(candidates, torch.Tensor):
+            return candidates.to(dev), None
+        if len(candidates) and not isinstance(candidates[0], (int,)) and getattr(candidates[0], "__len__", None) is not None:
+            if len(candidates) != Q:
+                raise ValueError(f"candidates: {len(candidates)} lists for {Q} queries")
+            parts = [torch.as_tensor(c, dtype=torch.int64).reshape(-1) for c in candidates]
+            lims = torch.zeros((Q + 1,), dtype=torch.int64)
+            lims[1:] = torch.cumsum(torch.tensor([p.numel() for p in parts], dtype=torch.int64), 0)
+            return torch.cat(parts).to(dev), lims.to(dev)
+        return torch.as_tensor(candidates, dtype=torch.int64).to(dev), None
 
     def range_tensors(self, query_embeddings: torch.Tensor, threshold, corpus=None):
         """Device-level range search: ``(lims int64 [Q+1], scores float32 [T], indices int64 [T])`` — EVERY corpus row whose
@@ -184,12 +207,15 @@ class SentenceMiningPipeline(SearchPipeline):
         qid, idx, scores = _sort_columns([qid, idx, scores], ((1, False), (0, False), (2, True)))
         return list(zip(scores.cpu().tolist(), qid.cpu().tolist(), idx.cpu().tolist()))
 
-    def _search(self, queries, corpus=None, max_num_results: int = 10, return_embeddings: bool = False
+    def _search(self, queries, corpus=None, max_num_results: int = 10, return_embeddings: bool = False, candidates=None
                 ) -> Dict[int, Union[list, torch.Tensor]]:
         query_embeddings = self.encode_corpus(documents=queries, return_embeddings=return_embeddings)
         if corpus is not None:
             self.corpus = corpus
-        scores, indices = self.search_tensors(query_embeddings, self.corpus, max_num_results)
+        if candidates is None:
+            scores, indices = self.search_tensors(query_embeddings, self.corpus, max_num_results)
+        else:
+            scores, indices = self.search_tensors(query_embeddings, self.corpus, max_num_results, candidates=candidates)
         self.last_scores, self.last_indices = scores, indices
         top_candidates = {}
         idx_host = indices.cpu()
@@ -205,8 +231,8 @@ class SentenceMiningPipeline(SearchPipeline):
                 top_candidates[query_idx] = [(int(c), self.corpus[int(c)]) for c in actual]
         return top_candidates
 
-    def __call__(self, queries, max_num_results: int, return_embeddings: bool = False):
-        return self._search(queries, None, max_num_results, return_embeddings)
+    def __call__(self, queries, max_num_results: int, return_embeddings: bool = False, candidates=None):
+        return self._search(queries, None, max_num_results, return_embeddings, candidates)
 
 
 class SemanticSearchPipeline(SearchPipeline):
@@ -240,17 +266,20 @@ class SemanticSearchPipeline(SearchPipeline):
         self.index.save_index(self.index_path)
         self.index.set_ef(getattr(self.params, "ef", 0))
 
-    def _search(self, queries, max_num_results: int):
+    def _search(self, queries, max_num_results: int, filter=None):
         query_embeddings = self.encode_corpus(queries)
-        labels, scores = self.index.search(query_embeddings, max_num_results)
+        if filter is None:
+            labels, scores = self.index.search(query_embeddings, max_num_results)
+        else:   # (labels of this index are corpus positions; the forms GpuFlatIndex.search takes)
+            labels, scores = self.index.search(query_embeddings, max_num_results, filter=filter)
         self.last_labels, self.last_scores = labels, scores
         top_results = {}
         for qidx, row in enumerate(labels.cpu().tolist()):
             top_results[qidx] = [self.corpus[i] for i in row if i >= 0]
         return top_results
 
-    def __call__(self, queries, max_num_results: int):
-        return self._search(queries, max_num_results)
+    def __call__(self, queries, max_num_results: int, filter=None):
+        return self._search(queries, max_num_results, filter)
 
     def add_to_index(self, text):
         if isinstance(text, str):

@@ -16,7 +16,13 @@ median over a sample of 64 queries of their H-th smallest squared distance (ops.
 --tau-array: pass the threshold of a range run as a per-query tensor [Q] holding that one value (the _tau entries) instead of a float.
 With --score l2 --range-hits the tensor holds every query's OWN H-th smallest squared distance instead (one radius hits very
 different numbers of rows for queries of different norm: dist^2 ~ |q|^2 + |c|^2), so every query has H hits.
---range-merge R Q HITS: time ops.range_merge alone on R synthetic lists of Q queries x HITS sorted entries each (no corpus is made)."""
+--range-merge R Q HITS: time ops.range_merge alone on R synthetic lists of Q queries x HITS sorted entries each (no corpus is made).
+--list-len L ...: time the exact search WITHIN LISTS (ops.cosine_list_topk / dot_list_topk / l2_list_topk on the float32 rows) instead:
+every query gets its own list of L random rows (CSR), or with --shared all queries share ONE list of L rows; --list-order
+sorted|shuffled|arange orders the shared list (arange: rows 0 .. L-1).  ms per call and GB/s of (sum of list lengths) x d x 4; one
+line per (Q, L, k).
+--filter-frac F ...: GpuFlatIndex.search(filter=a shared allow-list of F x N labels) in both regimes, ms per call each and what
+filter_plan would choose; one line per (Q, F, k)."""
 import argparse
 import json
 import os
@@ -39,14 +45,18 @@ ap.add_argument("--range", nargs="+", type=float, default=[], dest="taus")
 ap.add_argument("--range-hits", nargs="+", type=float, default=[])
 ap.add_argument("--tau-array", action="store_true")
 ap.add_argument("--range-merge", nargs=3, type=int, default=None, metavar=("R", "Q", "HITS"))
+ap.add_argument("--list-len", nargs="+", type=int, default=[])
+ap.add_argument("--shared", action="store_true")
+ap.add_argument("--list-order", choices=("sorted", "shuffled", "arange"), default="sorted")
+ap.add_argument("--filter-frac", nargs="+", type=float, default=[])
 a = ap.parse_args()
 N, d, Qs = a.N, a.d, a.Q
 dev = "cuda:0"
 g = torch.Generator(device=dev).manual_seed(4321)
 
 
-def timed(run, iters):
-    for _ in range(2):
+def timed(run, iters, warm=2):
+    for _ in range(warm):
         run()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -77,6 +87,41 @@ if a.range_merge:
 cf = torch.randn((N, d), generator=g, device=dev)
 if a.spread:
     cf *= 10.0 ** (2.0 * torch.rand((N, 1), generator=g, device=dev) - 1.0)
+if a.list_len:
+    fn = {"cosine": ops.cosine_list_topk, "dot": ops.dot_list_topk, "l2": ops.l2_list_topk}[a.score]
+    for Q, L, k in [(Q, L, k) for Q in Qs for L in a.list_len for k in a.k]:
+        qf = torch.randn((Q, d), generator=g, device=dev)
+        if a.shared:
+            cand = torch.arange(L, device=dev) if a.list_order == "arange" else torch.randperm(N, generator=g, device=dev)[:L]
+            cand = cand.sort().values if a.list_order == "sorted" else cand
+            lims = None
+        else:      # (random rows, a repeat now and then: the lists go to the kernel as they are)
+            cand = torch.randint(0, N, (Q * L,), generator=g, device=dev)
+            cand = cand.view(Q, L).sort(dim=1).values.reshape(-1) if a.list_order == "sorted" else cand
+            lims = torch.arange(Q + 1, device=dev, dtype=torch.int64) * L
+        ms = timed(lambda: fn(qf, cf, cand, lims, k=k, assume_unique=True), 5 if Q * L <= 1 << 26 else 2)
+        print(json.dumps({"score": a.score, "list": True, "shared": a.shared, "order": a.list_order, "Q": Q, "N": N, "d": d, "L": L,
+                          "k": k, "ms": round(ms, 4), "gather_GBs": round(Q * L * d * 4 / ms / 1e6, 1)}), flush=True)
+    sys.exit(0)
+if a.filter_frac:
+    from text_similarity_amd.index import GpuFlatIndex
+    ix = GpuFlatIndex(space={"cosine": "cosine", "dot": "ip", "l2": "euclidean"}[a.score], dim=d, device=dev)
+    ix.add_items(cf, range(N))
+    del cf
+    for Q, F, k in [(Q, F, k) for Q in Qs for F in a.filter_frac for k in a.k]:
+        qf = torch.randn((Q, d), generator=g, device=dev)
+        allowed = torch.randperm(N, generator=g, device=dev)[:max(1, int(F * N))]
+        rec = {"score": a.score, "filter": True, "Q": Q, "N": N, "d": d, "frac": F, "n_allowed": allowed.numel(), "k": k,
+               "plan": ix.filter_plan(Q, allowed.numel())}
+        gathered = Q * allowed.numel() * d * 4      # what the list regime reads; beyond 7e13 B it is not run (minutes per call)
+        for plan in ("list", "compact"):
+            if plan == "list" and gathered > 7e13:
+                rec["ms_list"] = None
+                continue
+            long = plan == "list" and gathered > 5e12
+            rec["ms_" + plan] = round(timed(lambda: ix.search(qf, k, filter=allowed, filter_plan=plan), 1 if long else 3, 1 if long else 2), 4)
+        print(json.dumps(rec), flush=True)
+    sys.exit(0)
 if a.score in ("dot", "l2"):
     rows_fn = ops.dot_scaled_rows if a.score == "dot" else ops.l2_rows
     corpus, rho, scale = rows_fn(cf)
