@@ -832,218 +832,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NB > 4 ? 1 
     }
 }
 
-// k rounds of "best entry strictly after the previous winner" over LDS arrays sc/ix[0..n): a 256-thread workgroup.
-// red_s/red_i: 4-entry scratch.  Writes (-inf, -1) when the entries run out.  emit(t, score, row) is called by thread 0.
-template <typename EMIT>
-__device__ __forceinline__ void wg_select_topk(const float *sc, const int *ix, int n, int k, float *red_s, int *red_i,
-                                               EMIT emit) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float last_s = INFINITY;
-    int last_i = -1;
-    for (int t = 0; t < k; ++t) {
-        float bs = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int e = threadIdx.x; e < n; e += 256) {
-            const float s = sc[e];
-            const int i = ix[e];
-            if (i >= 0 && key_before(last_s, last_i, s, i) && key_before(s, i, bs, bi)) {
-                bs = s;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float os = __shfl_xor(bs, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (key_before(os, oi, bs, bi)) {
-                bs = os;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red_s[wave] = bs;
-            red_i[wave] = bi;
-        }
-        __syncthreads();
-        bs = red_s[0];
-        bi = red_i[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (key_before(red_s[w], red_i[w], bs, bi)) {
-                bs = red_s[w];
-                bi = red_i[w];
-            }
-        __syncthreads();
-        const bool none = bi == 0x7fffffff;
-        if (threadIdx.x == 0) emit(t, none ? -INFINITY : bs, none ? -1 : bi);
-        if (none) {
-            last_s = -INFINITY;
-            last_i = 0x7fffffff;   // nothing ranks after this: the remaining slots pad
-        } else {
-            last_s = bs;
-            last_i = bi;
-        }
-    }
-}
-
-// =====================================================================================================
-// The k <= 64 forms of widen_finalize / bf_partial / bf_merge (further down: the sorted-list forms, which take any k): the
-// exact top-k by k rounds of wg_select_topk.  search_tail still sends k <= 64 here: the sorted-list kernels compute the same
-// bits, but their speed at k <= 64 has not been measured against these, and this is the serving path for k = 29 .. 64.
-// =====================================================================================================
-constexpr int COLL_CAP = 1024;   // entries per slot
-
-template <typename T, int SM>
-__global__ __launch_bounds__(256) void widen_finalize_k64_kernel(const unsigned long long *__restrict__ coll_buf,
-                                                                 const int *__restrict__ coll_cnt, int64_t Q, int64_t N,
-                                                                 const T *__restrict__ xq, int64_t ldq,
-                                                                 const T *__restrict__ xc, int64_t ldc, int d, int k,
-                                                                 float *__restrict__ out_s, int64_t *__restrict__ out_i,
-                                                                 int64_t idx_offset, GuardArgs g) {
-    constexpr bool COS = SM == SM_COS, DOT = SM == SM_DOT, L2 = SM == SM_L2;
-    static_assert(L2 == is_l2_rows<T>, "SM_L2 scores rows of l2_f32");
-    __shared__ float sc[COLL_CAP];
-    __shared__ int ix[COLL_CAP];
-    __shared__ float red_s[4];
-    __shared__ int red_i[4];
-    __shared__ float s_err[4];
-    __shared__ float s_top[64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int nflag = g.ctl[CTL_NFLAG];
-    nflag = nflag < Q ? nflag : (int)Q;
-    for (int slot = blockIdx.x; slot < nflag; slot += gridDim.x) {
-        const int q = g.flag_q[slot];
-        const int cnt = coll_cnt[slot];
-        const int n = cnt < COLL_CAP ? cnt : COLL_CAP;
-        bool resolved = cnt <= COLL_CAP;
-        if (resolved) {   // workgroup-uniform
-            ExactQuery<T> eqr;
-            exact_load_query<T, L2 ? NORM_SQ : COS || DOT>(eqr, xq + (int64_t)q * ldq, d, lane);
-            double nqs = 1.0;
-            if constexpr (DOT) nqs = eqr.norm * dot_scale(*g.c_maxnorm);
-            if constexpr (L2) nqs = l2_nqs(eqr.norm, dot_scale(*g.c_maxnorm));
-            float err = 0.f;
-            for (int e = wave; e < n; e += 4) {
-                const unsigned long long ent = coll_buf[(int64_t)slot * COLL_CAP + e];
-                const int row = (int)(ent >> 32);
-                const float s = exact_score<T, COS>(eqr, xc + (int64_t)row * ldc, d, lane);
-                if constexpr (DOT) err = fmaxf(err, (float)fabs((double)__uint_as_float((uint32_t)ent) - (double)s / nqs));
-                else if constexpr (L2) err = fmaxf(err, l2_err(__uint_as_float((uint32_t)ent), s, nqs, eqr.norm));
-                else err = fmaxf(err, fabsf(__uint_as_float((uint32_t)ent) - s));
-                if (lane == 0) {
-                    sc[e] = s;
-                    ix[e] = row;
-                }
-            }
-            if (lane == 0) s_err[wave] = err;
-            __syncthreads();
-            wg_select_topk(sc, ix, n, k, red_s, red_i, [&](int t, float s, int row) {
-                out_s[(int64_t)q * k + t] = s;
-                out_i[(int64_t)q * k + t] = row < 0 ? -1 : (int64_t)row + idx_offset;
-                s_top[t] = s;
-            });
-            __syncthreads();
-            // guard again with the threshold the collection used: every row that was NOT collected has an MFMA score below
-            // it, hence an exact score below thr + eps.  COS: eps is the query's bound from the first pass (and it must hold on
-            // everything that was re-scored here, else the inputs are inconsistent -> brute force); unit rows only: the largest
-            // difference seen on this larger sample with half the safety factor of the first pass (not below 1).
-            const float errmax = fmaxf(fmaxf(s_err[0], s_err[1]), fmaxf(s_err[2], s_err[3]));
-            float eps;
-            if constexpr (COS || DOT || L2) {
-                eps = g.flag_eps[slot];
-                if (!(errmax <= eps)) eps = INFINITY;
-            } else {
-                eps = fmaxf(fmaxf(0.5f * g.c1, 1.f) * errmax, g.floor);
-            }
-            const float thr = ordered_to_float(g.flag_thr[slot]);
-            if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)s_top[k - 1];
-            else if constexpr (L2) resolved = n >= k && l2_bound_low(thr, eps, nqs, eqr.norm) > l2_dist_up(-s_top[k - 1]);
-            else resolved = n >= k && (double)thr + (double)eps < (double)s_top[k - 1];
-        }
-        if (threadIdx.x == 0) {
-            if (!resolved) g.unres_q[atomicAdd(g.ctl + CTL_NUNRES, 1)] = q;
-            if (g.status) g.status[q] = resolved ? ST_WIDENED : ST_BRUTE;
-        }
-        __syncthreads();
-    }
-}
-
-// brute force, k <= 64: rows of a chunk in blocks of BF_SB, a running exact top-k per chunk; chunk lists pad with (-inf, -1)
-constexpr int BF_SB = 2048;
-constexpr int BF_MAXK = 64;
-
-template <typename T, bool COS>
-__global__ __launch_bounds__(256) void bf_partial_k64_kernel(int64_t Q, int64_t N, int rows_per_chunk,
-                                                             const T *__restrict__ xq, int64_t ldq,
-                                                             const T *__restrict__ xc, int64_t ldc, int d, int k,
-                                                             float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
-    __shared__ float sc[BF_SB + BF_MAXK];
-    __shared__ int ix[BF_SB + BF_MAXK];
-    __shared__ float top_s[BF_MAXK];
-    __shared__ int top_i[BF_MAXK];
-    __shared__ float red_s[4];
-    __shared__ int red_i[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nch = gridDim.x, chunk = blockIdx.x;
-    int nu = g.ctl[CTL_NUNRES];
-    nu = nu < Q ? nu : (int)Q;
-    const int64_t r0 = (int64_t)chunk * rows_per_chunk;
-    const int64_t r1 = r0 + rows_per_chunk < N ? r0 + rows_per_chunk : N;
-    for (int u = blockIdx.y; u < nu; u += gridDim.y) {
-        const int q = g.unres_q[u];
-        ExactQuery<T> eqr;
-        exact_load_query<T, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
-        if (threadIdx.x < BF_MAXK) {
-            top_s[threadIdx.x] = -INFINITY;
-            top_i[threadIdx.x] = -1;
-        }
-        __syncthreads();
-        for (int64_t b = r0; b < r1; b += BF_SB) {
-            const int nb = (int)(r1 - b < BF_SB ? r1 - b : BF_SB);
-            for (int e = wave; e < nb; e += 4) {
-                const float s = exact_score<T, COS>(eqr, xc + (b + e) * ldc, d, lane);
-                if (lane == 0) {
-                    sc[e] = s;
-                    ix[e] = (int)(b + e);
-                }
-            }
-            if (threadIdx.x < k) {   // the running list competes with the new block
-                sc[nb + threadIdx.x] = top_s[threadIdx.x];
-                ix[nb + threadIdx.x] = top_i[threadIdx.x];
-            }
-            __syncthreads();
-            wg_select_topk(sc, ix, nb + k, k, red_s, red_i, [&](int t, float s, int row) {
-                top_s[t] = s;
-                top_i[t] = row;
-            });
-            __syncthreads();
-        }
-        if (threadIdx.x < k) {
-            bf_s[((int64_t)u * nch + chunk) * k + threadIdx.x] = top_s[threadIdx.x];
-            bf_i[((int64_t)u * nch + chunk) * k + threadIdx.x] = top_i[threadIdx.x];
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void bf_merge_k64_kernel(int64_t Q, int nch, int k, const float *__restrict__ bf_s,
-                                                           const int *__restrict__ bf_i, float *__restrict__ out_s,
-                                                           int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
-    __shared__ float red_s[4];
-    __shared__ int red_i[4];
-    int nu = g.ctl[CTL_NUNRES];
-    nu = nu < Q ? nu : (int)Q;
-    for (int u = blockIdx.x; u < nu; u += gridDim.x) {
-        const int q = g.unres_q[u];
-        wg_select_topk(bf_s + (int64_t)u * nch * k, bf_i + (int64_t)u * nch * k, nch * k, k, red_s, red_i,
-                       [&](int t, float s, int row) {
-                           out_s[(int64_t)q * k + t] = s;
-                           out_i[(int64_t)q * k + t] = row < 0 ? -1 : (int64_t)row + idx_offset;
-                       });
-        if (threadIdx.x == 0 && g.status) g.status[q] = ST_BRUTE;
-    }
-}
-
 // k > 28: every query goes to the widening pass (or straight to the brute-force pass: all_brute).  gthr[q] = B, the k-th
 // largest block maximum = a lower bound of the k-th best MFMA score: k rows score >= B on the MFMA, hence >= B - eps exactly,
 // so the k-th best EXACT score is >= B - eps and every row of the exact top-k has an MFMA score >= B - 2 eps: that is the
@@ -1197,7 +985,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
 }
 
 // =====================================================================================================
-// Sorted lists in LDS (sl_*): what the widening pass, the brute-force pass (any k up to 1 024) and tsim_topk_merge_strided
+// Sorted lists in LDS (sl_*): what the widening pass and the brute-force pass (every k, 1 .. 1 024) and tsim_topk_merge_strided
 // with k_out > 64 keep their entries in.  Lists are sorted by (score desc, index asc), new entries are sorted with a bitonic
 // network and merged in by rank (each entry's place in the other list by binary search), never selected one round at a time.
 // Padding is (-inf, PAD): it ranks behind every real entry, a real entry with score -inf included; NaN scores become padding
@@ -1475,7 +1263,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
 //               kp >= k entries in LDS (only rows ahead of its k-th entry are sorted and merged in); writes the first k,
 //               sorted, padding (-inf, INT_MAX) included.
 //   bf_merge:   one workgroup per slot merges the chunk lists and writes the query's final list.
-// HBM-bound (N*d*4 bytes per query); last resort, and the serving path for k > 28 on small shards.
+// HBM-bound (N*d*4 bytes per query); last resort for every k, and the serving path for k > 28 on small shards.
 // =====================================================================================================
 template <typename T, bool COS>
 __global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, int rows_per_chunk,
@@ -1808,7 +1596,6 @@ constexpr int TOPK_MAX_LISTS = 28;   // largest k the list kernels (KL = 32) ser
 constexpr int TOPK_MAX_K = 64;       // largest k of tsim_cosine_topk_ex / tsim_dot_topk_ex / tsim_cosine_topk_workspace_bytes
 constexpr int TOPK_LARGE_MAX_K = TSIM_TOPK_MAX_K;   // largest k of the _large entries
 static_assert(TOPK_LARGE_MAX_K == SL_MAX_K, "LDS lists of the brute-force kernels");
-static_assert(TOPK_MAX_K == BF_MAXK && COLL_CAP == 1024, "the k <= 64 kernels: plan_workspace gives cap = 1 024 there");
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1955,9 +1742,6 @@ static void with_score_mode(int sm, const SearchOperands &o, F f) {
 // when there is nothing to do)
 static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N, const SearchOperands &o, int k, float *out_s,
                        int64_t *out_i, int64_t idx_offset, const GuardArgs &g, bool run_collect, hipStream_t st) {
-    // k <= 64 keeps its arg-max kernels (same workspace: w.cap = COLL_CAP there) until the sorted-list ones, which give the same
-    // bits, have been measured against them at these k
-    const bool k64 = k <= TOPK_MAX_K;
     if (run_collect) {
         TopkPlan cp;
         plan_collect(Q, N, o.ld, &cp);
@@ -1973,12 +1757,8 @@ static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N
         with_score_mode(sm, o, [&](auto x, auto smc) {
             using T = typename decltype(x)::row_t;
             constexpr int SM = decltype(smc)::value;
-            if (k64)
-                hipLaunchKernelGGL((widen_finalize_k64_kernel<T, SM>), dim3(wg), dim3(256), 0, st, coll.buf, coll.cnt, Q, N, x.xq,
-                                   x.ldq, x.xc, x.ldc, x.d, k, out_s, out_i, idx_offset, g);
-            else
-                hipLaunchKernelGGL((widen_finalize_kernel<T, SM>), dim3(wg), dim3(256), (size_t)w.cap * 8, st, coll.buf, coll.cnt,
-                                   w.cap, Q, x.xq, x.ldq, x.xc, x.ldc, x.d, k, out_s, out_i, idx_offset, g);
+            hipLaunchKernelGGL((widen_finalize_kernel<T, SM>), dim3(wg), dim3(256), (size_t)w.cap * 8, st, coll.buf, coll.cnt, w.cap, Q,
+                               x.xq, x.ldq, x.xc, x.ldc, x.d, k, out_s, out_i, idx_offset, g);
         });
         TSIM_HIP_CHECK(hipGetLastError());
     }
@@ -1989,17 +1769,12 @@ static int search_tail(int sm, const SearchWs &w, char *ws, int64_t Q, int64_t N
     with_score_mode(sm, o, [&](auto x, auto smc) {
         using T = typename decltype(x)::row_t;
         constexpr bool COS = decltype(smc)::value == SM_COS;
-        if (k64)
-            hipLaunchKernelGGL((bf_partial_k64_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, x.xq, x.ldq,
-                               x.xc, x.ldc, x.d, k, bf_s, bf_i, g);
-        else
-            hipLaunchKernelGGL((bf_partial_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, x.xq, x.ldq,
-                               x.xc, x.ldc, x.d, k, w.kp, bf_s, bf_i, g);
+        hipLaunchKernelGGL((bf_partial_kernel<T, COS>), dim3(w.bf_nch, us), dim3(256), 0, st, Q, N, w.bf_rows, x.xq, x.ldq, x.xc,
+                           x.ldc, x.d, k, w.kp, bf_s, bf_i, g);
     });
     TSIM_HIP_CHECK(hipGetLastError());
     const unsigned mg = (unsigned)(Q < 1024 ? Q : 1024);
-    if (k64) hipLaunchKernelGGL(bf_merge_k64_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, bf_s, bf_i, out_s, out_i, idx_offset, g);
-    else hipLaunchKernelGGL(bf_merge_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s, bf_i, out_s, out_i, idx_offset, g);
+    hipLaunchKernelGGL(bf_merge_kernel, dim3(mg), dim3(256), 0, st, Q, w.bf_nch, k, w.kp, bf_s, bf_i, out_s, out_i, idx_offset, g);
     TSIM_HIP_CHECK(hipGetLastError());
     if (sm == SM_L2) {   // every kernel above wrote -dist^2 (and -inf padding)
         const int64_t n = Q * k;
