@@ -10,7 +10,8 @@
 //   x0, x1 [Tp, H]   residual stream (LayerNorm outputs)      qkv [Tp, 3H]   fused Q|K|V projections
 //   ctx    [Tp, H]   attention output                         h1  [Tp, F]    GELU(FFN1)
 // Weights bf16 in nn.Linear layout [out, in] (K contiguous for both GEMM operands); embedding tables,
-// biases and LayerNorm parameters float32.
+// biases and LayerNorm parameters float32.  (Hidden 384, BERT family: qkv, h1 and, between the layers, x0 / x1 are block-packed,
+// see packed_off / group_off.)
 #include <math.h>
 #include <cmath>
 
@@ -41,6 +42,14 @@ namespace tsim {
 // =====================================================================================================
 __device__ __forceinline__ int64_t packed_off(int64_t t, int f, int W) {   // element offset of (t, f), f a multiple of 8 here
     return ((t >> 5) * (W >> 3) + (f >> 3)) * 256 + (t & 31) * 8 + (f & 7);
+}
+// The residual stream x0 / x1 [T, 384] moves in 16-byte groups of 8 features per lane (the resident fragments of gemm_xres2, the
+// residual reads and result stores of the LayerNorm GEMMs).  BYTE offset of group g (features 8 g .. 8 g + 7) of token row t in a
+// [rows, W] bf16 buffer, row-major or block-packed: the one address rule of every such access.  Linear in g, so a lane computes
+// group_off(t, g0) once and adds multiples of the wave-uniform group_off(0, 1): in the packed layout the 32 rows x 2 groups
+// of one wave instruction are one contiguous KiB instead of 32 pieces of 32 B.
+__device__ __forceinline__ int64_t group_off(int64_t t, int g, int W, int packed) {
+    return packed ? packed_off(t, 8 * g, W) * 2 : (t * W + 8 * g) * 2;
 }
 
 // =====================================================================================================
@@ -146,8 +155,10 @@ template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int EPI, int NST = 2
 __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
     const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, const float *__restrict__ bias,
     const bf16_t *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
-    bf16_t *__restrict__ out, int M, int N, int K, int mtiles, int ntiles, const bf16_t *__restrict__ Wimg, int xpacked) {
+    bf16_t *__restrict__ out, int M, int N, int K, int mtiles, int ntiles, const bf16_t *__restrict__ Wimg, int xpacked,
+    int respacked, int opacked) {
     // xpacked: X is in the block-packed layout (packed_off; BM is a multiple of 32, so a tile starts on a block)
+    // respacked / opacked (EPI_RES_LN): so is the residual / goes the output (group_off)
     // Wimg (optional, BN == N): W re-laid at load time as the LDS images of its k-tiles (pack_gemm_w_kernel), so that every
     // DMA piece of the W operand is 1 KiB of CONTIGUOUS memory.  From row-major W a piece gathers 8 rows x 128 B, and that
     // shape streams from L2 at half the rate (tools/microbench/dma_stream: 60 vs 115-128 GB/s per CU); W is 3/4 of the bytes
@@ -335,15 +346,18 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
         // 43 % of this kernel.)
         float *red = reinterpret_cast<float *>(smem);            // [2][WAVES_N][BM] partial sums
         __builtin_amdgcn_s_barrier();                            // every wave is past its last fragment read
+        const int g0 = (n0 + wn * TN) / 8 + h;                   // the lane's first 8-feature group
+        const int rgs = (int)group_off(0, 1, N, respacked), ogs = (int)group_off(0, 1, N, opacked);
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
             const int64_t m = m0 + wm * TM + j * 32 + r;
             const int64_t mr = m < M ? m : M - 1;
+            const char *rp = reinterpret_cast<const char *>(res) + group_off(mr, g0, N, respacked);
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
                 for (int gq = 0; gq < 4; gq += 2) {
-                    const uint4 o = *reinterpret_cast<const uint4 *>(res + mr * N + n0 + wn * TN + i * 32 + 8 * gq + 8 * h);
+                    const uint4 o = *reinterpret_cast<const uint4 *>(rp + (i * 4 + gq) * rgs);
                     auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
                     const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
@@ -411,13 +425,12 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
                     pk[2 * gq + 1] = pack_bf16x2(y2, y3);
                 }
                 const int64_t m = m0 + wm * TM + j * 32 + r;
+                char *op = reinterpret_cast<char *>(out) + group_off(m, g0, N, opacked);
 #pragma unroll
                 for (int gq = 0; gq < 4; gq += 2) {
                     auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
-                    if (m < M)
-                        *reinterpret_cast<uint4 *>(out + m * N + n0 + wn * TN + i * 32 + 8 * gq + 8 * h) =
-                            make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                    if (m < M) *reinterpret_cast<uint4 *>(op + (i * 4 + gq) * ogs) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
                 }
             }
         }
@@ -452,13 +465,14 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 #ifdef TSIM_PP_STAMPS
 // DIAGNOSTIC build only (python -m text_similarity_amd.build --stamps; tools/x2_stamps.py): cycles of wave 0 of gemm_xres2 per
-// workgroup: [0] steps, [1] wait (vmcnt + barrier), [3] fragment reads + MFMAs, [4] stores, [6] items.
-__device__ unsigned long long g_xr_stamps[8];
+// workgroup: [0] steps, [1] wait (vmcnt + barrier), [2] workgroups, [3] fragment reads + MFMAs, [4] stores, [5] activation
+// fragment (re)loads, [6] items, [7] number of (re)loads.  Slots 0-7: EPI_BIAS (QKV), 8-15: EPI_GELU (FFN1).
+__device__ unsigned long long g_xr_stamps[16];
 #define XR_T() __builtin_amdgcn_s_memtime()
 #ifndef TSIM_XR_STAMP_TID
 #define TSIM_XR_STAMP_TID 0   // 256: wave 4, the SIMD partner of wave 0
 #endif
-#define XR_ACC(i, v) do { if (threadIdx.x == TSIM_XR_STAMP_TID) atomicAdd(&g_xr_stamps[i], (unsigned long long)(v)); } while (0)
+#define XR_ACC(i, v) do { if (threadIdx.x == TSIM_XR_STAMP_TID) atomicAdd(&g_xr_stamps[(i) + (EPI == EPI_GELU ? 8 : 0)], (unsigned long long)(v)); } while (0)
 #else
 #define XR_T() 0ull
 #define XR_ACC(i, v) do { } while (0)
@@ -489,7 +503,8 @@ __device__ __forceinline__ void ff_static_for(std::integer_sequence<int, I...>, 
 // MEASURED: QKV 73.1 -> 71.2 us, FFN1 119.6 -> 115.3 us (-3 %): the wait is mostly not a per-barrier constant.
 constexpr int X2_BN = 96, X2_BK = 128, X2_NSTAGE = 6, X2_PD = 4, X2_KG = 3, X2_NSUB = 3;
 
-template <int EPI, bool PK>   // PK: the output goes out in the block-packed layout (see packed_off)
+// PK: the output goes out in the block-packed layout (see packed_off); XPK: X comes in it (group_off)
+template <int EPI, bool PK, bool XPK>
 __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W,
                                                          const float *__restrict__ bias, bf16_t *__restrict__ out,
                                                          int M, int N, int items_total) {
@@ -584,18 +599,24 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
 
 #pragma unroll
     for (int i = 0; i < X2_PD; ++i) issue(i, i);
-    [[maybe_unused]] unsigned x2_n = 0, x2_w = 0, x2_c = 0, x2_e = 0;   // (diagnostic build only; 32-bit sums: a workgroup runs < 2^32 cycles)
+    [[maybe_unused]] unsigned x2_n = 0, x2_w = 0, x2_c = 0, x2_e = 0, x2_r = 0, x2_nr = 0;   // (diagnostic build only; 32-bit sums: a workgroup runs < 2^32 cycles)
     auto run_item = [&](f32x16 (&cur)[X2_NSUB], f32x16 (&old)[X2_NSUB], int item, auto with_old) __attribute__((always_inline)) {
         constexpr bool OLD = decltype(with_old)::value;
         if (item / ntiles != cur_mb) {                        // wave-uniform: new token block -> reload fragments
+            [[maybe_unused]] const unsigned long long xr0 = XR_T();
             cur_mb = item / ntiles;
             m0 = cur_mb * BMX + wave * 32;
-            const bf16_t *xp = X + (int64_t)(m0 + r) * K + 8 * h;
+            // fragment s = groups 2 s + h of row m0 + r (packed: rows past M of the last block are the buffer's padding)
+            const char *xp = reinterpret_cast<const char *>(X) + group_off(m0 + r, h, K, XPK);
+            constexpr int xgs = XPK ? 512 : 16;               // group_off(0, 1, ..)
 #pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 16 * s);
+            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 2 * s * xgs);
 #pragma unroll
             for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));   // retire these ordinary loads here
             young1 = young2 = young3 = 0;                     // ... and with them (vmcnt(0)) everything older
+#ifdef TSIM_PP_STAMPS
+            x2_r += (unsigned)(XR_T() - xr0); x2_nr += 1;
+#endif
         }
         const int n0 = (item % ntiles) * X2_BN;
         // accumulators start from the bias: cur[i][q] belongs to feature n0 + 32 i + (q & 3) + 8 (q >> 2) + 4 h
@@ -713,7 +734,7 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
         }
     };
     if (lastA) flush(accA); else flush(accB);
-    XR_ACC(0, x2_n); XR_ACC(1, x2_w); XR_ACC(3, x2_c); XR_ACC(4, x2_e); XR_ACC(6, x2_n / 3);
+    XR_ACC(0, x2_n); XR_ACC(1, x2_w); XR_ACC(3, x2_c); XR_ACC(4, x2_e); XR_ACC(6, x2_n / 3); XR_ACC(2, 1); XR_ACC(5, x2_r); XR_ACC(7, x2_nr);
 }
 
 // W [BN rows, K] -> per k-tile of BK the W-region LDS image of gemm_bf16_kernel<.., BN, BK, ..>: 16-byte slot sl of the image
@@ -763,8 +784,10 @@ template <int NW, int LR_NST>
 __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
                                                                const float *__restrict__ bias, const bf16_t *__restrict__ res,
                                                                const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                               float eps, bf16_t *__restrict__ out, int M, int K, int xpacked) {
-    // xpacked: X is in the block-packed layout (packed_off): FFN2's operand h1
+                                                               float eps, bf16_t *__restrict__ out, int M, int K, int xpacked,
+                                                               int respacked, int opacked) {
+    // xpacked: X is in the block-packed layout (packed_off): FFN2's operand h1.  respacked / opacked: so is the residual / goes the
+    // output (group_off; one base and 32-bit offsets: M * 768 < 4 GiB, checked by the launcher)
     constexpr int N = 384, XBYTES = NW * 32 * LR_BK * 2, STAGE = XBYTES + LR_WBYTES;
     constexpr int XP = XBYTES / 1024, PIECES = STAGE / 1024, PPW = PIECES / NW;   // pieces 0..XP-1: X, the rest: W
     static_assert(PIECES % NW == 0 && XP == 2 * NW, "every wave issues two X pieces and PPW - 2 W pieces per k-tile");
@@ -866,11 +889,12 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
     const int64_t m = m0 + wave * 32 + r;
     const bool live = m < M;
     const int64_t mr = live ? m : M - 1;
+    const uint32_t ro = (uint32_t)group_off(mr, h, N, respacked), rgs = (uint32_t)group_off(0, 1, N, respacked);
 #pragma unroll
     for (int t = 0; t < 12; ++t)
 #pragma unroll
         for (int gq = 0; gq < 4; gq += 2) {
-            const uint4 o = *reinterpret_cast<const uint4 *>(res + mr * N + 32 * t + 8 * gq + 8 * h);
+            const uint4 o = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(res) + (ro + (4 * t + gq) * rgs));
             auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
             const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
@@ -912,6 +936,7 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         else
             rstd = 1.0f / sqrtf(tot / (float)N + eps);
     }
+    const uint32_t oo = (uint32_t)group_off(m, h, N, opacked), ogs = (uint32_t)group_off(0, 1, N, opacked);
 #pragma unroll
     for (int t = 0; t < 12; ++t) {
         uint32_t pk[8];
@@ -930,7 +955,8 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         for (int gq = 0; gq < 4; gq += 2) {
             auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
             auto s1w = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
-            if (live) *reinterpret_cast<uint4 *>(out + m * N + 32 * t + 8 * gq + 8 * h) = make_uint4(s0[0], s1w[0], s0[1], s1w[1]);
+            if (live)
+                *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (oo + (4 * t + gq) * ogs)) = make_uint4(s0[0], s1w[0], s0[1], s1w[1]);
         }
     }
 }
@@ -1698,7 +1724,7 @@ static int mpnet_bucket(int rel, int num_buckets) {
 template <int BM, int BN, int BK, int WM, int WN, int EPI, int NST = 2>
 static int launch_gemm(const bf16_t *X, const bf16_t *W, const float *bias, const bf16_t *res, const float *gamma,
                        const float *beta, float eps, bf16_t *out, int M, int N, int K, hipStream_t st,
-                       const bf16_t *Wimg = nullptr, bool xpacked = false) {
+                       const bf16_t *Wimg = nullptr, bool xpacked = false, bool respacked = false, bool opacked = false) {
     constexpr int lds = gemm_lds_bytes<BM, BN, BK, WM, WN, NST>();
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = gemm_bf16_kernel<BM, BN, BK, WM, WN, EPI, NST>;
@@ -1709,17 +1735,17 @@ static int launch_gemm(const bf16_t *X, const bf16_t *W, const float *bias, cons
     const int grid = ((mtiles + 7) / 8) * 8 * ntiles;
     if (Wimg && ntiles != 1) return fail(TSIM_EINVAL, "gemm: a packed W image needs BN == N");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), lds, st, X, W, bias, res, gamma, beta, eps, out, M, N, K,
-                       mtiles, ntiles, Wimg, xpacked ? 1 : 0);
+                       mtiles, ntiles, Wimg, xpacked ? 1 : 0, respacked ? 1 : 0, opacked ? 1 : 0);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-template <int EPI, bool PK>
+template <int EPI, bool PK, bool XPK = false>
 static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_t *out, int M, int N, hipStream_t st) {
     constexpr int lds = X2_NSTAGE * X2_BN * X2_BK * 2 + 8192;   // ring | bias (N <= 2048)
     if (N > 2048) return fail(TSIM_EUNSUPPORTED, "gemm_xres2: N=%d > 2048", N);
     if (((int64_t)M + 256) * N * 2 >= (1ll << 32)) return fail(TSIM_EUNSUPPORTED, "gemm_xres2: output of %d x %d exceeds 4 GiB", M, N);
-    auto kern = gemm_xres2_kernel<EPI, PK>;
+    auto kern = gemm_xres2_kernel<EPI, PK, XPK>;
     static DevOnce lds_once;
     TSIM_MAX_LDS(lds_once, kern, lds);
     const int items = ((M + 255) / 256) * (N / X2_BN);
@@ -1755,7 +1781,7 @@ constexpr int LT_PF = 12;   // k-steps in flight (4 loads each: vmcnt <= 63 allo
 template <int PF>
 __device__ __forceinline__ void lt_gemm_slice(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32,
                                               const float *__restrict__ bias, const bf16_t *__restrict__ res, int M, int K,
-                                              int xpacked, int wn, int m0, f32x16 (&acc)[3]) {
+                                              int xpacked, int respacked, int wn, int m0, f32x16 (&acc)[3]) {
     constexpr int N = 384, NT = 3;
     const int lane = threadIdx.x & 63;
     const int r = lane & 31, h = lane >> 5;
@@ -1820,11 +1846,12 @@ __device__ __forceinline__ void lt_gemm_slice(const bf16_t *__restrict__ X, cons
     {
         const int64_t m = m0 + r;
         const int64_t mr = m < M ? m : M - 1;
+        const uint32_t ro = (uint32_t)group_off(mr, wn * 12 + h, N, respacked), rgs = (uint32_t)group_off(0, 1, N, respacked);
 #pragma unroll
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int gq = 0; gq < 4; gq += 2) {
-                const uint4 o = *reinterpret_cast<const uint4 *>(res + mr * N + wn * 96 + i * 32 + 8 * gq + 8 * h);
+                const uint4 o = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(res) + (ro + (4 * i + gq) * rgs));
                 auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
                 const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
@@ -1844,7 +1871,7 @@ __device__ __forceinline__ void lt_gemm_slice(const bf16_t *__restrict__ X, cons
 // four feature waves of the row block call it in one workgroup (red: its 2 x 4 x 32 floats of LDS).
 __device__ __forceinline__ void lt_layernorm(f32x16 (&acc)[3], float *red, const float *__restrict__ gamma,
                                              const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int wn,
-                                             int m0) {
+                                             int m0, int opacked) {
     constexpr int N = 384, NT = 3, WAVES_N = 4, BM = 32;
     const int lane = threadIdx.x & 63;
     const int r = lane & 31, h = lane >> 5;
@@ -1894,12 +1921,13 @@ __device__ __forceinline__ void lt_layernorm(f32x16 (&acc)[3], float *red, const
             pk[2 * gq + 1] = pack_bf16x2(y2, y3);
         }
         const int64_t m = m0 + r;
+        const uint32_t oo = (uint32_t)group_off(m, wn * 12 + h, N, opacked), ogs = (uint32_t)group_off(0, 1, N, opacked);
 #pragma unroll
         for (int gq = 0; gq < 4; gq += 2) {
             auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
             if (m < M)
-                *reinterpret_cast<uint4 *>(out + m * N + wn * 96 + i * 32 + 8 * gq + 8 * h) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+                *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (oo + (4 * i + gq) * ogs)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
         }
     }
 }
@@ -1907,13 +1935,14 @@ __device__ __forceinline__ void lt_layernorm(f32x16 (&acc)[3], float *red, const
 template <int PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_tail_gemm_kernel(
     const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
-    const float *__restrict__ gamma, const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int K, int xpacked) {
+    const float *__restrict__ gamma, const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int M, int K, int xpacked,
+    int respacked, int opacked) {
     __shared__ float red[2 * 4 * 32];
     const int wn = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m0 = blockIdx.x * 32;
     f32x16 acc[3];
-    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, wn, m0, acc);
-    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0);
+    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, respacked, wn, m0, acc);
+    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0, opacked);
 }
 
 // =====================================================================================================
@@ -1931,12 +1960,12 @@ constexpr int LS_MAX_BLOCKS = 256;   // ln_tail's limit of 8 192 rows: the image
 template <int PF, int S>
 __global__ __launch_bounds__(256 / S) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_split_gemm_kernel(
     const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
-    float4 *__restrict__ img, int M, int K, int xpacked) {
+    float4 *__restrict__ img, int M, int K, int xpacked, int respacked) {
     const int blk = blockIdx.x / S, sl = blockIdx.x % S;
     const int wn = __builtin_amdgcn_readfirstlane(sl * (4 / S) + (threadIdx.x >> 6));
     const int m0 = blk * 32;
     f32x16 acc[3];
-    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, wn, m0, acc);
+    lt_gemm_slice<PF>(X, Wimg32, bias, res, M, K, xpacked, respacked, wn, m0, acc);
     float4 *dst = img + (int64_t)(blk * 4 + wn) * 12 * 64 + (threadIdx.x & 63);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -1947,7 +1976,7 @@ __global__ __launch_bounds__(256 / S) __attribute__((amdgpu_waves_per_eu(1, 1)))
 
 __global__ __launch_bounds__(256) void ln_split_finish_kernel(const float4 *__restrict__ img, const float *__restrict__ gamma,
                                                               const float *__restrict__ beta, float eps, bf16_t *__restrict__ out,
-                                                              int M) {
+                                                              int M, int opacked) {
     __shared__ float red[2 * 4 * 32];
     const int wn = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m0 = blockIdx.x * 32;
@@ -1963,31 +1992,33 @@ __global__ __launch_bounds__(256) void ln_split_finish_kernel(const float4 *__re
             acc[i][4 * gq + 2] = v.z;
             acc[i][4 * gq + 3] = v.w;
         }
-    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0);
+    lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0, opacked);
 }
 
 // The LayerNorm GEMM of width 384 for M <= 8 192 rows: ln_tail, or ln_split where blocks x slices still fit one round of the
 // chip's 256 CUs (img: LS_MAX_BLOCKS row blocks of image; null: ln_tail only)
 static int ln_tail_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
-                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, float *img) {
+                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, float *img, bool respacked,
+                        bool opacked) {
+    const int rpk = respacked ? 1 : 0, opk = opacked ? 1 : 0;
     if (K % (16 * LT_PF) != 0) return fail(TSIM_EUNSUPPORTED, "ln_tail_gemm: K=%d", K);
     const int nb = (M + 31) / 32;
     const int S = !img || nb > LS_MAX_BLOCKS ? 1 : nb <= 64 ? 4 : nb <= 128 ? 2 : 1;
     if (S == 1) {
         hipLaunchKernelGGL(ln_tail_gemm_kernel<LT_PF>, dim3((unsigned)nb), dim3(256), 0, st, X, Wimg32, bias, res, gamma, beta, eps,
-                           out, M, K, xpacked ? 1 : 0);
+                           out, M, K, xpacked ? 1 : 0, rpk, opk);
         TSIM_HIP_CHECK(hipGetLastError());
         return TSIM_OK;
     }
     float4 *im = reinterpret_cast<float4 *>(img);
     if (S == 4)
         hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 4>), dim3((unsigned)(nb * 4)), dim3(64), 0, st, X, Wimg32, bias, res, im, M, K,
-                           xpacked ? 1 : 0);
+                           xpacked ? 1 : 0, rpk);
     else
         hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 2>), dim3((unsigned)(nb * 2)), dim3(128), 0, st, X, Wimg32, bias, res, im, M,
-                           K, xpacked ? 1 : 0);
+                           K, xpacked ? 1 : 0, rpk);
     TSIM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(ln_split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, im, gamma, beta, eps, out, M);
+    hipLaunchKernelGGL(ln_split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, im, gamma, beta, eps, out, M, opk);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
@@ -1995,15 +2026,16 @@ static int ln_tail_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias
 // LayerNorm GEMM of width 384 over rows [0, M) in workgroups of NW * 32 token rows (the last one may be partial)
 template <int NW, int NST>
 static int ln_rows_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
-                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked) {
+                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, bool respacked, bool opacked) {
     constexpr int lds = NST * (NW * 32 * LR_BK * 2 + LR_WBYTES);   // <8, 3>: 120 KiB
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = ln_rows_gemm_kernel<NW, NST>;
     static DevOnce lds_once;
     TSIM_MAX_LDS(lds_once, kern, lds);
     if (K % LR_BK != 0 || K < NST * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: K=%d", K);
+    if (((int64_t)M + 256) * 768 >= (1ll << 32)) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: %d rows of 384 exceed 4 GiB", M);
     hipLaunchKernelGGL(kern, dim3((unsigned)((M + NW * 32 - 1) / (NW * 32))), dim3(NW * 64), lds, st, X, Wimg32, bias, res, gamma,
-                       beta, eps, out, M, K, xpacked ? 1 : 0);
+                       beta, eps, out, M, K, xpacked ? 1 : 0, respacked ? 1 : 0, opacked ? 1 : 0);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
@@ -2027,8 +2059,10 @@ static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const 
 static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, const bf16_t *res,
                        const float *gamma, const float *beta, float eps, bf16_t *out, int M, int N, int K, float *ybuf,
                        hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false,
-                       float *lnimg = nullptr) {
-    if (xpacked && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed operand layout is a hidden-384 form");
+                       float *lnimg = nullptr, bool respacked = false, bool opacked = false) {
+    // respacked / opacked: the residual comes / the output goes in the block-packed layout (the residual stream between the layers
+    // of the hidden-384 BERT path).  Row offsets below are multiples of 32: a block starts at the same element in both layouts.
+    if ((xpacked || respacked || opacked) && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed layouts are a hidden-384 form");
     if (ybuf && N >= 512 && N % 256 == 0 && gemm_pp_supported(N, K)) {
         // wide rows: a workgroup cannot own whole 768-feature rows at a 256-token tile, so the projection writes
         // fp32 sums and a row kernel adds the residual and normalises (HBM-bound, 8 B per element)
@@ -2048,7 +2082,7 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                 if (use > 0) {
                     // (a four-slot ring with the second half of the waves issuing behind their MFMAs measured equal, 68.5 vs 66-68 us
                     // per launch)
-                    int rc = ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked);
+                    int rc = ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked, respacked, opacked);
                     const int m1 = use * 256;
                     if (rc || m1 == M) return rc;
                     X += (int64_t)m1 * K; res += (int64_t)m1 * N; out += (int64_t)m1 * N; M -= m1;
@@ -2057,7 +2091,7 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                 // few rows (a remainder, or a small batch): one round of 32-row workgroups (or of 32-row x feature-slice
                 // workgroups) that stream W straight into registers
                 if (M <= LS_MAX_BLOCKS * 32 && K % (16 * LT_PF) == 0)
-                    return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked, lnimg);
+                    return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked, lnimg, respacked, opacked);
             }
             // 128-token tiles, one workgroup per CU: mt tiles take ceil(mt/256) rounds and a nearly empty last round costs a full
             // one.  A small remainder is launched separately with 64-token tiles (2x more, 2x shorter workgroups).
@@ -2067,7 +2101,7 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
             // (four 32-k ring slots instead of two 64-k ones — prefetch distance 3 — measured 2.5 % SLOWER per forward: the deep
             // path issues a k-tile's DMA pieces in one burst ahead of the MFMAs instead of behind each k-step's)
             auto main_launch = [&](int rows) {
-                return launch_gemm<128, 384, 64, 2, 4, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, rows, N, K, st, Wimg, xpacked);
+                return launch_gemm<128, 384, 64, 2, 4, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, rows, N, K, st, Wimg, xpacked, respacked, opacked);
             };
             if (rem > 0 && rem <= 96 && (full > 0 || after_rows)) {
                 const int m_main = full * 128;
@@ -2078,7 +2112,7 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
                 // remainder launch: 64 token rows (eight waves) per workgroup.  (A three-slot ring measured no different:
                 // 2.744-2.751 vs 2.751-2.752 ms per forward.)
                 return launch_gemm<64, 384, 64, 2, 4, EPI_RES_LN>(X + (int64_t)m_main * K, W, bias, res + (int64_t)m_main * N,
-                                                                  gamma, beta, eps, out + (int64_t)m_main * N, M - m_main, N, K, st, Wimg, xpacked);
+                                                                  gamma, beta, eps, out + (int64_t)m_main * N, M - m_main, N, K, st, Wimg, xpacked, respacked, opacked);
             }
             return main_launch(M);
         }
@@ -2245,9 +2279,9 @@ extern "C" int tsim_gemm_mxfp8(const void *xq, const void *xs, const void *wq, c
 }
 
 #ifdef TSIM_PP_STAMPS
-extern "C" int tsim_debug_xr_stamps(unsigned long long *out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(tsim::g_xr_stamps), 64) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(tsim::g_xr_stamps), z, 64) != hipSuccess) return 1; }
+extern "C" int tsim_debug_xr_stamps(unsigned long long *out16, int reset) {
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(tsim::g_xr_stamps), 128) != hipSuccess) return 1;
+    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(tsim::g_xr_stamps), z, 128) != hipSuccess) return 1; }
     return 0;
 }
 #endif
@@ -2350,12 +2384,18 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
         const dim3 agrid((unsigned)(((B + 7) / 8) * 8), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks);   // xcd_map = 1
         for (int l = 0; l < c.num_layers; ++l) {
             const tsim_encoder::Layer &L = e->layers[l];
+            // The residual stream is block-packed between the layers of the pk path (group_off): x1 always, x0 except as the
+            // embedding kernel leaves it (layer 0 reads it row-major) and as the last layer leaves it (pooling, heads and the
+            // last_hidden copy read it row-major).
+            const bool x0pk = pk && l > 0, x0pk_next = pk && l + 1 < c.num_layers;
             if (mx) {   // projections on MXFP8 operands (v_mfma_scale_f32_32x32x64_f8f6f4); x0's image comes fused from the
                         // previous layer's LayerNorm kernel, for layer 0 from the stand-alone quantiser
                 if (l == 0 && (rc = quant_mx(e->x0, T, H, e->aq, e->as, st))) return rc;
                 if ((rc = gemm_pp_mx(PP_EPI_BIAS, e->aq, e->as, L.qqkv, 1, L.sqkv, L.bqkv, e->qkv, nullptr, T, 3 * H, H, st))) return rc;
             } else if (pk) {
-                if ((rc = gemm_xres2<EPI_BIAS, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st))) return rc;
+                rc = x0pk ? gemm_xres2<EPI_BIAS, true, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st)
+                          : gemm_xres2<EPI_BIAS, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
+                if (rc) return rc;
             } else if ((rc = gemm_plain<EPI_BIAS>(e->x0, L.wqkv, L.pqkv, L.bqkv, e->qkv, T, 3 * H, H, st))) return rc;
 #define ATT(D)                                                                                                 \
     do {                                                                                                       \
@@ -2381,11 +2421,11 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
                 if ((rc = res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, c.ln_eps, e->x0, e->aq, e->as, T, H, st))) return rc;
                 continue;
             }
-            if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg))) return rc;
+            if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk))) return rc;
             if (pk) {
-                if ((rc = gemm_xres2<EPI_GELU, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
+                if ((rc = gemm_xres2<EPI_GELU, true, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
             } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;
-            if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg))) return rc;
+            if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, x0pk_next))) return rc;
         }
         if (last_hidden_bf16)
             TSIM_HIP_CHECK(hipMemcpyAsync(last_hidden_bf16, e->x0, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));

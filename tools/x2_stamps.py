@@ -13,7 +13,7 @@ enc = NativeEncoder.from_preset("all-MiniLM-L6-v2", max_tokens=int(cu[-1]), max_
 fd, cd = torch.from_numpy(flat).cuda(), torch.from_numpy(cu).cuda()
 pos, cols = enc.positions(fd, cd)
 L = C.CDLL(_lib.lib()._name)
-buf = (C.c_ulonglong * 8)()
+buf = (C.c_ulonglong * 16)()
 for _ in range(3):
     enc.forward_packed(fd, cd, pos, cols, int(np.diff(cu).max()))
 torch.cuda.synchronize()
@@ -21,7 +21,8 @@ L.tsim_debug_xr_stamps(buf, 1)
 enc.forward_packed(fd, cd, pos, cols, int(np.diff(cu).max()))
 torch.cuda.synchronize()
 L.tsim_debug_xr_stamps(buf, 0)
-steps, wait, _, comp, store, pro, items = [buf[i] for i in range(7)]
-print(f"gemm_xres2 (QKV + FFN1, 6 layers): {steps} steps, {items} items of the stamped wave over all workgroups; cycles per step: "
-      f"wait (vmcnt + barrier) {wait / steps:.0f}, reads + MFMAs + shadow epilogue {comp / steps:.0f}, swap + stores {store / steps:.0f}; "
-      f"per item: fragment reload / bias init {pro / max(items, 1):.0f}")
+for name, o in (("QKV", 0), ("FFN1", 8)):
+    steps, wait, wgs, comp, store, reload, items, nreload = [buf[o + i] for i in range(8)]
+    print(f"gemm_xres2 {name} (6 layers): {steps} steps, {items} items, {wgs} workgroups (the stamped wave of each); cycles per step: "
+          f"wait (vmcnt + barrier) {wait / steps:.0f}, reads + MFMAs + shadow epilogue {comp / steps:.0f}, swap + stores {store / steps:.0f}; "
+          f"activation fragment (re)loads: {nreload / max(wgs, 1):.2f} per workgroup, {reload / max(nreload, 1):.0f} cycles each")
