@@ -9,8 +9,8 @@
 //
 // Work.  cand is cut at the absolute positions 0, S, 2S, ... (S = TSIM_LIST_SLICE = SL_NB: one slice is one block of the running
 // list).  CSR: workgroup (slice g, y) serves the queries whose lists meet [gS, (g+1)S), found by binary search in the cleaned
-// lims.  For each it scores the entries of the query inside the slice, sorts the ones that can matter (sl_offer / sl_absorb, as
-// bf_partial_kernel) and writes k sorted entries to the pair's slot.  The host knows T, not the list lengths: with monotone lims
+// lims.  For each it passes the entries of the query inside the slice through a running list (SlList, as bf_partial_kernel)
+// and writes its first k entries to the pair's slot.  The host knows T, not the list lengths: with monotone lims
 // the pairs (g, q) that exist form a staircase, g + q is unique among them, and Q + ceil(T / S) slots hold them all.  Shared:
 // workgroup (chunk c, q) walks a chunk of whole slices with the running list, slot q * nch + c (list_shared_chunks).
 // list_merge_kernel, one workgroup per query, joins the query's slots in blocks of SL_NB entries (several slots per block when k
@@ -85,9 +85,7 @@ __global__ __launch_bounds__(256) void list_partial_kernel(int64_t Q, int64_t N,
                                                            const int64_t *__restrict__ L, int64_t nch, int64_t spc, int k, int kp,
                                                            float *__restrict__ ls_s, int *__restrict__ ls_i,
                                                            int32_t *__restrict__ status) {
-    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
-    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
-    __shared__ int s_nb;
+    SlList<int, false> top = sl_shared_list<int, false>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t c = blockIdx.x;   // chunk: spc slices (CSR: one)
     const int64_t s0 = c * spc * TSIM_LIST_SLICE, s1 = s0 + spc * TSIM_LIST_SLICE < Tn ? s0 + spc * TSIM_LIST_SLICE : Tn;
@@ -105,17 +103,11 @@ __global__ __launch_bounds__(256) void list_partial_kernel(int64_t Q, int64_t N,
         }
         ExactQuery<T> eqr;
         exact_load_query<T, COS>(eqr, xq + q * ldq, d, lane);
-        for (int t = threadIdx.x; t < kp; t += 256) {
-            top_s[t] = -INFINITY;
-            top_i[t] = 0x7fffffff;
-        }
-        if (threadIdx.x == 0) s_nb = 0;
-        __syncthreads();
+        top.reset(kp);
         bool beyond = false;
         for (int64_t b = e0; b < e1; b += SL_NB) {   // (CSR: once)
             const int nb = (int)(e1 - b < SL_NB ? e1 - b : SL_NB);
-            const float ws = top_s[k - 1];
-            const int wi = top_i[k - 1];
+            const SlBound<int> w = top.bound(k);
             for (int g0 = wave * 64; g0 < nb; g0 += 256) {   // wave-uniform
                 const int e = g0 + lane;
                 const int nvalid = nb - g0 < 64 ? nb - g0 : 64;
@@ -124,22 +116,15 @@ __global__ __launch_bounds__(256) void list_partial_kernel(int64_t Q, int64_t N,
                 const int row = usable ? (int)r : 0;   // clamped: the row is loaded and scored, the score dropped
                 const float s = wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
                 if (e < nb) {
-                    if (usable) sl_offer(blk_s, blk_i, &s_nb, s, row, ws, wi);
+                    if (usable) top.offer(s, row, w);
                     beyond |= r >= N;
                 }
             }
-            __syncthreads();
-            const int n = s_nb;
-            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
-            if (threadIdx.x == 0) s_nb = 0;
-            __syncthreads();
+            top.flush(kp);
         }
         if (status && __any(beyond) && lane == 0) atomicOr(status + q, TSIM_LIST_ST_ROW);
         const int64_t slot = L ? q + c : q * nch + c;
-        for (int t = threadIdx.x; t < k; t += 256) {
-            ls_s[slot * k + t] = top_s[t];
-            ls_i[slot * k + t] = top_i[t];
-        }
+        top.store_raw(ls_s, ls_i, slot * k, k);
         __syncthreads();
     }
 }
@@ -149,9 +134,7 @@ __global__ __launch_bounds__(256) void list_merge_kernel(int64_t Q, int64_t Tn, 
                                                          int kp, const float *__restrict__ ls_s, const int *__restrict__ ls_i,
                                                          float *__restrict__ out_s, int64_t *__restrict__ out_i,
                                                          int64_t idx_offset) {
-    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
-    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
-    __shared__ int s_nb;
+    SlList<int, false> top = sl_shared_list<int, false>();
     for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
         int64_t slot0 = q * nch, ns = Tn > 0 ? nch : 0;
         if (L) {
@@ -159,32 +142,17 @@ __global__ __launch_bounds__(256) void list_merge_kernel(int64_t Q, int64_t Tn, 
             ns = hi > lo ? (hi - 1) / TSIM_LIST_SLICE - lo / TSIM_LIST_SLICE + 1 : 0;
             slot0 = q + lo / TSIM_LIST_SLICE;
         }
-        for (int t = threadIdx.x; t < kp; t += 256) {
-            top_s[t] = -INFINITY;
-            top_i[t] = 0x7fffffff;
-        }
-        if (threadIdx.x == 0) s_nb = 0;
-        __syncthreads();
+        top.reset(kp);
         const int64_t E = ns * k;   // the slots of a query are consecutive: E entries from slot0 * k on
         for (int64_t b0 = 0; b0 < E; b0 += SL_NB) {
-            const float ws = top_s[k - 1];
-            const int wi = top_i[k - 1];
+            const SlBound<int> w = top.bound(k);
             for (int64_t e = b0 + threadIdx.x; e < E && e < b0 + SL_NB; e += 256) {
                 const int i = ls_i[slot0 * k + e];
-                if (i != 0x7fffffff) sl_offer(blk_s, blk_i, &s_nb, ls_s[slot0 * k + e], i, ws, wi);
+                if (i != sl_pad<int>()) top.offer(ls_s[slot0 * k + e], i, w);
             }
-            __syncthreads();
-            const int n = s_nb;
-            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
-            if (threadIdx.x == 0) s_nb = 0;
-            __syncthreads();
+            top.flush(kp);
         }
-        for (int t = threadIdx.x; t < k; t += 256) {
-            const int row = top_i[t];
-            const float s = NEG ? -top_s[t] : top_s[t];   // (-(-inf) = +inf: the Euclidean padding)
-            out_s[q * k + t] = s;
-            out_i[q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
-        }
+        top.store_result<NEG>(out_s, out_i, q * k, k, idx_offset);
         __syncthreads();
     }
 }
@@ -239,8 +207,7 @@ static int list_topk(int sm, const char *what, const float *eq_f32, int64_t ldq_
     int64_t *clean = lims ? reinterpret_cast<int64_t *>(ws + w.clean) : nullptr;
     float *ls_s = reinterpret_cast<float *>(ws + w.ls_s);
     int *ls_i = reinterpret_cast<int *>(ws + w.ls_i);
-    int kp = 64;
-    while (kp < k) kp <<= 1;
+    const int kp = sl_list_len(k);
     if (lims || out_status) {
         hipLaunchKernelGGL(list_prep_kernel, dim3(1), dim3(LIST_PREP_T), 0, st, Q, T, lims, clean, out_status);
         TSIM_HIP_CHECK(hipGetLastError());

@@ -990,9 +990,24 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
 // network and merged in by rank (each entry's place in the other list by binary search), never selected one round at a time.
 // Padding is (-inf, PAD): it ranks behind every real entry, a real entry with score -inf included; NaN scores become padding
 // (the list kernels never select them either).
+//
+// The running list (SlList, one per workgroup of 256 threads) holds the best kp >= k entries seen so far, kp a power of two
+// (sl_list_len).  Its protocol, per query: reset; then for every block of at most SL_NB candidate entries: every thread reads
+// bound(k), the list's k-th entry, BEFORE anyone offers (the list does not change until flush); offer() appends the entries
+// that rank before the bound to the block through an LDS counter; flush() reads the count BEHIND a barrier (so n > 0 is
+// workgroup-uniform), sorts the block and merges it in, and resets the counter BEHIND the absorb, then a barrier.  After the
+// last flush the first k entries are the exact top-k; store_raw / sl_store_result write them, and the kernel puts a barrier
+// before the next query's reset.
 // =====================================================================================================
 constexpr int SL_MAX_K = 1024;   // TSIM_TOPK_MAX_K
 constexpr int SL_NB = 1024;      // entries of one block merged into a running list
+
+// length of the running list for k entries: the smallest power of two >= max(k, 64)
+static inline int sl_list_len(int k) {
+    int kp = 64;
+    while (kp < k) kp <<= 1;
+    return kp;
+}
 
 template <typename I>
 __device__ __forceinline__ I sl_pad();
@@ -1127,28 +1142,93 @@ __device__ __forceinline__ void sl_merge(float *ts, I *ti, int kp, const float *
     }
 }
 
-// Append (s, i) to the block b (LDS counter *nb) when it ranks before the list's k-th entry (ws, wi); NaN is dropped.
-template <typename I>
-__device__ __forceinline__ void sl_offer(float *bs, I *bi, int *nb, float s, I i, float ws, I wi) {
-    if (s == s && key_before(s, i, ws, wi)) {
-        const int p = atomicAdd(nb, 1);
-        bs[p] = s;
-        bi[p] = i;
+// The first k entries of a sorted list as the caller sees them: padding becomes (-inf, -1), a row gets idx_offset; NEG (the
+// Euclidean space, whose lists hold -dist^2) negates the scores, padding +inf.
+template <bool NEG, typename I>
+__device__ __forceinline__ void sl_store_result(const float *s, const I *ix, int k, float *out_s, int64_t *out_i, int64_t at,
+                                                int64_t idx_offset) {
+    for (int t = threadIdx.x; t < k; t += 256) {
+        const I row = ix[t];
+        const bool pad = row == sl_pad<I>();
+        out_s[at + t] = pad ? (NEG ? INFINITY : -INFINITY) : NEG ? -s[t] : s[t];
+        out_i[at + t] = pad ? -1 : (int64_t)row + idx_offset;
     }
 }
 
-// Sort the block (n entries, padded to a power of two) and merge it into the running list; workgroup-uniform n.
+template <typename I>
+struct SlBound {   // the list's k-th entry
+    float s;
+    I i;
+};
+// The running list (protocol: the block comment above): a handle on the LDS arrays that sl_shared_list declares.  The arrays
+// are separate __shared__ variables: as members of one __shared__ struct the same code measured up to 1.9 % slower (DESIGN.md,
+// "One running-list type").
 template <typename I, bool DEDUP>
-__device__ __forceinline__ void sl_absorb(float *ts, I *ti, int kp, float *bs, I *bi, int n, float *m_s, I *m_i, int *wsum) {
-    int np = 1;
-    while (np < n) np <<= 1;
-    for (int t = n + threadIdx.x; t < np; t += 256) {
-        bs[t] = -INFINITY;
-        bi[t] = sl_pad<I>();
+struct SlList {
+    float *top_s, *blk_s, *m_s;   // m_s, m_i, wsum: sl_merge's scratch, null unless DEDUP
+    I *top_i, *blk_i, *m_i;
+    int *nb, *wsum;               // nb: entries offered to the block since the last flush
+
+    __device__ __forceinline__ void reset(int kp) {
+        for (int t = threadIdx.x; t < kp; t += 256) {
+            top_s[t] = -INFINITY;
+            top_i[t] = sl_pad<I>();
+        }
+        if (threadIdx.x == 0) *nb = 0;
+        __syncthreads();
     }
-    __syncthreads();
-    sl_sort(bs, bi, np);
-    sl_merge<I, DEDUP>(ts, ti, kp, bs, bi, np, m_s, m_i, wsum);
+    __device__ __forceinline__ SlBound<I> bound(int k) const { return {top_s[k - 1], top_i[k - 1]}; }
+    // append (s, i) to the block when it ranks before the bound; NaN is dropped
+    __device__ __forceinline__ void offer(float s, I i, SlBound<I> w) {
+        if (s == s && key_before(s, i, w.s, w.i)) {
+            const int p = atomicAdd(nb, 1);
+            blk_s[p] = s;
+            blk_i[p] = i;
+        }
+    }
+    // sort the block (padded to a power of two) and merge it into the list
+    __device__ __forceinline__ void flush(int kp) {
+        __syncthreads();
+        const int n = *nb;
+        if (n > 0) {   // workgroup-uniform
+            int np = 1;
+            while (np < n) np <<= 1;
+            for (int t = n + threadIdx.x; t < np; t += 256) {
+                blk_s[t] = -INFINITY;
+                blk_i[t] = sl_pad<I>();
+            }
+            __syncthreads();
+            sl_sort(blk_s, blk_i, np);
+            sl_merge<I, DEDUP>(top_s, top_i, kp, blk_s, blk_i, np, m_s, m_i, wsum);
+        }
+        if (threadIdx.x == 0) *nb = 0;
+        __syncthreads();
+    }
+    // the first k entries as they are, padding included (a chunk list)
+    __device__ __forceinline__ void store_raw(float *dst_s, I *dst_i, int64_t at, int k) const {
+        for (int t = threadIdx.x; t < k; t += 256) {
+            dst_s[at + t] = top_s[t];
+            dst_i[at + t] = top_i[t];
+        }
+    }
+    template <bool NEG>
+    __device__ __forceinline__ void store_result(float *out_s, int64_t *out_i, int64_t at, int k, int64_t idx_offset) const {
+        sl_store_result<NEG>(top_s, top_i, k, out_s, out_i, at, idx_offset);
+    }
+};
+// The workgroup's list: one set of arrays per (I, DEDUP), 16 388 B, with the scratch of DEDUP 49 172 B.
+template <typename I, bool DEDUP>
+__device__ __forceinline__ SlList<I, DEDUP> sl_shared_list() {
+    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
+    __shared__ I top_i[SL_MAX_K], blk_i[SL_NB];
+    __shared__ int nb;
+    if constexpr (DEDUP) {
+        __shared__ float m_s[SL_MAX_K + SL_NB];
+        __shared__ I m_i[SL_MAX_K + SL_NB];
+        __shared__ int wsum[4];
+        return {top_s, blk_s, m_s, top_i, blk_i, m_i, &nb, wsum};
+    }
+    return {top_s, blk_s, nullptr, top_i, blk_i, nullptr, &nb, nullptr};
 }
 
 // Exact scores of the rows held by lanes 0 .. nvalid-1 (my_i), eight at a time (exact_score_batch: the bits of exact_score).
@@ -1202,7 +1282,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             for (int g0 = wave * 64; g0 < np; g0 += 256) {   // wave-uniform
                 const int e = g0 + lane;
                 float s = -INFINITY;
-                int row = 0x7fffffff;
+                int row = sl_pad<int>();
                 if (g0 < n) {
                     const unsigned long long ent = coll_buf[(int64_t)slot * cap + (e < n ? e : g0)];
                     const int my_row = (int)(ent >> 32);
@@ -1226,11 +1306,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
             if (lane == 0) s_err[wave] = err;
             __syncthreads();
             sl_sort(sc, ix, np);
-            for (int t = threadIdx.x; t < k; t += 256) {
-                const int row = ix[t];
-                out_s[(int64_t)q * k + t] = row == 0x7fffffff ? -INFINITY : sc[t];
-                out_i[(int64_t)q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
-            }
+            sl_store_result<false>(sc, ix, k, out_s, out_i, (int64_t)q * k, idx_offset);
             // guard again with the threshold the collection used: every row that was NOT collected has an MFMA score below
             // it, hence an exact score below thr + eps.  COS: eps is the query's bound from the first pass (and it must hold on
             // everything that was re-scored here, else the inputs are inconsistent -> brute force); unit rows only: the largest
@@ -1244,7 +1320,7 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
                 eps = fmaxf(fmaxf(0.5f * g.c1, 1.f) * errmax, g.floor);
             }
             const float thr = ordered_to_float(g.flag_thr[slot]);
-            const float sk = ix[k - 1] == 0x7fffffff ? -INFINITY : sc[k - 1];
+            const float sk = ix[k - 1] == sl_pad<int>() ? -INFINITY : sc[k - 1];
             if constexpr (DOT) resolved = n >= k && dot_bound_up(thr, eps, nqs) < (double)sk;
             else if constexpr (L2) resolved = n >= k && l2_bound_low(thr, eps, nqs, eqr.norm) > l2_dist_up(-sk);
             else resolved = n >= k && (double)thr + (double)eps < (double)sk;
@@ -1259,10 +1335,9 @@ __global__ __launch_bounds__(256) void widen_finalize_kernel(const unsigned long
 
 // =====================================================================================================
 // Brute-force exact pass for the queries nothing else resolved: every row of the shard is scored exactly.
-//   bf_partial: workgroup (chunk c, slot u) scores the chunk's rows in blocks of SL_NB and keeps a running sorted list of
-//               kp >= k entries in LDS (only rows ahead of its k-th entry are sorted and merged in); writes the first k,
-//               sorted, padding (-inf, INT_MAX) included.
-//   bf_merge:   one workgroup per slot merges the chunk lists and writes the query's final list.
+//   bf_partial: workgroup (chunk c, slot u) passes the chunk's rows in blocks of SL_NB through a running list and writes its
+//               first k entries, padding included.
+//   bf_merge:   one workgroup per slot passes the chunk lists through a running list, one per block, and writes the result.
 // HBM-bound (N*d*4 bytes per query); last resort for every k, and the serving path for k > 28 on small shards.
 // =====================================================================================================
 template <typename T, bool COS>
@@ -1270,9 +1345,7 @@ __global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, i
                                                          const T *__restrict__ xq, int64_t ldq,
                                                          const T *__restrict__ xc, int64_t ldc, int d, int k, int kp,
                                                          float *__restrict__ bf_s, int *__restrict__ bf_i, GuardArgs g) {
-    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
-    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
-    __shared__ int s_nb;
+    SlList<int, false> top = sl_shared_list<int, false>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = gridDim.x, chunk = blockIdx.x;
     int nu = g.ctl[CTL_NUNRES];
@@ -1283,33 +1356,20 @@ __global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, i
         const int q = g.unres_q[u];
         ExactQuery<T> eqr;
         exact_load_query<T, COS>(eqr, xq + (int64_t)q * ldq, d, lane);
-        for (int t = threadIdx.x; t < kp; t += 256) {
-            top_s[t] = -INFINITY;
-            top_i[t] = 0x7fffffff;
-        }
-        if (threadIdx.x == 0) s_nb = 0;
-        __syncthreads();
+        top.reset(kp);
         for (int64_t b = r0; b < r1; b += SL_NB) {
             const int nb = (int)(r1 - b < SL_NB ? r1 - b : SL_NB);
-            const float ws = top_s[k - 1];
-            const int wi = top_i[k - 1];
+            const SlBound<int> w = top.bound(k);
             for (int g0 = wave * 64; g0 < nb; g0 += 256) {   // wave-uniform
                 const int e = g0 + lane;
                 const int nvalid = nb - g0 < 64 ? nb - g0 : 64;
                 const int row = (int)(b + (e < nb ? e : g0));
                 const float s = wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
-                if (e < nb) sl_offer(blk_s, blk_i, &s_nb, s, row, ws, wi);
+                if (e < nb) top.offer(s, row, w);
             }
-            __syncthreads();
-            const int n = s_nb;
-            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
-            if (threadIdx.x == 0) s_nb = 0;
-            __syncthreads();
+            top.flush(kp);
         }
-        for (int t = threadIdx.x; t < k; t += 256) {
-            bf_s[((int64_t)u * nch + chunk) * k + t] = top_s[t];
-            bf_i[((int64_t)u * nch + chunk) * k + t] = top_i[t];
-        }
+        top.store_raw(bf_s, bf_i, ((int64_t)u * nch + chunk) * k, k);
         __syncthreads();
     }
 }
@@ -1317,79 +1377,47 @@ __global__ __launch_bounds__(256) void bf_partial_kernel(int64_t Q, int64_t N, i
 __global__ __launch_bounds__(256) void bf_merge_kernel(int64_t Q, int nch, int k, int kp, const float *__restrict__ bf_s,
                                                        const int *__restrict__ bf_i, float *__restrict__ out_s,
                                                        int64_t *__restrict__ out_i, int64_t idx_offset, GuardArgs g) {
-    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB];
-    __shared__ int top_i[SL_MAX_K], blk_i[SL_NB];
-    __shared__ int s_nb;
+    SlList<int, false> top = sl_shared_list<int, false>();
     int nu = g.ctl[CTL_NUNRES];
     nu = nu < Q ? nu : (int)Q;
     for (int u = blockIdx.x; u < nu; u += gridDim.x) {
         const int q = g.unres_q[u];
-        for (int t = threadIdx.x; t < kp; t += 256) {
-            top_s[t] = -INFINITY;
-            top_i[t] = 0x7fffffff;
-        }
-        if (threadIdx.x == 0) s_nb = 0;
-        __syncthreads();
+        top.reset(kp);
         for (int c = 0; c < nch; ++c) {
-            const float ws = top_s[k - 1];
-            const int wi = top_i[k - 1];
+            const SlBound<int> w = top.bound(k);
             for (int t = threadIdx.x; t < k; t += 256) {
                 const int64_t at = ((int64_t)u * nch + c) * k + t;
-                sl_offer(blk_s, blk_i, &s_nb, bf_s[at], bf_i[at], ws, wi);
+                top.offer(bf_s[at], bf_i[at], w);
             }
-            __syncthreads();
-            const int n = s_nb;
-            if (n > 0) sl_absorb<int, false>(top_s, top_i, kp, blk_s, blk_i, n, nullptr, nullptr, nullptr);
-            if (threadIdx.x == 0) s_nb = 0;
-            __syncthreads();
+            top.flush(kp);
         }
-        for (int t = threadIdx.x; t < k; t += 256) {
-            const int row = top_i[t];
-            out_s[(int64_t)q * k + t] = row == 0x7fffffff ? -INFINITY : top_s[t];
-            out_i[(int64_t)q * k + t] = row == 0x7fffffff ? -1 : (int64_t)row + idx_offset;
-        }
+        top.store_result<false>(out_s, out_i, (int64_t)q * k, k, idx_offset);
         if (threadIdx.x == 0 && g.status) g.status[q] = ST_BRUTE;
         __syncthreads();
     }
 }
 
-// topk_merge for 64 < k_out <= 1024: one workgroup per query; the nlists * k_in entries pass in blocks of SL_NB through the
-// running list (kp >= k_out) with duplicates of (score, index) dropped.  Same output as topk_merge_kernel.
+// topk_merge for 64 < k_out <= 1024: one workgroup per query; the nlists * k_in entries pass in blocks of SL_NB through a
+// running list that drops duplicates of (score, index).  Same output as topk_merge_kernel.
 __global__ __launch_bounds__(256) void topk_merge_large_kernel(const float *__restrict__ scores, const int64_t *__restrict__ idx,
                                                                int nlists, int64_t Q, int k_in, int k_out, int kp,
                                                                int64_t lstride_s, int64_t lstride_i, float *__restrict__ out_s,
                                                                int64_t *__restrict__ out_i) {
-    __shared__ float top_s[SL_MAX_K], blk_s[SL_NB], m_s[SL_MAX_K + SL_NB];
-    __shared__ int64_t top_i[SL_MAX_K], blk_i[SL_NB], m_i[SL_MAX_K + SL_NB];
-    __shared__ int s_nb, wsum[4];
+    SlList<int64_t, true> top = sl_shared_list<int64_t, true>();
     const int64_t E = (int64_t)nlists * k_in;
     for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-        for (int t = threadIdx.x; t < kp; t += 256) {
-            top_s[t] = -INFINITY;
-            top_i[t] = INT64_MAX;
-        }
-        if (threadIdx.x == 0) s_nb = 0;
-        __syncthreads();
+        top.reset(kp);
         for (int64_t e0 = 0; e0 < E; e0 += SL_NB) {
-            const float ws = top_s[k_out - 1];
-            const int64_t wi = top_i[k_out - 1];
+            const SlBound<int64_t> w = top.bound(k_out);
             for (int64_t e = e0 + threadIdx.x; e < E && e < e0 + SL_NB; e += 256) {
                 const int l = (int)(e / k_in), j = (int)(e % k_in);
                 const int64_t off = q * k_in + j;
                 const int64_t i = idx[(int64_t)l * lstride_i + off];
-                if (i >= 0) sl_offer(blk_s, blk_i, &s_nb, scores[(int64_t)l * lstride_s + off], i, ws, wi);
+                if (i >= 0) top.offer(scores[(int64_t)l * lstride_s + off], i, w);
             }
-            __syncthreads();
-            const int n = s_nb;
-            if (n > 0) sl_absorb<int64_t, true>(top_s, top_i, kp, blk_s, blk_i, n, m_s, m_i, wsum);
-            if (threadIdx.x == 0) s_nb = 0;
-            __syncthreads();
+            top.flush(kp);
         }
-        for (int t = threadIdx.x; t < k_out; t += 256) {
-            const bool pad = top_i[t] == INT64_MAX;
-            out_s[q * k_out + t] = pad ? -INFINITY : top_s[t];
-            out_i[q * k_out + t] = pad ? -1 : top_i[t];
-        }
+        top.store_result<false>(out_s, out_i, q * k_out, k_out, 0);
         __syncthreads();
     }
 }
@@ -1628,8 +1656,7 @@ static void plan_workspace(int64_t Q, int64_t N, int k, SearchWs *w) {
     }
     w->cap = 1024;
     while (w->cap < 4 * k) w->cap <<= 1;
-    w->kp = 64;
-    while (w->kp < k) w->kp <<= 1;
+    w->kp = sl_list_len(k);
     const bool large = k > TOPK_MAX_K;
     const int64_t min_rows = large ? SL_NB : 256, within_budget = large ? (int64_t)(BF_BUDGET / ((size_t)Q * k * 8)) : 64;
     const int64_t nch = std::max<int64_t>(1, std::min<int64_t>({64, (N + min_rows - 1) / min_rows, within_budget}));
@@ -2048,10 +2075,8 @@ extern "C" int tsim_topk_merge_strided(const float *scores, const int64_t *idx, 
                  (long long)list_stride_idx, (long long)(Q * k_in));
     if (Q == 0) return TSIM_OK;
     if (k_out > TOPK_MAX_K && k_out <= TOPK_LARGE_MAX_K) {   // sort-and-merge in LDS instead of k_out rounds of a wave max
-        int kp = 64;
-        while (kp < k_out) kp <<= 1;
         hipLaunchKernelGGL(topk_merge_large_kernel, dim3((unsigned)(Q < 4096 ? Q : 4096)), dim3(256), 0, as_stream(stream), scores,
-                           idx, nlists, Q, k_in, k_out, kp, list_stride_scores, list_stride_idx, out_scores, out_idx);
+                           idx, nlists, Q, k_in, k_out, sl_list_len(k_out), list_stride_scores, list_stride_idx, out_scores, out_idx);
         TSIM_HIP_CHECK(hipGetLastError());
         return TSIM_OK;
     }
