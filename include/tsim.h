@@ -387,6 +387,46 @@ int tsim_l2_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const flo
                       int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Binary embeddings: sign-bit codes, exact Hamming top-k and the re-score of its candidates (sentence-transformers'
+ * `quantize_embeddings(precision="ubinary")` with `semantic_search_faiss(..., rescore=True)`; faiss' `IndexBinaryFlat`).
+ * Codes.  A code row is the `np.packbits(x > 0, axis=1)` bytes of the float row: element 8j is bit 7 of byte j, the last byte
+ * is zero-filled.  1 <= d <= 1024.  Rows lie tsim_code_bytes(d) bytes apart — ceil(d / 8) rounded up to a multiple of 16 (0 for a
+ * d outside 1..1024), so every row is read with 16-byte loads — or further: ldq, ldc and ld_code are in BYTES, multiples of 16
+ * and >= tsim_code_bytes(d), and the rows start on a 16-byte boundary (else TSIM_EINVAL).  The bytes from ceil(d / 8) to
+ * tsim_code_bytes(d) are zero in everything the library writes; what it READS may hold anything at bit positions >= d: they
+ * never count.
+ * tsim_pack_sign_rows: x [rows, d] float32 (TSIM_F32) or bf16 (TSIM_BF16), row stride ld_in >= d elements -> codes, the first
+ * tsim_code_bytes(d) bytes of each row.  The bit is x > 0: 0.0, -0.0, NaN, -inf and negative subnormals give 0, positive
+ * subnormals and +inf 1.  HBM-bound on x.
+ * tsim_hamming_topk: the k rows of c_codes [N] nearest to each row of q_codes [Q] by Hamming distance over the first d bits.
+ * Exact: the true top-k, ordered by (distance asc, row asc).  out_dist [Q, k] int32, out_idx [Q, k] int64 = row + idx_offset;
+ * N < k is padded with (INT32_MAX, -1) as faiss pads, N == 0 is legal (c_codes may be NULL then).  1 <= k <= TSIM_TOPK_MAX_K,
+ * N < 2^31 - 64, Q <= 8 x 65535 per call.  One pass over the codes per group of min(8, ceil(Q / 4)) queries (each lane loads its
+ * row once and compares it with the group's query codes, held in scalar registers), a running sorted list per (chunk of rows,
+ * query), one merge workgroup per query.  workspace: tsim_hamming_topk_workspace_bytes(Q, N, k) — pure host, 0 for Q <= 0, N < 0 or k outside
+ * 1..TSIM_TOPK_MAX_K, non-decreasing in each argument, never above 64 MiB + what one list per query takes.  The call reads
+ * nothing back from the device.
+ * tsim_sign_rescore_topk: the second stage.  Each query's candidates cand [Q, m] int64 (row numbers) are scored with the
+ * float32 query eq_f32 [Q, d] (row stride ldq_f32 >= d elements) against the +-1 expansion of their codes, s_j = bit_j ? +1 : -1:
+ * score = float32(sum_j q_j s_j), the sum in float64 in the canonical lane order of the exact scores above (lane l adds elements
+ * l, l + 64, .., then the xor butterfly 32 .. 1; restated in oracle/search_ref._lane_sum) and rounded once — for d <= 768 the
+ * bits tsim_dot_list_topk gives on the unpacked +-1 float32 matrix.  out_scores [Q, k] float32, out_idx [Q, k] int64 =
+ * row + idx_offset, ordered by (score desc, row asc), short lists padded with (-inf, -1).  A negative entry of cand is padding and
+ * is skipped (the out_idx of tsim_hamming_topk can be passed as it stands, idx_offset 0); an entry >= N is never dereferenced and
+ * sets TSIM_LIST_ST_ROW in out_status[q] (int32 [Q], may be NULL; written, not accumulated); a row listed twice is returned
+ * twice.  m >= 0, 1 <= k <= TSIM_TOPK_MAX_K.  No workspace. */
+int tsim_code_bytes(int d);
+int tsim_pack_sign_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, uint8_t *codes, int64_t ld_code,
+                        void *stream);
+size_t tsim_hamming_topk_workspace_bytes(int64_t Q, int64_t N, int k);
+int tsim_hamming_topk(const uint8_t *q_codes, int64_t ldq, int64_t Q, const uint8_t *c_codes, int64_t ldc, int64_t N, int d, int k,
+                      int32_t *out_dist, int64_t *out_idx, int64_t idx_offset, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int tsim_sign_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const uint8_t *c_codes, int64_t ldc, int64_t N, int d,
+                           const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
+                           int32_t *out_status, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

@@ -205,17 +205,29 @@ class _EncodeMixin:
         return [t.cpu().numpy() for t in out] if output_np else out
 
     def encode_text(self, documents: List[str], output_np: bool = False,
-                    output_value: str = "sentence_embedding") -> Union[torch.Tensor, np.ndarray, list]:
+                    output_value: str = "sentence_embedding", precision: str = "float32") -> Union[torch.Tensor, np.ndarray, list]:
         """sentence_encoder.py:136-173: sort by character length, encode in batches, un-sort, stack.
         Returns float32 [N, H] on params.device (or numpy when ``output_np``), un-normalised.
         ``output_value="token_embeddings"`` (the sentence-transformers name) returns instead a list of [len_i, H] float32
         tensors in input order: the final hidden states of each sentence's tokens, special tokens included, no padding.
         The host tokenizer is the end-to-end bottleneck of this path, so it runs one chunk AHEAD on a
         host thread: chunk i+1 is tokenised while the GPU encodes chunk i (kernel launches are asynchronous; fast
-        tokenizers release the GIL).  ``self.last_encode_stats`` holds the split of the wall time."""
+        tokenizers release the GIL).  ``self.last_encode_stats`` holds the split of the wall time.
+        ``precision="ubinary"`` (sentence-transformers' keyword and layout) returns instead uint8 [N, ceil(H / 8)]:
+        ``np.packbits(embeddings > 0, axis=1)`` of the same pooled rows, packed on the device (``ops.pack_sign_rows``) — what
+        ``GpuBinaryIndex.add_items`` and ``ops.codes_from_packbits`` take.  Any width up to 1024."""
         import time
         if output_value not in ("sentence_embedding", "token_embeddings"):
             raise ValueError(f"output_value must be 'sentence_embedding' or 'token_embeddings', got {output_value!r}")
+        if precision not in ("float32", "ubinary"):
+            raise ValueError(f"precision must be 'float32' or 'ubinary', got {precision!r}")
+        if precision == "ubinary":
+            if output_value != "sentence_embedding":
+                raise ValueError("precision='ubinary' quantises sentence embeddings, not token embeddings")
+            from .. import ops
+            rows = self.encode_text(documents, output_np=False)
+            codes = ops.pack_sign_rows(rows)[:, :(rows.shape[1] + 7) // 8].contiguous()
+            return codes.cpu().numpy() if output_np else codes
         enc: NativeEncoder = self.context_embedder
         dev = enc.device
         n = len(documents)

@@ -452,6 +452,148 @@ def l2_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor,
 
 
 # ------------------------------------------------------------------------------------------------- exact range search
+# ------------------------------------------------------------------------------------------------- binary embeddings
+MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit codes
+
+
+def code_bytes(d: int) -> int:
+    """Bytes between the rows of a [rows, code_bytes(d)] uint8 code matrix: ceil(d / 8) rounded up to a multiple of 16."""
+    b = _lib.lib().tsim_code_bytes(int(d))
+    if b == 0:
+        raise ValueError(f"binary codes take 1 <= d <= {MAX_CODE_DIM}, got d={d}")
+    return b
+
+
+def pack_sign_rows(x: torch.Tensor) -> torch.Tensor:
+    """[rows, d] float32/bf16 -> uint8 [rows, code_bytes(d)]: the ``np.packbits(x > 0, axis=1)`` bytes of every row (element 8j
+    is bit 7 of byte j; sentence-transformers' ``precision="ubinary"``), zero from byte ceil(d / 8) on.  The bit is ``x > 0``:
+    0.0, -0.0, NaN, -inf and negative subnormals give 0.  Strided row views are read in place."""
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise ValueError("pack_sign_rows expects a 2-D tensor")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    rows, d = x.shape
+    cb = code_bytes(d)
+    out = torch.empty((rows, cb), dtype=torch.uint8, device=x.device)
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    if rows:
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().tsim_pack_sign_rows(x.data_ptr(), dt, rows, d, _row_stride(x), out.data_ptr(), cb, _stream(x)),
+                       "pack_sign_rows")
+    return out
+
+
+def codes_from_packbits(a, d: int, device=None) -> torch.Tensor:
+    """A ``[rows, ceil(d / 8)]`` uint8 array or tensor (``np.packbits(x > 0, axis=1)``, ``encode_text(precision="ubinary")``,
+    sentence-transformers' ubinary embeddings) -> the padded device layout uint8 [rows, code_bytes(d)].  A numpy array goes to
+    ``device`` (default: the current one); the unused bits of the last byte are cleared."""
+    cb = code_bytes(d)
+    nb = (int(d) + 7) // 8
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+    _need_gpu(a)
+    if a.dtype != torch.uint8 or a.dim() != 2 or a.shape[1] != nb:
+        raise ValueError(f"codes_from_packbits: expected uint8 [rows, {nb}] for d={d}, got {a.dtype} {tuple(a.shape)}")
+    out = torch.zeros((a.shape[0], cb), dtype=torch.uint8, device=a.device)
+    out[:, :nb] = a
+    if d % 8:
+        out[:, nb - 1] &= (0xFF00 >> (d % 8)) & 0xFF
+    return out
+
+
+def _check_codes(what, name, t, d, dev=None):
+    cb = code_bytes(d)
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] < cb
+            or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % 16) or t.data_ptr() % 16):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _need_gpu(t)
+        raise ValueError(f"{what}: {name} must be uint8 [rows, >= code_bytes({d})={cb}] on the device with unit inner stride, "
+                         "rows a multiple of 16 bytes apart and 16-byte aligned (pack_sign_rows / codes_from_packbits)")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {t.device})")
+    return t.stride(0) if t.shape[0] > 1 else (t.shape[1] // 16) * 16
+
+
+def hamming_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, idx_offset: int = 0,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Exact Hamming top-k over the first ``d`` bits of the code rows: dist [Q,k] int32, idx [Q,k] int64, ordered by
+    (distance asc, row asc); fewer than k rows are padded with (2**31 - 1, -1), as faiss' ``IndexBinaryFlat`` pads.
+    ``q_codes`` / ``c_codes``: uint8 from :func:`pack_sign_rows` or :func:`codes_from_packbits` (row views with a stride that is
+    a multiple of 16 bytes are read in place; bits at positions >= d are ignored).  1 <= k <= 1024, 1 <= d <= 1024.  Query sets
+    above MAX_QUERIES_PER_CALL rows are searched in slices.  ``out`` = (dist, idx): preallocated contiguous tensors."""
+    what = "hamming_topk"
+    _need_gpu(q_codes, c_codes)
+    dev = q_codes.device
+    ldq = _check_codes(what, "q_codes", q_codes, d)
+    ldc = _check_codes(what, "c_codes", c_codes, d, dev)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = q_codes.shape[0], c_codes.shape[0]
+    if out is not None:
+        dist, idx = out
+        _need_gpu(dist, idx)
+        if (dist.shape != (Q, k) or idx.shape != (Q, k) or dist.dtype != torch.int32 or idx.dtype != torch.int64
+                or not dist.is_contiguous() or not idx.is_contiguous() or dist.device != dev or idx.device != dev):
+            raise ValueError(f"{what}: out must be contiguous int32 / int64 [{Q}, {k}] tensors on {dev}")
+    else:
+        dist = torch.empty((Q, k), dtype=torch.int32, device=dev)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    if Q == 0:
+        return dist, idx
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_hamming_topk_workspace_bytes(step, N, k)
+        if nbytes == 0:
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k}")
+        ws = _workspace(dev, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = L.tsim_hamming_topk(q_codes.data_ptr() + q0 * ldq, ldq, nq, c_codes.data_ptr() if N else 0, ldc, N, int(d), k,
+                                     dist.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(),
+                                     _stream(q_codes))
+            _lib.check(rc, what)
+    return dist, idx
+
+
+def sign_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand: torch.Tensor, k: int, idx_offset: int = 0,
+                      return_status: bool = False):
+    """The second stage of a binary search: every query's candidates ``cand`` [Q, m] (row numbers; the ``idx`` of
+    :func:`hamming_topk` as it stands) scored with the FLOAT32 query against the +-1 expansion of the code rows, scores [Q,k] f32
+    and idx [Q,k] i64 ordered by (score desc, row asc), padded with (-inf, -1).  score = float32(sum_j q_j (2 bit_j - 1)) summed
+    in float64 in the library's canonical order — for d <= 768 the bits of :func:`dot_list_topk` on the unpacked matrix.
+    Negative entries are skipped; entries >= N are skipped and set ``LIST_ST_ROW`` in the status (``return_status``); a row
+    listed twice is returned twice."""
+    what = "sign_rescore_topk"
+    _need_gpu(eq_f32, c_codes, cand)
+    dev = eq_f32.device
+    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
+        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
+    ldc = _check_codes(what, "c_codes", c_codes, d, dev)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = eq_f32.shape[0], c_codes.shape[0]
+    if cand.dim() != 2 or cand.shape[0] != Q or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+        raise ValueError(f"{what}: cand must hold integers [{Q}, m]")
+    cand = cand.to(torch.int64).contiguous()
+    m = cand.shape[1]
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q:
+        with torch.cuda.device(dev):
+            rc = _lib.lib().tsim_sign_rescore_topk(eq_f32.data_ptr(), _row_stride(eq_f32), Q, c_codes.data_ptr() if N else 0, ldc, N,
+                                                   int(d), cand.data_ptr() if m else 0, m, k, scores.data_ptr(), idx.data_ptr(),
+                                                   idx_offset, status.data_ptr() if return_status else 0, _stream(eq_f32))
+            _lib.check(rc, what)
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins
 MAX_RANGE_QUERIES_PER_CALL = 4096       # the workspace holds RANGE_SLOT_CAP entries of 8 bytes per query: 64 MiB per call
