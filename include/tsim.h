@@ -651,6 +651,13 @@ int tsim_encoder_forward_spans(tsim_encoder *enc, const int32_t *tok_ids, const 
 #define TSIM_ENC_ERR_SPAN 16   /* tsim_encoder_forward_spans: a position, sequence index or list offset of the span table */
 int tsim_encoder_error_flags(tsim_encoder *enc, int32_t *flags_host, void *stream);
 
+/* Introspection (host only, no launch): the work items of workgroup b of G in a chained LayerNorm-GEMM + projection launch of the
+ * hidden-384 layer, as the kernel computes them.  The launch has one workgroup per whole 256-token block (blocks == G, anything
+ * else is refused): workgroup b owns block b, all ntiles = N / 96 items of it; the rem_blocks * ntiles items of the blocks behind them are cut into G contiguous shares.  An item
+ * is block * ntiles + feature tile.  Returns the number of items of workgroup b (negative: bad arguments) and writes the first
+ * min(count, cap) of them. */
+int tsim_chain_items_host(int blocks, int rem_blocks, int ntiles, int G, int b, int32_t *items, int cap);
+
 /* ---- tokenizer (host code, no GPU): BERT WordPiece for pure-ASCII sentences -------------------------------------------------
  * Replaces, for the sentences it handles, the host tokenizer call of the reference's encode_text
  * (/root/reference/src/models/sentence_encoder.py:144-153: tokenizer(text=batch, padding=True, truncation=True,

@@ -153,6 +153,7 @@ _SIGS = {
                                       C.POINTER(C.c_void_p)]),
     "tsim_encoder_destroy": (None, [C.c_void_p]),
     "tsim_encoder_error_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "tsim_chain_items_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "tsim_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

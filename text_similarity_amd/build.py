@@ -20,7 +20,7 @@ OBJ = os.path.join(CSRC, "_obj" + ("_" + TAG if TAG else ""))
 LIB = os.path.join(HERE, "libtsim" + ("_" + TAG if TAG else "") + ".so")
 SOURCES = ["common.hip", "search.hip", "k1_kl16.hip", "k1_d384.hip", "k1_kl32.hip", "k1_collect.hip", "gemm_pp.hip", "encoder.hip",
            "wordpiece.cpp"]   # (host-only C++: the ASCII WordPiece tokenizer)
-HOT_KERNELS = ("l2_rows_kernel", "l2_query_rows_kernel", "l2_negate_scores", "flag_all_kernel", "cos_topk_partial", "cos_topk_finalize", "gemm_bf16", "gemm_xres", "ln_rows_gemm", "ln_tail_gemm", "gemm_pp", "attention_kernel",
+HOT_KERNELS = ("l2_rows_kernel", "l2_query_rows_kernel", "l2_negate_scores", "flag_all_kernel", "cos_topk_partial", "cos_topk_finalize", "gemm_bf16", "gemm_xres", "ln_rows_gemm", "ln_rows_xres2", "ln_tail_gemm", "gemm_pp", "attention_kernel",
                "pool_packed_kernel", "dense_rows_kernel", "widen_finalize", "bf_partial", "bf_merge",
                "topk_merge_large", "list_prep", "list_partial", "list_merge", "range_setup", "range_finalize", "range_bf", "range_fill", "range_merge", "span_pool_kernel",
                "pack_sign_rows", "hamming_partial", "hamming_merge", "sign_rescore",

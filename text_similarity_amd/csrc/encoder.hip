@@ -501,6 +501,7 @@ __device__ __forceinline__ void ff_static_for(std::integer_sequence<int, I...>, 
 // (both issued four steps earlier), the odd step runs straight on; a step issues the tile of step st + 4 into the slot the pair
 // before the current one has left (everyone is past that pair: they passed this pair's barrier).
 // MEASURED: QKV 73.1 -> 71.2 us, FFN1 119.6 -> 115.3 us (-3 %): the wait is mostly not a per-barrier constant.
+// (ln_rows_xres2_kernel holds a COPY of this kernel's item loop, store_half included: a fix here belongs there too.)
 constexpr int X2_BN = 96, X2_BK = 128, X2_NSTAGE = 6, X2_PD = 4, X2_KG = 3, X2_NSUB = 3;
 
 // PK: the output goes out in the block-packed layout (see packed_off); XPK: X comes in it (group_off)
@@ -778,6 +779,7 @@ __global__ __launch_bounds__(256) void pack_frag_w_kernel(const uint4 *__restric
 // Per k-tile: 40 KiB staged (640 LDS cycles) + 208 KiB read (832) for 1 536 MFMA cycles per SIMD.
 // =====================================================================================================
 // NW = waves = 32-token row blocks per workgroup, LR_NST = ring slots: <8, 3> (256 tokens, 120 KiB).
+// (ln_rows_xres2_kernel holds a COPY of the <8, 3> k loop and epilogue: a fix here belongs there too.)
 constexpr int LR_BK = 32, LR_WBYTES = 384 * LR_BK * 2;
 
 template <int NW, int LR_NST>
@@ -959,6 +961,419 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
                 *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (oo + (4 * t + gq) * ogs)) = make_uint4(s0[0], s1w[0], s0[1], s1w[1]);
         }
     }
+}
+
+// =====================================================================================================
+// ln_rows_xres2: the LayerNorm GEMM of a 256-token block and the K = 384 projection that follows it, in the SAME workgroup —
+// O-projection -> FFN1 (EPI_GELU) and FFN2 -> the next layer's QKV (EPI_BIAS) of the block-packed hidden-384 path.
+//
+// ln_rows_gemm_kernel<8, 3> and gemm_xres2_kernel<EPI, true, true> use one decomposition (a workgroup owns 256 tokens, a wave 32
+// token rows and all 384 features), and the 16-byte groups the LayerNorm epilogue stores after its half-wave swap ARE the resident
+// fragments bx[24] of the projection (group 4 t + gq + h = 2 s + h for s = 2 t + gq / 2).  So the workgroup keeps them, and the
+// projection starts without the store drain, the kernel boundary, the W-ring prologue and the fragment load in between.  No
+// arithmetic changes: the first phase is ln_rows_gemm_kernel (k order, accumulators from the bias, residual add, two-pass
+// statistics), the second gemm_xres2_kernel's item loop; both are COPIES, so that the stand-alone kernels keep their code.
+//
+// Hand-over:
+//   LDS     the three 40-KiB slots of the LayerNorm ring and the six 24-KiB slots of the W ring overlap (one barrier after the last
+//           k-tile, W pieces only behind it); the projection's bias and gamma / beta sit above both (144 KiB ..), loaded once.
+//   vmcnt   the W ring is primed (X2_PD tiles) right behind that barrier, BEFORE the epilogue's 24 result stores; the stores are
+//           inline asm (an exact count) and are carried as `carry` in the ring waits of steps 0 and 2, which would otherwise wait
+//           for the whole burst.  gamma / beta come from LDS so that no load of the epilogue waits behind a store either.
+//           The epilogue's residual loads are ordinary loads issued behind the primed tiles, so the first wait on a residual row
+//           also waits for the four W tiles (they come from L2 and are needed next anyway): part of the hand-over's cost.
+//   rows    the row is still stored (x1 / x0 is the next LayerNorm's residual).
+// Items: workgroup b takes the N / 96 items of its own block, then its share of the remainder blocks' items (chain_part), whose
+// fragments it loads from memory as gemm_xres2 does: their rows were written by the remainder launch BEFORE this kernel.
+// =====================================================================================================
+struct ChainPart { int own, r0, n; };   // own items, first remainder item, items in all
+// The item-assignment rule (host and device: tsim_chain_items_host).  Workgroup b of G owns whole block b (the grid is the whole
+// blocks), the R = rem_blocks * ntiles items of the blocks behind them are cut into G contiguous shares.
+__host__ __device__ inline ChainPart chain_part(int G, int rem_blocks, int ntiles, int b) {
+    const long long R = (long long)rem_blocks * ntiles;
+    const int r0 = (int)(R * b / G), r1 = (int)(R * (b + 1) / G);
+    return {ntiles, r0, ntiles + r1 - r0};
+}
+// the workgroup's i-th item as block * ntiles + feature tile
+__host__ __device__ inline int chain_item(const ChainPart &p, int G, int ntiles, int b, int i) {
+    return i < p.own ? b * ntiles + i : G * ntiles + p.r0 + (i - p.own);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(512) void ln_rows_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
+                                                            const float *__restrict__ lbias, const bf16_t *__restrict__ res,
+                                                            const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                            float eps, bf16_t *xout, int K, int xpacked, int respacked,
+                                                            const bf16_t *__restrict__ W2, const float *__restrict__ bias2,
+                                                            bf16_t *__restrict__ out2, int M, int N2, int rem_blocks) {
+    // grid = the whole blocks (all of their rows exist); M = all token rows, the remainder blocks included; xout and out2 packed
+    constexpr int NW = 8, N = 384, LR_NST = 3;
+    constexpr int XBYTES = NW * 32 * LR_BK * 2, LSTAGE = XBYTES + LR_WBYTES;
+    constexpr int XP = XBYTES / 1024, LPPW = LSTAGE / 1024 / NW;
+    constexpr int KSTEPS = N / 16, BMX = NW * 32;
+    constexpr int STAGE = X2_BN * X2_BK * 2, PPW = STAGE / 1024 / NW;
+    constexpr int BIAS_OFF = X2_NSTAGE * STAGE, GB_OFF = BIAS_OFF + 6144;   // bias2 (N2 <= 1536) | gamma | beta
+    static_assert(LR_NST * LSTAGE <= BIAS_OFF && XP == 2 * NW && PPW == 3 && 2 * PPW + 24 <= 63, "hand-over layout");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int m0l = blockIdx.x * BMX;
+    const int nk = K / LR_BK;
+    const uint32_t lbase = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem);
+
+    // the projection's bias and the LayerNorm parameters -> LDS, above both rings
+    for (int p = wave; p * 256 < N2; p += NW)
+        if (p * 256 + lane * 4 < N2) glds16(bias2 + p * 256 + lane * 4, smem + BIAS_OFF + p * 1024);
+    if (wave < 2 && wave * 256 + lane * 4 < N) {
+        glds16(gamma + wave * 256 + lane * 4, smem + GB_OFF + wave * 1024);
+        glds16(beta + wave * 256 + lane * 4, smem + GB_OFF + N * 4 + wave * 1024);
+    }
+
+    // ---------------------------------------------------------------- LayerNorm phase (ln_rows_gemm_kernel<8, 3>)
+    f32x16 acc[12];
+#pragma unroll
+    for (int t = 0; t < 12; ++t)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const f32x4 bv = *reinterpret_cast<const f32x4 *>(lbias + 32 * t + 8 * gq + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[t][4 * gq + e] = bv[e];
+        }
+    {
+        const char *xsrc[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int sl = (wave + i * NW) * 64 + lane;
+            const int sr = sl >> 4, ch = (sl & 15) ^ (sr & 15);
+            const int64_t m = m0l + sr * 4 + (ch >> 2);
+            xsrc[i] = xpacked ? reinterpret_cast<const char *>(X + packed_off(m, (ch & 3) * 8, K))
+                              : reinterpret_cast<const char *>(X) + m * K * 2 + (ch & 3) * 16;
+        }
+        const int xkstride = xpacked ? (LR_BK / 8) * 512 : LR_BK * 2;
+        const char *wsrc = reinterpret_cast<const char *>(Wimg) + lane * 16;
+        auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
+            const int k2 = kt < nk ? kt : nk - 1;
+            char *dst = smem + stage * LSTAGE;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) glds16(xsrc[i] + k2 * xkstride, dst + (wave + i * NW) * 1024);
+#pragma unroll
+            for (int i = 2; i < LPPW; ++i)
+                glds16(wsrc + (int64_t)k2 * LR_WBYTES + (wave + i * NW - XP) * 1024, dst + (wave + i * NW) * 1024);
+        };
+        uint32_t xo[2];
+#pragma unroll
+        for (int sk = 0; sk < 2; ++sk) {
+            const int ch = (r & 3) * 4 + 2 * sk + h;
+            xo[sk] = lbase + wave * 2048 + (r >> 2) * 256 + ((ch ^ ((((wave & 1) << 3) + (r >> 2)) & 15)) << 4);
+        }
+        const uint32_t wl = lbase + XBYTES + lane * 16;
+#pragma unroll
+        for (int i = 0; i < LR_NST - 1; ++i) issue(i, i);
+#pragma unroll
+        for (int t = 0; t < 12; ++t) asm volatile("" : "+v"(acc[t]));
+        auto do_tile = [&](int kt, auto stc) __attribute__((always_inline)) {
+            constexpr int stage = decltype(stc)::value;
+            wait_vmcnt<(LR_NST - 2) * LPPW>();
+            __builtin_amdgcn_s_barrier();
+            issue(kt + LR_NST - 1, (stage + LR_NST - 1) % LR_NST);
+            constexpr int PF = 4, NRD = 24;
+            lds_u32x4 bfr[2], fr[PF + 1];
+            const uint32_t so = stage * LSTAGE;
+            lds_read_b128_imm<0>(bfr[0], xo[0] + so);
+            lds_read_b128_imm<0>(bfr[1], xo[1] + so);
+            const uint32_t wa = wl + so;
+            auto rd = [&](auto nc) __attribute__((always_inline)) {
+                constexpr int n = decltype(nc)::value;
+                lds_read_b128_imm<n * 1024>(fr[n % (PF + 1)], wa);
+            };
+            ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
+            ff_static_for(std::make_integer_sequence<int, NRD>{}, [&](auto nc) __attribute__((always_inline)) {
+                constexpr int n = decltype(nc)::value;
+                if constexpr (n + PF < NRD) rd(std::integral_constant<int, n + PF>{});
+                constexpr int younger = n + PF < NRD ? PF : NRD - 1 - n;
+                lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
+                if constexpr (n == 0) { asm volatile("" : "+v"(bfr[0])); asm volatile("" : "+v"(bfr[1])); }
+                acc[n % 12] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]),
+                                                                       __builtin_bit_cast(bf16x8, bfr[n / 12]), acc[n % 12], 0, 0, 0);
+            });
+        };
+        int kt = 0;
+        for (; kt + LR_NST <= nk; kt += LR_NST)
+            ff_static_for(std::make_integer_sequence<int, LR_NST>{}, [&](auto sc) __attribute__((always_inline)) {
+                do_tile(kt + decltype(sc)::value, sc);
+            });
+        ff_static_for(std::make_integer_sequence<int, LR_NST - 1>{}, [&](auto sc) __attribute__((always_inline)) {
+            if (kt + decltype(sc)::value < nk) do_tile(kt + decltype(sc)::value, sc);
+        });
+    }
+    wait_vmcnt<0>();                    // the last tiles (past-the-end ones too) have landed in my slots ...
+    __builtin_amdgcn_s_barrier();       // ... and in everyone's, and everyone has read its last fragments: the LayerNorm ring is free
+
+    // ---------------------------------------------------------------- hand-over: prime the W ring
+    const int ntiles = N2 / X2_BN, G = (int)gridDim.x, wg = (int)blockIdx.x;
+    const ChainPart part = chain_part(G, rem_blocks, ntiles, wg);
+    // LDS image of a W tile as in gemm_xres2_kernel: 16-byte slot c of row rr holds source chunk c ^ (rr & 15)
+    auto w_src_off = [&](int ln, int i) __attribute__((always_inline)) {
+        const int sl = (wave * PPW + i) * 64 + ln;
+        const int row = sl >> 4, ch = (sl & 15) ^ (row & 15);
+        return row * N * 2 + ch * 16;
+    };
+    // the next W tile to issue: k-group pg of the workgroup's item pi, feature tile pj (past the end: the last tile again)
+    int pi = 0, pg = 0, pj = chain_item(part, G, ntiles, wg, 0) % ntiles;
+    auto tile_base = [&]() __attribute__((always_inline)) {
+        return reinterpret_cast<const char *>(W2) + ((int64_t)pj * X2_BN * N + pg * X2_BK) * 2;
+    };
+    auto advance = [&]() __attribute__((always_inline)) {
+        if (++pg == X2_KG) {
+            if (pi + 1 < part.n) {
+                pg = 0;
+                ++pi;
+                pj = chain_item(part, G, ntiles, wg, pi) % ntiles;
+            } else {
+                pg = X2_KG - 1;
+            }
+        }
+    };
+    // (the offsets are computed again behind the epilogue: held across it they cost registers the epilogue has not got)
+    const int lanep = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#pragma unroll
+    for (int i = 0; i < X2_PD; ++i) {
+        const char *base = tile_base();
+#pragma unroll
+        for (int p = 0; p < PPW; ++p) glds16(base + w_src_off(lanep, p), smem + i * STAGE + (wave * PPW + p) * 1024);
+        advance();
+    }
+
+    // ---------------------------------------------------------------- LayerNorm epilogue: + residual, statistics, store AND keep
+    bf16x8 bx[KSTEPS];
+    {
+        // (lane ids from mbcnt, not from threadIdx: nothing lane-derived has to live through the k loop or the residual phase)
+        const int lane1 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const uint32_t ro = (uint32_t)group_off(m0l + wave * 32 + (lane1 & 31), lane1 >> 5, N, respacked), rgs = (uint32_t)group_off(0, 1, N, respacked);
+#pragma unroll
+        for (int t = 0; t < 12; ++t)
+#pragma unroll
+            for (int gq = 0; gq < 4; gq += 2) {
+                const uint4 o = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(res) + (ro + (4 * t + gq) * rgs));
+                auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
+                auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
+                const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
+                acc[t][4 * gq + 0] += __uint_as_float(a0 << 16);
+                acc[t][4 * gq + 1] += __uint_as_float(a0 & 0xffff0000u);
+                acc[t][4 * gq + 2] += __uint_as_float(a1 << 16);
+                acc[t][4 * gq + 3] += __uint_as_float(a1 & 0xffff0000u);
+                acc[t][4 * gq + 4] += __uint_as_float(c0 << 16);
+                acc[t][4 * gq + 5] += __uint_as_float(c0 & 0xffff0000u);
+                acc[t][4 * gq + 6] += __uint_as_float(c1 << 16);
+                acc[t][4 * gq + 7] += __uint_as_float(c1 & 0xffff0000u);
+            }
+        float mean, rstd;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            float tot = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                float sg = 0.f;
+#pragma unroll
+                for (int t = 3 * w; t < 3 * w + 3; ++t)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (pass == 0) {
+                            sg += acc[t][q];
+                        } else {
+                            const float dlt = acc[t][q] - mean;
+                            sg = fmaf(dlt, dlt, sg);
+                        }
+                    }
+                sg += __shfl_xor(sg, 32, 64);
+                tot += sg;
+            }
+            if (pass == 0)
+                mean = tot / (float)N;
+            else
+                rstd = 1.0f / sqrtf(tot / (float)N + eps);
+        }
+        int lane3 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane3));
+        const int h3 = lane3 >> 5;
+        const uint32_t oo = (uint32_t)group_off(m0l + wave * 32 + (lane3 & 31), h3, N, 1);
+        constexpr uint32_t ogs = 512;   // group_off(0, 1, N, 1)
+        const uint64_t xb = (uint64_t)(uintptr_t)xout;
+        const float *gl = reinterpret_cast<const float *>(smem + GB_OFF), *bl = gl + N;
+#pragma unroll
+        for (int t = 0; t < 12; ++t) {
+            uint32_t pk[8];
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const int n = 32 * t + 8 * gq + 4 * h3;
+                const f32x4 gv = *reinterpret_cast<const f32x4 *>(gl + n), bv = *reinterpret_cast<const f32x4 *>(bl + n);
+                const float o0 = fmaf((acc[t][4 * gq + 0] - mean) * rstd, gv[0], bv[0]);
+                const float o1 = fmaf((acc[t][4 * gq + 1] - mean) * rstd, gv[1], bv[1]);
+                const float o2 = fmaf((acc[t][4 * gq + 2] - mean) * rstd, gv[2], bv[2]);
+                const float o3 = fmaf((acc[t][4 * gq + 3] - mean) * rstd, gv[3], bv[3]);
+                pk[2 * gq] = pack_bf16x2(o0, o1);
+                pk[2 * gq + 1] = pack_bf16x2(o2, o3);
+            }
+#pragma unroll
+            for (int gq = 0; gq < 4; gq += 2) {
+                auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
+                auto s1w = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
+                const u32x4 o = {s0[0], s1w[0], s0[1], s1w[1]};
+                const uint32_t voff = oo + (4 * t + gq) * ogs;
+                // (asm: exactly one store instruction each, counted below; s_nop: see gemm_xres2_kernel's store_half)
+                asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(xb) : "memory");
+                bx[2 * t + gq / 2] = __builtin_bit_cast(bf16x8, o);
+            }
+        }
+    }
+
+    // ---------------------------------------------------------------- projection phase (gemm_xres2_kernel<EPI, true, true>)
+    // (lane-derived values of this phase start from an opaque copy of the lane id, so that none of them is computed early and
+    // carried through the epilogue, where every register is taken)
+    int lane2 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(lane2));
+    const int r2 = lane2 & 31, h2 = lane2 >> 5;
+    int src_off[PPW];
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) src_off[i] = w_src_off(lane2, i);
+    auto issue_pieces = [&](int stage, int i0, int i1) __attribute__((always_inline)) {
+        const char *base = tile_base();
+        for (int i = i0; i < i1; ++i)
+            glds16(base + src_off[i], smem + stage * STAGE + (wave * PPW + i) * 1024);
+    };
+    int cks[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) cks[ks] = r2 * 256 + (((2 * ks + h2) ^ (r2 & 15)) << 4);
+    const uint32_t bias_lds = lbase + BIAS_OFF;
+    int cur_mb = wg, m0 = wg * BMX + wave * 32;
+    f32x16 accA[X2_NSUB], accB[X2_NSUB];
+    int old_m0 = 0, old_n0 = 0;
+    int st = 0, ring = 0;
+    int young1 = 0, young2 = 0, young3 = 0;
+    int carry = 1;                    // the 24 stores of the LayerNorm epilogue are younger than the primed tiles (steps 0 and 2)
+    uint32_t old_rowoff = 0;
+    const uint64_t out_base = (uint64_t)(uintptr_t)out2;
+    auto store_half = [&](const uint32_t (&pk)[8], int mrow0, int ncol, auto gqc) __attribute__((always_inline)) {
+        constexpr int gq = decltype(gqc)::value;
+        const bool full = mrow0 + 32 <= M;    // wave-uniform
+        uint32_t a0 = pk[2 * gq], a1 = pk[2 * gq + 1], b0 = pk[2 * gq + 2], b1 = pk[2 * gq + 3];
+        auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+        auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+        const uint32_t voff = old_rowoff + (uint32_t)(ncol + 8 * gq) * 64u;
+        const uint64_t ob = out_base;
+        if (full || mrow0 + r2 < M)
+            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(ob) : "memory");
+    };
+    auto finish2 = [&](float y0, float y1) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (EPI == EPI_GELU) gelu2(y0, y1);
+        return pack_bf16x2(y0, y1);
+    };
+    auto run_item = [&](f32x16 (&cur)[X2_NSUB], f32x16 (&old)[X2_NSUB], int item, auto with_old) __attribute__((always_inline)) {
+        constexpr bool OLD = decltype(with_old)::value;
+        const int gi = chain_item(part, G, ntiles, wg, item);
+        if (gi / ntiles != cur_mb) {                          // wave-uniform: a remainder block -> load its fragments
+            cur_mb = gi / ntiles;
+            m0 = cur_mb * BMX + wave * 32;
+            const char *xp = reinterpret_cast<const char *>(xout) + group_off(m0 + r2, h2, N, 1);
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 2 * s * 512);
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));
+            young1 = young2 = young3 = 0;
+            carry = 0;
+        }
+        const int n0 = (gi % ntiles) * X2_BN;
+        const uint32_t baddr = bias_lds + (n0 + 4 * h2) * 4;
+        ff_static_for(std::make_integer_sequence<int, X2_NSUB>{}, [&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(ic)::value;
+            f32x4 bv[4];
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[0]) : "v"(baddr), "n"((i * 32 + 0) * 4) : "memory");
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[1]) : "v"(baddr), "n"((i * 32 + 8) * 4) : "memory");
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[2]) : "v"(baddr), "n"((i * 32 + 16) * 4) : "memory");
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[3]) : "v"(baddr), "n"((i * 32 + 24) * 4) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3])::"memory");
+#pragma unroll
+            for (int q = 0; q < 16; ++q) cur[i][q] = bv[q >> 2][q & 3];
+        });
+#pragma unroll
+        for (int g = 0; g < X2_KG; ++g) {
+            asm volatile("" : "+s"(ring));
+            const int stage = ring;
+            if ((st & 1) == 0) {
+                const int ys = (young1 >= 0 && young2 >= 0 && young3 >= 0) ? young1 + young2 + young3 : 0;
+                if (carry) wait_vmcnt<2 * PPW + 24>();       // (no projection store has been issued yet: ys = 0)
+                else if (ys == 6) wait_vmcnt<2 * PPW + 6>();
+                else if (ys == 4) wait_vmcnt<2 * PPW + 4>();
+                else if (ys == 2) wait_vmcnt<2 * PPW + 2>();
+                else wait_vmcnt<2 * PPW>();
+                __builtin_amdgcn_s_barrier();
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            uint32_t pk[8];
+            {
+                constexpr int PF = 3, NRD = 8 * X2_NSUB;
+                lds_u32x4 fr[PF + 1];
+                const uint32_t wsl = lbase + stage * STAGE;
+                auto rd = [&](auto nc) __attribute__((always_inline)) {
+                    constexpr int n = decltype(nc)::value;
+                    lds_read_b128_imm<(n % X2_NSUB) * 8192>(fr[n % (PF + 1)], wsl + cks[n / X2_NSUB]);
+                };
+                ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
+                ff_static_for(std::make_integer_sequence<int, NRD>{}, [&](auto nc) __attribute__((always_inline)) {
+                    constexpr int n = decltype(nc)::value;
+                    constexpr int ks = n / X2_NSUB, i = n % X2_NSUB;
+                    if constexpr (n + PF < NRD) rd(std::integral_constant<int, n + PF>{});
+                    constexpr int younger = n + PF < NRD ? PF : NRD - 1 - n;
+                    lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
+                    cur[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]), bx[g * 8 + ks], cur[i], 0, 0, 0);
+                    if constexpr (i == X2_NSUB - 1) {
+                        if constexpr (ks == 1 || ks == 3 || ks == 5) {
+                            const int ns = stage + X2_PD;
+                            issue_pieces(ns >= X2_NSTAGE ? ns - X2_NSTAGE : ns, ks >> 1, (ks >> 1) + 1);
+                            if constexpr (ks == 5) advance();
+                        }
+                        if constexpr (OLD) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);
+                    }
+                });
+            }
+            young3 = young2;
+            young2 = young1;
+            young1 = 0;
+            if constexpr (OLD) {
+                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
+                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
+                young1 = old_m0 + 32 <= M ? 2 : -1;
+            }
+            ++st;
+            ring = ring + 1 == X2_NSTAGE ? 0 : ring + 1;
+            if (st >= 3) carry = 0;   // the wait of step 4 is for tiles issued after the epilogue's stores
+        }
+        old_m0 = m0;
+        old_n0 = n0;
+        old_rowoff = (uint32_t)(m0 >> 5) * (uint32_t)(N2 * 64) + 16u * r2 + 512u * h2;
+    };
+    int item = 0;
+    run_item(accA, accB, item++, std::false_type{});
+    for (; item + 2 <= part.n; item += 2) {
+        run_item(accB, accA, item, std::true_type{});
+        run_item(accA, accB, item + 1, std::true_type{});
+    }
+    const bool lastA = item >= part.n;
+    if (!lastA) run_item(accB, accA, item, std::true_type{});
+    wait_vmcnt<0>();
+    auto flush = [&](f32x16 (&a)[X2_NSUB]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < X2_NSUB; ++g) {
+            uint32_t pk[8];
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) pk[ks] = finish2(a[g][2 * ks], a[g][2 * ks + 1]);
+            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
+            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
+        }
+    };
+    if (lastA) flush(accA); else flush(accB);
 }
 
 // =====================================================================================================
@@ -2040,6 +2455,36 @@ static int ln_rows_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias
     return TSIM_OK;
 }
 
+// Whole 256-token blocks of an M-row hidden-384 LayerNorm GEMM that go to ln_rows_gemm (or ln_rows_xres2): whole rounds of 256
+// blocks, and a last round that is at least half full
+static int ln_rows_blocks(int M) {
+    const int t256 = M / 256;
+    return (t256 % 256) >= 128 ? t256 : (t256 / 256) * 256;
+}
+
+// ln_rows_xres2: LayerNorm GEMM of the first `blocks` 256-token blocks + the projection [M, 384] x W2^T -> out2 [M, N2] of ALL M rows
+// (the rows behind the whole blocks must have been written to xout before: gemm_res_ln(.., tail_only))
+template <int EPI>
+static int ln_rows_xres2(const bf16_t *X, const bf16_t *Wimg32, const float *lbias, const bf16_t *res, const float *gamma,
+                         const float *beta, float eps, bf16_t *xout, int blocks, int K, bool xpacked, bool respacked, const bf16_t *W2,
+                         const float *bias2, bf16_t *out2, int M, int N2, hipStream_t st) {
+    constexpr int lds = X2_NSTAGE * X2_BN * X2_BK * 2 + 6144 + 2 * 384 * 4;   // W ring (over the LayerNorm ring) | bias2 | gamma | beta
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    if (N2 % X2_BN != 0 || N2 > 1536) return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: N=%d", N2);
+    if (K % LR_BK != 0 || K < 3 * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: K=%d", K);
+    if (blocks <= 0 || (int64_t)blocks * 256 > M) return fail(TSIM_EINVAL, "ln_rows_xres2: %d blocks of %d rows", blocks, M);
+    if (((int64_t)M + 256) * N2 * 2 >= (1ll << 32) || ((int64_t)M + 256) * 768 >= (1ll << 32))
+        return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: output of %d x %d exceeds 4 GiB", M, N2);
+    auto kern = ln_rows_xres2_kernel<EPI>;
+    static DevOnce lds_once;
+    TSIM_MAX_LDS(lds_once, kern, lds);
+    const int rem_blocks = (M - blocks * 256 + 255) / 256;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, st, X, Wimg32, lbias, res, gamma, beta, eps, xout, K,
+                       xpacked ? 1 : 0, respacked ? 1 : 0, W2, bias2, out2, M, N2, rem_blocks);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
 // The block-packed qkv / h1 layout (packed_off) needs gemm_xres2 as the producer on both projections
 static bool use_packed_layout(int H, int F) {
     return H == 384 && (3 * H) % X2_BN == 0 && F % X2_BN == 0 && F <= 2048;
@@ -2059,7 +2504,8 @@ static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const 
 static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, const bf16_t *res,
                        const float *gamma, const float *beta, float eps, bf16_t *out, int M, int N, int K, float *ybuf,
                        hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false,
-                       float *lnimg = nullptr, bool respacked = false, bool opacked = false) {
+                       float *lnimg = nullptr, bool respacked = false, bool opacked = false, bool tail_only = false) {
+    // tail_only: the rows of ln_rows_blocks(M) whole blocks are left to the caller (ln_rows_xres2), only the rows behind them run
     // respacked / opacked: the residual comes / the output goes in the block-packed layout (the residual stream between the layers
     // of the hidden-384 BERT path).  Row offsets below are multiples of 32: a block starts at the same element in both layouts.
     if ((xpacked || respacked || opacked) && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed layouts are a hidden-384 form");
@@ -2077,12 +2523,12 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
             // forms give a row the same bits (bit-wise large-vs-small-batch test).
             bool after_rows = false;   // the rest below is the remainder of a ln_rows launch: a true tail
             if (Wimg32) {
-                const int t256 = M / 256;
-                const int use = (t256 % 256) >= 128 ? t256 : (t256 / 256) * 256;
+                const int use = ln_rows_blocks(M);
                 if (use > 0) {
                     // (a four-slot ring with the second half of the waves issuing behind their MFMAs measured equal, 68.5 vs 66-68 us
                     // per launch)
-                    int rc = ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked, respacked, opacked);
+                    int rc = tail_only ? TSIM_OK
+                                       : ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked, respacked, opacked);
                     const int m1 = use * 256;
                     if (rc || m1 == M) return rc;
                     X += (int64_t)m1 * K; res += (int64_t)m1 * N; out += (int64_t)m1 * N; M -= m1;
@@ -2123,6 +2569,15 @@ static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const
 }
 
 }  // namespace tsim
+
+// Introspection (host only, no launch): the items workgroup b of G takes in a chained launch (chain_part / chain_item as
+// ln_rows_xres2_kernel evaluates them), as block * ntiles + feature tile.  Returns the count (< 0: bad arguments); fills at most cap.
+extern "C" int tsim_chain_items_host(int blocks, int rem_blocks, int ntiles, int G, int b, int32_t *items, int cap) {
+    if (blocks != G || rem_blocks < 0 || ntiles <= 0 || G <= 0 || b < 0 || b >= G || (cap > 0 && !items)) return -1;
+    const ChainPart p = chain_part(G, rem_blocks, ntiles, b);
+    for (int i = 0; i < p.n && i < cap; ++i) items[i] = chain_item(p, G, ntiles, b, i);
+    return p.n;
+}
 
 extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_encoder_weights_host *w,
                                    tsim_encoder **out) {
@@ -2382,6 +2837,7 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
         const int32_t *col = rel ? (tok_col ? tok_col : tok_pos) : nullptr;
         const int qblocks = (max_len + 31) / 32 > 0 ? (max_len + 31) / 32 : 1;
         const dim3 agrid((unsigned)(((B + 7) / 8) * 8), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks);   // xcd_map = 1
+        bool qkv_chained = false;
         for (int l = 0; l < c.num_layers; ++l) {
             const tsim_encoder::Layer &L = e->layers[l];
             // The residual stream is block-packed between the layers of the pk path (group_off): x1 always, x0 except as the
@@ -2393,9 +2849,11 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
                 if (l == 0 && (rc = quant_mx(e->x0, T, H, e->aq, e->as, st))) return rc;
                 if ((rc = gemm_pp_mx(PP_EPI_BIAS, e->aq, e->as, L.qqkv, 1, L.sqkv, L.bqkv, e->qkv, nullptr, T, 3 * H, H, st))) return rc;
             } else if (pk) {
-                rc = x0pk ? gemm_xres2<EPI_BIAS, true, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st)
-                          : gemm_xres2<EPI_BIAS, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
-                if (rc) return rc;
+                if (!qkv_chained) {   // (chained: the previous layer's FFN2 launch has written this layer's qkv)
+                    rc = x0pk ? gemm_xres2<EPI_BIAS, true, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st)
+                              : gemm_xres2<EPI_BIAS, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
+                    if (rc) return rc;
+                }
             } else if ((rc = gemm_plain<EPI_BIAS>(e->x0, L.wqkv, L.pqkv, L.bqkv, e->qkv, T, 3 * H, H, st))) return rc;
 #define ATT(D)                                                                                                 \
     do {                                                                                                       \
@@ -2421,11 +2879,29 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
                 if ((rc = res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, c.ln_eps, e->x0, e->aq, e->as, T, H, st))) return rc;
                 continue;
             }
-            if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk))) return rc;
-            if (pk) {
-                if ((rc = gemm_xres2<EPI_GELU, true, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
-            } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;
-            if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, x0pk_next))) return rc;
+            // Chained launches (ln_rows_xres2): wherever the LayerNorm GEMM has whole 256-token blocks for ln_rows_gemm, those blocks'
+            // workgroups run the next projection too — O-projection -> FFN1, FFN2 -> the next layer's QKV.  The rows behind the
+            // whole blocks go first (their LayerNorm launches as before), the projection's items of those rows are shared out.
+            // Only whole rounds of 256 blocks are chained: the stand-alone projection always runs on 256 persistent workgroups, and a
+            // chained launch of 128 .. 255 (or 384) blocks would run it on a half-empty round.
+            const int chain_blocks = pk && F <= 1536 && ln_rows_blocks(T) % 256 == 0 ? ln_rows_blocks(T) : 0;
+            if (chain_blocks > 0 && L.lo32) {
+                if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk, true))) return rc;
+                if ((rc = ln_rows_xres2<EPI_GELU>(e->ctx, L.lo32, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, chain_blocks, H, false, x0pk,
+                                                  L.w1, L.b1, e->h1, T, F, st))) return rc;
+            } else {
+                if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk))) return rc;
+                if (pk) {
+                    if ((rc = gemm_xres2<EPI_GELU, true, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
+                } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;
+            }
+            qkv_chained = chain_blocks > 0 && L.l232 && x0pk_next;
+            if (qkv_chained) {
+                const tsim_encoder::Layer &Ln = e->layers[l + 1];
+                if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, true, true))) return rc;
+                if ((rc = ln_rows_xres2<EPI_BIAS>(e->h1, L.l232, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, chain_blocks, F, true, true,
+                                                  Ln.wqkv, Ln.bqkv, e->qkv, T, 3 * H, st))) return rc;
+            } else if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, x0pk_next))) return rc;
         }
         if (last_hidden_bf16)
             TSIM_HIP_CHECK(hipMemcpyAsync(last_hidden_bf16, e->x0, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
