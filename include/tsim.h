@@ -427,6 +427,45 @@ int tsim_sign_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, cons
                            const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
                            int32_t *out_status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * int8 embeddings: calibrated scalar quantisation, exact inner-product top-k on the codes and the re-score of its candidates
+ * (sentence-transformers' `quantize_embeddings(precision="int8", ranges=...)` with `semantic_search_faiss` /
+ * `semantic_search_usearch(..., rescore=True)`; usearch's `Index(dtype="i8", metric="ip")`).
+ * Codes.  A code row is d int8 values, 1 <= d <= 1024.  Rows lie tsim_int8_bytes(d) bytes apart — d rounded up to a multiple of 16
+ * (0 for a d outside 1..1024) — or further: ldq, ldc and ld_code are in BYTES, multiples of 16 and >= tsim_int8_bytes(d), and the
+ * rows start on a 16-byte boundary (else TSIM_EINVAL).  The bytes from d to tsim_int8_bytes(d) are zero in everything the library
+ * writes; what it READS may hold anything there: bytes at positions >= d never count.
+ * tsim_quantize_int8_rows (replaces `quantize_embeddings(x, "int8", ranges=ranges)`): x [rows, d] float32, row stride
+ * ld_in >= d elements; ranges [2, d] float32 contiguous on the device, row 0 the per-column start (minimum), row 1 the maximum.
+ * In float32: step = (ranges[1] - ranges[0]) / 255, t = (x - ranges[0]) / step - 128, code = trunc(t) towards zero — numpy's
+ * `astype(np.int8)` wherever that is defined.  Where it is not: t saturates to [-128, 127], +-inf included, and NaN (a NaN input,
+ * or 0 / 0 in a constant column) gives 0.  HBM-bound on x.
+ * tsim_int8_ip_topk (replaces usearch's i8 inner-product search / faiss' IndexFlatIP over int8 rows): the k rows of c_codes [N]
+ * with the largest score = sum_{j < d} q_j c_j for each row of q_codes [Q], the sum an exact int32 (|score| <= 2^24).  Exact: the
+ * true top-k, ordered by (score desc, row asc).  out_score [Q, k] int32, out_idx [Q, k] int64 = row + idx_offset; N < k is padded
+ * with (INT32_MIN, -1), N == 0 is legal (c_codes may be NULL then).  1 <= k <= TSIM_TOPK_MAX_K, N < 2^31 - 64, at most 65535
+ * query groups per call (a group is at most 16 queries while k <= 64, else 8; fewer for a small Q).  One pass over the codes per group on
+ * v_mfma_i32_16x16x64_i8 (the group's queries stay in registers as the B operand, 16 code rows at a time are loaded straight
+ * into the A operand), a running sorted list per (chunk of rows, query), one merge workgroup per query.  workspace:
+ * tsim_int8_ip_topk_workspace_bytes(Q, N, k) — pure host, 0 for Q <= 0, N < 0 or k outside 1..TSIM_TOPK_MAX_K, non-decreasing in
+ * each argument, never above 64 MiB + what one list per query takes.  The call reads nothing back from the device.
+ * tsim_int8_rescore_topk (replaces the `rescore=True` stage: float query x int8 document): the contract of
+ * tsim_sign_rescore_topk with the code value in place of +-1: score = float32(sum_j q_j c_j), the sum in float64 in the canonical
+ * lane order (oracle/search_ref._lane_sum) and rounded once — for d <= 768 the bits tsim_dot_list_topk gives on the codes as a
+ * float32 matrix.  Ordered by (score desc, row asc), padded with (-inf, -1); negative entries of cand are skipped, an entry >= N
+ * is never dereferenced and sets TSIM_LIST_ST_ROW in out_status[q] (may be NULL), a row listed twice is returned twice.
+ * No workspace. */
+int tsim_int8_bytes(int d);
+int tsim_quantize_int8_rows(const float *x, int64_t rows, int d, int64_t ld_in, const float *ranges, int8_t *codes, int64_t ld_code,
+                            void *stream);
+size_t tsim_int8_ip_topk_workspace_bytes(int64_t Q, int64_t N, int k);
+int tsim_int8_ip_topk(const int8_t *q_codes, int64_t ldq, int64_t Q, const int8_t *c_codes, int64_t ldc, int64_t N, int d, int k,
+                      int32_t *out_score, int64_t *out_idx, int64_t idx_offset, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int tsim_int8_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const int8_t *c_codes, int64_t ldc, int64_t N, int d,
+                           const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
+                           int32_t *out_status, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

@@ -205,7 +205,8 @@ class _EncodeMixin:
         return [t.cpu().numpy() for t in out] if output_np else out
 
     def encode_text(self, documents: List[str], output_np: bool = False,
-                    output_value: str = "sentence_embedding", precision: str = "float32") -> Union[torch.Tensor, np.ndarray, list]:
+                    output_value: str = "sentence_embedding", precision: str = "float32",
+                    ranges=None) -> Union[torch.Tensor, np.ndarray, list]:
         """sentence_encoder.py:136-173: sort by character length, encode in batches, un-sort, stack.
         Returns float32 [N, H] on params.device (or numpy when ``output_np``), un-normalised.
         ``output_value="token_embeddings"`` (the sentence-transformers name) returns instead a list of [len_i, H] float32
@@ -215,12 +216,29 @@ class _EncodeMixin:
         tokenizers release the GIL).  ``self.last_encode_stats`` holds the split of the wall time.
         ``precision="ubinary"`` (sentence-transformers' keyword and layout) returns instead uint8 [N, ceil(H / 8)]:
         ``np.packbits(embeddings > 0, axis=1)`` of the same pooled rows, packed on the device (``ops.pack_sign_rows``) — what
-        ``GpuBinaryIndex.add_items`` and ``ops.codes_from_packbits`` take.  Any width up to 1024."""
+        ``GpuBinaryIndex.add_items`` and ``ops.codes_from_packbits`` take.  Any width up to 1024.
+        ``precision="int8"`` with ``ranges=R`` (float [2, H]: per-column minimum and maximum, ``ops.int8_ranges`` of a
+        calibration set) returns int8 [N, H]: sentence-transformers' ``quantize_embeddings(embeddings, "int8", ranges=R)`` of the
+        same pooled rows, quantised on the device (``ops.quantize_int8_rows``) — what ``GpuInt8Index.add_items`` and
+        ``ops.int8_codes_from_numpy`` take.  Without ``ranges`` it raises: calibrating on the call's own rows would give every
+        call its own code."""
         import time
         if output_value not in ("sentence_embedding", "token_embeddings"):
             raise ValueError(f"output_value must be 'sentence_embedding' or 'token_embeddings', got {output_value!r}")
-        if precision not in ("float32", "ubinary"):
-            raise ValueError(f"precision must be 'float32' or 'ubinary', got {precision!r}")
+        if precision not in ("float32", "ubinary", "int8"):
+            raise ValueError(f"precision must be 'float32', 'ubinary' or 'int8', got {precision!r}")
+        if ranges is not None and precision != "int8":
+            raise ValueError("ranges= belongs to precision='int8'")
+        if precision == "int8":
+            if output_value != "sentence_embedding":
+                raise ValueError("precision='int8' quantises sentence embeddings, not token embeddings")
+            if ranges is None:
+                raise ValueError("precision='int8' needs calibration ranges: pass ranges=R, float [2, H] with the per-column "
+                                 "minimum and maximum of a calibration set (ops.int8_ranges)")
+            from .. import ops
+            rows = self.encode_text(documents, output_np=False)
+            codes = ops.quantize_int8_rows(rows, ranges)[:, :rows.shape[1]].contiguous()
+            return codes.cpu().numpy() if output_np else codes
         if precision == "ubinary":
             if output_value != "sentence_embedding":
                 raise ValueError("precision='ubinary' quantises sentence embeddings, not token embeddings")

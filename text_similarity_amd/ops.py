@@ -594,6 +594,176 @@ def sign_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand:
     return (scores, idx, status) if return_status else (scores, idx)
 
 
+# ------------------------------------------------------------------------------------------------- int8 embeddings
+def int8_bytes(d: int) -> int:
+    """Bytes between the rows of a [rows, int8_bytes(d)] int8 code matrix: d rounded up to a multiple of 16."""
+    b = _lib.lib().tsim_int8_bytes(int(d))
+    if b == 0:
+        raise ValueError(f"int8 codes take 1 <= d <= {MAX_CODE_DIM}, got d={d}")
+    return b
+
+
+def int8_ranges(x: torch.Tensor) -> torch.Tensor:
+    """The calibration ranges of sentence-transformers' ``quantize_embeddings(precision="int8")``: float32 [2, d], row 0 the
+    per-column minimum of ``x`` [rows, d], row 1 the maximum.  Once per corpus; not on the search path."""
+    _need_gpu(x)
+    if x.dim() != 2 or x.shape[0] == 0 or not x.dtype.is_floating_point:
+        raise ValueError("int8_ranges expects a non-empty 2-D float tensor")
+    x = x.float()
+    return torch.stack([torch.amin(x, dim=0), torch.amax(x, dim=0)]).contiguous()
+
+
+def _check_ranges(what, ranges, d, dev):
+    if not isinstance(ranges, torch.Tensor):
+        ranges = torch.as_tensor(np.asarray(ranges, dtype=np.float32), device=dev)
+    _need_gpu(ranges)
+    if ranges.dim() != 2 or tuple(ranges.shape) != (2, d) or not ranges.dtype.is_floating_point:
+        raise ValueError(f"{what}: ranges must be float [2, {d}] (per-column minimum and maximum), got {ranges.dtype} {tuple(ranges.shape)}")
+    if ranges.device != dev:
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {ranges.device})")
+    return ranges.to(torch.float32).contiguous()
+
+
+def quantize_int8_rows(x: torch.Tensor, ranges, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[rows, d] float32 -> int8 [rows, int8_bytes(d)]: sentence-transformers' ``quantize_embeddings(x, "int8", ranges=ranges)``
+    in float32 — ``((x - ranges[0]) / ((ranges[1] - ranges[0]) / 255) - 128).astype(np.int8)`` — zero from column d on.  Where
+    numpy's cast is undefined the value saturates to [-128, 127] (+-inf included) and NaN gives 0.  Strided row views are read
+    in place.  ``out``: an int8 [rows, >= int8_bytes(d)] tensor (or row view, stride a multiple of 16) whose first int8_bytes(d)
+    columns are written."""
+    what = "quantize_int8_rows"
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise ValueError(f"{what} expects a 2-D tensor")
+    if not x.dtype.is_floating_point:
+        raise ValueError(f"{what} expects float rows, got {x.dtype}")
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    rows, d = x.shape
+    cb = int8_bytes(d)
+    ranges = _check_ranges(what, ranges, d, x.device)
+    if out is None:
+        out = torch.empty((rows, cb), dtype=torch.int8, device=x.device)
+        ld = cb
+    else:
+        ld = _check_int8(what, "out", out, d, x.device)
+        if out.shape[0] != rows:
+            raise ValueError(f"{what}: out has {out.shape[0]} rows, x {rows}")
+    if rows:
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().tsim_quantize_int8_rows(x.data_ptr(), rows, d, _row_stride(x), ranges.data_ptr(), out.data_ptr(), ld,
+                                                          _stream(x)), what)
+    return out
+
+
+def int8_codes_from_numpy(a, d: int, device=None) -> torch.Tensor:
+    """A ``[rows, d]`` int8 array or tensor (sentence-transformers' int8 embeddings, ``encode_text(precision="int8")``) -> the
+    padded device layout int8 [rows, int8_bytes(d)], zero from column d on.  A numpy array goes to ``device`` (default: the
+    current one)."""
+    cb = int8_bytes(d)
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.int8:
+            raise ValueError(f"int8_codes_from_numpy: expected int8 [rows, {d}], got {a.dtype} {a.shape}")
+        a = torch.from_numpy(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+    _need_gpu(a)
+    if a.dtype != torch.int8 or a.dim() != 2 or a.shape[1] != int(d):
+        raise ValueError(f"int8_codes_from_numpy: expected int8 [rows, {d}], got {a.dtype} {tuple(a.shape)}")
+    out = torch.zeros((a.shape[0], cb), dtype=torch.int8, device=a.device)
+    out[:, :int(d)] = a
+    return out
+
+
+def _check_int8(what, name, t, d, dev=None):
+    cb = int8_bytes(d)
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int8 or t.dim() != 2 or t.shape[1] < cb
+            or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % 16) or t.data_ptr() % 16):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _need_gpu(t)
+        raise ValueError(f"{what}: {name} must be int8 [rows, >= int8_bytes({d})={cb}] on the device with unit inner stride, "
+                         "rows a multiple of 16 bytes apart and 16-byte aligned (quantize_int8_rows / int8_codes_from_numpy)")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {t.device})")
+    return t.stride(0) if t.shape[0] > 1 else (t.shape[1] // 16) * 16
+
+
+def int8_ip_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, idx_offset: int = 0,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Exact inner-product top-k over the first ``d`` values of int8 code rows: score [Q,k] int32 = sum_j q_j c_j, idx [Q,k]
+    int64, ordered by (score desc, row asc); fewer than k rows are padded with (-2**31, -1).  ``q_codes`` / ``c_codes``: int8
+    from :func:`quantize_int8_rows` or :func:`int8_codes_from_numpy` (row views with a stride that is a multiple of 16 bytes are
+    read in place; bytes at positions >= d are ignored).  1 <= k <= 1024, 1 <= d <= 1024.  Query sets above
+    MAX_QUERIES_PER_CALL rows are searched in slices.  ``out`` = (score, idx): preallocated contiguous tensors."""
+    what = "int8_ip_topk"
+    _need_gpu(q_codes, c_codes)
+    dev = q_codes.device
+    ldq = _check_int8(what, "q_codes", q_codes, d)
+    ldc = _check_int8(what, "c_codes", c_codes, d, dev)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = q_codes.shape[0], c_codes.shape[0]
+    if out is not None:
+        score, idx = out
+        _need_gpu(score, idx)
+        if (score.shape != (Q, k) or idx.shape != (Q, k) or score.dtype != torch.int32 or idx.dtype != torch.int64
+                or not score.is_contiguous() or not idx.is_contiguous() or score.device != dev or idx.device != dev):
+            raise ValueError(f"{what}: out must be contiguous int32 / int64 [{Q}, {k}] tensors on {dev}")
+    else:
+        score = torch.empty((Q, k), dtype=torch.int32, device=dev)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    if Q == 0:
+        return score, idx
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_int8_ip_topk_workspace_bytes(step, N, k)
+        if nbytes == 0:
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k}")
+        ws = _workspace(dev, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = L.tsim_int8_ip_topk(q_codes.data_ptr() + q0 * ldq, ldq, nq, c_codes.data_ptr() if N else 0, ldc, N, int(d), k,
+                                     score.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(),
+                                     _stream(q_codes))
+            _lib.check(rc, what)
+    return score, idx
+
+
+def int8_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand: torch.Tensor, k: int, idx_offset: int = 0,
+                      return_status: bool = False):
+    """The second stage of an int8 search: every query's candidates ``cand`` [Q, m] (row numbers; the ``idx`` of
+    :func:`int8_ip_topk` as it stands) scored with the FLOAT32 query against the int8 code rows, scores [Q,k] f32 and idx [Q,k]
+    i64 ordered by (score desc, row asc), padded with (-inf, -1).  score = float32(sum_j q_j c_j) summed in float64 in the
+    library's canonical order — for d <= 768 the bits of :func:`dot_list_topk` on ``c_codes.float()``.  Negative entries are
+    skipped; entries >= N are skipped and set ``LIST_ST_ROW`` in the status (``return_status``); a row listed twice is returned
+    twice."""
+    what = "int8_rescore_topk"
+    _need_gpu(eq_f32, c_codes, cand)
+    dev = eq_f32.device
+    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
+        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
+    ldc = _check_int8(what, "c_codes", c_codes, d, dev)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = eq_f32.shape[0], c_codes.shape[0]
+    if cand.dim() != 2 or cand.shape[0] != Q or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+        raise ValueError(f"{what}: cand must hold integers [{Q}, m]")
+    cand = cand.to(torch.int64).contiguous()
+    m = cand.shape[1]
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q:
+        with torch.cuda.device(dev):
+            rc = _lib.lib().tsim_int8_rescore_topk(eq_f32.data_ptr(), _row_stride(eq_f32), Q, c_codes.data_ptr() if N else 0, ldc, N,
+                                                   int(d), cand.data_ptr() if m else 0, m, k, scores.data_ptr(), idx.data_ptr(),
+                                                   idx_offset, status.data_ptr() if return_status else 0, _stream(eq_f32))
+            _lib.check(rc, what)
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins
 MAX_RANGE_QUERIES_PER_CALL = 4096       # the workspace holds RANGE_SLOT_CAP entries of 8 bytes per query: 64 MiB per call
