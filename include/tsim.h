@@ -466,6 +466,43 @@ int tsim_int8_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, cons
                            const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
                            int32_t *out_status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Inverted-file (IVF) scan: the best k of each query among the rows of the LISTS it probes (faiss' `IndexIVFFlat` after its coarse
+ * quantiser; what makes one query cheaper than a pass over the corpus).  rows_f32 [N, d] float32, row stride ld_rows >= d, holds
+ * the rows in LIST order: list l is rows [list_off[l], list_off[l+1]), list_off int64 [nlist+1].  row_ids int32 [N] gives, for each
+ * POSITION, the id that is reported and ranked by.  probes int64 [Q, nprobe] contiguous: the list numbers of each query, e.g. the
+ * out_idx of a top-k call of the queries against the nlist centroids, as it stands.  eq_f32 [Q, d], row stride ldq_f32 >= d.
+ * Scores are those of the list entries above, bit for bit (space: TSIM_SPACE_COSINE / _DOT / _L2, the last through -dist^2 inside, the
+ * sign flipped by the last kernel).  out_scores [Q, k] float32, out_idx [Q, k] int64 = id + idx_offset, ordered by (score desc, ID
+ * asc), Euclidean by (dist^2 asc, id asc) — equal rows in different lists rank as in a search of all rows; fewer than k usable rows
+ * pad with -inf / -1 (Euclidean +inf / -1).  1 <= k <= TSIM_TOPK_MAX_K, 1 <= d <= 768 (Euclidean <= 767), N < 2^31 - 64,
+ * Q nprobe < 2^31 - 1, nprobe >= 1.
+ *   - a negative probes entry is padding and is skipped;
+ *   - a probes entry >= nlist is never dereferenced; it is skipped and sets TSIM_IVF_ST_LIST in out_status[q];
+ *   - a list probed twice by one query is scanned twice and its rows are returned twice, in adjacent positions, as a row listed
+ *     twice is in the list entries;
+ *   - a negative row_ids entry is a tombstone: the row is loaded and scored and the score dropped;
+ *   - an empty list is legal;
+ *   - list_off is expected non-decreasing within [0, N].  Otherwise every word counts as the running maximum of the words up to it,
+ *     clamped to [0, N] (the rule of the list entries' lims): a decreasing pair gives an EMPTY list, and every query that probed a
+ *     list one of whose two words was changed gets TSIM_IVF_ST_OFF.  Nothing outside rows_f32[0 .. N) and row_ids[0 .. N) is read;
+ *   - out_status [Q] int32 (may be NULL): 0 or the TSIM_IVF_ST_* bits; written, not accumulated.
+ * Work.  A list is cut into segments of TSIM_IVF_SEG rows; the workgroups of a (query, probe) pair take its segments in turn, each
+ * keeping the running sorted list of the brute-force pass; one workgroup per query merges.  max_list_len is a SIZING HINT only (the
+ * length of the longest list, which the caller knows on the host): it sets the grid and the slots per pair — enough for a single
+ * query with a few tens of probes to reach every CU — and a longer list is still scanned completely; the result never depends on
+ * it.  workspace: tsim_ivf_scan_workspace_bytes(Q, nprobe, max_list_len, k) — pure host, 0 for Q <= 0, nprobe <= 0, max_list_len < 0 or
+ * k outside 1..TSIM_TOPK_MAX_K, non-decreasing in each argument, never above 64 MiB + what one list per (query, probe) takes; callers
+ * slice large query sets.  The call reads nothing back from the device. */
+#define TSIM_IVF_SEG 512
+#define TSIM_IVF_ST_LIST 1 /* probes held an entry >= nlist */
+#define TSIM_IVF_ST_OFF 2  /* a probed list's list_off pair was decreasing or outside [0, N] */
+size_t tsim_ivf_scan_workspace_bytes(int64_t Q, int nprobe, int64_t max_list_len, int k);
+int tsim_ivf_scan_topk(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *rows_f32, int64_t ld_rows, int64_t N,
+                       int d, const int64_t *list_off, int64_t nlist, const int32_t *row_ids, const int64_t *probes, int nprobe,
+                       int64_t max_list_len, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

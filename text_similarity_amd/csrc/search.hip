@@ -1883,6 +1883,7 @@ static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, cons
 #include "list_search.h"    // exact top-k within candidate lists: the indirect form of the brute-force pass
 #include "hamming_search.h" // binary embeddings: sign-bit codes, exact Hamming top-k, re-score against the +-1 expansion
 #include "int8_search.h"    // int8 embeddings: calibrated quantiser, exact inner-product top-k on the int8 MFMA, re-score
+#include "ivf_search.h"     // inverted lists: exact scan of the contiguous lists each query probes
 
 extern "C" int tsim_cosine_topk_plan(int64_t Q, int64_t N, int ld, int k, int32_t plan[4]) {
     if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_MAX_K || !plan || tsim_pad_dim(ld) != ld)

@@ -451,6 +451,80 @@ def l2_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor,
                       assume_unique)
 
 
+# ------------------------------------------------------------------------------------------------- inverted lists
+IVF_SEG = _lib.IVF_SEG          # include/tsim.h TSIM_IVF_SEG: rows of one segment of an inverted list
+IVF_ST_LIST, IVF_ST_OFF = _lib.IVF_ST_LIST, _lib.IVF_ST_OFF
+IVF_SPACES = {"cosine": _lib.SPACE_COSINE, "dot": _lib.SPACE_DOT, "l2": _lib.SPACE_L2}
+IVF_MAX_WORKSPACE = 64 << 20    # csrc/ivf_search.h IVF_BUDGET (a call of one query may exceed it: one slot per probe)
+
+
+def ivf_scan_topk(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, list_off: torch.Tensor, row_ids: torch.Tensor,
+                  probes: torch.Tensor, k: int, idx_offset: int = 0, return_status: bool = False,
+                  max_list_len: Optional[int] = None):
+    """Exact top-k of every query among the rows of the inverted lists it probes (include/tsim.h tsim_ivf_scan_topk): scores
+    [Q,k] f32 and ids [Q,k] i64 ordered by (score desc, id asc) — ``space`` 'cosine' | 'dot' | 'l2' (squared distances, ascending) —
+    with the bits of :func:`cosine_list_topk` / :func:`dot_list_topk` / :func:`l2_list_topk`.  ``rows_f32`` [N,d] float32 holds
+    the rows in LIST order (strided row views are fine), ``list_off`` int64 [nlist+1] the lists' bounds, ``row_ids`` int32 [N] the
+    id reported for each position (negative: a tombstone, skipped), ``probes`` int64 [Q,nprobe] the list numbers per query (the
+    ``idx`` of a search against the centroids as it stands; negative: padding).  A probe >= nlist sets status bit
+    ``IVF_ST_LIST``, a list whose offsets are decreasing or outside [0, N] is clamped and sets ``IVF_ST_OFF``; ``return_status``
+    adds the int32 [Q] status.  ``max_list_len``: the longest list's length, known to the caller on the host — a sizing hint
+    for the grid, never read back from the device; the result does not depend on it (default: N / nlist, the mean).  Query sets are
+    searched in slices that keep one call's workspace within IVF_MAX_WORKSPACE."""
+    what = "ivf_scan_topk"
+    if space not in IVF_SPACES:
+        raise ValueError(f"{what}: space {space!r}: one of {tuple(IVF_SPACES)}")
+    _need_gpu(eq_f32, rows_f32, list_off, row_ids, probes)
+    dev = eq_f32.device
+    for t, name in ((eq_f32, "eq_f32"), (rows_f32, "rows_f32")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be float32 [rows, d] with unit inner stride")
+    Q, d = eq_f32.shape
+    N = rows_f32.shape[0]
+    if rows_f32.shape[1] != d:
+        raise ValueError(f"{what}: query rows are {d} wide, stored rows {rows_f32.shape[1]}")
+    if space == "l2":
+        _l2_dim(d, what)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    if list_off.dtype != torch.int64 or list_off.dim() != 1 or list_off.numel() < 2 or not list_off.is_contiguous():
+        raise ValueError(f"{what}: list_off must be a contiguous int64 [nlist + 1] tensor")
+    nlist = list_off.numel() - 1
+    if row_ids.dtype != torch.int32 or row_ids.shape != (N,) or not row_ids.is_contiguous():
+        raise ValueError(f"{what}: row_ids must be a contiguous int32 [{N}] tensor")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != Q or probes.shape[1] < 1 or not probes.is_contiguous():
+        raise ValueError(f"{what}: probes must be a contiguous int64 [{Q}, nprobe >= 1] tensor")
+    nprobe = probes.shape[1]
+    hint = max(1, N // nlist) if max_list_len is None else int(max_list_len)
+    if hint < 0:
+        raise ValueError(f"{what}: max_list_len={hint} < 0")
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q == 0:
+        return (scores, idx, status) if return_status else (scores, idx)
+    if N == 0:
+        raise ValueError(f"{what}: no rows")
+    L = _lib.lib()
+    ldq, ldr = _row_stride(eq_f32), _row_stride(rows_f32)
+    with torch.cuda.device(dev):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_ivf_scan_workspace_bytes(step, nprobe, hint, k)
+        while step > 1 and nbytes > IVF_MAX_WORKSPACE + 1024:      # (+ the flag word and the alignment of the two halves)
+            step = (step + 1) // 2
+            nbytes = L.tsim_ivf_scan_workspace_bytes(step, nprobe, hint, k)
+        ws = _workspace(dev, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = L.tsim_ivf_scan_topk(IVF_SPACES[space], eq_f32.data_ptr() + q0 * ldq * 4, ldq, nq, rows_f32.data_ptr(), ldr, N, d,
+                                      list_off.data_ptr(), nlist, row_ids.data_ptr(), probes.data_ptr() + q0 * nprobe * 8, nprobe, hint,
+                                      k, scores.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset,
+                                      status.data_ptr() + q0 * 4 if return_status else 0, ws.data_ptr(), ws.numel(), _stream(eq_f32))
+            _lib.check(rc, what)
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
 # ------------------------------------------------------------------------------------------------- exact range search
 # ------------------------------------------------------------------------------------------------- binary embeddings
 MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit codes

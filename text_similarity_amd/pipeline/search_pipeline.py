@@ -24,6 +24,7 @@ import os
 
 from .. import ops
 from ..index import GpuFlatIndex
+from ..ivf_index import GpuIVFIndex
 
 
 SCORE_FUNCTIONS = {"cosine": "cosine", "dot": "dot", "dot_product": "dot"}
@@ -244,14 +245,22 @@ class SemanticSearchPipeline(SearchPipeline):
     ``self.corpus`` — the reference only grows the index, so its new ids cannot be mapped back to text.
     ``max_num_results`` up to 1024 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768.
     ``score_function='dot'`` keeps an inner-product index (``GpuFlatIndex(space='ip')``); an index file of the other space
-    at ``index_path`` raises ``ValueError``."""
+    at ``index_path`` raises ``ValueError``.  ``index_type='ivf'`` (with ``nlist=``, ``nprobe=``) keeps a
+    :class:`text_similarity_amd.ivf_index.GpuIVFIndex` instead: approximate, exact within the lists it probes."""
 
-    def __init__(self, index_path, *args, score_function: Optional[str] = None, **kwargs):
+    def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat", nlist: int = 1024,
+                 nprobe: int = 8, **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
         self.score_function = resolve_score_function(score_function, self.model)
         hidden = getattr(self.params.model_parameters, "hidden_size", None) or self.model.get_sentence_embedding_dimension()
-        self.index = GpuFlatIndex(space="ip" if self.score_function == "dot" else "cosine", dim=hidden, device=self.params.device)
+        space = "ip" if self.score_function == "dot" else "cosine"
+        if index_type == "flat":
+            self.index = GpuFlatIndex(space=space, dim=hidden, device=self.params.device)
+        elif index_type == "ivf":   # approximate: each query is scored against the nprobe of nlist lists nearest to it
+            self.index = GpuIVFIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, device=self.params.device)
+        else:
+            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf'")
         if os.path.exists(os.path.join(self.index_path, "index.bin")):
             self.index.load_index(self.index_path)
         else:
