@@ -128,6 +128,20 @@ def test_hamming_topk_groups_do_not_leak(d, N, k):
     assert torch.equal(gd, torch.cat([o[0] for o in one])) and torch.equal(gi, torch.cat([o[1] for o in one]))
 
 
+def test_hamming_topk_query_slices(monkeypatch):
+    """more queries than one call takes: slices of 5, 5 and 2 strided query rows, each written to its own rows of the outputs"""
+    monkeypatch.setattr(ops, "MAX_QUERIES_PER_CALL", 5)
+    d, N, Q, k = 65, 300, 12, 3
+    qc, cc = _codes(d, N, Q)
+    cb = hc.code_bytes(d)
+    wide = np.full((Q, cb + 16), 0xA5, np.uint8)
+    wide[:, :cb] = qc
+    wd, wi = hc.hamming_topk_ref(qc, cc, d, k)
+    assert len({tuple(row) for row in wi.tolist()}) > 1
+    gd, gi = ops.hamming_topk(_dev(wide)[:, :cb], _dev(cc), d, k)
+    assert np.array_equal(gd.cpu().numpy(), wd) and np.array_equal(gi.cpu().numpy(), wi)
+
+
 def test_hamming_topk_empty_sides():
     qc, cc = _codes(65, 9, 33)
     gd, gi = ops.hamming_topk(_dev(qc), _dev(cc)[:0], 65, 5)                      # N = 0: all padding

@@ -179,6 +179,37 @@ def test_int8_ip_topk_groups_do_not_leak(d, N, k):
     assert _eq(gs, ws) and _eq(gi, wi)
 
 
+@pytest.mark.parametrize("Q", (1, 5))
+def test_int8_ip_topk_every_row_improves(Q):
+    """The in-between flush of a 512-entry block.  Row r scores exactly r - 1024 against the all-ones query, so every row beats
+    all before it and no bound spares an offer: one query (one group, two chunks of 1 024 rows, four steps each) has 512 > 512 -
+    256 entries in its block after a chunk's third step, which is neither its first nor its last.  Q = 5: groups of 2, 2, 1."""
+    d, N, k = 16, 2048, 10
+    r = np.arange(N)
+    cc = np.repeat((r // 16 - 64)[:, None], d, axis=1)
+    cc += np.arange(d)[None, :] < (r % 16)[:, None]
+    assert cc.min() == -64 and cc.max() == 64
+    cc, qc = ic.pad_codes(cc.astype(np.int8)), ic.pad_codes(np.ones((Q, d), np.int8))
+    ws, wi = ic.ip_topk_ref(qc, cc, d, k)
+    assert wi.tolist() == [list(range(N - 1, N - 1 - k, -1))] * Q and ws.tolist() == [list(range(1023, 1023 - k, -1))] * Q
+    gs, gi = ops.int8_ip_topk(_dev(qc), _dev(cc), d, k)
+    assert _eq(gs, ws) and _eq(gi, wi)
+
+
+def test_int8_ip_topk_query_slices(monkeypatch):
+    """more queries than one call takes: slices of 5, 5 and 2 strided query rows, each written to its own rows of the outputs"""
+    monkeypatch.setattr(ops, "MAX_QUERIES_PER_CALL", 5)
+    d, N, Q, k = 65, 300, 12, 3
+    qc, cc = _codes("uniform", d, N, Q)
+    cb = ic.int8_bytes(d)
+    wide = np.full((Q, cb + 16), 0xA5 - 256, np.int8)
+    wide[:, :cb] = qc
+    ws, wi = ic.ip_topk_ref(qc, cc, d, k)
+    assert len({tuple(row) for row in wi.tolist()}) > 1
+    gs, gi = ops.int8_ip_topk(_dev(wide)[:, :cb], _dev(cc), d, k)
+    assert _eq(gs, ws) and _eq(gi, wi)
+
+
 def test_int8_ip_topk_empty_sides():
     qc, cc = _codes("uniform", 65, 9, 5)
     gs, gi = ops.int8_ip_topk(_dev(qc), _dev(cc)[:0], 65, 5)                      # N = 0: all padding

@@ -1,5 +1,5 @@
-// Binary embeddings (included by search.hip, after the helpers it uses): sign-bit codes, exact Hamming top-k, and the re-score of
-// Hamming candidates with the float32 query against the +-1 expansion of the codes.
+// Binary embeddings (included by search.hip, after code_search.h, whose frame it fills in): sign-bit codes, exact Hamming top-k,
+// and the re-score of Hamming candidates with the float32 query against the +-1 expansion of the codes (code_rescore_kernel<true>).
 //
 // Codes.  A code row is np.packbits(x > 0, axis=1) of the float row: element 8j is bit 7 of byte j, the last byte is zero-filled.
 // Rows lie tsim_code_bytes(d) = ceil(d / 8) rounded up to 16 bytes apart (or more: every stride is a multiple of 16), so a row is
@@ -9,21 +9,13 @@
 // Hamming distance is an integer, so "exact" is the true top-k under (dist asc, row asc).  A lane offers (-float(dist), row) to
 // the running list (SlList): dist <= 1024 is exact in float32 and the list's key order (score desc, index asc) is that order.
 //
-// Work.  hamming_partial_kernel<NW> (NW 16-byte words per code row): workgroup (chunk c, group g) owns rows_per_chunk rows and
-// the ng <= G queries g G .. g G + ng - 1.  Every lane owns one row at a time, loads it ONCE with 16-byte loads (consecutive lanes
-// read consecutive rows: a wave reads one contiguous span) and compares it with each of the group's queries in turn — the
-// query's dwords are workgroup-uniform, so they come through scalar loads and sit in SGPRs: one v_xor and one accumulating
-// v_bcnt per dword.  Each query has its own running list, carved from dynamic LDS (hm_list); the block protocol is the one of
-// bf_partial_kernel — the bound is read before anyone offers since the list's last flush (the list does not change until its
-// flush), at most SL_NB entries are offered between two flushes — with one difference: a block is SL_NB OFFERS, not SL_NB rows.
-// Once a list has its bound a step of 256 rows offers a handful of entries, and a flush costs a sort and a merge behind a dozen
-// barriers whatever it holds; the sort of a chunk's first full block of 1 024 entries is the dearest of them.  At Q = 16, N = 1 M
-// the first version (every list flushed once per 1 024 rows, eight queries a workgroup) took 0.62 ms, this one 0.19 ms
-// (DESIGN.md section 7).
-// So a list is flushed after the chunk's first step (256 entries: that sets its bound), after the last, and in between only
-// when its block could not take the 256 offers of another step.  Chunk lists go to the workspace raw; hamming_merge_kernel,
-// one workgroup per query, passes the query's nch k consecutive entries through one list in blocks of SL_NB and writes int32
-// distances and int64 indices.
+// Work.  hamming_partial_kernel<NW> (NW 16-byte words per code row), in the frame of code_search.h: workgroup (chunk c, group g)
+// owns rows_per_chunk rows and the ng <= G queries g G .. g G + ng - 1.  Every lane owns one row at a time, loads it ONCE with
+// 16-byte loads (consecutive lanes read consecutive rows: a wave reads one contiguous span) and compares it with each of the
+// group's queries in turn — the query's dwords are workgroup-uniform, so they come through scalar loads and sit in SGPRs: one
+// v_xor and one accumulating v_bcnt per dword.  Lists (hm_list: blocks of SL_NB offers) and flushes follow the frame's protocol.
+// At Q = 16, N = 1 M the first version (every list flushed once per 1 024 rows, eight queries a workgroup) took 0.62 ms, this one
+// 0.19 ms.
 //
 // G = min(8, ceil(Q / 4)) (hm_group).  Per (row, query) pair the loop issues 8 NW VALU instructions plus about ten for the offer; the row costs 16 NW
 // bytes of HBM once per group.  At d = 384 that is 34 lane-instructions against 48 / G bytes: with the chip's 39 T
@@ -33,20 +25,13 @@
 // A small query set takes fewer queries per workgroup — at least four groups while Q allows: the sorts of a flush are bound by
 // barriers and LDS latency, not by bandwidth, so they want many small workgroups resident per CU (8.5 KiB a list for k <= 64),
 // and the codes of a million rows (48 MB) are re-read from the cache, not from HBM.
-// Chunks: enough that chunks x groups reaches HM_WGS = 1 024 workgroups (four per CU — a single query still spreads over all
-// 256 CUs), of at least max(SL_NB, 4 k) rows (every chunk pays one full sort of its first block per query), and no more than
-// keep the chunk lists within HM_BUDGET.
 #pragma once
 
 namespace tsim {
-constexpr int HM_MAX_D = 1024;
 constexpr int HM_G = 8;                           // queries of one workgroup at most (above)
 static inline int hm_group(int64_t Q) { return (int)std::max<int64_t>(1, std::min<int64_t>(HM_G, (Q + 3) / 4)); }
-constexpr int HM_WGS = 1024;                      // workgroups the partial pass aims for
-constexpr int HM_MAX_CHUNKS = 1024;
-constexpr size_t HM_BUDGET = (size_t)64 << 20;    // chunk lists of one call (8 B an entry)
 
-__host__ __device__ inline int hm_code_bytes(int d) { return d >= 1 && d <= HM_MAX_D ? ((d + 7) / 8 + 15) / 16 * 16 : 0; }
+__host__ __device__ inline int hm_code_bytes(int d) { return d >= 1 && d <= CS_MAX_D ? ((d + 7) / 8 + 15) / 16 * 16 : 0; }
 
 // =====================================================================================================
 // pack_sign_rows: one wave per 64 elements.  The ballot of x > 0 holds element e of the wave's 64 at bit e; numpy's order wants
@@ -189,118 +174,6 @@ __global__ __launch_bounds__(256) void hamming_partial_kernel(int64_t Q, int64_t
     }
     for (int g = 0; g < ng; ++g) hm_list(hm_smem, g, kp, counters).store_raw(ws_s, ws_i, ((q0 + g) * nch + chunk) * k, k);
 }
-
-// one workgroup per query: the query's nch chunk lists are consecutive, E = nch k entries from q nch k on
-__global__ __launch_bounds__(256) void hamming_merge_kernel(int64_t Q, int64_t nch, int k, int kp, const float *__restrict__ ws_s,
-                                                            const int *__restrict__ ws_i, int32_t *__restrict__ out_d,
-                                                            int64_t *__restrict__ out_i, int64_t idx_offset) {
-    SlList<int, false> top = sl_shared_list<int, false>();
-    const int64_t E = nch * k;
-    for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-        top.reset(kp);
-        for (int64_t b0 = 0; b0 < E; b0 += SL_NB) {
-            const SlBound<int> w = top.bound(k);
-            for (int64_t e = b0 + threadIdx.x; e < E && e < b0 + SL_NB; e += 256) {
-                const int i = ws_i[q * E + e];
-                if (i != sl_pad<int>()) top.offer(ws_s[q * E + e], i, w);
-            }
-            top.flush(kp);
-        }
-        for (int t = threadIdx.x; t < k; t += 256) {
-            const int row = top.top_i[t];
-            const bool pad = row == sl_pad<int>();
-            out_d[q * k + t] = pad ? INT32_MAX : (int32_t)(-top.top_s[t]);
-            out_i[q * k + t] = pad ? -1 : (int64_t)row + idx_offset;
-        }
-        __syncthreads();
-    }
-}
-
-// =====================================================================================================
-// sign_rescore: one workgroup per query.  Each lane holds the query's elements j = lane + 64 i, i < 16, as float64.  A wave takes
-// one candidate at a time: every lane reads the 8 bytes of the code row that hold its element of group i (one address for the
-// whole wave), adds +q_j or -q_j in the order i = 0, 1, .. (the first term starts the sum, groups at or beyond d add nothing, an
-// element beyond d inside the last group adds +0), the xor butterfly 32 .. 1 joins the lanes and the sum is rounded once to
-// float32: float32(oracle.search_ref._lane_sum(q, s)), s = +-1 — every product is exact.  Candidates pass through one SlList in
-// blocks of SL_NB; negative entries are skipped, entries >= N never dereferenced and reported in the status word.
-// =====================================================================================================
-constexpr int SR_MAXI = HM_MAX_D / 64;
-
-__global__ __launch_bounds__(256) void sign_rescore_kernel(int64_t Q, int64_t N, const float *__restrict__ xq, int64_t ldq,
-                                                           const uint8_t *__restrict__ c_codes, int64_t ldc, int d,
-                                                           const int64_t *__restrict__ cand, int64_t m, int k, int kp,
-                                                           float *__restrict__ out_s, int64_t *__restrict__ out_i,
-                                                           int64_t idx_offset, int32_t *__restrict__ status) {
-    SlList<int, false> top = sl_shared_list<int, false>();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int shift = 8 * (lane >> 3) + 7 - (lane & 7);   // this lane's element within the 8 bytes of a group
-    for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-        double qv[SR_MAXI];
-        row_elems_f64<float, SR_MAXI>(qv, xq + q * ldq, d, lane);
-        top.reset(kp);
-        int beyond = 0;
-        for (int64_t b = 0; b < m; b += SL_NB) {
-            const int nb = (int)(m - b < SL_NB ? m - b : SL_NB);
-            const SlBound<int> w = top.bound(k);
-            for (int e = wave; e < nb; e += 4) {   // wave-uniform
-                const int64_t r = cand[q * m + b + e];
-                beyond |= r >= N;
-                if (r < 0 || r >= N) continue;
-                const unsigned long long *rp = reinterpret_cast<const unsigned long long *>(c_codes + r * ldc);
-                double acc = 0.0;
-#pragma unroll
-                for (int i = 0; i < SR_MAXI; ++i) {
-                    if (64 * i < d) {   // wave-uniform
-                        const bool set = (rp[i] >> shift) & 1;
-                        const double term = lane + 64 * i < d ? (set ? qv[i] : -qv[i]) : 0.0;
-                        acc = i == 0 ? term : acc + term;
-                    }
-                }
-                const float s = (float)wave_sum_f64(acc);
-                if (lane == 0) top.offer(s, (int)r, w);
-            }
-            top.flush(kp);
-        }
-        const int any_beyond = __syncthreads_or(beyond);
-        top.store_result<false>(out_s, out_i, q * k, k, idx_offset);
-        if (status && threadIdx.x == 0) status[q] = any_beyond ? TSIM_LIST_ST_ROW : 0;
-        __syncthreads();
-    }
-}
-
-// ----------------------------------------------------------------------------------------------------- host side
-// Chunks of one call: at most HM_MAX_CHUNKS, of at least max(SL_NB, 4 k) rows, as many as bring chunks x groups to HM_WGS
-// workgroups, and no more than keep the chunk lists within HM_BUDGET.
-static inline int64_t hm_chunks(int64_t Q, int64_t N, int k) {
-    const int64_t groups = (Q + hm_group(Q) - 1) / hm_group(Q);
-    const int64_t min_rows = std::max<int64_t>(SL_NB, ((int64_t)4 * k + SL_NB - 1) / SL_NB * SL_NB);
-    const int64_t fit = (int64_t)(HM_BUDGET / ((size_t)Q * k * 8));
-    return std::max<int64_t>(1, std::min<int64_t>({HM_MAX_CHUNKS, (N + min_rows - 1) / min_rows, (HM_WGS + groups - 1) / groups, fit}));
-}
-// The workspace holds the chunk lists: Q x chunks x k entries of 8 B.  The chunk count falls as Q grows, so the size asked for
-// is a bound that does not: with every chunk the corpus allows, capped where the budget caps the chunk count.
-static inline size_t hm_workspace_half(int64_t Q, int64_t N, int k) {
-    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(HM_MAX_CHUNKS, (N + SL_NB - 1) / SL_NB));
-    const size_t one = (size_t)Q * k * 8;
-    return align256(std::min(one * (size_t)cap, std::max(HM_BUDGET, one)) / 2);
-}
-
-static int check_code_stride(const char *what, const char *name, const void *codes, int64_t ld, int d) {
-    TSIM_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 15) == 0, "%s: the rows of %s do not start on a 16-byte boundary", what, name);
-    TSIM_REQUIRE(ld % 16 == 0, "%s: %s=%lld is not a multiple of 16", what, name, (long long)ld);
-    TSIM_REQUIRE(ld >= hm_code_bytes(d), "%s: %s=%lld < tsim_code_bytes(%d)=%d", what, name, (long long)ld, d, hm_code_bytes(d));
-    return TSIM_OK;
-}
-
-template <int NW>
-static int hamming_partial_launch(dim3 grid, size_t lds, hipStream_t st, int64_t Q, int64_t N, int64_t rpc, int G, const uint8_t *q_codes,
-                                  int64_t ldq, const uint8_t *c_codes, int64_t ldc, int d, int k, int kp, float *ws_s, int *ws_i) {
-    static DevOnce once;
-    TSIM_MAX_LDS(once, hamming_partial_kernel<NW>, 160 * 1024);
-    hipLaunchKernelGGL(hamming_partial_kernel<NW>, grid, dim3(256), lds, st, Q, N, rpc, G, q_codes, ldq, c_codes, ldc, d, k, kp, ws_s,
-                       ws_i);
-    return TSIM_OK;
-}
 }  // namespace tsim
 
 extern "C" int tsim_code_bytes(int d) { return tsim::hm_code_bytes(d); }
@@ -309,10 +182,10 @@ extern "C" int tsim_pack_sign_rows(const void *x, int x_dtype, int64_t rows, int
                                    void *stream) {
     using namespace tsim;
     TSIM_REQUIRE(x && codes, "pack_sign_rows: null pointer");
-    TSIM_REQUIRE(d >= 1 && d <= HM_MAX_D, "pack_sign_rows: d=%d outside 1..%d", d, HM_MAX_D);
+    TSIM_REQUIRE(d >= 1 && d <= CS_MAX_D, "pack_sign_rows: d=%d outside 1..%d", d, CS_MAX_D);
     TSIM_REQUIRE(rows >= 0 && rows < (1ll << 31) - 64 && ld_in >= d, "pack_sign_rows: bad shape rows=%lld d=%d ld_in=%lld", (long long)rows,
                  d, (long long)ld_in);
-    if (int rc = check_code_stride("pack_sign_rows", "ld_code", codes, ld_code, d)) return rc;
+    if (int rc = cs_check_stride("pack_sign_rows", "ld_code", codes, ld_code, d, hm_code_bytes(d), "tsim_code_bytes")) return rc;
     if (rows == 0) return TSIM_OK;
     const int64_t blocks = (rows * (hm_code_bytes(d) / 8) + 3) / 4;
     const dim3 grid((unsigned)std::min<int64_t>(blocks, 1 << 22));
@@ -328,71 +201,31 @@ extern "C" int tsim_pack_sign_rows(const void *x, int x_dtype, int64_t rows, int
     return TSIM_OK;
 }
 
-extern "C" size_t tsim_hamming_topk_workspace_bytes(int64_t Q, int64_t N, int k) {
-    if (Q <= 0 || N < 0 || k <= 0 || k > tsim::TOPK_LARGE_MAX_K) return 0;
-    return 2 * tsim::hm_workspace_half(Q, N, k);
-}
+
+extern "C" size_t tsim_hamming_topk_workspace_bytes(int64_t Q, int64_t N, int k) { return tsim::cs_workspace_bytes(Q, N, k); }
 
 extern "C" int tsim_hamming_topk(const uint8_t *q_codes, int64_t ldq, int64_t Q, const uint8_t *c_codes, int64_t ldc, int64_t N, int d,
                                  int k, int32_t *out_dist, int64_t *out_idx, int64_t idx_offset, void *workspace,
                                  size_t workspace_bytes, void *stream) {
     using namespace tsim;
-    const char *what = "hamming_topk";
-    TSIM_REQUIRE(q_codes && out_dist && out_idx && (c_codes || N == 0), "%s: null pointer", what);
-    TSIM_REQUIRE(d >= 1 && d <= HM_MAX_D, "%s: d=%d outside 1..%d", what, d, HM_MAX_D);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
-    TSIM_REQUIRE(Q > 0 && N >= 0, "%s: bad shape Q=%lld N=%lld", what, (long long)Q, (long long)N);
-    TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: too large for 32-bit row ids", what);
-    if (int rc = check_code_stride(what, "ldq", q_codes, ldq, d)) return rc;
-    if (int rc = check_code_stride(what, "ldc", c_codes, ldc, d)) return rc;
-    const size_t half = hm_workspace_half(Q, N, k);
-    if (!workspace || workspace_bytes < 2 * half) return fail(TSIM_ENOMEM, "%s: workspace %zu B < %zu B", what, workspace_bytes, 2 * half);
-    hipStream_t st = as_stream(stream);
-    float *ws_s = reinterpret_cast<float *>(workspace);
-    int *ws_i = reinterpret_cast<int *>(reinterpret_cast<char *>(workspace) + half);
-    const int kp = sl_list_len(k);
-    int64_t nch = 0;
-    if (N > 0) {
-        const int64_t want = hm_chunks(Q, N, k);
-        const int64_t rpc = ((N + want - 1) / want + SL_NB - 1) / SL_NB * SL_NB;   // whole blocks
-        nch = (N + rpc - 1) / rpc;                                                // (<= want: every chunk holds a row)
-        const int G = hm_group(Q);
-        const int64_t groups = (Q + G - 1) / G;
-        TSIM_REQUIRE(groups <= 65535, "%s: Q=%lld needs more than 65535 query groups: slice the queries", what, (long long)Q);
-        const dim3 grid((unsigned)nch, (unsigned)groups);
-        const size_t lds = (size_t)G * hm_list_bytes(kp) + (size_t)G * 4;
-        int rc = TSIM_OK;
-        switch (hm_code_bytes(d) / 16) {
+    return cs_topk<true>(
+        "hamming_topk", hm_code_bytes(d), "tsim_code_bytes", [](int64_t nq, int, int) { return hm_group(nq); }, [](int) { return SL_NB; },
+        q_codes, ldq, Q, c_codes, ldc, N, d, k, out_dist, out_idx, idx_offset, workspace, workspace_bytes, stream, [&](const CsLaunch &l) {
+            switch (hm_code_bytes(d) / 16) {
 #define TSIM_HM_CASE(NW)                                                                                                          \
     case NW:                                                                                                                      \
-        rc = hamming_partial_launch<NW>(grid, lds, st, Q, N, rpc, G, q_codes, ldq, c_codes, ldc, d, k, kp, ws_s, ws_i);             \
-        break;
-            TSIM_HM_CASE(1) TSIM_HM_CASE(2) TSIM_HM_CASE(3) TSIM_HM_CASE(4) TSIM_HM_CASE(5) TSIM_HM_CASE(6) TSIM_HM_CASE(7) TSIM_HM_CASE(8)
+        return cs_launch_partial<hamming_partial_kernel<NW>>(l, Q, N, l.rpc, l.G, q_codes, ldq, c_codes, ldc, d, k, l.kp, l.ws_s,    \
+                                                             l.ws_i);
+                TSIM_HM_CASE(1) TSIM_HM_CASE(2) TSIM_HM_CASE(3) TSIM_HM_CASE(4) TSIM_HM_CASE(5) TSIM_HM_CASE(6) TSIM_HM_CASE(7) TSIM_HM_CASE(8)
 #undef TSIM_HM_CASE
-        }
-        if (rc) return rc;
-        TSIM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(hamming_merge_kernel, dim3((unsigned)std::min<int64_t>(Q, 4096)), dim3(256), 0, st, Q, nch, k, kp, ws_s, ws_i,
-                       out_dist, out_idx, idx_offset);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
+            }
+            return (int)TSIM_OK;
+        });
 }
 
 extern "C" int tsim_sign_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const uint8_t *c_codes, int64_t ldc, int64_t N,
                                       int d, const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx,
                                       int64_t idx_offset, int32_t *out_status, void *stream) {
-    using namespace tsim;
-    const char *what = "sign_rescore_topk";
-    TSIM_REQUIRE(eq_f32 && out_scores && out_idx && (c_codes || N == 0) && (cand || m == 0), "%s: null pointer", what);
-    TSIM_REQUIRE(d >= 1 && d <= HM_MAX_D, "%s: d=%d outside 1..%d", what, d, HM_MAX_D);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
-    TSIM_REQUIRE(Q > 0 && N >= 0 && m >= 0, "%s: bad shape Q=%lld N=%lld m=%lld", what, (long long)Q, (long long)N, (long long)m);
-    TSIM_REQUIRE(N < (1ll << 31) - 64, "%s: too large for 32-bit row ids", what);
-    TSIM_REQUIRE(ldq_f32 >= d, "%s: ldq_f32=%lld < d=%d", what, (long long)ldq_f32, d);
-    if (int rc = check_code_stride(what, "ldc", c_codes, ldc, d)) return rc;
-    hipLaunchKernelGGL(sign_rescore_kernel, dim3((unsigned)std::min<int64_t>(Q, 1 << 20)), dim3(256), 0, as_stream(stream), Q, N, eq_f32,
-                       ldq_f32, c_codes, ldc, d, cand, m, k, sl_list_len(k), out_scores, out_idx, idx_offset, out_status);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
+    return tsim::cs_rescore<true>("sign_rescore_topk", tsim::hm_code_bytes(d), "tsim_code_bytes", eq_f32, ldq_f32, Q, c_codes, ldc, N, d,
+                                  cand, m, k, out_scores, out_idx, idx_offset, out_status, stream);
 }

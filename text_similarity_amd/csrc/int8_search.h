@@ -1,6 +1,6 @@
-// int8 embeddings (included by search.hip, after hamming_search.h, whose chunk budget and workspace rule it uses): the calibrated
-// scalar quantiser, exact inner-product top-k on the int8 matrix pipe, and the re-score of its candidates with the float32 query
-// against the code values.
+// int8 embeddings (included by search.hip, after code_search.h, whose frame it fills in): the calibrated scalar quantiser, exact
+// inner-product top-k on the int8 matrix pipe, and the re-score of its candidates with the float32 query against the code values
+// (code_rescore_kernel<false>).
 //
 // Codes.  A code row is d int8 values, 1 <= d <= 1024.  Rows lie tsim_int8_bytes(d) = d rounded up to 16 bytes apart (or more:
 // every stride is a multiple of 16), so a row is read with 16-byte loads; the bytes from d to tsim_int8_bytes(d) are zero in
@@ -21,19 +21,15 @@
 // list of its query.  The tile of the NEXT 16 rows is loaded before the current one is multiplied and offered, so a wave has two
 // tiles of loads in flight (16 lists leave room for two workgroups a CU at the most).
 //
-// Lists and flushes: those of hamming_partial_kernel.  One SlList per query in dynamic LDS (i8_list), a step is 256 rows (four
-// tiles a wave), a list is flushed after the chunk's first step, after the last, and in between only when its block could not
-// take the 256 offers of another step.  A block holds bc = 512 or SL_NB entries (i8_block_cap).  G (i8_group): at most 16
-// while k <= 64, else 8 (the other eight columns of the tile are zero and never offered).  Chunks and workspace: hm_chunks'
-// rules with this G.
-// int8_ip_merge_kernel is hamming_merge_kernel writing int32 scores, padding (INT32_MIN, -1).
+// Lists (i8_list) and flushes follow the frame's protocol.  A step is 256 rows (four tiles a wave); a list's block holds bc = 512
+// or SL_NB entries (i8_block_cap).  G (i8_group): at most 16 while k <= 64, else 8 (the other eight columns of the tile are zero
+// and never offered).
 #pragma once
 
 namespace tsim {
-constexpr int I8_MAX_D = 1024;
 constexpr int I8_STEP = 256;   // rows of one step of the partial kernel: 4 waves x 4 tiles x 16 rows
 
-__host__ __device__ inline int i8_bytes(int d) { return d >= 1 && d <= I8_MAX_D ? (d + 15) / 16 * 16 : 0; }
+__host__ __device__ inline int i8_bytes(int d) { return d >= 1 && d <= CS_MAX_D ? (d + 15) / 16 * 16 : 0; }
 // Queries of one workgroup: at most 16 while k <= 64, else 8, and for a small query set fewer, so that several groups exist:
 // ceil(Q / 4) a group for rows up to 512 bytes, ceil(Q / 2) beyond (every group reads the whole corpus once more, and a wide row
 // makes that pass dearer than the lists it spares: at Q = 16, N = 1 M, d = 1024 two groups took 0.64 ms, four 0.81, one 0.76; at
@@ -70,8 +66,8 @@ __device__ __forceinline__ int i8_quantize_one(float x, float start, float step)
 __global__ __launch_bounds__(256) void quantize_int8_rows_kernel(const float *__restrict__ x, int64_t rows, int d, int64_t ld_in,
                                                                  const float *__restrict__ ranges, int8_t *__restrict__ codes,
                                                                  int64_t ld_code) {
-    __shared__ __attribute__((aligned(16))) int8_t stage[4][I8_MAX_D];
-    constexpr int NI = I8_MAX_D / 64;
+    __shared__ __attribute__((aligned(16))) int8_t stage[4][CS_MAX_D];
+    constexpr int NI = CS_MAX_D / 64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cb = i8_bytes(d);
     float start[NI], step[NI];
@@ -204,112 +200,6 @@ __global__ __launch_bounds__(256) void int8_ip_partial_kernel(int64_t Q, int64_t
     }
     for (int g = 0; g < ng; ++g) i8_list(i8_smem, g, kp, bc, counters).store_raw(ws_s, ws_i, ((q0 + g) * nch + chunk) * k, k);
 }
-
-// one workgroup per query: the query's nch chunk lists are consecutive, E = nch k entries from q nch k on
-__global__ __launch_bounds__(256) void int8_ip_merge_kernel(int64_t Q, int64_t nch, int k, int kp, const float *__restrict__ ws_s,
-                                                            const int *__restrict__ ws_i, int32_t *__restrict__ out_s,
-                                                            int64_t *__restrict__ out_i, int64_t idx_offset) {
-    SlList<int, false> top = sl_shared_list<int, false>();
-    const int64_t E = nch * k;
-    for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-        top.reset(kp);
-        for (int64_t b0 = 0; b0 < E; b0 += SL_NB) {
-            const SlBound<int> w = top.bound(k);
-            for (int64_t e = b0 + threadIdx.x; e < E && e < b0 + SL_NB; e += 256) {
-                const int i = ws_i[q * E + e];
-                if (i != sl_pad<int>()) top.offer(ws_s[q * E + e], i, w);
-            }
-            top.flush(kp);
-        }
-        for (int t = threadIdx.x; t < k; t += 256) {
-            const int row = top.top_i[t];
-            const bool pad = row == sl_pad<int>();
-            out_s[q * k + t] = pad ? INT32_MIN : (int32_t)top.top_s[t];
-            out_i[q * k + t] = pad ? -1 : (int64_t)row + idx_offset;
-        }
-        __syncthreads();
-    }
-}
-
-// =====================================================================================================
-// int8_rescore: sign_rescore_kernel with the code value in place of +-1.  One workgroup per query; each lane holds the query's
-// elements j = lane + 64 i as float64; a wave takes one candidate at a time, lane l reads byte lane + 64 i of the code row (one
-// 64-byte span a wave) and adds q_j c_j in the order i = 0, 1, .. (the first product starts the sum, groups at or beyond d add
-// nothing, an element beyond d inside the last group adds +0), the xor butterfly joins the lanes and the sum is rounded once:
-// float32(oracle.search_ref._lane_sum(q, codes)) — every product of a float32 and an int8 is exact in float64.
-// =====================================================================================================
-__global__ __launch_bounds__(256) void int8_rescore_kernel(int64_t Q, int64_t N, const float *__restrict__ xq, int64_t ldq,
-                                                           const int8_t *__restrict__ c_codes, int64_t ldc, int d,
-                                                           const int64_t *__restrict__ cand, int64_t m, int k, int kp,
-                                                           float *__restrict__ out_s, int64_t *__restrict__ out_i,
-                                                           int64_t idx_offset, int32_t *__restrict__ status) {
-    SlList<int, false> top = sl_shared_list<int, false>();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-        double qv[SR_MAXI];
-        row_elems_f64<float, SR_MAXI>(qv, xq + q * ldq, d, lane);
-        top.reset(kp);
-        int beyond = 0;
-        for (int64_t b = 0; b < m; b += SL_NB) {
-            const int nb = (int)(m - b < SL_NB ? m - b : SL_NB);
-            const SlBound<int> w = top.bound(k);
-            for (int e = wave; e < nb; e += 4) {   // wave-uniform
-                const int64_t r = cand[q * m + b + e];
-                beyond |= r >= N;
-                if (r < 0 || r >= N) continue;
-                const int8_t *rp = c_codes + r * ldc;
-                int c[SR_MAXI];
-#pragma unroll
-                for (int i = 0; i < SR_MAXI; ++i) {   // (branch-free loads: the address of an element past d is clamped)
-                    const int j = lane + 64 * i;
-                    c[i] = 64 * i < d ? (int)rp[j < d ? j : d - 1] : 0;
-                }
-                double acc = 0.0;
-#pragma unroll
-                for (int i = 0; i < SR_MAXI; ++i) {
-                    if (64 * i < d) {   // wave-uniform
-                        const double term = lane + 64 * i < d ? qv[i] * (double)c[i] : 0.0;
-                        acc = i == 0 ? term : acc + term;
-                    }
-                }
-                const float s = (float)wave_sum_f64(acc);
-                if (lane == 0) top.offer(s, (int)r, w);
-            }
-            top.flush(kp);
-        }
-        const int any_beyond = __syncthreads_or(beyond);
-        top.store_result<false>(out_s, out_i, q * k, k, idx_offset);
-        if (status && threadIdx.x == 0) status[q] = any_beyond ? TSIM_LIST_ST_ROW : 0;
-        __syncthreads();
-    }
-}
-
-// ----------------------------------------------------------------------------------------------------- host side
-// hm_chunks with this kernel's group size
-static inline int64_t i8_chunks(int64_t Q, int64_t N, int k, int d) {
-    const int G = i8_group(Q, k, d);
-    const int64_t groups = (Q + G - 1) / G;
-    const int64_t min_rows = std::max<int64_t>(SL_NB, ((int64_t)4 * k + SL_NB - 1) / SL_NB * SL_NB);
-    const int64_t fit = (int64_t)(HM_BUDGET / ((size_t)Q * k * 8));
-    return std::max<int64_t>(1, std::min<int64_t>({HM_MAX_CHUNKS, (N + min_rows - 1) / min_rows, (HM_WGS + groups - 1) / groups, fit}));
-}
-
-static int check_int8_stride(const char *what, const char *name, const void *codes, int64_t ld, int d) {
-    TSIM_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 15) == 0, "%s: the rows of %s do not start on a 16-byte boundary", what, name);
-    TSIM_REQUIRE(ld % 16 == 0, "%s: %s=%lld is not a multiple of 16", what, name, (long long)ld);
-    TSIM_REQUIRE(ld >= i8_bytes(d), "%s: %s=%lld < tsim_int8_bytes(%d)=%d", what, name, (long long)ld, d, i8_bytes(d));
-    return TSIM_OK;
-}
-
-template <int KS>
-static int int8_ip_partial_launch(dim3 grid, size_t lds, hipStream_t st, int64_t Q, int64_t N, int64_t rpc, int G, const int8_t *q_codes,
-                                  int64_t ldq, const int8_t *c_codes, int64_t ldc, int d, int k, int kp, int bc, float *ws_s, int *ws_i) {
-    static DevOnce once;
-    TSIM_MAX_LDS(once, int8_ip_partial_kernel<KS>, 160 * 1024);
-    hipLaunchKernelGGL(int8_ip_partial_kernel<KS>, grid, dim3(256), lds, st, Q, N, rpc, G, q_codes, ldq, c_codes, ldc, d, k, kp, bc, ws_s,
-                       ws_i);
-    return TSIM_OK;
-}
 }  // namespace tsim
 
 extern "C" int tsim_int8_bytes(int d) { return tsim::i8_bytes(d); }
@@ -319,10 +209,10 @@ extern "C" int tsim_quantize_int8_rows(const float *x, int64_t rows, int d, int6
     using namespace tsim;
     const char *what = "quantize_int8_rows";
     TSIM_REQUIRE(x && ranges && codes, "%s: null pointer", what);
-    TSIM_REQUIRE(d >= 1 && d <= I8_MAX_D, "%s: d=%d outside 1..%d", what, d, I8_MAX_D);
+    TSIM_REQUIRE(d >= 1 && d <= CS_MAX_D, "%s: d=%d outside 1..%d", what, d, CS_MAX_D);
     TSIM_REQUIRE(rows >= 0 && rows < (1ll << 31) - 64 && ld_in >= d, "%s: bad shape rows=%lld d=%d ld_in=%lld", what, (long long)rows, d,
                  (long long)ld_in);
-    if (int rc = check_int8_stride(what, "ld_code", codes, ld_code, d)) return rc;
+    if (int rc = cs_check_stride(what, "ld_code", codes, ld_code, d, i8_bytes(d), "tsim_int8_bytes")) return rc;
     if (rows == 0) return TSIM_OK;
     const dim3 grid((unsigned)std::min<int64_t>((rows + 3) / 4, 256 * 16));
     hipLaunchKernelGGL(quantize_int8_rows_kernel, grid, dim3(256), 0, as_stream(stream), x, rows, d, ld_in, ranges, codes, ld_code);
@@ -330,74 +220,33 @@ extern "C" int tsim_quantize_int8_rows(const float *x, int64_t rows, int d, int6
     return TSIM_OK;
 }
 
-extern "C" size_t tsim_int8_ip_topk_workspace_bytes(int64_t Q, int64_t N, int k) {
-    if (Q <= 0 || N < 0 || k <= 0 || k > tsim::TOPK_LARGE_MAX_K) return 0;
-    return 2 * tsim::hm_workspace_half(Q, N, k);
-}
+extern "C" size_t tsim_int8_ip_topk_workspace_bytes(int64_t Q, int64_t N, int k) { return tsim::cs_workspace_bytes(Q, N, k); }
 
 extern "C" int tsim_int8_ip_topk(const int8_t *q_codes, int64_t ldq, int64_t Q, const int8_t *c_codes, int64_t ldc, int64_t N, int d,
                                  int k, int32_t *out_score, int64_t *out_idx, int64_t idx_offset, void *workspace,
                                  size_t workspace_bytes, void *stream) {
     using namespace tsim;
-    const char *what = "int8_ip_topk";
-    TSIM_REQUIRE(q_codes && out_score && out_idx && (c_codes || N == 0), "%s: null pointer", what);
-    TSIM_REQUIRE(d >= 1 && d <= I8_MAX_D, "%s: d=%d outside 1..%d", what, d, I8_MAX_D);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
-    TSIM_REQUIRE(Q > 0 && N >= 0, "%s: bad shape Q=%lld N=%lld", what, (long long)Q, (long long)N);
-    TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31) - 512, "%s: too large for 32-bit row ids", what);
-    if (int rc = check_int8_stride(what, "ldq", q_codes, ldq, d)) return rc;
-    if (int rc = check_int8_stride(what, "ldc", c_codes, ldc, d)) return rc;
-    const size_t half = hm_workspace_half(Q, N, k);
-    if (!workspace || workspace_bytes < 2 * half) return fail(TSIM_ENOMEM, "%s: workspace %zu B < %zu B", what, workspace_bytes, 2 * half);
-    hipStream_t st = as_stream(stream);
-    float *ws_s = reinterpret_cast<float *>(workspace);
-    int *ws_i = reinterpret_cast<int *>(reinterpret_cast<char *>(workspace) + half);
-    const int kp = sl_list_len(k);
-    int64_t nch = 0;
-    if (N > 0) {
-        const int64_t want = i8_chunks(Q, N, k, d);
-        const int64_t rpc = ((N + want - 1) / want + SL_NB - 1) / SL_NB * SL_NB;   // whole blocks
-        nch = (N + rpc - 1) / rpc;                                                // (<= want: every chunk holds a row)
-        const int G = i8_group(Q, k, d);
-        const int64_t groups = (Q + G - 1) / G;
-        TSIM_REQUIRE(groups <= 65535, "%s: Q=%lld needs more than 65535 query groups: slice the queries", what, (long long)Q);
-        const dim3 grid((unsigned)nch, (unsigned)groups);
-        const int bc = i8_block_cap(kp);
-        const size_t lds = (size_t)G * i8_list_bytes(kp, bc) + (size_t)G * 4;
-        int rc = TSIM_OK;
-        switch ((d + 63) / 64) {
+    return cs_topk<false>(
+        "int8_ip_topk", i8_bytes(d), "tsim_int8_bytes", i8_group, i8_block_cap, q_codes, ldq, Q, c_codes, ldc, N, d, k, out_score, out_idx,
+        idx_offset, workspace, workspace_bytes, stream, [&](const CsLaunch &l) {
+            switch ((d + 63) / 64) {
 #define TSIM_I8_CASE(KS)                                                                                                          \
     case KS:                                                                                                                      \
-        rc = int8_ip_partial_launch<KS>(grid, lds, st, Q, N, rpc, G, q_codes, ldq, c_codes, ldc, d, k, kp, bc, ws_s, ws_i);         \
-        break;
-            TSIM_I8_CASE(1) TSIM_I8_CASE(2) TSIM_I8_CASE(3) TSIM_I8_CASE(4) TSIM_I8_CASE(5) TSIM_I8_CASE(6) TSIM_I8_CASE(7) TSIM_I8_CASE(8)
-            TSIM_I8_CASE(9) TSIM_I8_CASE(10) TSIM_I8_CASE(11) TSIM_I8_CASE(12) TSIM_I8_CASE(13) TSIM_I8_CASE(14) TSIM_I8_CASE(15)
-            TSIM_I8_CASE(16)
+        return cs_launch_partial<int8_ip_partial_kernel<KS>>(l, Q, N, l.rpc, l.G, q_codes, ldq, c_codes, ldc, d, k, l.kp, l.bc,      \
+                                                             l.ws_s, l.ws_i);
+                TSIM_I8_CASE(1) TSIM_I8_CASE(2) TSIM_I8_CASE(3) TSIM_I8_CASE(4) TSIM_I8_CASE(5) TSIM_I8_CASE(6) TSIM_I8_CASE(7) TSIM_I8_CASE(8)
+                TSIM_I8_CASE(9) TSIM_I8_CASE(10) TSIM_I8_CASE(11) TSIM_I8_CASE(12) TSIM_I8_CASE(13) TSIM_I8_CASE(14) TSIM_I8_CASE(15)
+                TSIM_I8_CASE(16)
 #undef TSIM_I8_CASE
-        }
-        if (rc) return rc;
-        TSIM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(int8_ip_merge_kernel, dim3((unsigned)std::min<int64_t>(Q, 4096)), dim3(256), 0, st, Q, nch, k, kp, ws_s, ws_i,
-                       out_score, out_idx, idx_offset);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
+            }
+            return (int)TSIM_OK;
+        });
 }
 
 extern "C" int tsim_int8_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const int8_t *c_codes, int64_t ldc, int64_t N,
                                       int d, const int64_t *cand, int64_t m, int k, float *out_scores, int64_t *out_idx,
                                       int64_t idx_offset, int32_t *out_status, void *stream) {
-    using namespace tsim;
-    const char *what = "int8_rescore_topk";
-    TSIM_REQUIRE(eq_f32 && out_scores && out_idx && (c_codes || N == 0) && (cand || m == 0), "%s: null pointer", what);
-    TSIM_REQUIRE(d >= 1 && d <= I8_MAX_D, "%s: d=%d outside 1..%d", what, d, I8_MAX_D);
-    TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
-    TSIM_REQUIRE(Q > 0 && N >= 0 && m >= 0, "%s: bad shape Q=%lld N=%lld m=%lld", what, (long long)Q, (long long)N, (long long)m);
-    TSIM_REQUIRE(N < (1ll << 31) - 64, "%s: too large for 32-bit row ids", what);
-    TSIM_REQUIRE(ldq_f32 >= d, "%s: ldq_f32=%lld < d=%d", what, (long long)ldq_f32, d);
-    if (int rc = check_int8_stride(what, "ldc", c_codes, ldc, d)) return rc;
-    hipLaunchKernelGGL(int8_rescore_kernel, dim3((unsigned)std::min<int64_t>(Q, 1 << 20)), dim3(256), 0, as_stream(stream), Q, N, eq_f32,
-                       ldq_f32, c_codes, ldc, d, cand, m, k, sl_list_len(k), out_scores, out_idx, idx_offset, out_status);
-    TSIM_HIP_CHECK(hipGetLastError());
-    return TSIM_OK;
+    return tsim::cs_rescore<false>("int8_rescore_topk", tsim::i8_bytes(d), "tsim_int8_bytes", eq_f32, ldq_f32, Q, c_codes, ldc, N, d,
+                                   cand, m, k, out_scores, out_idx, idx_offset, out_status, stream);
 }
+

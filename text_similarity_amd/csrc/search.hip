@@ -1881,6 +1881,7 @@ static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, cons
 
 #include "range_search.h"   // exact range search: kernels and entry points, on the helpers above
 #include "list_search.h"    // exact top-k within candidate lists: the indirect form of the brute-force pass
+#include "code_search.h"    // what the two code searches below share: list carve, flush policy, merge, re-score, host drivers
 #include "hamming_search.h" // binary embeddings: sign-bit codes, exact Hamming top-k, re-score against the +-1 expansion
 #include "int8_search.h"    // int8 embeddings: calibrated quantiser, exact inner-product top-k on the int8 MFMA, re-score
 #include "ivf_search.h"     // inverted lists: exact scan of the contiguous lists each query probes

@@ -19,15 +19,13 @@ codes ``[n, dim]`` int8, the labels, ``dim`` and the ranges (shape [0, dim] whil
 """
 from __future__ import annotations
 
-import os
-from typing import Iterable, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
-
-INT32_MIN = -2 ** 31
+from ._code_index import _CodeIndex
 
 
 def pack_index_file(path, codes: np.ndarray, labels: np.ndarray, dim: int, ranges: Optional[np.ndarray]):
@@ -56,24 +54,21 @@ def unpack_index_file(path, dim: int):
     return codes, labels, (r if r.shape == (2, dim) else None)
 
 
-class GpuInt8Index:
+class GpuInt8Index(_CodeIndex):
+    _CODE_DTYPE, _NP_DTYPE, _FILE_NAME = torch.int8, np.int8, "int8_index.bin"
+    _first_stage = staticmethod(ops.int8_ip_topk)
+    _rescore = staticmethod(ops.int8_rescore_topk)
+    _pad_codes = staticmethod(ops.int8_codes_from_numpy)
+
     def __init__(self, dim: int, ranges=None, device: Optional[torch.device] = None):
-        self.dim = int(dim)
-        self._cb = ops.int8_bytes(self.dim)            # raises outside 1..1024
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        super().__init__(dim, ops.int8_bytes(int(dim)), device)   # raises outside 1..1024
         self._ranges: Optional[torch.Tensor] = None    # [2, dim] float32 on the device
         if ranges is not None:
             self._set_ranges(ranges)
-        self._codes: Optional[torch.Tensor] = None     # [capacity, int8_bytes(dim)] int8
-        self._labels: Optional[torch.Tensor] = None    # [capacity] int64
-        self._n = 0
 
     @property
     def ranges(self) -> Optional[torch.Tensor]:
         return self._ranges
-
-    def get_current_count(self) -> int:
-        return self._n
 
     def _set_ranges(self, ranges):
         r = ranges if isinstance(ranges, torch.Tensor) else torch.as_tensor(np.asarray(ranges, dtype=np.float32))
@@ -81,8 +76,9 @@ class GpuInt8Index:
             raise ValueError(f"ranges must be float [2, {self.dim}] (per-column minimum and maximum), got {tuple(r.shape)}")
         self._ranges = r.to(self.device, dtype=torch.float32).contiguous()
 
-    def _as_codes(self, data, calibrate: bool = False) -> torch.Tensor:
-        """float rows [n, dim] are quantised on the device with the index's ranges; int8 rows [n, dim] are codes"""
+    def _as_codes(self, data, adding: bool = False) -> torch.Tensor:
+        """float rows [n, dim] are quantised on the device with the index's ranges (rows being added calibrate an index that has
+        none); int8 rows [n, dim] are codes"""
         x = data if isinstance(data, torch.Tensor) else torch.as_tensor(np.asarray(data))
         if x.dim() == 1:
             x = x.unsqueeze(0)
@@ -96,96 +92,30 @@ class GpuInt8Index:
             raise ValueError(f"expected float rows or int8 codes, got {x.dtype}")
         x = x.to(self.device, dtype=torch.float32)
         if self._ranges is None:
-            if not calibrate or x.shape[0] == 0:
+            if not adding or x.shape[0] == 0:
                 raise ValueError("the index has no calibration ranges yet: pass ranges=, or add float rows first")
             self._ranges = ops.int8_ranges(x)
         return ops.quantize_int8_rows(x, self._ranges)
-
-    def add_items(self, data, ids: Optional[Iterable[int]] = None):
-        codes = self._as_codes(data, calibrate=True)
-        n = codes.shape[0]
-        if ids is None:
-            ids = np.arange(self._n, self._n + n)
-        lab = torch.as_tensor(np.asarray(list(ids), dtype=np.int64))
-        if lab.numel() != n:
-            raise ValueError("ids and data disagree in length")
-        self._reserve(self._n + n)
-        self._codes[self._n:self._n + n] = codes
-        self._labels[self._n:self._n + n] = lab.to(self.device)
-        self._n += n
 
     def search(self, data, k: int, rescore_multiplier: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Without ``rescore_multiplier``: (score [Q,k] int32, labels [Q,k] int64) by (score desc, row asc), padded with
         (-2**31, -1) when the index holds fewer than k rows.  With it (float queries only): the min(k * multiplier, 1024, count)
         best codes are re-scored with the float32 queries; returns (scores [Q,k] float32, labels) by (score desc, row asc),
         padded with (-inf, -1)."""
-        k = int(k)
-        q = data if isinstance(data, torch.Tensor) else torch.as_tensor(np.asarray(data))
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        qc = self._as_codes(q)
-        Q = qc.shape[0]
-        codes = self._codes[:self._n] if self._n else torch.zeros((0, self._cb), dtype=torch.int8, device=self.device)
-        if rescore_multiplier is None:
-            score, idx = ops.int8_ip_topk(qc, codes, self.dim, k)
-            return score, self._to_labels(idx)
-        if q.dtype == torch.int8:
-            raise ValueError("re-scoring needs the float queries, not their codes")
-        mult = int(rescore_multiplier)
-        if mult < 1:
-            raise ValueError(f"rescore_multiplier={rescore_multiplier} must be >= 1")
-        qf = q.to(self.device, dtype=torch.float32).contiguous()
-        m = min(k * mult, ops.MAX_K, self._n)
-        if m == 0 or Q == 0:
-            return (torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device),
-                    torch.full((Q, k), -1, dtype=torch.int64, device=self.device))
-        _, cand = ops.int8_ip_topk(qc, codes, self.dim, m)
-        scores, idx = ops.int8_rescore_topk(qf, codes, self.dim, cand, k)
-        return scores, self._to_labels(idx)
+        return super().search(data, k, rescore_multiplier)
 
     def knn_query(self, data, k: int = 1, rescore_multiplier: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(labels [Q,k] int64, scores [Q,k]) as numpy arrays, best first — the order of ``GpuFlatIndex.knn_query``.  Scores are
         the int32 code products, or with ``rescore_multiplier`` the float32 re-scores (larger is better either way)."""
-        s, lab = self.search(data, k, rescore_multiplier)
-        return lab.cpu().numpy(), s.cpu().numpy()
+        return super().knn_query(data, k, rescore_multiplier)
 
     def save_index(self, path: str):
-        if os.path.isdir(path):
-            path = os.path.join(path, "int8_index.bin")
-        codes = self._codes[:self._n, :self.dim].cpu().numpy() if self._n else np.zeros((0, self.dim), np.int8)
-        labels = self._labels[:self._n].cpu().numpy() if self._n else np.zeros((0,), np.int64)
-        pack_index_file(path, codes, labels, self.dim, None if self._ranges is None else self._ranges.cpu().numpy())
+        codes, labels = self._stored(self.dim)
+        pack_index_file(self._file(path), codes, labels, self.dim, None if self._ranges is None else self._ranges.cpu().numpy())
 
     def load_index(self, path: str, max_elements: int = 0):
-        if os.path.isdir(path):
-            path = os.path.join(path, "int8_index.bin")
-        codes, labels, ranges = unpack_index_file(path, self.dim)
-        self._codes = self._labels = None
-        self._n = 0
+        codes, labels, ranges = unpack_index_file(self._file(path), self.dim)
         self._ranges = None
         if ranges is not None:
             self._set_ranges(ranges)
-        n = codes.shape[0]
-        self._reserve(max(n, int(max_elements)))
-        if n:
-            self._codes[:n] = ops.int8_codes_from_numpy(codes, self.dim, device=self.device)
-            self._labels[:n] = torch.from_numpy(labels).to(self.device)
-            self._n = n
-
-    # ------------------------------------------------------------------ internals
-    def _to_labels(self, idx: torch.Tensor) -> torch.Tensor:
-        if self._n == 0:
-            return torch.full_like(idx, -1)
-        return torch.where(idx >= 0, self._labels[idx.clamp(min=0)], torch.full_like(idx, -1))
-
-    def _reserve(self, n: int):
-        cap = 0 if self._codes is None else self._codes.shape[0]
-        if n <= cap:
-            return
-        new_cap = max(n, 2 * cap, 1024)
-        codes = torch.zeros((new_cap, self._cb), dtype=torch.int8, device=self.device)
-        labels = torch.full((new_cap,), -1, dtype=torch.int64, device=self.device)
-        if self._codes is not None and self._n:
-            codes[:self._n] = self._codes[:self._n]
-            labels[:self._n] = self._labels[:self._n]
-        self._codes, self._labels = codes, labels
+        self._restore(codes, labels, max_elements)

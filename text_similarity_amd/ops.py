@@ -525,9 +525,91 @@ def ivf_scan_topk(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, list
     return (scores, idx, status) if return_status else (scores, idx)
 
 
-# ------------------------------------------------------------------------------------------------- exact range search
+# ------------------------------------------------------------------------------------------------- code searches: the shared frame
+MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit and the int8 codes
+
+
+def _check_code_rows(what, name, t, d, dev, dtype, width_fn, made_by):
+    """the row stride of a code matrix ``t``: ``dtype`` [rows, >= width_fn(d)], rows read with 16-byte loads"""
+    cb = width_fn(d)
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != 2 or t.shape[1] < cb
+            or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % 16) or t.data_ptr() % 16):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _need_gpu(t)
+        kind = str(dtype).replace("torch.", "")
+        raise ValueError(f"{what}: {name} must be {kind} [rows, >= {width_fn.__name__}({d})={cb}] on the device with unit inner stride, "
+                         f"rows a multiple of 16 bytes apart and 16-byte aligned ({made_by})")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {t.device})")
+    return t.stride(0) if t.shape[0] > 1 else (t.shape[1] // 16) * 16
+
+
+def _code_topk(what, rows, ws_fn_name, fn_name, q_codes, c_codes, d, k, idx_offset, out):
+    """the first stage over code rows (``rows``: the code type's arguments of _check_code_rows): (value int32 [Q,k], idx int64
+    [Q,k])"""
+    _need_gpu(q_codes, c_codes)
+    dev = q_codes.device
+    ldq = _check_code_rows(what, "q_codes", q_codes, d, None, **rows)
+    ldc = _check_code_rows(what, "c_codes", c_codes, d, dev, **rows)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = q_codes.shape[0], c_codes.shape[0]
+    if out is not None:
+        val, idx = out
+        _need_gpu(val, idx)
+        if (val.shape != (Q, k) or idx.shape != (Q, k) or val.dtype != torch.int32 or idx.dtype != torch.int64
+                or not val.is_contiguous() or not idx.is_contiguous() or val.device != dev or idx.device != dev):
+            raise ValueError(f"{what}: out must be contiguous int32 / int64 [{Q}, {k}] tensors on {dev}")
+    else:
+        val = torch.empty((Q, k), dtype=torch.int32, device=dev)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    if Q == 0:
+        return val, idx
+    L = _lib.lib()
+    fn = getattr(L, fn_name)
+    with torch.cuda.device(dev):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = getattr(L, ws_fn_name)(step, N, k)
+        if nbytes == 0:
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k}")
+        ws = _workspace(dev, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = fn(q_codes.data_ptr() + q0 * ldq, ldq, nq, c_codes.data_ptr() if N else 0, ldc, N, int(d), k,
+                    val.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(), _stream(q_codes))
+            _lib.check(rc, what)
+    return val, idx
+
+
+def _code_rescore(what, rows, fn_name, eq_f32, c_codes, d, cand, k, idx_offset, return_status):
+    """the second stage: the float32 queries against the code rows of every query's candidates"""
+    _need_gpu(eq_f32, c_codes, cand)
+    dev = eq_f32.device
+    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
+        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
+    ldc = _check_code_rows(what, "c_codes", c_codes, d, dev, **rows)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    Q, N = eq_f32.shape[0], c_codes.shape[0]
+    if cand.dim() != 2 or cand.shape[0] != Q or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+        raise ValueError(f"{what}: cand must hold integers [{Q}, m]")
+    cand = cand.to(torch.int64).contiguous()
+    m = cand.shape[1]
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q:
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.lib(), fn_name)(eq_f32.data_ptr(), _row_stride(eq_f32), Q, c_codes.data_ptr() if N else 0, ldc, N, int(d),
+                                              cand.data_ptr() if m else 0, m, k, scores.data_ptr(), idx.data_ptr(), idx_offset,
+                                              status.data_ptr() if return_status else 0, _stream(eq_f32))
+            _lib.check(rc, what)
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
 # ------------------------------------------------------------------------------------------------- binary embeddings
-MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit codes
 
 
 def code_bytes(d: int) -> int:
@@ -578,17 +660,7 @@ def codes_from_packbits(a, d: int, device=None) -> torch.Tensor:
     return out
 
 
-def _check_codes(what, name, t, d, dev=None):
-    cb = code_bytes(d)
-    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] < cb
-            or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % 16) or t.data_ptr() % 16):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            _need_gpu(t)
-        raise ValueError(f"{what}: {name} must be uint8 [rows, >= code_bytes({d})={cb}] on the device with unit inner stride, "
-                         "rows a multiple of 16 bytes apart and 16-byte aligned (pack_sign_rows / codes_from_packbits)")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{what}: operands on different devices ({dev} vs {t.device})")
-    return t.stride(0) if t.shape[0] > 1 else (t.shape[1] // 16) * 16
+_BINARY_ROWS = dict(dtype=torch.uint8, width_fn=code_bytes, made_by="pack_sign_rows / codes_from_packbits")
 
 
 def hamming_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, idx_offset: int = 0,
@@ -598,40 +670,8 @@ def hamming_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, i
     ``q_codes`` / ``c_codes``: uint8 from :func:`pack_sign_rows` or :func:`codes_from_packbits` (row views with a stride that is
     a multiple of 16 bytes are read in place; bits at positions >= d are ignored).  1 <= k <= 1024, 1 <= d <= 1024.  Query sets
     above MAX_QUERIES_PER_CALL rows are searched in slices.  ``out`` = (dist, idx): preallocated contiguous tensors."""
-    what = "hamming_topk"
-    _need_gpu(q_codes, c_codes)
-    dev = q_codes.device
-    ldq = _check_codes(what, "q_codes", q_codes, d)
-    ldc = _check_codes(what, "c_codes", c_codes, d, dev)
-    k = int(k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
-    Q, N = q_codes.shape[0], c_codes.shape[0]
-    if out is not None:
-        dist, idx = out
-        _need_gpu(dist, idx)
-        if (dist.shape != (Q, k) or idx.shape != (Q, k) or dist.dtype != torch.int32 or idx.dtype != torch.int64
-                or not dist.is_contiguous() or not idx.is_contiguous() or dist.device != dev or idx.device != dev):
-            raise ValueError(f"{what}: out must be contiguous int32 / int64 [{Q}, {k}] tensors on {dev}")
-    else:
-        dist = torch.empty((Q, k), dtype=torch.int32, device=dev)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    if Q == 0:
-        return dist, idx
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        step = min(Q, MAX_QUERIES_PER_CALL)
-        nbytes = L.tsim_hamming_topk_workspace_bytes(step, N, k)
-        if nbytes == 0:
-            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k}")
-        ws = _workspace(dev, nbytes)
-        for q0 in range(0, Q, step):
-            nq = min(step, Q - q0)
-            rc = L.tsim_hamming_topk(q_codes.data_ptr() + q0 * ldq, ldq, nq, c_codes.data_ptr() if N else 0, ldc, N, int(d), k,
-                                     dist.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(),
-                                     _stream(q_codes))
-            _lib.check(rc, what)
-    return dist, idx
+    return _code_topk("hamming_topk", _BINARY_ROWS, "tsim_hamming_topk_workspace_bytes", "tsim_hamming_topk", q_codes, c_codes, d, k,
+                      idx_offset, out)
 
 
 def sign_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand: torch.Tensor, k: int, idx_offset: int = 0,
@@ -642,30 +682,8 @@ def sign_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand:
     in float64 in the library's canonical order — for d <= 768 the bits of :func:`dot_list_topk` on the unpacked matrix.
     Negative entries are skipped; entries >= N are skipped and set ``LIST_ST_ROW`` in the status (``return_status``); a row
     listed twice is returned twice."""
-    what = "sign_rescore_topk"
-    _need_gpu(eq_f32, c_codes, cand)
-    dev = eq_f32.device
-    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
-        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
-    ldc = _check_codes(what, "c_codes", c_codes, d, dev)
-    k = int(k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
-    Q, N = eq_f32.shape[0], c_codes.shape[0]
-    if cand.dim() != 2 or cand.shape[0] != Q or cand.dtype.is_floating_point or cand.dtype == torch.bool:
-        raise ValueError(f"{what}: cand must hold integers [{Q}, m]")
-    cand = cand.to(torch.int64).contiguous()
-    m = cand.shape[1]
-    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
-    if Q:
-        with torch.cuda.device(dev):
-            rc = _lib.lib().tsim_sign_rescore_topk(eq_f32.data_ptr(), _row_stride(eq_f32), Q, c_codes.data_ptr() if N else 0, ldc, N,
-                                                   int(d), cand.data_ptr() if m else 0, m, k, scores.data_ptr(), idx.data_ptr(),
-                                                   idx_offset, status.data_ptr() if return_status else 0, _stream(eq_f32))
-            _lib.check(rc, what)
-    return (scores, idx, status) if return_status else (scores, idx)
+    return _code_rescore("sign_rescore_topk", _BINARY_ROWS, "tsim_sign_rescore_topk", eq_f32, c_codes, d, cand, k, idx_offset,
+                         return_status)
 
 
 # ------------------------------------------------------------------------------------------------- int8 embeddings
@@ -675,6 +693,9 @@ def int8_bytes(d: int) -> int:
     if b == 0:
         raise ValueError(f"int8 codes take 1 <= d <= {MAX_CODE_DIM}, got d={d}")
     return b
+
+
+_INT8_ROWS = dict(dtype=torch.int8, width_fn=int8_bytes, made_by="quantize_int8_rows / int8_codes_from_numpy")
 
 
 def int8_ranges(x: torch.Tensor) -> torch.Tensor:
@@ -721,7 +742,7 @@ def quantize_int8_rows(x: torch.Tensor, ranges, out: Optional[torch.Tensor] = No
         out = torch.empty((rows, cb), dtype=torch.int8, device=x.device)
         ld = cb
     else:
-        ld = _check_int8(what, "out", out, d, x.device)
+        ld = _check_code_rows(what, "out", out, d, x.device, **_INT8_ROWS)
         if out.shape[0] != rows:
             raise ValueError(f"{what}: out has {out.shape[0]} rows, x {rows}")
     if rows:
@@ -748,19 +769,6 @@ def int8_codes_from_numpy(a, d: int, device=None) -> torch.Tensor:
     return out
 
 
-def _check_int8(what, name, t, d, dev=None):
-    cb = int8_bytes(d)
-    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int8 or t.dim() != 2 or t.shape[1] < cb
-            or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) % 16) or t.data_ptr() % 16):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            _need_gpu(t)
-        raise ValueError(f"{what}: {name} must be int8 [rows, >= int8_bytes({d})={cb}] on the device with unit inner stride, "
-                         "rows a multiple of 16 bytes apart and 16-byte aligned (quantize_int8_rows / int8_codes_from_numpy)")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{what}: operands on different devices ({dev} vs {t.device})")
-    return t.stride(0) if t.shape[0] > 1 else (t.shape[1] // 16) * 16
-
-
 def int8_ip_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, idx_offset: int = 0,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """Exact inner-product top-k over the first ``d`` values of int8 code rows: score [Q,k] int32 = sum_j q_j c_j, idx [Q,k]
@@ -768,40 +776,8 @@ def int8_ip_topk(q_codes: torch.Tensor, c_codes: torch.Tensor, d: int, k: int, i
     from :func:`quantize_int8_rows` or :func:`int8_codes_from_numpy` (row views with a stride that is a multiple of 16 bytes are
     read in place; bytes at positions >= d are ignored).  1 <= k <= 1024, 1 <= d <= 1024.  Query sets above
     MAX_QUERIES_PER_CALL rows are searched in slices.  ``out`` = (score, idx): preallocated contiguous tensors."""
-    what = "int8_ip_topk"
-    _need_gpu(q_codes, c_codes)
-    dev = q_codes.device
-    ldq = _check_int8(what, "q_codes", q_codes, d)
-    ldc = _check_int8(what, "c_codes", c_codes, d, dev)
-    k = int(k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
-    Q, N = q_codes.shape[0], c_codes.shape[0]
-    if out is not None:
-        score, idx = out
-        _need_gpu(score, idx)
-        if (score.shape != (Q, k) or idx.shape != (Q, k) or score.dtype != torch.int32 or idx.dtype != torch.int64
-                or not score.is_contiguous() or not idx.is_contiguous() or score.device != dev or idx.device != dev):
-            raise ValueError(f"{what}: out must be contiguous int32 / int64 [{Q}, {k}] tensors on {dev}")
-    else:
-        score = torch.empty((Q, k), dtype=torch.int32, device=dev)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    if Q == 0:
-        return score, idx
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        step = min(Q, MAX_QUERIES_PER_CALL)
-        nbytes = L.tsim_int8_ip_topk_workspace_bytes(step, N, k)
-        if nbytes == 0:
-            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} k={k}")
-        ws = _workspace(dev, nbytes)
-        for q0 in range(0, Q, step):
-            nq = min(step, Q - q0)
-            rc = L.tsim_int8_ip_topk(q_codes.data_ptr() + q0 * ldq, ldq, nq, c_codes.data_ptr() if N else 0, ldc, N, int(d), k,
-                                     score.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(),
-                                     _stream(q_codes))
-            _lib.check(rc, what)
-    return score, idx
+    return _code_topk("int8_ip_topk", _INT8_ROWS, "tsim_int8_ip_topk_workspace_bytes", "tsim_int8_ip_topk", q_codes, c_codes, d, k,
+                      idx_offset, out)
 
 
 def int8_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand: torch.Tensor, k: int, idx_offset: int = 0,
@@ -812,32 +788,11 @@ def int8_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand:
     library's canonical order — for d <= 768 the bits of :func:`dot_list_topk` on ``c_codes.float()``.  Negative entries are
     skipped; entries >= N are skipped and set ``LIST_ST_ROW`` in the status (``return_status``); a row listed twice is returned
     twice."""
-    what = "int8_rescore_topk"
-    _need_gpu(eq_f32, c_codes, cand)
-    dev = eq_f32.device
-    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
-        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
-    ldc = _check_int8(what, "c_codes", c_codes, d, dev)
-    k = int(k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
-    Q, N = eq_f32.shape[0], c_codes.shape[0]
-    if cand.dim() != 2 or cand.shape[0] != Q or cand.dtype.is_floating_point or cand.dtype == torch.bool:
-        raise ValueError(f"{what}: cand must hold integers [{Q}, m]")
-    cand = cand.to(torch.int64).contiguous()
-    m = cand.shape[1]
-    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
-    if Q:
-        with torch.cuda.device(dev):
-            rc = _lib.lib().tsim_int8_rescore_topk(eq_f32.data_ptr(), _row_stride(eq_f32), Q, c_codes.data_ptr() if N else 0, ldc, N,
-                                                   int(d), cand.data_ptr() if m else 0, m, k, scores.data_ptr(), idx.data_ptr(),
-                                                   idx_offset, status.data_ptr() if return_status else 0, _stream(eq_f32))
-            _lib.check(rc, what)
-    return (scores, idx, status) if return_status else (scores, idx)
+    return _code_rescore("int8_rescore_topk", _INT8_ROWS, "tsim_int8_rescore_topk", eq_f32, c_codes, d, cand, k, idx_offset,
+                         return_status)
 
 
+# ------------------------------------------------------------------------------------------------- exact range search
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins
 MAX_RANGE_QUERIES_PER_CALL = 4096       # the workspace holds RANGE_SLOT_CAP entries of 8 bytes per query: 64 MiB per call
