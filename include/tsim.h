@@ -595,6 +595,10 @@ typedef struct tsim_encoder_weights_host {
     const tsim_layer_weights_host *layers;
 } tsim_encoder_weights_host;
 
+/* Accepted shapes (anything else: TSIM_EUNSUPPORTED / TSIM_EINVAL with a message that names the accepted values, before any
+ * launch): hidden 64, 384, 768 or 1024; heads with hidden / heads = 16, 32 or 64 (any count, a multiple of 4 or not);
+ * ffn a multiple of 64, and at least 128 unless hidden is 64; TSIM_W_MXFP8 with hidden and ffn multiples of 256.  DESIGN.md
+ * "Encoder routes by configuration" names the kernel and the test of every class of these. */
 int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_encoder_weights_host *w,
                         tsim_encoder **out);
 void tsim_encoder_destroy(tsim_encoder *enc);

@@ -46,6 +46,8 @@ DEFECTS = (
     "leak_prev_sequence",       # every query also sees the last token of the preceding sequence of the batch
     "drop_last_key",            # the last key of a sequence with length = 1 (mod 16), length > 1, is left out
     "gelu_tanh",                # tanh approximation instead of erf
+    "drop_last_head_group",     # context of the heads >= 4 (heads // 4) is zero: a wrong bound on attention's partial group of 4 heads
+    "ffn_tail_dropped",         # the last F % 128 (when that is 0: the last 64) features of GELU(FFN1) are zero: a wrong N edge of a tile
 )
 
 
@@ -203,12 +205,16 @@ def probe_forward(cfg, w: Dict[str, np.ndarray], flat_ids, cu, *, rounding: Opti
                 stats.setdefault("softmax_max", []).append((S, (1.0 / den).reshape(-1).numpy()))
             o = torch.matmul(rnd(e), v[keys].transpose(0, 1)) / den     # [heads, S, dh]
             ctx[a:b] = o.transpose(0, 1)
+        if defect == "drop_last_head_group":
+            ctx[:, 4 * (nh // 4):] = 0.0
         ctx = rnd(ctx.reshape(T, H))
         x1 = rnd(_layer_norm(lin(ctx, no, defect != "no_o_bias") + x, g(ln1 + ".weight"), g(ln1 + ".bias"), eps, unb))
         pre = lin(x1, p + "intermediate.dense")
         if stats is not None:
             stats.setdefault("ffn1_absmax", []).append(float(pre.abs().max()) if T else 0.0)
         h1 = rnd(_gelu(pre, defect == "gelu_tanh"))
+        if defect == "ffn_tail_dropped":
+            h1[:, cfg.ffn - (cfg.ffn % 128 or 64):] = 0.0
         x = rnd(_layer_norm(lin(h1, p + "output.dense") + x1, g(p + "output.LayerNorm.weight"),
                             g(p + "output.LayerNorm.bias"), eps, unb))
         out.append(x)

@@ -2493,7 +2493,7 @@ static bool use_packed_layout(int H, int F) {
 template <int EPI>
 static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, bf16_t *out, int M, int N,
                       int K, hipStream_t st) {
-    if (K == 384 && N % XR_BN == 0) return gemm_xres2<EPI, false>(X, W, bias, out, M, N, st);
+    if (K == 384 && N % XR_BN == 0 && N <= 2048) return gemm_xres2<EPI, false>(X, W, bias, out, M, N, st);   // (its bias image holds 2048)
     if (K >= 768 && gemm_pp_supported(N, K))
         return gemm_pp(EPI == EPI_GELU ? PP_EPI_GELU : PP_EPI_BIAS, X, Wp ? Wp : W, Wp != nullptr, bias, out, M, N, K, st);
     if (N % 128 == 0)
@@ -2587,7 +2587,11 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
     TSIM_REQUIRE(cfg->heads > 0 && H % cfg->heads == 0, "encoder_create: heads=%d does not divide hidden=%d", cfg->heads, H);
     const int dh = H / cfg->heads;
     TSIM_REQUIRE(dh == 16 || dh == 32 || dh == 64, "encoder_create: head_dim=%d unsupported (16, 32, 64)", dh);
-    TSIM_REQUIRE(F % 64 == 0 && L > 0 && cfg->max_tokens > 0 && cfg->max_seqs > 0, "encoder_create: bad ffn/layers/capacity");
+    TSIM_REQUIRE(F > 0 && F % 64 == 0 && L > 0 && cfg->max_tokens > 0 && cfg->max_seqs > 0, "encoder_create: bad ffn/layers/capacity");
+    // FFN2 runs with K = ffn: the hidden-384 LayerNorm GEMM of large batches (ln_rows_gemm) needs three 32-wide k-tiles, the
+    // ping-pong GEMM of hidden 768 / 1024 two 64-wide ones, and hidden 1024 has no other FFN2 kernel
+    if (H != 64 && F < 128)
+        return fail(TSIM_EUNSUPPORTED, "encoder_create: ffn=%d unsupported at hidden=%d (a multiple of 64, at least 128)", F, H);
     TSIM_REQUIRE(cfg->arch == TSIM_ARCH_BERT || cfg->arch == TSIM_ARCH_MPNET || cfg->arch == TSIM_ARCH_ROBERTA, "encoder_create: unknown arch");
     TSIM_REQUIRE(w->word_emb && w->pos_emb && w->emb_ln_g && w->emb_ln_b && w->layers, "encoder_create: missing weights");
     TSIM_REQUIRE(cfg->arch != TSIM_ARCH_MPNET || w->rel_bias, "encoder_create: MPNet needs rel_bias");
