@@ -744,8 +744,11 @@ int tsim_chain_items_host(int blocks, int rem_blocks, int ntiles, int G, int b, 
  * max_length=...)) with the same ids: BertNormalizer (clean_text, lowercase) -> BertPreTokenizer -> WordPiece -> prefix /
  * suffix special ids -> truncation on the right to max_len, as the `tokenizers` library the reference depends on does it.
  * The vocabulary is one blob of UTF-8 keys + vocab_size + 1 byte offsets; the id of a key is its position.  `added_*`: the
- * contents of the library's added / special tokens: a sentence containing one of them, or any non-ASCII byte, is NOT
- * handled.  Thread-safe after creation. */
+ * contents of the library's added / special tokens, as written and, for the tokens the library matches on the normalised
+ * text (normalized=True, the default of add_tokens), also as its normaliser rewrites them.  A sentence that holds one of
+ * them in its raw bytes or in its normalised text (control characters dropped, white space mapped to ' ', lower-cased when
+ * `lowercase`), or any non-ASCII byte, is NOT handled.  The contents are fixed at creation: after the tokenizer gains a
+ * token, create a new handle.  Thread-safe after creation. */
 int tsim_wordpiece_create(const char *vocab_text, const int64_t *vocab_offsets, int32_t vocab_size,
                           const char *continuing_prefix, int32_t unk_id, const int32_t *prefix_ids, int32_t n_prefix,
                           const int32_t *suffix_ids, int32_t n_suffix, int32_t lowercase, int32_t max_input_chars_per_word,

@@ -115,3 +115,41 @@ def test_non_bert_template_is_refused():
 def test_max_length_below_four_is_refused():
     with pytest.raises(ValueError):
         PairTokenizer(_tok(), 3)
+
+
+def _added_tok():
+    from tokenizers import AddedToken
+    tok = _tok()
+    tok.add_tokens(["qqfoo", "QQbar", "new york", AddedToken("ZZtop", normalized=False)])
+    return tok
+
+
+def _added_pairs():
+    """Segments that hold the added contents in changed case, glued, cut by a control character, with other white space."""
+    import tokenizer_cases as tc
+    segs = []
+    for c in ("qqfoo", "QQbar", "new york", "ZZtop"):
+        for f in tc.case_forms(c):
+            segs += [f, _words(3, 5) + " " + f, f + " " + _words(6, 9), _words(2, 1) + " " + f + ", " + f + " " + _words(9, 4),
+                     "x" + f + "y " + _words(2, 3), f[:2] + "\x01" + f[2:] + " " + _words(4, 6), f.replace(" ", "\t")]
+    plain = [_words(n, 40 + n) for n in (1, 4, 11)]
+    pairs = [[a, b] for a in segs[::3] for b in plain] + [[a, b] for a in plain for b in segs[1::3]]
+    pairs += [[a, b] for a, b in zip(segs, segs[5:] + segs[:5])]
+    return pairs
+
+
+@pytest.mark.parametrize("L", [9, 64])
+def test_pairs_with_added_tokens_equal_library(L):
+    """A tokenizer with user-added tokens: the library matches them on the normalised text, so a segment that holds one in
+    another letter case must come out with the added id (and ``longest_first`` must count ONE token for it)."""
+    tok = _added_tok()
+    pt = PairTokenizer(tok, 512)
+    assert tok._tsim_native_wordpiece, "the native single-sentence path must stay in use"
+    pairs = _added_pairs()
+    ids, types, lens = pt(pairs, max_length=L)
+    r_ids, r_types, r_lens = _library(tok, pairs, L)
+    added = np.fromiter(set(tok.added_tokens_decoder) - {tok.cls_token_id, tok.sep_token_id, tok.unk_token_id}, dtype=np.int64)
+    assert np.isin(r_ids, added).sum() > len(pairs) // 2, "the pairs hardly hold an added token: the case tests nothing"
+    np.testing.assert_array_equal(lens, r_lens)
+    np.testing.assert_array_equal(ids, r_ids)
+    np.testing.assert_array_equal(types, r_types)

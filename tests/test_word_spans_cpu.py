@@ -199,3 +199,28 @@ def test_word_encoder_is_exported_and_needs_a_gpu():
                                device=torch.device("cpu"))
         with pytest.raises(_lib.TsimError):
             WordEncoder.from_preset("tiny-bert", params)
+
+
+@pytest.mark.parametrize("lower", [True, False])
+def test_word_ids_of_added_tokens_in_any_case_equal_the_library(lower):
+    """A target word that is an added token written in another letter case: the library matches normalized=True tokens on the
+    normalised text, so the native tokenizer must hand such a word to the library and not cut it into word pieces."""
+    import tokenizer_cases as tc
+    from text_similarity_amd.wordpiece import NativeWordPiece
+    if not os.path.exists(_lib.LIB_PATH):
+        from text_similarity_amd.build import build
+        build(verbose=False)
+    vocab, _ = tc.matrix_vocab()
+    for variant in tc.VARIANTS:
+        tok = tc.make_tokenizer(variant, lower, vocab)
+        wp = NativeWordPiece.from_tokenizer(tok)
+        assert wp is not None
+        added = tc.user_added_ids(tok)
+        hits = 0
+        for content in tc.every_content():
+            for w in tc.case_forms(content) + [content[:2] + "\x01" + content[2:], content.replace(" ", "\t")]:
+                want = tok.encode(w, add_special_tokens=False)
+                assert word_spans.word_ids(wp, w) == want, (variant, lower, w)
+                assert word_spans.word_ids(tok, w) == want
+                hits += bool(added & set(want))
+        assert hits >= len(tc.CONTENTS[variant]), (variant, hits)     # at least each of its own contents as written

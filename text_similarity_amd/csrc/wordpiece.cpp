@@ -13,8 +13,17 @@
 //   WordPiece     greedy longest-match-first with the continuing-subword prefix; a word longer than max_input_chars_per_word
 //                 or with an unmatched remainder is ONE unk token.
 //   post          prefix ids (CLS) + at most max_len - specials word pieces (truncation on the right) + suffix ids (SEP).
-// A sentence that is not pure ASCII, or that contains the text of an added / special token (matched by the library on the
-// raw text before normalisation), is NOT handled: handled[i] = 0 and the caller runs it through the library itself.
+// NOT handled (handled[i] = 0, the caller runs the sentence through the library itself) is a sentence
+//   * that is not pure ASCII, or
+//   * whose raw bytes OR whose normalised text (clean_text and lower-casing applied, the text the word pieces are cut from)
+//     contain one of the added contents.  The library matches a normalized=False token (the special tokens) on the raw text
+//     and a normalized=True token (the default of add_tokens) on the normalised text, and it normalises that token's content
+//     too: after add_tokens(["QQfoo"]) on a lower-casing tokenizer "the qq\x01FOO and" holds the token.  The caller hands in
+//     every content as written and, for normalized=True tokens, as the library's normaliser rewrites it (wordpiece.py); each
+//     is searched in both texts.  That is a superset of the library's matches (single_word, lstrip and rstrip only narrow or
+//     widen a match that this search already finds), and a sentence too many on the library path is still tokenised correctly.
+// The added contents are fixed at tsim_wordpiece_create: the caller rebuilds the handle when the tokenizer's added tokens,
+// size or truncation side change (models/sentence_encoder.py: _native_wordpiece).
 // The library stays the oracle: tests/test_wordpiece_cpu.py compares ids on generated and hand-written sentences.
 #include <stdint.h>
 #include <string.h>
@@ -83,8 +92,19 @@ struct WordPiece {
     std::vector<int32_t> prefix_ids, suffix_ids;
     bool lowercase = true;
     int max_chars = 100;
-    std::vector<std::string> added;   // added-token contents: a sentence containing one is not handled
+    std::vector<std::string> added;   // added-token contents, raw and normalised: a sentence containing one is not handled
+    bool added_first[256] = {};       // bytes that start one of them
 };
+
+// one pass over the text: only a byte that starts some added content is compared further
+inline bool contains_added(const WordPiece &wp, const char *s, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        if (!wp.added_first[(unsigned char)s[i]]) continue;
+        for (const std::string &a : wp.added)
+            if (a[0] == s[i] && a.size() <= n - i && memcmp(s + i, a.data(), a.size()) == 0) return true;
+    }
+    return false;
+}
 
 inline bool is_punct(unsigned char c) { return (c >= 33 && c <= 47) || (c >= 58 && c <= 64) || (c >= 91 && c <= 96) || (c >= 123 && c <= 126); }
 
@@ -113,19 +133,20 @@ bool encode_one(const WordPiece &wp, const char *s, int64_t n, int max_len, std:
                 int32_t *out, int32_t *out_len) {
     for (int64_t i = 0; i < n; ++i)
         if ((unsigned char)s[i] >= 0x80) return false;
-    for (const std::string &a : wp.added)
-        if (!a.empty() && (int64_t)a.size() <= n && std::search(s, s + n, a.begin(), a.end()) != s + n) return false;
     const int nspec = (int)(wp.prefix_ids.size() + wp.suffix_ids.size());
     const int room = max_len > nspec ? max_len - nspec : 0;
     // normalise
     norm.clear();
+    bool changed = false;   // norm differs from the raw bytes
     for (int64_t i = 0; i < n; ++i) {
         unsigned char c = (unsigned char)s[i];
-        if (c == '\t' || c == '\n' || c == '\r') c = ' ';
-        else if (c < 0x20 || c == 0x7f) continue;
-        if (wp.lowercase && c >= 'A' && c <= 'Z') c = (unsigned char)(c + 32);
+        if (c == '\t' || c == '\n' || c == '\r') { c = ' '; changed = true; }
+        else if (c < 0x20 || c == 0x7f) { changed = true; continue; }
+        if (wp.lowercase && c >= 'A' && c <= 'Z') { c = (unsigned char)(c + 32); changed = true; }
         norm.push_back((char)c);
     }
+    // an added content in the raw bytes (normalized=False tokens) or in the normalised text (normalized=True ones): not handled
+    if (contains_added(wp, s, (size_t)n) || (changed && contains_added(wp, norm.data(), norm.size()))) return false;
     pieces.clear();
     const int m = (int)norm.size();
     int i = 0;
@@ -189,8 +210,11 @@ extern "C" int tsim_wordpiece_create(const char *vocab_text, const int64_t *voca
     wp->suffix_ids.assign(suffix_ids, suffix_ids + n_suffix);
     wp->lowercase = lowercase != 0;
     wp->max_chars = max_input_chars_per_word;
-    for (int32_t i = 0; i < n_added; ++i)
-        wp->added.emplace_back(added_text + added_offsets[i], added_text + added_offsets[i + 1]);
+    for (int32_t i = 0; i < n_added; ++i) {   // (an empty content matches nothing; a duplicate is searched once)
+        std::string a(added_text + added_offsets[i], added_text + added_offsets[i + 1]);
+        if (!a.empty() && std::find(wp->added.begin(), wp->added.end(), a) == wp->added.end()) wp->added.push_back(std::move(a));
+    }
+    for (const std::string &a : wp->added) wp->added_first[(unsigned char)a[0]] = true;
     *handle = wp;
     return TSIM_OK;
 }

@@ -26,17 +26,37 @@ from .st_format import (read_sentence_transformers_dir, similarity_fn, write_sen
 _RESOLVE = object()   # encode_packed(head=...): look the head up from the wrapper's pooler
 
 
+def _tokenizer_signature(tokenizer):
+    """What a NativeWordPiece was built from, as far as a caller can change it on a live tokenizer: its size, its added tokens
+    (id, content, ``normalized``), its truncation side, and the TSIM_NATIVE_TOKENIZER switch.  A few microseconds: the added
+    tokens are a handful of entries, the vocabulary itself is not read."""
+    try:
+        size = len(tokenizer)
+    except Exception:
+        size = None
+    try:
+        added = tuple((int(i), str(getattr(t, "content", t)), bool(getattr(t, "normalized", False)))
+                      for i, t in tokenizer.added_tokens_decoder.items())
+    except Exception:
+        added = None
+    return (size, added, getattr(tokenizer, "truncation_side", "right"), os.environ.get("TSIM_NATIVE_TOKENIZER", "1") != "0")
+
+
 def _native_wordpiece(tokenizer):
-    """The tokenizer's NativeWordPiece (built once, kept on the tokenizer object), or None when its pipeline is not BERT's,
-    the library is not built, or TSIM_NATIVE_TOKENIZER=0."""
+    """The tokenizer's NativeWordPiece, or None when its pipeline is not BERT's, the library is not built, or
+    TSIM_NATIVE_TOKENIZER=0.  Kept on the tokenizer object together with the signature it was built from
+    (``_tokenizer_signature``) and rebuilt when that changes: after ``add_tokens`` / ``add_special_tokens`` the new contents
+    must send their sentences to the library, and after ``truncation_side = "left"`` the native path steps aside."""
+    sig = _tokenizer_signature(tokenizer)
     wp = getattr(tokenizer, "_tsim_native_wordpiece", None)
-    if wp is None:
+    if wp is None or getattr(tokenizer, "_tsim_native_signature", None) != sig:
         wp = False
-        if os.environ.get("TSIM_NATIVE_TOKENIZER", "1") != "0":
+        if sig[-1]:
             from ..wordpiece import NativeWordPiece
             wp = NativeWordPiece.from_tokenizer(tokenizer) or False
         try:
             tokenizer._tsim_native_wordpiece = wp
+            tokenizer._tsim_native_signature = sig
         except Exception:
             pass
     return wp or None
@@ -44,7 +64,8 @@ def _native_wordpiece(tokenizer):
 
 def _tokenize_packed(tokenizer, docs: List[str], max_len: int, batch_size: int):
     """Tokenise without padding -> (flat ids int32, lengths): the native WordPiece path for the sentences it handles (pure
-    ASCII; csrc/wordpiece.cpp — same ids, tests/test_wordpiece_cpu.py), the library for the rest."""
+    ASCII, no added-token content in the raw or the normalised text; csrc/wordpiece.cpp — same ids,
+    tests/test_wordpiece_cpu.py), the library for the rest."""
     wp = _native_wordpiece(tokenizer)
     if wp is not None:
         return wp.tokenize_packed(docs, int(max_len), lambda rest: _tokenize_library(tokenizer, rest, max_len, batch_size))
@@ -57,7 +78,8 @@ def _tokenize_library(tokenizer, docs: List[str], max_len: int, batch_size: int)
     because padded positions are masked out of attention and pooling.
 
     Fast (Rust-backed) tokenizers are driven through their backend ``encode_batch`` on the whole chunk: the same code the
-    ``tokenizer(text=...)`` call ends in — identical ids (tests/test_host_cpu.py) — without the per-call Python wrapping
+    ``tokenizer(text=...)`` call ends in — identical ids, and the backend's truncation and padding settings put back
+    (tests/test_wordpiece_cpu.py::test_tokenize_library_equals_the_tokenizer_call) — without the per-call Python wrapping
     (BatchEncoding construction, per-batch option handling), which is single-threaded and was about half of the tokenizer
     time; the backend itself spreads a batch over the host cores (rayon), so one call per chunk uses all of them."""
     bt = getattr(tokenizer, "backend_tokenizer", None) if getattr(tokenizer, "is_fast", False) else None

@@ -2,8 +2,10 @@
 
 The reference calls the HuggingFace tokenizer it is configured with (sentence_encoder.py:144-153).  ``NativeWordPiece`` is
 built FROM that tokenizer — vocabulary, special ids, lower-casing and truncation side are read out of its `tokenizers`
-backend — and produces the same ids for the sentences it handles (pure ASCII, no added-token text inside); every other
-sentence goes through the library itself, so the result is the library's for any input.  A tokenizer whose backend is not
+backend — and produces the same ids for the sentences it handles (pure ASCII, no added-token content in the raw or in the
+normalised text); every other sentence goes through the library itself, so the result is the library's for any input.  It is a
+snapshot: tokens added to the tokenizer afterwards are unknown to it (``_native_wordpiece`` in models/sentence_encoder.py
+rebuilds it when the tokenizer's signature changes).  A tokenizer whose backend is not
 the BERT pipeline (BertNormalizer / BertPreTokenizer / WordPiece / CLS..SEP template) is not supported: ``from_tokenizer``
 returns None and the caller keeps using the library for everything."""
 from __future__ import annotations
@@ -41,9 +43,11 @@ class NativeWordPiece:
                 pass
 
     # ------------------------------------------------------------------------------------------------------------------
-    @classmethod
-    def from_tokenizer(cls, tokenizer) -> Optional["NativeWordPiece"]:
-        """None when the tokenizer's pipeline is not the one csrc/wordpiece.cpp restates."""
+    @staticmethod
+    def create_args(tokenizer) -> Optional[dict]:
+        """What ``tsim_wordpiece_create`` is called with for this tokenizer, as plain Python values (``from_tokenizer`` passes
+        them on; tests/wordpiece_driver.cpp is fed the same); None when the tokenizer's pipeline is not the one
+        csrc/wordpiece.cpp restates."""
         bt = getattr(tokenizer, "backend_tokenizer", None) if getattr(tokenizer, "is_fast", False) else None
         if bt is None:
             return None
@@ -91,17 +95,39 @@ class NativeWordPiece:
             prefix_ids, suffix_ids = [int(post["cls"][1])], [int(post["sep"][1])]
         else:
             return None
-        added = [a["content"] for a in cfg.get("added_tokens", [])]
-        vtext, voff = _blob(keys)
-        atext, aoff = _blob(added)
+        # The library matches a normalized=False token on the raw text and a normalized=True one (the default of add_tokens)
+        # on the normalised text, after normalising the token's content as well.  The native code gets every content as
+        # written and, for the normalized=True ones, as the backend normaliser rewrites it, and searches each in both texts.
+        added = []
+        for a in cfg.get("added_tokens", []):
+            added.append(a["content"])
+            if a.get("normalized", False):
+                try:
+                    added.append(bt.normalizer.normalize_str(a["content"]))
+                except Exception:
+                    return None
+        return {"vocab": keys, "continuing_prefix": model.get("continuing_subword_prefix", "##"), "unk_id": int(unk),
+                "prefix_ids": [int(t) for t in prefix_ids], "suffix_ids": [int(t) for t in suffix_ids],
+                "lowercase": bool(norm.get("lowercase", True)), "max_chars": int(model.get("max_input_chars_per_word", 100)),
+                "added": list(dict.fromkeys(c for c in added if c))}
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer) -> Optional["NativeWordPiece"]:
+        """None when the tokenizer's pipeline is not the one csrc/wordpiece.cpp restates."""
+        a = cls.create_args(tokenizer)
+        if a is None:
+            return None
+        prefix_ids, suffix_ids = a["prefix_ids"], a["suffix_ids"]
+        vtext, voff = _blob(a["vocab"])
+        atext, aoff = _blob(a["added"])
         pre_a = np.asarray(prefix_ids, dtype=np.int32)
         suf_a = np.asarray(suffix_ids, dtype=np.int32)
         h = C.c_void_p()
         _lib.check(_lib.lib().tsim_wordpiece_create(
-            vtext, voff.ctypes.data, size, model.get("continuing_subword_prefix", "##").encode(), int(unk),
+            vtext, voff.ctypes.data, len(a["vocab"]), a["continuing_prefix"].encode(), a["unk_id"],
             pre_a.ctypes.data if len(pre_a) else None, len(pre_a), suf_a.ctypes.data if len(suf_a) else None, len(suf_a),
-            1 if norm.get("lowercase", True) else 0, int(model.get("max_input_chars_per_word", 100)),
-            atext, aoff.ctypes.data, len(added), C.byref(h)), "tsim_wordpiece_create")
+            1 if a["lowercase"] else 0, a["max_chars"], atext, aoff.ctypes.data, len(a["added"]), C.byref(h)),
+            "tsim_wordpiece_create")
         wp = cls(h, len(prefix_ids) + len(suffix_ids), tokenizer)
         wp.n_prefix, wp.n_suffix = len(prefix_ids), len(suffix_ids)     # where the special ids sit (word_spans.special_layout)
         return wp
