@@ -64,3 +64,24 @@ def digests(pooled, hidden):
 
 def case_id(layers: int, T: int) -> str:
     return f"bert384-L{layers}-T{T}"
+
+
+# The row-major K = 384 projection (gemm_xres2_kernel<EPI, false, false>: an MPNet-style hidden-384 model keeps its residual
+# stream row-major): the mpnet-384 case of tests/encoder_cases.py on the sentences above, at the smallest token counts that reach
+# every state of the item loop.  Items per workgroup are ceil(T / 256) * N / 96 over min(items, 256) workgroups, N = 1152, 1536:
+# 33: one partial block (the row guard of the stores); 257: one item per workgroup (first item and flush only); 10 000: 1-2 and
+# 2-3 items (both flush sides, a fragment reload inside a workgroup); 16 417: 3-4 and 4-5 items (the two-item loop body taken
+# more than once, odd and even tails).
+X384_CASE = "mpnet-384"
+X384_TOKENS = (33, 257, 10000, 16417)
+
+
+def x384_encoder():
+    import encoder_cases as ec
+    from text_similarity_amd.native_encoder import NativeEncoder
+    cfg, wdtype = ec.CASES[X384_CASE]
+    return NativeEncoder(cfg, ec.sharp_weights(cfg, X384_CASE), max_tokens=max(X384_TOKENS), max_seqs=N_SENT, weight_dtype=wdtype)
+
+
+def x384_case_id(T: int) -> str:
+    return f"{X384_CASE}-T{T}"

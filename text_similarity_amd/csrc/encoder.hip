@@ -501,126 +501,175 @@ __device__ __forceinline__ void ff_static_for(std::integer_sequence<int, I...>, 
 // (both issued four steps earlier), the odd step runs straight on; a step issues the tile of step st + 4 into the slot the pair
 // before the current one has left (everyone is past that pair: they passed this pair's barrier).
 // MEASURED: QKV 73.1 -> 71.2 us, FFN1 119.6 -> 115.3 us (-3 %): the wait is mostly not a per-barrier constant.
-// (ln_rows_xres2_kernel holds a COPY of this kernel's item loop, store_half included: a fix here belongs there too.)
+// The item loop is X2Loop below; gemm_xres2_kernel runs it on a contiguous range of items, ln_rows_xres2_kernel behind its
+// LayerNorm phase on the items of its own token block and its share of the remainder blocks'.
 constexpr int X2_BN = 96, X2_BK = 128, X2_NSTAGE = 6, X2_PD = 4, X2_KG = 3, X2_NSUB = 3;
 
-// PK: the output goes out in the block-packed layout (see packed_off); XPK: X comes in it (group_off)
-template <int EPI, bool PK, bool XPK>
-__global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W,
-                                                         const float *__restrict__ bias, bf16_t *__restrict__ out,
-                                                         int M, int N, int items_total) {
-    constexpr int K = 384, KSTEPS = K / 16, NW = 8, BMX = NW * 32;
-    constexpr int STAGE = X2_BN * X2_BK * 2;                 // 24 KiB
-    constexpr int PIECES = STAGE / 1024, PPW = PIECES / NW;  // 24 pieces, 3 per wave
-    static_assert(PIECES % NW == 0 && X2_KG * X2_BK == K, "tile shape");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int ntiles = N / X2_BN;
-    const int it0 = (int)((int64_t)items_total * blockIdx.x / gridDim.x);
-    const int it1 = (int)((int64_t)items_total * (blockIdx.x + 1) / gridDim.x);
-    const int total = (it1 - it0) * X2_KG;                   // W tiles (steps) of this workgroup
-    if (total <= 0) return;
+// One 16-byte result store in the SGPR-base + 32-bit-offset form, as inline asm: inside the MFMA stream there is no room for a
+// 64-bit address per store (the output is < 4 GiB, checked by the launchers), and an asm statement is exactly ONE store
+// instruction, which the manual vmcnt bookkeeping of these kernels counts.
+// (s_nop: a store of more than 64 bits needs one wait state before a VALU may overwrite its data registers; hipcc pads its own
+// stores but cannot see into an asm statement — without it the next instruction now and then replaced the data under the store:
+// a corrupted 16-byte group, non-finite rows after the LayerNorm, the whole sequence after the next attention, in ~20 % of the
+// forwards on some boxes and none on others)
+__device__ __forceinline__ void x2_store16(uint32_t voff, const u32x4 &o, uint64_t base) {
+    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(base) : "memory");
+}
 
-    // LDS image of a W tile: 96 rows of 256 B (128 k), 16-byte slot c of row rr holds source chunk c ^ (rr & 15)
-    int src_off[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
+// item i of a workgroup -> block * ntiles + feature tile: a contiguous range (ln_rows_xres2_kernel: X2Chain)
+struct X2Range {
+    int it0;
+    __device__ __forceinline__ int operator()(int i) const { return it0 + i; }
+};
+
+// The item loop of the K = 384 projection for one workgroup of eight waves: items map(0) .. map(n_items - 1), W tiles through
+// the six-slot ring at smem, the bias at smem + bias_off.  A kernel constructs it, loads the bias, then prime() (the first
+// X2_PD W tiles), start() (lane-derived addresses and the loop's state) and run().  Nothing here reads threadIdx: the lane id
+// comes in as an argument, so that a caller can hand prime() and start() separately derived copies of it.
+//   PK / XPK  the output goes out / the activations come in the block-packed layout (packed_off, group_off)
+//   CARRY     24 stores issued between prime() and start() (ln_rows_xres2_kernel's LayerNorm rows) are younger than the primed
+//             tiles and are counted in the ring waits of steps 0 and 2, which would otherwise wait for the whole burst; a
+//             compile-time flag, so that the wait chain grows no branch without them
+//   resident  the token block whose fragments bx[] the caller has filled before run() (-1: none)
+template <int EPI, bool PK, bool XPK, bool CARRY, class Map>
+struct X2Loop {
+    static constexpr int K = 384, KSTEPS = K / 16, NW = 8, BMX = NW * 32;
+    static constexpr int STAGE = X2_BN * X2_BK * 2;                 // 24 KiB
+    static constexpr int PIECES = STAGE / 1024, PPW = PIECES / NW;  // 24 pieces, 3 per wave
+    static_assert(PIECES % NW == 0 && X2_KG * X2_BK == K, "tile shape");
+    static_assert(PPW == 3, "the issue schedule of a step places three pieces");
+
+    const char *X, *W;
+    char *smem;
+    uint64_t out_base;
+    uint32_t lbase, bias_lds;
+    int M, N, ntiles, n_items, wave;
+    Map map;
+    int pi, pg, pj;     // the next W tile to issue: k-group pg of item pi, feature tile pj (past the end: the last tile again)
+    int r, h, src_off[PPW], cks[8];
+    bf16x8 bx[KSTEPS];  // the resident activation fragments of token block cur_mb
+    f32x16 accA[X2_NSUB], accB[X2_NSUB];
+    int cur_mb, m0, old_m0, old_n0;
+    int st;             // steps done
+    int ring;           // st % X2_NSTAGE, kept as a counter
+    int young1, young2, young3;   // global stores issued in the last three steps, youngest first (-1: unknown)
+    int carry;
+    uint32_t old_rowoff;          // byte offset of this lane's 16-byte column group in its token row of the PREVIOUS item's block
+    bool old_live;                // ... and whether that row exists (one compare per item: the mask guards its six stores per step)
+    unsigned x2_n, x2_w, x2_c, x2_e, x2_r, x2_nr;   // (diagnostic build only; 32-bit sums: a workgroup runs < 2^32 cycles)
+
+    __device__ __forceinline__ X2Loop(const void *X_, const bf16_t *W_, bf16_t *out_, char *smem_, int bias_off, int M_, int N_,
+                                      int wave_, const Map &map_, int n_items_, int resident)
+        : X(reinterpret_cast<const char *>(X_)), W(reinterpret_cast<const char *>(W_)), smem(smem_),
+          out_base((uint64_t)(uintptr_t)out_), lbase((uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem_)),
+          bias_lds(lbase + bias_off), M(M_), N(N_), ntiles(N_ / X2_BN), n_items(n_items_), wave(wave_), map(map_),
+          cur_mb(resident), m0(resident * BMX + wave_ * 32) {
+        // (pinned in its SGPR pair here: left alone hipcc sinks the kernel-argument load into the loop's first block and then
+        // waits lgkmcnt(0) in front of every store, on the paths where it cannot tell that the load has long landed)
+        asm volatile("" : "+s"(out_base));
+    }
+
+    // LDS image of a W tile: 96 rows of 256 B (128 k), 16-byte slot c of row rr holds source chunk c ^ (rr & 15); piece i of
+    // this wave is 1 KiB of it, the lane's 16 bytes come from this offset in the tile's first row
+    __device__ __forceinline__ int piece_off(int lane, int i) const {
         const int sl = (wave * PPW + i) * 64 + lane;
         const int row = sl >> 4, ch = (sl & 15) ^ (row & 15);
-        src_off[i] = row * K * 2 + ch * 16;
+        return row * K * 2 + ch * 16;
     }
-    auto issue_pieces = [&](int st, int stage, int i0, int i1) __attribute__((always_inline)) {
-        const int s2 = st < total ? st : total - 1;           // past-the-end: re-read the last tile (uniform vmcnt)
-        const int j = (it0 + s2 / X2_KG) % ntiles, g = s2 % X2_KG;
-        const char *base = reinterpret_cast<const char *>(W) + ((int64_t)j * X2_BN * K + g * X2_BK) * 2;
+    __device__ __forceinline__ const char *tile_base() const { return W + ((int64_t)pj * X2_BN * K + pg * X2_BK) * 2; }
+    __device__ __forceinline__ void advance() {
+        if (++pg == X2_KG) {
+            if (pi + 1 < n_items) {
+                pg = 0;
+                ++pi;
+                pj = map(pi) % ntiles;
+            } else {
+                pg = X2_KG - 1;       // past-the-end: re-read the last tile (uniform vmcnt)
+            }
+        }
+    }
+    __device__ __forceinline__ void issue_piece(const char *src, int stage, int i) const {
 #if defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 4)   // TIMING-ONLY: no W stream (stale tiles)
-        (void)base;
+        (void)src;
 #else
-        for (int i = i0; i < i1; ++i)
-            glds16(base + src_off[i], smem + stage * STAGE + (wave * PPW + i) * 1024);
+        glds16(src, smem + stage * STAGE + (wave * PPW + i) * 1024);
 #endif
-    };
-    auto issue = [&](int st, int stage) __attribute__((always_inline)) { issue_pieces(st, stage, 0, PPW); };
-    // fragment of sub-tile i, k-step ks (of 8 in a tile): row i*32 + r, source chunk 2 ks + h -> slot (2 ks + h) ^ (r & 15)
-    int cks[8];
+    }
+    // the first X2_PD tiles (offsets from the lane id given here, not kept: start() computes them again from its own)
+    __device__ __forceinline__ void prime(int lane) {
+        pi = 0, pg = 0, pj = map(0) % ntiles;
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) cks[ks] = r * 256 + (((2 * ks + h) ^ (r & 15)) << 4);
-
-    // bias -> LDS once per workgroup (an ordinary global load inside the loop would drain the W ring at its first use)
-    const uint32_t bias_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + X2_NSTAGE * STAGE;
-    for (int p = wave; p * 256 < N; p += NW)
-        if (p * 256 + lane * 4 < N) glds16(bias + p * 256 + lane * 4, smem + X2_NSTAGE * STAGE + p * 1024);
-    wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-
-    bf16x8 bx[KSTEPS];
-    int cur_mb = -1, m0 = 0;
-    f32x16 accA[X2_NSUB], accB[X2_NSUB];
-    int old_m0 = 0, old_n0 = 0;
-    int st = 0;                       // steps done
-    int ring = 0;                     // st % X2_NSTAGE, kept as a counter
-    int young1 = 0, young2 = 0, young3 = 0;   // global stores issued in the last three steps, youngest first (-1: unknown)
+        for (int s = 0; s < X2_PD; ++s) {
+            const char *base = tile_base();
+#pragma unroll
+            for (int i = 0; i < PPW; ++i) issue_piece(base + piece_off(lane, i), s, i);
+            advance();
+        }
+    }
+    __device__ __forceinline__ void start(int lane) {
+        r = lane & 31, h = lane >> 5;
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) src_off[i] = piece_off(lane, i);
+        // fragment of sub-tile i, k-step ks (of 8 in a tile): row i*32 + r, source chunk 2 ks + h -> slot (2 ks + h) ^ (r & 15)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) cks[ks] = r * 256 + (((2 * ks + h) ^ (r & 15)) << 4);
+        old_m0 = old_n0 = 0;
+        st = ring = 0;
+        young1 = young2 = young3 = 0;
+        carry = CARRY;
+        old_rowoff = 0;
+        old_live = false;
+        x2_n =x2_w = x2_c = x2_e = x2_r = x2_nr = 0;
+    }
 
     // epilogue of ONE finished sub-tile whose 16 registers have been packed into pk[8] (pk[2gq], pk[2gq+1] = the lane's four
     // features 8gq + 4h .. +3 of group gq): swap half-waves so that every lane owns 8 contiguous features, two 16-byte stores
     // at the end of the step.  (Issuing them inside the MFMA stream instead measured equal: what costs is the store's PATTERN.)
-    // (the store is inline asm in the SGPR-base + 32-bit-offset form: inside the stream there is no room for a 64-bit address
-    // per store; the output is < 4 GiB, checked by the launcher.  All vmcnt bookkeeping of this kernel is manual anyway.)
-    uint32_t old_rowoff = 0;   // byte offset of this lane's 16-byte column group in its token row of the PREVIOUS item's block
-    const uint64_t out_base = (uint64_t)(uintptr_t)out;
-    auto store_half = [&](const uint32_t (&pk)[8], int mrow0, int ncol, auto gqc) __attribute__((always_inline)) {
-        constexpr int gq = decltype(gqc)::value;
-        const bool full = mrow0 + 32 <= M;    // wave-uniform
+    template <int gq>
+    __device__ __forceinline__ void store_half(const uint32_t (&pk)[8], int ncol) const {
         uint32_t a0 = pk[2 * gq], a1 = pk[2 * gq + 1], b0 = pk[2 * gq + 2], b1 = pk[2 * gq + 3];
         auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
         const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
         const uint32_t voff = old_rowoff + (uint32_t)(ncol + 8 * gq) * (PK ? 64u : 2u);
-        const uint64_t ob = out_base;   // (an asm operand alone does not make a generic lambda capture the variable)
 #if !(defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 1))   // (bit 1: TIMING-ONLY, no output stores)
-        if (full || mrow0 + r < M)
-            // (s_nop: a store of more than 64 bits needs one wait state before a VALU may overwrite its data registers; hipcc
-            // pads its own stores but cannot see into an asm statement — without it the next instruction now and then replaced the
-            // data under the store: a corrupted 16-byte group, non-finite rows after the LayerNorm, the whole sequence after the
-            // next attention, in ~20 % of the forwards on some boxes and none on others)
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(ob) : "memory");
+        if (old_live) x2_store16(voff, o, out_base);
 #else
         asm volatile("" ::"v"(voff), "v"(o));
 #endif
-    };
-    auto finish2 = [&](float y0, float y1) __attribute__((always_inline)) -> uint32_t {
+    }
+    __device__ __forceinline__ uint32_t finish2(float y0, float y1) const {
 #if !(defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 2))   // (bit 2: TIMING-ONLY, no activation function)
         // (two independent scalar Horner chains instead of the packed one: measured equal, 2.633 vs 2.632 ms per forward)
         if constexpr (EPI == EPI_GELU) gelu2(y0, y1);
 #endif
         return pack_bf16x2(y0, y1);
-    };
+    }
 
-#pragma unroll
-    for (int i = 0; i < X2_PD; ++i) issue(i, i);
-    [[maybe_unused]] unsigned x2_n = 0, x2_w = 0, x2_c = 0, x2_e = 0, x2_r = 0, x2_nr = 0;   // (diagnostic build only; 32-bit sums: a workgroup runs < 2^32 cycles)
-    auto run_item = [&](f32x16 (&cur)[X2_NSUB], f32x16 (&old)[X2_NSUB], int item, auto with_old) __attribute__((always_inline)) {
-        constexpr bool OLD = decltype(with_old)::value;
-        if (item / ntiles != cur_mb) {                        // wave-uniform: new token block -> reload fragments
+    // one item into cur; OLD: the previous item, finished in old, goes out in the shadow of this one's MFMAs
+    template <bool OLD>
+    __device__ __forceinline__ void run_item(f32x16 (&cur)[X2_NSUB], f32x16 (&old)[X2_NSUB], int item) {
+        const int gi = map(item);
+        if (gi / ntiles != cur_mb) {                          // wave-uniform: new token block -> reload fragments
             [[maybe_unused]] const unsigned long long xr0 = XR_T();
-            cur_mb = item / ntiles;
+            cur_mb = gi / ntiles;
             m0 = cur_mb * BMX + wave * 32;
             // fragment s = groups 2 s + h of row m0 + r (packed: rows past M of the last block are the buffer's padding)
-            const char *xp = reinterpret_cast<const char *>(X) + group_off(m0 + r, h, K, XPK);
+            const char *xp = X + group_off(m0 + r, h, K, XPK);
             constexpr int xgs = XPK ? 512 : 16;               // group_off(0, 1, ..)
 #pragma unroll
             for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 2 * s * xgs);
 #pragma unroll
             for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));   // retire these ordinary loads here
             young1 = young2 = young3 = 0;                     // ... and with them (vmcnt(0)) everything older
+            carry = 0;
 #ifdef TSIM_PP_STAMPS
             x2_r += (unsigned)(XR_T() - xr0); x2_nr += 1;
 #endif
         }
-        const int n0 = (item % ntiles) * X2_BN;
-        // accumulators start from the bias: cur[i][q] belongs to feature n0 + 32 i + (q & 3) + 8 (q >> 2) + 4 h
+        const int n0 = (gi % ntiles) * X2_BN;
+        // accumulators start from the bias (in LDS: an ordinary global load inside the loop would drain the W ring at its first
+        // use): cur[i][q] belongs to feature n0 + 32 i + (q & 3) + 8 (q >> 2) + 4 h
         // (ONE address register + immediates: twelve separately computed addresses were hoisted out of the loop and spilled)
         const uint32_t baddr = bias_lds + (n0 + 4 * h) * 4;
         ff_static_for(std::make_integer_sequence<int, X2_NSUB>{}, [&](auto ic) __attribute__((always_inline)) {
@@ -645,7 +694,8 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             // the pieces of steps st + 2 and st + 3 and the stores of the last three steps
             if ((st & 1) == 0) {
                 const int ys = (young1 >= 0 && young2 >= 0 && young3 >= 0) ? young1 + young2 + young3 : 0;
-                if (ys == 6) wait_vmcnt<2 * PPW + 6>();
+                if (CARRY && carry) wait_vmcnt<2 * PPW + 24>();   // (no store of the loop has been issued yet: ys = 0)
+                else if (ys == 6) wait_vmcnt<2 * PPW + 6>();
                 else if (ys == 4) wait_vmcnt<2 * PPW + 4>();
                 else if (ys == 2) wait_vmcnt<2 * PPW + 2>();
                 else wait_vmcnt<2 * PPW>();               // none, or unknown store count: always safe
@@ -656,7 +706,6 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             // Right behind the barrier all eight waves have LDS-DMA to issue and queue at the CU's one address path while the
             // matrix pipe idles; the tile is not needed for two steps, so its three pieces are dropped between the k-steps'
             // MFMAs instead.
-            static_assert(PPW == 3, "issue schedule below places three pieces");
             uint32_t pk[8];
             // The step's 24 fragment reads (n = 3 ks + i) roll PF reads ahead of their MFMAs with COUNTED lgkmcnt waits, as in the
             // search kernel's tile loop: hipcc's own schedule of plain loads waits lgkmcnt(0) in front of every k-step, i.e. for
@@ -666,7 +715,7 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             {
                 constexpr int PF = 3, NRD = 8 * X2_NSUB;
                 lds_u32x4 fr[PF + 1];
-                const uint32_t wsl = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + stage * STAGE;
+                const uint32_t wsl = lbase + stage * STAGE;
                 auto rd = [&](auto nc) __attribute__((always_inline)) {
                     constexpr int n = decltype(nc)::value;
                     lds_read_b128_imm<(n % X2_NSUB) * 8192>(fr[n % (PF + 1)], wsl + cks[n / X2_NSUB]);
@@ -680,8 +729,11 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
                     lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
                     cur[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]), bx[g * 8 + ks], cur[i], 0, 0, 0);
                     if constexpr (i == X2_NSUB - 1) {
-                        if constexpr (ks == 1 || ks == 3 || ks == 5)
-                            issue_pieces(st + X2_PD, (stage + X2_PD) % X2_NSTAGE, ks >> 1, (ks >> 1) + 1);
+                        if constexpr (ks == 1 || ks == 3 || ks == 5) {       // one piece of the tile of step st + X2_PD
+                            const int ns = stage + X2_PD;
+                            issue_piece(tile_base() + src_off[ks >> 1], ns >= X2_NSTAGE ? ns - X2_NSTAGE : ns, ks >> 1);
+                            if constexpr (ks == 5) advance();
+                        }
                         if constexpr (OLD) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);   // in the MFMAs' shadow
                     }
                 });
@@ -695,8 +747,8 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             young2 = young1;
             young1 = 0;
             if constexpr (OLD) {
-                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
+                store_half<0>(pk, old_n0 + g * 32);
+                store_half<2>(pk, old_n0 + g * 32);
 #if defined(TSIM_X2_DIAG) && (TSIM_X2_DIAG & 1)
                 young1 = 0;
 #else
@@ -705,37 +757,66 @@ __global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restric
             }
             ++st;
             ring = ring + 1 == X2_NSTAGE ? 0 : ring + 1;
+            if constexpr (CARRY)
+                if (st >= 3) carry = 0;   // the wait of step 4 is for tiles issued after the carried stores
 #ifdef TSIM_PP_STAMPS
             { const unsigned long long xs3 = XR_T(); x2_n += 1; x2_w += (unsigned)(xs1 - xs0); x2_c += (unsigned)(xs2 - xs1); x2_e += (unsigned)(xs3 - xs2); }
 #endif
         }
         old_m0 = m0;
         old_n0 = n0;
+        old_live = m0 + r < M;
         old_rowoff = PK ? (uint32_t)(m0 >> 5) * (uint32_t)(N * 64) + 16u * r + 512u * h     // m0 is a multiple of 32
                         : (uint32_t)(m0 + r) * (uint32_t)(N * 2) + 16u * h;
-    };
-    int item = it0;
-    run_item(accA, accB, item++, std::false_type{});
-    for (; item + 2 <= it1; item += 2) {
-        run_item(accB, accA, item, std::true_type{});
-        run_item(accA, accB, item + 1, std::true_type{});
     }
-    const bool lastA = item >= it1;          // the last finished item sits in accA, unless one more item goes into accB
-    if (!lastA) run_item(accB, accA, item, std::true_type{});
-    wait_vmcnt<0>();                         // no LDS-DMA may outlive the workgroup (past-the-end tiles)
-    // flush: the last item's three sub-tiles
-    auto flush = [&](f32x16 (&acc)[X2_NSUB]) __attribute__((always_inline)) {
+    // the last item's three sub-tiles
+    __device__ __forceinline__ void flush(f32x16 (&acc)[X2_NSUB]) const {
 #pragma unroll
         for (int g = 0; g < X2_NSUB; ++g) {
             uint32_t pk[8];
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) pk[ks] = finish2(acc[g][2 * ks], acc[g][2 * ks + 1]);
-            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
+            store_half<0>(pk, old_n0 + g * 32);
+            store_half<2>(pk, old_n0 + g * 32);
         }
-    };
-    if (lastA) flush(accA); else flush(accB);
-    XR_ACC(0, x2_n); XR_ACC(1, x2_w); XR_ACC(3, x2_c); XR_ACC(4, x2_e); XR_ACC(6, x2_n / 3); XR_ACC(2, 1); XR_ACC(5, x2_r); XR_ACC(7, x2_nr);
+    }
+    // all items: the two accumulator sets alternate, the last item is flushed
+    __device__ __forceinline__ void run() {
+        int item = 0;
+        run_item<false>(accA, accB, item++);
+        for (; item + 2 <= n_items; item += 2) {
+            run_item<true>(accB, accA, item);
+            run_item<true>(accA, accB, item + 1);
+        }
+        const bool lastA = item >= n_items;      // the last finished item sits in accA, unless one more item goes into accB
+        if (!lastA) run_item<true>(accB, accA, item);
+        wait_vmcnt<0>();                         // no LDS-DMA may outlive the workgroup (past-the-end tiles)
+        if (lastA) flush(accA); else flush(accB);
+    }
+};
+
+// PK: the output goes out in the block-packed layout (see packed_off); XPK: X comes in it (group_off)
+template <int EPI, bool PK, bool XPK>
+__global__ __launch_bounds__(512) void gemm_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W,
+                                                         const float *__restrict__ bias, bf16_t *__restrict__ out,
+                                                         int M, int N, int items_total) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int it0 = (int)((int64_t)items_total * blockIdx.x / gridDim.x);
+    const int it1 = (int)((int64_t)items_total * (blockIdx.x + 1) / gridDim.x);
+    if (it1 <= it0) return;
+    typedef X2Loop<EPI, PK, XPK, false, X2Range> Loop;
+    Loop x2(X, W, out, smem, X2_NSTAGE * Loop::STAGE, M, N, wave, X2Range{it0}, it1 - it0, -1);
+    // bias -> LDS once per workgroup, above the ring
+    for (int p = wave; p * 256 < N; p += Loop::NW)
+        if (p * 256 + lane * 4 < N) glds16(bias + p * 256 + lane * 4, smem + X2_NSTAGE * Loop::STAGE + p * 1024);
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    x2.prime(lane);
+    x2.start(lane);
+    x2.run();
+    XR_ACC(0, x2.x2_n); XR_ACC(1, x2.x2_w); XR_ACC(3, x2.x2_c); XR_ACC(4, x2.x2_e); XR_ACC(6, x2.x2_n / 3); XR_ACC(2, 1); XR_ACC(5, x2.x2_r); XR_ACC(7, x2.x2_nr);
 }
 
 // W [BN rows, K] -> per k-tile of BK the W-region LDS image of gemm_bf16_kernel<.., BN, BK, ..>: 16-byte slot sl of the image
@@ -779,29 +860,13 @@ __global__ __launch_bounds__(256) void pack_frag_w_kernel(const uint4 *__restric
 // Per k-tile: 40 KiB staged (640 LDS cycles) + 208 KiB read (832) for 1 536 MFMA cycles per SIMD.
 // =====================================================================================================
 // NW = waves = 32-token row blocks per workgroup, LR_NST = ring slots: <8, 3> (256 tokens, 120 KiB).
-// (ln_rows_xres2_kernel holds a COPY of the <8, 3> k loop and epilogue: a fix here belongs there too.)
+// The phases are the ln384_* functions below; ln_rows_xres2_kernel runs the same ones in front of its projection.  They take the
+// lane id (and r = lane & 31, h = lane >> 5) as arguments and never read threadIdx, so a caller short of registers can hand each
+// phase a freshly derived copy.
 constexpr int LR_BK = 32, LR_WBYTES = 384 * LR_BK * 2;
 
-template <int NW, int LR_NST>
-__global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
-                                                               const float *__restrict__ bias, const bf16_t *__restrict__ res,
-                                                               const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                               float eps, bf16_t *__restrict__ out, int M, int K, int xpacked,
-                                                               int respacked, int opacked) {
-    // xpacked: X is in the block-packed layout (packed_off): FFN2's operand h1.  respacked / opacked: so is the residual / goes the
-    // output (group_off; one base and 32-bit offsets: M * 768 < 4 GiB, checked by the launcher)
-    constexpr int N = 384, XBYTES = NW * 32 * LR_BK * 2, STAGE = XBYTES + LR_WBYTES;
-    constexpr int XP = XBYTES / 1024, PIECES = STAGE / 1024, PPW = PIECES / NW;   // pieces 0..XP-1: X, the rest: W
-    static_assert(PIECES % NW == 0 && XP == 2 * NW, "every wave issues two X pieces and PPW - 2 W pieces per k-tile");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int m0 = blockIdx.x * (NW * 32);
-    const int nk = K / LR_BK;
-
-    // accumulators start from the bias: acc[t][q] = output feature 32 t + (q & 3) + 8 (q >> 2) + 4 h of token m0 + 32 wave + r
-    f32x16 acc[12];
+// accumulators start from the bias: acc[t][q] = output feature 32 t + (q & 3) + 8 (q >> 2) + 4 h of the lane's token row
+__device__ __forceinline__ void ln384_bias_start(f32x16 (&acc)[12], const float *bias, int h) {
 #pragma unroll
     for (int t = 0; t < 12; ++t)
 #pragma unroll
@@ -810,6 +875,18 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[t][4 * gq + e] = bv[e];
         }
+}
+
+// The k loop of a workgroup of NW waves on token rows m0 .. m0 + 32 NW - 1 through LR_NST ring slots at smem (a stage is the X
+// tile of 32 NW rows plus the W tile).  CLAMP: rows past M repeat row M - 1 (never stored); without it all rows exist.
+// On return the last tiles (past-the-end ones too) are still in flight: the caller waits vmcnt(0).
+template <int NW, int LR_NST, bool CLAMP>
+__device__ __forceinline__ void ln384_kloop(f32x16 (&acc)[12], const bf16_t *X, const bf16_t *Wimg, char *smem, int wave, int lane,
+                                            int r, int h, int m0, int M, int K, int xpacked) {
+    constexpr int XBYTES = NW * 32 * LR_BK * 2, STAGE = XBYTES + LR_WBYTES;
+    constexpr int XP = XBYTES / 1024, PIECES = STAGE / 1024, PPW = PIECES / NW;   // pieces 0..XP-1: X, the rest: W
+    static_assert(PIECES % NW == 0 && XP == 2 * NW, "every wave issues two X pieces and PPW - 2 W pieces per k-tile");
+    const int nk = K / LR_BK;
     // LDS image of the X region (as gemm_bf16_kernel at BK = 32): rows of 64 B, four to a 256-byte super-row; 16-byte slot (sr, chp)
     // holds chunk ch = chp ^ (sr & 15) of the super-row = chunk ch & 3 of row 4 sr + (ch >> 2).  The permutation goes on the SOURCE
     // address (LDS-DMA writes lane-linearly).  The W region is the tile's 24 fragment blocks (pack_frag_w_kernel), copied verbatim.
@@ -819,7 +896,7 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         const int sl = (wave + i * NW) * 64 + lane;
         const int sr = sl >> 4, ch = (sl & 15) ^ (sr & 15);
         const int row = sr * 4 + (ch >> 2);
-        const int64_t m = m0 + row < M ? m0 + row : M - 1;     // rows past M repeat the last one (never stored)
+        const int64_t m = !CLAMP || m0 + row < M ? m0 + row : M - 1;
         xsrc[i] = xpacked ? reinterpret_cast<const char *>(X + packed_off(m, (ch & 3) * 8, K))
                           : reinterpret_cast<const char *>(X) + m * K * 2 + (ch & 3) * 16;
     }
@@ -884,14 +961,11 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
     ff_static_for(std::make_integer_sequence<int, LR_NST - 1>{}, [&](auto sc) __attribute__((always_inline)) {
         if (kt + decltype(sc)::value < nk) do_tile(kt + decltype(sc)::value, sc);
     });
-    wait_vmcnt<0>();   // past-the-end tiles must not outlive the workgroup
+}
 
-    // ---------------------------------------------------------------- epilogue: + residual, LayerNorm, store (wave-local)
-    // + residual: the lane's 16 bytes are the 8 features of group gq + h; the swap turns them into the accumulator layout
-    const int64_t m = m0 + wave * 32 + r;
-    const bool live = m < M;
-    const int64_t mr = live ? m : M - 1;
-    const uint32_t ro = (uint32_t)group_off(mr, h, N, respacked), rgs = (uint32_t)group_off(0, 1, N, respacked);
+// + residual: the lane's 16 bytes at res + ro + group * rgs are the 8 features of group gq + h; the swap turns them into the
+// accumulator layout (one base and 32-bit offsets: M * 768 < 4 GiB, checked by the launchers)
+__device__ __forceinline__ void ln384_add_residual(f32x16 (&acc)[12], const bf16_t *res, uint32_t ro, uint32_t rgs) {
 #pragma unroll
     for (int t = 0; t < 12; ++t)
 #pragma unroll
@@ -909,10 +983,14 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
             acc[t][4 * gq + 6] += __uint_as_float(c1 << 16);
             acc[t][4 * gq + 7] += __uint_as_float(c1 & 0xffff0000u);
         }
-    // two-pass statistics in the association order of gemm_bf16_kernel<.., 384, .., WAVES_N = 4, ..>: four groups of three
-    // sub-tiles (there: one wave each), each summed tile by tile, register by register, then across the half-waves, then
-    // ((0 + g0) + g1) + g2) + g3
-    float mean, rstd;
+}
+
+// two-pass statistics of the lane's row (wave-local: no barrier, no LDS round trip) in the association order of
+// gemm_bf16_kernel<.., 384, .., WAVES_N = 4, ..>, which is what makes rows bit-equal across the kernels: four groups of three
+// sub-tiles (there: one wave each), each summed tile by tile, register by register, then across the half-waves, then
+// ((0 + g0) + g1) + g2) + g3
+__device__ __forceinline__ void ln384_stats(const f32x16 (&acc)[12], float eps, float &mean, float &rstd) {
+    constexpr int N = 384;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         float tot = 0.f;
@@ -938,7 +1016,13 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         else
             rstd = 1.0f / sqrtf(tot / (float)N + eps);
     }
-    const uint32_t oo = (uint32_t)group_off(m, h, N, opacked), ogs = (uint32_t)group_off(0, 1, N, opacked);
+}
+
+// normalise, pack to bf16, swap half-waves so that every lane owns 8 contiguous features: sink(4 t + gq, o) gets the 16-byte
+// group 4 t + gq + h of the lane's row.  gamma / beta: global memory or LDS
+template <class Sink>
+__device__ __forceinline__ void ln384_normalise(const f32x16 (&acc)[12], float mean, float rstd, const float *gamma,
+                                                const float *beta, int h, Sink &&sink) {
 #pragma unroll
     for (int t = 0; t < 12; ++t) {
         uint32_t pk[8];
@@ -957,10 +1041,43 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
         for (int gq = 0; gq < 4; gq += 2) {
             auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
             auto s1w = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
-            if (live)
-                *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(out) + (oo + (4 * t + gq) * ogs)) = make_uint4(s0[0], s1w[0], s0[1], s1w[1]);
+            const u32x4 o = {s0[0], s1w[0], s0[1], s1w[1]};
+            sink(4 * t + gq, o);
         }
     }
+}
+
+template <int NW, int LR_NST>
+__global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
+                                                               const float *__restrict__ bias, const bf16_t *__restrict__ res,
+                                                               const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                               float eps, bf16_t *__restrict__ out, int M, int K, int xpacked,
+                                                               int respacked, int opacked) {
+    // xpacked: X is in the block-packed layout (packed_off): FFN2's operand h1.  respacked / opacked: so is the residual / goes the
+    // output (group_off)
+    constexpr int N = 384;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int m0 = blockIdx.x * (NW * 32);
+
+    f32x16 acc[12];
+    ln384_bias_start(acc, bias, h);
+    ln384_kloop<NW, LR_NST, true>(acc, X, Wimg, smem, wave, lane, r, h, m0, M, K, xpacked);
+    wait_vmcnt<0>();   // past-the-end tiles must not outlive the workgroup
+
+    // ---------------------------------------------------------------- epilogue: + residual, LayerNorm, store
+    const int64_t m = m0 + wave * 32 + r;
+    const bool live = m < M;
+    const int64_t mr = live ? m : M - 1;
+    ln384_add_residual(acc, res, (uint32_t)group_off(mr, h, N, respacked), (uint32_t)group_off(0, 1, N, respacked));
+    float mean, rstd;
+    ln384_stats(acc, eps, mean, rstd);
+    const uint32_t oo = (uint32_t)group_off(m, h, N, opacked), ogs = (uint32_t)group_off(0, 1, N, opacked);
+    ln384_normalise(acc, mean, rstd, gamma, beta, h, [&](int g, const u32x4 &o) __attribute__((always_inline)) {
+        if (live) *reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(out) + (oo + g * ogs)) = o;
+    });
 }
 
 // =====================================================================================================
@@ -971,8 +1088,8 @@ __global__ __launch_bounds__(NW * 64) void ln_rows_gemm_kernel(const bf16_t *__r
 // token rows and all 384 features), and the 16-byte groups the LayerNorm epilogue stores after its half-wave swap ARE the resident
 // fragments bx[24] of the projection (group 4 t + gq + h = 2 s + h for s = 2 t + gq / 2).  So the workgroup keeps them, and the
 // projection starts without the store drain, the kernel boundary, the W-ring prologue and the fragment load in between.  No
-// arithmetic changes: the first phase is ln_rows_gemm_kernel (k order, accumulators from the bias, residual add, two-pass
-// statistics), the second gemm_xres2_kernel's item loop; both are COPIES, so that the stand-alone kernels keep their code.
+// arithmetic changes: the first phase is ln_rows_gemm_kernel's (the ln384_* functions: k order, accumulators from the bias,
+// residual add, two-pass statistics), the second gemm_xres2_kernel's item loop (X2Loop): the same code in both places.
 //
 // Hand-over:
 //   LDS     the three 40-KiB slots of the LayerNorm ring and the six 24-KiB slots of the W ring overlap (one barrier after the last
@@ -998,6 +1115,11 @@ __host__ __device__ inline ChainPart chain_part(int G, int rem_blocks, int ntile
 __host__ __device__ inline int chain_item(const ChainPart &p, int G, int ntiles, int b, int i) {
     return i < p.own ? b * ntiles + i : G * ntiles + p.r0 + (i - p.own);
 }
+struct X2Chain {   // X2Loop's item map of workgroup b
+    ChainPart part;
+    int G, ntiles, b;
+    __device__ __forceinline__ int operator()(int i) const { return chain_item(part, G, ntiles, b, i); }
+};
 
 template <int EPI>
 __global__ __launch_bounds__(512) void ln_rows_xres2_kernel(const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg,
@@ -1008,19 +1130,15 @@ __global__ __launch_bounds__(512) void ln_rows_xres2_kernel(const bf16_t *__rest
                                                             bf16_t *__restrict__ out2, int M, int N2, int rem_blocks) {
     // grid = the whole blocks (all of their rows exist); M = all token rows, the remainder blocks included; xout and out2 packed
     constexpr int NW = 8, N = 384, LR_NST = 3;
-    constexpr int XBYTES = NW * 32 * LR_BK * 2, LSTAGE = XBYTES + LR_WBYTES;
-    constexpr int XP = XBYTES / 1024, LPPW = LSTAGE / 1024 / NW;
-    constexpr int KSTEPS = N / 16, BMX = NW * 32;
-    constexpr int STAGE = X2_BN * X2_BK * 2, PPW = STAGE / 1024 / NW;
-    constexpr int BIAS_OFF = X2_NSTAGE * STAGE, GB_OFF = BIAS_OFF + 6144;   // bias2 (N2 <= 1536) | gamma | beta
-    static_assert(LR_NST * LSTAGE <= BIAS_OFF && XP == 2 * NW && PPW == 3 && 2 * PPW + 24 <= 63, "hand-over layout");
+    constexpr int LSTAGE = NW * 32 * LR_BK * 2 + LR_WBYTES;   // a stage of the LayerNorm ring
+    typedef X2Loop<EPI, true, true, true, X2Chain> Loop;   // the projection phase: packed in and out, the 24 row stores carried
+    constexpr int BMX = Loop::BMX;
+    constexpr int BIAS_OFF = X2_NSTAGE * Loop::STAGE, GB_OFF = BIAS_OFF + 6144;   // bias2 (N2 <= 1536) | gamma | beta
+    static_assert(LR_NST * LSTAGE <= BIAS_OFF && Loop::NW == NW && 2 * Loop::PPW + 24 <= 63, "hand-over layout");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 31, h = lane >> 5;
     const int m0l = blockIdx.x * BMX;
-    const int nk = K / LR_BK;
-    const uint32_t lbase = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem);
 
     // the projection's bias and the LayerNorm parameters -> LDS, above both rings
     for (int p = wave; p * 256 < N2; p += NW)
@@ -1030,350 +1148,50 @@ __global__ __launch_bounds__(512) void ln_rows_xres2_kernel(const bf16_t *__rest
         glds16(beta + wave * 256 + lane * 4, smem + GB_OFF + N * 4 + wave * 1024);
     }
 
-    // ---------------------------------------------------------------- LayerNorm phase (ln_rows_gemm_kernel<8, 3>)
+    // ---------------------------------------------------------------- LayerNorm phase: all rows of the block exist, no clamp
     f32x16 acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(lbias + 32 * t + 8 * gq + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[t][4 * gq + e] = bv[e];
-        }
-    {
-        const char *xsrc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int sl = (wave + i * NW) * 64 + lane;
-            const int sr = sl >> 4, ch = (sl & 15) ^ (sr & 15);
-            const int64_t m = m0l + sr * 4 + (ch >> 2);
-            xsrc[i] = xpacked ? reinterpret_cast<const char *>(X + packed_off(m, (ch & 3) * 8, K))
-                              : reinterpret_cast<const char *>(X) + m * K * 2 + (ch & 3) * 16;
-        }
-        const int xkstride = xpacked ? (LR_BK / 8) * 512 : LR_BK * 2;
-        const char *wsrc = reinterpret_cast<const char *>(Wimg) + lane * 16;
-        auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
-            const int k2 = kt < nk ? kt : nk - 1;
-            char *dst = smem + stage * LSTAGE;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) glds16(xsrc[i] + k2 * xkstride, dst + (wave + i * NW) * 1024);
-#pragma unroll
-            for (int i = 2; i < LPPW; ++i)
-                glds16(wsrc + (int64_t)k2 * LR_WBYTES + (wave + i * NW - XP) * 1024, dst + (wave + i * NW) * 1024);
-        };
-        uint32_t xo[2];
-#pragma unroll
-        for (int sk = 0; sk < 2; ++sk) {
-            const int ch = (r & 3) * 4 + 2 * sk + h;
-            xo[sk] = lbase + wave * 2048 + (r >> 2) * 256 + ((ch ^ ((((wave & 1) << 3) + (r >> 2)) & 15)) << 4);
-        }
-        const uint32_t wl = lbase + XBYTES + lane * 16;
-#pragma unroll
-        for (int i = 0; i < LR_NST - 1; ++i) issue(i, i);
-#pragma unroll
-        for (int t = 0; t < 12; ++t) asm volatile("" : "+v"(acc[t]));
-        auto do_tile = [&](int kt, auto stc) __attribute__((always_inline)) {
-            constexpr int stage = decltype(stc)::value;
-            wait_vmcnt<(LR_NST - 2) * LPPW>();
-            __builtin_amdgcn_s_barrier();
-            issue(kt + LR_NST - 1, (stage + LR_NST - 1) % LR_NST);
-            constexpr int PF = 4, NRD = 24;
-            lds_u32x4 bfr[2], fr[PF + 1];
-            const uint32_t so = stage * LSTAGE;
-            lds_read_b128_imm<0>(bfr[0], xo[0] + so);
-            lds_read_b128_imm<0>(bfr[1], xo[1] + so);
-            const uint32_t wa = wl + so;
-            auto rd = [&](auto nc) __attribute__((always_inline)) {
-                constexpr int n = decltype(nc)::value;
-                lds_read_b128_imm<n * 1024>(fr[n % (PF + 1)], wa);
-            };
-            ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
-            ff_static_for(std::make_integer_sequence<int, NRD>{}, [&](auto nc) __attribute__((always_inline)) {
-                constexpr int n = decltype(nc)::value;
-                if constexpr (n + PF < NRD) rd(std::integral_constant<int, n + PF>{});
-                constexpr int younger = n + PF < NRD ? PF : NRD - 1 - n;
-                lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
-                if constexpr (n == 0) { asm volatile("" : "+v"(bfr[0])); asm volatile("" : "+v"(bfr[1])); }
-                acc[n % 12] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]),
-                                                                       __builtin_bit_cast(bf16x8, bfr[n / 12]), acc[n % 12], 0, 0, 0);
-            });
-        };
-        int kt = 0;
-        for (; kt + LR_NST <= nk; kt += LR_NST)
-            ff_static_for(std::make_integer_sequence<int, LR_NST>{}, [&](auto sc) __attribute__((always_inline)) {
-                do_tile(kt + decltype(sc)::value, sc);
-            });
-        ff_static_for(std::make_integer_sequence<int, LR_NST - 1>{}, [&](auto sc) __attribute__((always_inline)) {
-            if (kt + decltype(sc)::value < nk) do_tile(kt + decltype(sc)::value, sc);
-        });
-    }
+    ln384_bias_start(acc, lbias, lane >> 5);
+    ln384_kloop<NW, LR_NST, false>(acc, X, Wimg, smem, wave, lane, lane & 31, lane >> 5, m0l, M, K, xpacked);
     wait_vmcnt<0>();                    // the last tiles (past-the-end ones too) have landed in my slots ...
     __builtin_amdgcn_s_barrier();       // ... and in everyone's, and everyone has read its last fragments: the LayerNorm ring is free
 
     // ---------------------------------------------------------------- hand-over: prime the W ring
     const int ntiles = N2 / X2_BN, G = (int)gridDim.x, wg = (int)blockIdx.x;
-    const ChainPart part = chain_part(G, rem_blocks, ntiles, wg);
-    // LDS image of a W tile as in gemm_xres2_kernel: 16-byte slot c of row rr holds source chunk c ^ (rr & 15)
-    auto w_src_off = [&](int ln, int i) __attribute__((always_inline)) {
-        const int sl = (wave * PPW + i) * 64 + ln;
-        const int row = sl >> 4, ch = (sl & 15) ^ (row & 15);
-        return row * N * 2 + ch * 16;
-    };
-    // the next W tile to issue: k-group pg of the workgroup's item pi, feature tile pj (past the end: the last tile again)
-    int pi = 0, pg = 0, pj = chain_item(part, G, ntiles, wg, 0) % ntiles;
-    auto tile_base = [&]() __attribute__((always_inline)) {
-        return reinterpret_cast<const char *>(W2) + ((int64_t)pj * X2_BN * N + pg * X2_BK) * 2;
-    };
-    auto advance = [&]() __attribute__((always_inline)) {
-        if (++pg == X2_KG) {
-            if (pi + 1 < part.n) {
-                pg = 0;
-                ++pi;
-                pj = chain_item(part, G, ntiles, wg, pi) % ntiles;
-            } else {
-                pg = X2_KG - 1;
-            }
-        }
-    };
-    // (the offsets are computed again behind the epilogue: held across it they cost registers the epilogue has not got)
-    const int lanep = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#pragma unroll
-    for (int i = 0; i < X2_PD; ++i) {
-        const char *base = tile_base();
-#pragma unroll
-        for (int p = 0; p < PPW; ++p) glds16(base + w_src_off(lanep, p), smem + i * STAGE + (wave * PPW + p) * 1024);
-        advance();
-    }
+    const X2Chain items{chain_part(G, rem_blocks, ntiles, wg), G, ntiles, wg};
+    // the block's own fragments are resident: the epilogue below leaves them in x2.bx
+    Loop x2(xout, W2, out2, smem, BIAS_OFF, M, N2, wave, items, items.part.n, wg);
+    // (the piece offsets are computed again behind the epilogue: held across it they cost registers the epilogue has not got)
+    x2.prime(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
 
     // ---------------------------------------------------------------- LayerNorm epilogue: + residual, statistics, store AND keep
-    bf16x8 bx[KSTEPS];
     {
         // (lane ids from mbcnt, not from threadIdx: nothing lane-derived has to live through the k loop or the residual phase)
         const int lane1 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const uint32_t ro = (uint32_t)group_off(m0l + wave * 32 + (lane1 & 31), lane1 >> 5, N, respacked), rgs = (uint32_t)group_off(0, 1, N, respacked);
-#pragma unroll
-        for (int t = 0; t < 12; ++t)
-#pragma unroll
-            for (int gq = 0; gq < 4; gq += 2) {
-                const uint4 o = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(res) + (ro + (4 * t + gq) * rgs));
-                auto s0 = __builtin_amdgcn_permlane32_swap(o.x, o.z, false, false);
-                auto s1 = __builtin_amdgcn_permlane32_swap(o.y, o.w, false, false);
-                const uint32_t a0 = s0[0], c0 = s0[1], a1 = s1[0], c1 = s1[1];
-                acc[t][4 * gq + 0] += __uint_as_float(a0 << 16);
-                acc[t][4 * gq + 1] += __uint_as_float(a0 & 0xffff0000u);
-                acc[t][4 * gq + 2] += __uint_as_float(a1 << 16);
-                acc[t][4 * gq + 3] += __uint_as_float(a1 & 0xffff0000u);
-                acc[t][4 * gq + 4] += __uint_as_float(c0 << 16);
-                acc[t][4 * gq + 5] += __uint_as_float(c0 & 0xffff0000u);
-                acc[t][4 * gq + 6] += __uint_as_float(c1 << 16);
-                acc[t][4 * gq + 7] += __uint_as_float(c1 & 0xffff0000u);
-            }
+        ln384_add_residual(acc, res, (uint32_t)group_off(m0l + wave * 32 + (lane1 & 31), lane1 >> 5, N, respacked),
+                           (uint32_t)group_off(0, 1, N, respacked));
         float mean, rstd;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                float sg = 0.f;
-#pragma unroll
-                for (int t = 3 * w; t < 3 * w + 3; ++t)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        if (pass == 0) {
-                            sg += acc[t][q];
-                        } else {
-                            const float dlt = acc[t][q] - mean;
-                            sg = fmaf(dlt, dlt, sg);
-                        }
-                    }
-                sg += __shfl_xor(sg, 32, 64);
-                tot += sg;
-            }
-            if (pass == 0)
-                mean = tot / (float)N;
-            else
-                rstd = 1.0f / sqrtf(tot / (float)N + eps);
-        }
+        ln384_stats(acc, eps, mean, rstd);
         int lane3 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         asm volatile("" : "+v"(lane3));
-        const int h3 = lane3 >> 5;
-        const uint32_t oo = (uint32_t)group_off(m0l + wave * 32 + (lane3 & 31), h3, N, 1);
+        const uint32_t oo = (uint32_t)group_off(m0l + wave * 32 + (lane3 & 31), lane3 >> 5, N, 1);
         constexpr uint32_t ogs = 512;   // group_off(0, 1, N, 1)
         const uint64_t xb = (uint64_t)(uintptr_t)xout;
-        const float *gl = reinterpret_cast<const float *>(smem + GB_OFF), *bl = gl + N;
-#pragma unroll
-        for (int t = 0; t < 12; ++t) {
-            uint32_t pk[8];
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int n = 32 * t + 8 * gq + 4 * h3;
-                const f32x4 gv = *reinterpret_cast<const f32x4 *>(gl + n), bv = *reinterpret_cast<const f32x4 *>(bl + n);
-                const float o0 = fmaf((acc[t][4 * gq + 0] - mean) * rstd, gv[0], bv[0]);
-                const float o1 = fmaf((acc[t][4 * gq + 1] - mean) * rstd, gv[1], bv[1]);
-                const float o2 = fmaf((acc[t][4 * gq + 2] - mean) * rstd, gv[2], bv[2]);
-                const float o3 = fmaf((acc[t][4 * gq + 3] - mean) * rstd, gv[3], bv[3]);
-                pk[2 * gq] = pack_bf16x2(o0, o1);
-                pk[2 * gq + 1] = pack_bf16x2(o2, o3);
-            }
-#pragma unroll
-            for (int gq = 0; gq < 4; gq += 2) {
-                auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gq], pk[2 * gq + 2], false, false);
-                auto s1w = __builtin_amdgcn_permlane32_swap(pk[2 * gq + 1], pk[2 * gq + 3], false, false);
-                const u32x4 o = {s0[0], s1w[0], s0[1], s1w[1]};
-                const uint32_t voff = oo + (4 * t + gq) * ogs;
-                // (asm: exactly one store instruction each, counted below; s_nop: see gemm_xres2_kernel's store_half)
-                asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(xb) : "memory");
-                bx[2 * t + gq / 2] = __builtin_bit_cast(bf16x8, o);
-            }
-        }
+        // gamma / beta from LDS; the row is stored (exactly one store instruction per group: the 24 that the item loop carries) AND
+        // kept: group 4 t + gq + h is fragment s = 2 t + gq / 2 of the projection
+        const float *gl = reinterpret_cast<const float *>(smem + GB_OFF);
+        ln384_normalise(acc, mean, rstd, gl, gl + N, lane3 >> 5, [&](int g, const u32x4 &o) __attribute__((always_inline)) {
+            x2_store16(oo + g * ogs, o, xb);
+            x2.bx[g / 2] = __builtin_bit_cast(bf16x8, o);
+        });
     }
 
-    // ---------------------------------------------------------------- projection phase (gemm_xres2_kernel<EPI, true, true>)
+    // ---------------------------------------------------------------- projection phase
     // (lane-derived values of this phase start from an opaque copy of the lane id, so that none of them is computed early and
     // carried through the epilogue, where every register is taken)
     int lane2 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(lane2));
-    const int r2 = lane2 & 31, h2 = lane2 >> 5;
-    int src_off[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) src_off[i] = w_src_off(lane2, i);
-    auto issue_pieces = [&](int stage, int i0, int i1) __attribute__((always_inline)) {
-        const char *base = tile_base();
-        for (int i = i0; i < i1; ++i)
-            glds16(base + src_off[i], smem + stage * STAGE + (wave * PPW + i) * 1024);
-    };
-    int cks[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) cks[ks] = r2 * 256 + (((2 * ks + h2) ^ (r2 & 15)) << 4);
-    const uint32_t bias_lds = lbase + BIAS_OFF;
-    int cur_mb = wg, m0 = wg * BMX + wave * 32;
-    f32x16 accA[X2_NSUB], accB[X2_NSUB];
-    int old_m0 = 0, old_n0 = 0;
-    int st = 0, ring = 0;
-    int young1 = 0, young2 = 0, young3 = 0;
-    int carry = 1;                    // the 24 stores of the LayerNorm epilogue are younger than the primed tiles (steps 0 and 2)
-    uint32_t old_rowoff = 0;
-    const uint64_t out_base = (uint64_t)(uintptr_t)out2;
-    auto store_half = [&](const uint32_t (&pk)[8], int mrow0, int ncol, auto gqc) __attribute__((always_inline)) {
-        constexpr int gq = decltype(gqc)::value;
-        const bool full = mrow0 + 32 <= M;    // wave-uniform
-        uint32_t a0 = pk[2 * gq], a1 = pk[2 * gq + 1], b0 = pk[2 * gq + 2], b1 = pk[2 * gq + 3];
-        auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-        const uint32_t voff = old_rowoff + (uint32_t)(ncol + 8 * gq) * 64u;
-        const uint64_t ob = out_base;
-        if (full || mrow0 + r2 < M)
-            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(o), "s"(ob) : "memory");
-    };
-    auto finish2 = [&](float y0, float y1) __attribute__((always_inline)) -> uint32_t {
-        if constexpr (EPI == EPI_GELU) gelu2(y0, y1);
-        return pack_bf16x2(y0, y1);
-    };
-    auto run_item = [&](f32x16 (&cur)[X2_NSUB], f32x16 (&old)[X2_NSUB], int item, auto with_old) __attribute__((always_inline)) {
-        constexpr bool OLD = decltype(with_old)::value;
-        const int gi = chain_item(part, G, ntiles, wg, item);
-        if (gi / ntiles != cur_mb) {                          // wave-uniform: a remainder block -> load its fragments
-            cur_mb = gi / ntiles;
-            m0 = cur_mb * BMX + wave * 32;
-            const char *xp = reinterpret_cast<const char *>(xout) + group_off(m0 + r2, h2, N, 1);
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) bx[s] = *reinterpret_cast<const bf16x8 *>(xp + 2 * s * 512);
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) asm volatile("" : "+v"(bx[s]));
-            young1 = young2 = young3 = 0;
-            carry = 0;
-        }
-        const int n0 = (gi % ntiles) * X2_BN;
-        const uint32_t baddr = bias_lds + (n0 + 4 * h2) * 4;
-        ff_static_for(std::make_integer_sequence<int, X2_NSUB>{}, [&](auto ic) __attribute__((always_inline)) {
-            constexpr int i = decltype(ic)::value;
-            f32x4 bv[4];
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[0]) : "v"(baddr), "n"((i * 32 + 0) * 4) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[1]) : "v"(baddr), "n"((i * 32 + 8) * 4) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[2]) : "v"(baddr), "n"((i * 32 + 16) * 4) : "memory");
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bv[3]) : "v"(baddr), "n"((i * 32 + 24) * 4) : "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2]), "+v"(bv[3])::"memory");
-#pragma unroll
-            for (int q = 0; q < 16; ++q) cur[i][q] = bv[q >> 2][q & 3];
-        });
-#pragma unroll
-        for (int g = 0; g < X2_KG; ++g) {
-            asm volatile("" : "+s"(ring));
-            const int stage = ring;
-            if ((st & 1) == 0) {
-                const int ys = (young1 >= 0 && young2 >= 0 && young3 >= 0) ? young1 + young2 + young3 : 0;
-                if (carry) wait_vmcnt<2 * PPW + 24>();       // (no projection store has been issued yet: ys = 0)
-                else if (ys == 6) wait_vmcnt<2 * PPW + 6>();
-                else if (ys == 4) wait_vmcnt<2 * PPW + 4>();
-                else if (ys == 2) wait_vmcnt<2 * PPW + 2>();
-                else wait_vmcnt<2 * PPW>();
-                __builtin_amdgcn_s_barrier();
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            uint32_t pk[8];
-            {
-                constexpr int PF = 3, NRD = 8 * X2_NSUB;
-                lds_u32x4 fr[PF + 1];
-                const uint32_t wsl = lbase + stage * STAGE;
-                auto rd = [&](auto nc) __attribute__((always_inline)) {
-                    constexpr int n = decltype(nc)::value;
-                    lds_read_b128_imm<(n % X2_NSUB) * 8192>(fr[n % (PF + 1)], wsl + cks[n / X2_NSUB]);
-                };
-                ff_static_for(std::make_integer_sequence<int, PF>{}, rd);
-                ff_static_for(std::make_integer_sequence<int, NRD>{}, [&](auto nc) __attribute__((always_inline)) {
-                    constexpr int n = decltype(nc)::value;
-                    constexpr int ks = n / X2_NSUB, i = n % X2_NSUB;
-                    if constexpr (n + PF < NRD) rd(std::integral_constant<int, n + PF>{});
-                    constexpr int younger = n + PF < NRD ? PF : NRD - 1 - n;
-                    lgkm_wait_counted<younger>(fr[n % (PF + 1)]);
-                    cur[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fr[n % (PF + 1)]), bx[g * 8 + ks], cur[i], 0, 0, 0);
-                    if constexpr (i == X2_NSUB - 1) {
-                        if constexpr (ks == 1 || ks == 3 || ks == 5) {
-                            const int ns = stage + X2_PD;
-                            issue_pieces(ns >= X2_NSTAGE ? ns - X2_NSTAGE : ns, ks >> 1, (ks >> 1) + 1);
-                            if constexpr (ks == 5) advance();
-                        }
-                        if constexpr (OLD) pk[ks] = finish2(old[g][2 * ks], old[g][2 * ks + 1]);
-                    }
-                });
-            }
-            young3 = young2;
-            young2 = young1;
-            young1 = 0;
-            if constexpr (OLD) {
-                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-                store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
-                young1 = old_m0 + 32 <= M ? 2 : -1;
-            }
-            ++st;
-            ring = ring + 1 == X2_NSTAGE ? 0 : ring + 1;
-            if (st >= 3) carry = 0;   // the wait of step 4 is for tiles issued after the epilogue's stores
-        }
-        old_m0 = m0;
-        old_n0 = n0;
-        old_rowoff = (uint32_t)(m0 >> 5) * (uint32_t)(N2 * 64) + 16u * r2 + 512u * h2;
-    };
-    int item = 0;
-    run_item(accA, accB, item++, std::false_type{});
-    for (; item + 2 <= part.n; item += 2) {
-        run_item(accB, accA, item, std::true_type{});
-        run_item(accA, accB, item + 1, std::true_type{});
-    }
-    const bool lastA = item >= part.n;
-    if (!lastA) run_item(accB, accA, item, std::true_type{});
-    wait_vmcnt<0>();
-    auto flush = [&](f32x16 (&a)[X2_NSUB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int g = 0; g < X2_NSUB; ++g) {
-            uint32_t pk[8];
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) pk[ks] = finish2(a[g][2 * ks], a[g][2 * ks + 1]);
-            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 0>{});
-            store_half(pk, old_m0, old_n0 + g * 32, std::integral_constant<int, 2>{});
-        }
-    };
-    if (lastA) flush(accA); else flush(accB);
+    x2.start(lane2);
+    x2.run();
 }
 
 // =====================================================================================================
