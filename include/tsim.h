@@ -598,7 +598,8 @@ typedef struct tsim_encoder_weights_host {
 /* Accepted shapes (anything else: TSIM_EUNSUPPORTED / TSIM_EINVAL with a message that names the accepted values, before any
  * launch): hidden 64, 384, 768 or 1024; heads with hidden / heads = 16, 32 or 64 (any count, a multiple of 4 or not);
  * ffn a multiple of 64, and at least 128 unless hidden is 64; TSIM_W_MXFP8 with hidden and ffn multiples of 256.  DESIGN.md
- * "Encoder routes by configuration" names the kernel and the test of every class of these. */
+ * "Encoder routes by configuration" names the kernel and the test of every class of these; tsim_encoder_route_host (below)
+ * answers the same question without a GPU. */
 int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_encoder_weights_host *w,
                         tsim_encoder **out);
 void tsim_encoder_destroy(tsim_encoder *enc);
@@ -737,6 +738,69 @@ int tsim_encoder_error_flags(tsim_encoder *enc, int32_t *flags_host, void *strea
  * is block * ntiles + feature tile.  Returns the number of items of workgroup b (negative: bad arguments) and writes the first
  * min(count, cap) of them. */
 int tsim_chain_items_host(int blocks, int rem_blocks, int ntiles, int G, int b, int32_t *items, int cap);
+
+/* Introspection (host only, no launch): the kernels an encoder of configuration cfg runs in layer `layer` of a forward of T
+ * tokens, as tsim_encoder_create plans them and the forward executes them (DESIGN.md "Encoder routes by configuration").
+ * A configuration that tsim_encoder_create refuses is refused here with the same code and text. */
+#define TSIM_FAMILY_H64 0             /* hidden 64: gemm_bf16 tiles */
+#define TSIM_FAMILY_H384_PACKED 1     /* hidden 384, BERT family: qkv, h1 and the residual stream block-packed */
+#define TSIM_FAMILY_H384_ROWMAJOR 2   /* hidden 384, MPNet or an ffn gemm_xres2 does not take */
+#define TSIM_FAMILY_PP 3              /* hidden 768 / 1024, bf16: gemm_pp + res_ln_rows */
+#define TSIM_FAMILY_PP_MX 4           /* hidden 768 / 1024, MXFP8 operands: gemm_pp_mx + res_ln_rows<QUANT> */
+/* form[]: the projections of a layer ... */
+#define TSIM_ROUTE_QKV 0
+#define TSIM_ROUTE_O 1       /* O-projection + residual + LayerNorm */
+#define TSIM_ROUTE_FFN1 2    /* + GELU */
+#define TSIM_ROUTE_FFN2 3    /* + residual + LayerNorm */
+/* ... and their kernel forms */
+#define TSIM_FORM_BF16_128x64 1          /* gemm_bf16 128 x 64 tile */
+#define TSIM_FORM_BF16_128x128 2         /* gemm_bf16 128 x 128 tile */
+#define TSIM_FORM_XRES2 3                /* gemm_xres2, row-major output */
+#define TSIM_FORM_XRES2_PACKED 4         /* gemm_xres2<PK>, or chained behind the previous LayerNorm GEMM (chain_blocks) */
+#define TSIM_FORM_PP_256_PACKED_W 5      /* gemm_pp, 256-wide feature tile, tile-major copy of W */
+#define TSIM_FORM_PP_256 6               /* gemm_pp, 256-wide feature tile, row-major W */
+#define TSIM_FORM_PP_128 7               /* gemm_pp, 128-wide feature tile, row-major W */
+#define TSIM_FORM_PP_MX 8                /* gemm_pp_mx (QKV behind quant_mx in layer 0; FFN1 with the GELU_MX epilogue) */
+#define TSIM_FORM_BF16_RES_LN 9          /* gemm_bf16 128 x 64 tile with the residual + LayerNorm epilogue */
+#define TSIM_FORM_LN384 10               /* hidden-384 LayerNorm GEMM: row segments by T (seg[]) */
+#define TSIM_FORM_PP_RES_LN_PACKED_W 11  /* gemm_pp F32 on the tile-major copy of W + res_ln_rows */
+#define TSIM_FORM_PP_RES_LN 12           /* gemm_pp F32 on row-major W + res_ln_rows */
+#define TSIM_FORM_PP_MX_RES_LN 13        /* (quant_mx +) gemm_pp_mx F32 + res_ln_rows<QUANT> */
+/* row segments of a TSIM_FORM_LN384 projection */
+#define TSIM_SEG_LN_ROWS 1          /* ln_rows_gemm: whole 256-token blocks */
+#define TSIM_SEG_LN_ROWS_CHAINED 2  /* ln_rows_xres2: the same blocks, their workgroups run the next projection too */
+#define TSIM_SEG_LN_TAIL 3          /* ln_tail_gemm */
+#define TSIM_SEG_LN_SPLIT2 4        /* ln_split, 2 feature slices per row block, + ln_split_finish */
+#define TSIM_SEG_LN_SPLIT4 5        /* ln_split, 4 feature slices */
+#define TSIM_SEG_BF16_128x384 6     /* gemm_bf16 128 x 384 tile, RES_LN epilogue */
+#define TSIM_SEG_BF16_64x384 7      /* gemm_bf16 64 x 384 tile, RES_LN epilogue */
+/* weight images beside the row-major bf16 matrices, and scratch buffers beside x0, x1, qkv, ctx, h1 */
+#define TSIM_IMG_PP_QKV_O 1   /* tile-major copies of the QKV and O matrices (gemm_pp) */
+#define TSIM_IMG_LN_KTILE 2   /* O and FFN2 matrices as k-tile LDS images (gemm_bf16 x 384 tiles) */
+#define TSIM_IMG_LN_FRAG 4    /* O and FFN2 matrices as MFMA fragment images (ln_rows, ln_tail, ln_split) */
+#define TSIM_IMG_MXFP8 8      /* e4m3 bytes (tile-major) and E8M0 scales of all four matrices */
+#define TSIM_BUF_YBUF 1       /* fp32 pre-LayerNorm sums */
+#define TSIM_BUF_LNIMG 2      /* ln_split's accumulator images */
+#define TSIM_BUF_MX_ACT 4     /* MXFP8 images of the projections' inputs */
+#define TSIM_ROUTE_MAX_SEGS 4
+
+typedef struct tsim_route_segment {
+    int32_t form, row0, rows;   /* TSIM_SEG_*; rows [row0, row0 + rows) */
+} tsim_route_segment;
+
+typedef struct tsim_encoder_route {
+    int32_t family;         /* TSIM_FAMILY_* */
+    int32_t form[4];        /* TSIM_FORM_* by TSIM_ROUTE_* */
+    int32_t images;         /* TSIM_IMG_* bits */
+    int32_t buffers;        /* TSIM_BUF_* bits */
+    int32_t chain_blocks;   /* 256-token blocks whose LayerNorm workgroups run the next projection too (FFN1 behind O, the
+                             * next layer's QKV behind FFN2); 0: none at this configuration or T */
+    int32_t qkv_chained;    /* 1: the previous layer's FFN2 launch has run this layer's QKV */
+    int32_t n_seg[2];       /* segments of O ([0]) and FFN2 ([1]); 0 unless their form is TSIM_FORM_LN384 */
+    tsim_route_segment seg[2][TSIM_ROUTE_MAX_SEGS];   /* in row order; they partition [0, T) */
+} tsim_encoder_route;
+
+int tsim_encoder_route_host(const tsim_encoder_config *cfg, int32_t T, int32_t layer, tsim_encoder_route *out);
 
 /* ---- tokenizer (host code, no GPU): BERT WordPiece for pure-ASCII sentences -------------------------------------------------
  * Replaces, for the sentences it handles, the host tokenizer call of the reference's encode_text

@@ -3,48 +3,14 @@
 tests/test_encoder_config_gpu.py (the kernels against it).  Weights, inputs, probe and tolerance rule are encoder_cases' own,
 borrowed through ``registered`` the way arch_cases does.
 
-ROUTE TABLE (DESIGN.md "Encoder routes by configuration" holds the same table).  Read from tsim_encoder_create,
-tsim_encoder_forward_ex, gemm_plain, gemm_res_ln, use_packed_layout, gemm_pp / launch_pp.  H = hidden, F = ffn, DH = H / heads,
-T = tokens of a call.  "new" cases are this file's, the others encoder_cases' / arch_cases'.
-
-Attention (every H): attention_kernel<DH, REL, PK>, one workgroup = 4 heads, a partial last group when heads % 4 != 0.
-    plain  DH 16 tiny-bert, bert-768-h48-f1984 (new) | DH 32 bert-384-f1024, bert-768-h24-f1920, bert-1024-h32-f2816 (new) | DH 64 bert-768
-    REL    DH 16 tiny-mpnet | DH 32 mpnet-384 | DH 64 mpnet-768, mpnet-64-h1-f320, mpnet-384-h6-f2048 (new)      (MPNet)
-    PK     DH 16 bert-384-h24-f1920 (new) | DH 32 bert-384 | DH 64 bert-384-h6-f768 (new)                        (H 384 packed)
-    partial group: bert-64-h2-f64 (2 of 4), mpnet-64-h1-f320 (1 of 4), bert-384-h6-f768 / mpnet-384-h6-f2048 (4 + 2) (new)
-
-H = 64 (bf16 only):
-    QKV   gemm_bf16 128x64 tile (N = 192)                      O + LN  gemm_bf16 128x64 RES_LN, K = 64
-    FFN1  F % 128 == 0: gemm_bf16 128x128 (tiny-bert)          F % 128 != 0: gemm_bf16 128x64 (bert-64-h2-f64 N = 64, mpnet-64-h1-f320 N = 320)
-    FFN2 + LN  gemm_bf16 128x64 RES_LN, K = F (128 tiny-*, 64, 320 new)
-
-H = 384 (bf16 only; MXFP8 refused: 384 % 256 != 0; F = 64 refused: test_refused_configurations):
-    packed (BERT family, F % 192 == 0, F <= 1920: use_packed_layout): qkv, h1 and the residual stream block-packed
-        QKV / FFN1  gemm_xres2<PK>, or chained behind the previous LayerNorm GEMM (ln_rows_xres2) when F <= 1536 and T has whole
-                    rounds of 256 x 256 tokens;  O / FFN2 + LN by T: ln_tail / ln_split (T <= 8192), ln_rows_gemm + tail, + the
-                    gemm_bf16 64x384 remainder.  F = 1536: bert-384.  F = 768 (K = 768, other tile counts): bert-384-h6-f768, also at
-                    n = 2300 / 4700 sentences (chained).  F = 1920 (chain off): bert-384-h24-f1920, also at n = 4700.
-    row-major (MPNet, or F not a multiple of 192, or F > 1920):
-        QKV  gemm_xres2 (N = 1152)
-        FFN1 F % 192 == 0 and F <= 2048: gemm_xres2 (mpnet-384) | otherwise gemm_bf16 128x128 (bert-384-f1024, mpnet-384-h6-f2048) or,
-             when F % 128 != 0, 128x64 (bert-384-f2112).  F % 192 == 0 above 2048 (bert-384-f2112) used to reach gemm_xres2's
-             N <= 2048 refusal at the first forward: fixed in gemm_plain, it now takes the plain tiles like any other F
-        O / FFN2 + LN  K % 192 == 0: as packed, row-major operands (mpnet-384 K = 1536, bert-384-f2112 K = 2112) | otherwise
-             ln_rows_gemm + gemm_bf16 128x384 / 64x384 (bert-384-f1024 K = 1024, also at n = 2300; mpnet-384-h6-f2048 K = 2048)
-
-H = 768 / 1024 (F = 64 refused: FFN2 has no kernel for K = 64; test_refused_configurations):
-    bf16, F % 128 == 0: QKV gemm_pp 256-wide tile on packed W (pqkv), O gemm_pp F32 on packed W (po) + res_ln_rows,
-        FFN1 gemm_pp GELU on row-major W, 256-wide (F % 256 == 0: bert-768 3072, bert-1024 4096, bert-1024-h32-f2816 11 tiles) or
-        128-wide (F = 128 x odd: bert-768-h24-f1920), FFN2 gemm_pp F32 K = F on row-major W + res_ln_rows
-    bf16, F = 64 x odd: no packed weights (QKV and O through gemm_pp on row-major W), FFN1 gemm_bf16 128x64, K = H,
-        FFN2 gemm_pp F32 with an odd number of k-tiles (bert-768-h48-f1984: 31)
-    mxfp8 (F % 256 == 0; any other F refused: test_refused_configurations): quant_mx, gemm_pp_mx BIAS / F32 / GELU_MX, res_ln_rows<QUANT>; F = 3072 / 4096 (encoder_cases, arch_cases),
-        F = 2048 (bert-768-h24-f2048-mxfp8: 8 GELU_MX tiles, scale rows of 64 bytes, FFN2 K = 2048)
+The routes these cases reach (and those of encoder_cases / arch_cases) are DESIGN.md's table "Encoder routes by configuration";
+tests/test_encoder_route_cpu.py holds that table as data and checks every case here against the encoder's plan
+(tsim_encoder_route_host), so the table is not repeated in this file.
 
 Departures from the proposed set: bert-768-h24-f1920 runs the 128-wide tile, but not pack_w(.., BN = 128): the encoder packs only
 the QKV and O matrices (N = 3H and H, multiples of 256) and FFN1 reads row-major W, so no accepted configuration calls pack_w
-with BN = 128.  bert-384-f2112 is added: the route table shows F % 192 == 0, F > 2048 reached gemm_xres2's N <= 2048 refusal at
-the first forward.  No case was dropped.
+with BN = 128.  bert-384-f2112 is added: F % 192 == 0 above 2048 used to reach gemm_xres2's N <= 2048 refusal at the first
+forward (it takes the 128x64 tile now, like any F that is no multiple of 128).  No case was dropped.
 
 Weight scales: ``encoder_cases._QK_A`` / ``_VO_A`` are keyed by hidden size; ``QK_A`` below holds a case's own scale where the
 head_dim moves the median largest probability out of [0.2, 0.9] (figures next to it, float64 probe, layer 1 / layer 2).

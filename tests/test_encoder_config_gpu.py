@@ -98,8 +98,8 @@ def test_many_tiles_per_workgroup(name):
 
 @pytest.mark.parametrize("name", list(cc.REFUSED))
 def test_refused_configurations(name):
-    """ffn = 64 above hidden 64: FFN2 would run with K = 64, for which hidden 1024 has no kernel, hidden 768 one that no
-    shipped shape ever ran and hidden 384 one that fails at the first large batch.  MXFP8 with an ffn that is no multiple of 256:
+    """ffn = 64 above hidden 64: FFN2 would run with K = 64, for which hidden 1024 has no kernel, hidden 768 had one that no
+    shipped shape ever ran (removed with the encoder's plan: no accepted configuration reaches it) and hidden 384 one that fails at the first large batch.  MXFP8 with an ffn that is no multiple of 256:
     no tile of the block-scaled GEMM.  Both refused in tsim_encoder_create (TSIM_EUNSUPPORTED, a ValueError here), before any
     allocation or launch, with the accepted values in the message."""
     cfg, wdtype, text = cc.REFUSED[name]

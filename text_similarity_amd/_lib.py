@@ -22,6 +22,14 @@ SPACE_COSINE, SPACE_DOT, SPACE_L2 = 0, 1, 2
 ENC_ERR_SPAN = 16                # include/tsim.h TSIM_ENC_ERR_SPAN
 RANGE_SLOT_CAP = 2048            # include/tsim.h TSIM_RANGE_SLOT_CAP
 RANGE_MERGE_MAX_LISTS = 64       # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS
+# tsim_encoder_route_host (include/tsim.h TSIM_FAMILY_*, TSIM_FORM_*, TSIM_SEG_*, TSIM_IMG_*, TSIM_BUF_*)
+FAMILY_H64, FAMILY_H384_PACKED, FAMILY_H384_ROWMAJOR, FAMILY_PP, FAMILY_PP_MX = range(5)
+(FORM_BF16_128x64, FORM_BF16_128x128, FORM_XRES2, FORM_XRES2_PACKED, FORM_PP_256_PACKED_W, FORM_PP_256, FORM_PP_128, FORM_PP_MX,
+ FORM_BF16_RES_LN, FORM_LN384, FORM_PP_RES_LN_PACKED_W, FORM_PP_RES_LN, FORM_PP_MX_RES_LN) = range(1, 14)
+SEG_LN_ROWS, SEG_LN_ROWS_CHAINED, SEG_LN_TAIL, SEG_LN_SPLIT2, SEG_LN_SPLIT4, SEG_BF16_128x384, SEG_BF16_64x384 = range(1, 8)
+IMG_PP_QKV_O, IMG_LN_KTILE, IMG_LN_FRAG, IMG_MXFP8 = 1, 2, 4, 8
+BUF_YBUF, BUF_LNIMG, BUF_MX_ACT = 1, 2, 4
+ROUTE_MAX_SEGS = 4
 
 
 class TsimError(RuntimeError):
@@ -33,6 +41,16 @@ class EncoderConfigC(C.Structure):
                 ("ffn", C.c_int32), ("vocab", C.c_int32), ("max_pos", C.c_int32), ("pad_id", C.c_int32),
                 ("rel_buckets", C.c_int32), ("ln_eps", C.c_float), ("max_tokens", C.c_int32),
                 ("max_seqs", C.c_int32), ("weight_dtype", C.c_int32)]
+
+
+class RouteSegmentC(C.Structure):
+    _fields_ = [("form", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32)]
+
+
+class EncoderRouteC(C.Structure):
+    _fields_ = [("family", C.c_int32), ("form", C.c_int32 * 4), ("images", C.c_int32), ("buffers", C.c_int32),
+                ("chain_blocks", C.c_int32), ("qkv_chained", C.c_int32), ("n_seg", C.c_int32 * 2),
+                ("seg", RouteSegmentC * ROUTE_MAX_SEGS * 2)]
 
 
 _FP = C.POINTER(C.c_float)
@@ -167,6 +185,7 @@ _SIGS = {
     "tsim_encoder_destroy": (None, [C.c_void_p]),
     "tsim_encoder_error_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "tsim_chain_items_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "tsim_encoder_route_host": (C.c_int, [C.POINTER(EncoderConfigC), C.c_int32, C.c_int32, C.POINTER(EncoderRouteC)]),
     "tsim_encoder_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

@@ -458,7 +458,7 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64) void gemm_bf16_kernel(
     }
 }
 
-// gemm_plain sends K = 384 projections whose width is a multiple of XR_BN to gemm_xres2 (below).  (192 is the feature tile of
+// encoder_plan sends row-major K = 384 projections whose width is a multiple of XR_BN to gemm_xres2 (below).  (192 is the feature tile of
 // the first form of that kernel; the predicate is kept as it was so that every shape keeps its kernel.)
 constexpr int XR_BN = 192;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -1822,10 +1822,13 @@ struct DevBuf {
 
 }  // namespace tsim
 
+#include "encoder_plan.h"   // EncoderPlan, encoder_plan, chain_blocks, ln384_segments: which kernels run
+
 using namespace tsim;
 
 struct tsim_encoder {
     tsim_encoder_config cfg;
+    EncoderPlan plan;   // (of cfg: tsim_encoder_create builds its images and buffers, the forward runs its forms)
     int Tp = 0;
     // weights
     float *word = nullptr, *pos = nullptr, *type0 = nullptr, *emb_g = nullptr, *emb_b = nullptr, *relb = nullptr;
@@ -1954,10 +1957,29 @@ static int mpnet_bucket(int rel, int num_buckets) {
     return ret + large;
 }
 
+// Where the rows of a hidden-384 LayerNorm GEMM's operands live: row-major, or the block-packed layout (packed_off) that qkv, h1
+// and the residual stream have between the kernels of the packed family.  (The kernels take them as 0 / 1.)
+enum Layout : int { ROW_MAJOR = 0, BLOCK_PACKED = 1 };
+struct Layouts { Layout x, res, out; };
+constexpr Layouts ALL_ROW_MAJOR = {ROW_MAJOR, ROW_MAJOR, ROW_MAJOR};
+
+// A hidden-384 LayerNorm GEMM: out = LayerNorm(X W^T + bias + res) gamma + beta, X [rows, K], W [384, K] row-major, as k-tile LDS
+// images (Wk: pack_gemm_w_kernel) and as MFMA fragment images (Wf: pack_frag_w_kernel)
+struct LnGemm {
+    const bf16_t *X, *W, *Wk, *Wf;
+    const float *bias;
+    const bf16_t *res;
+    const float *gamma, *beta;
+    float eps;
+    bf16_t *out;
+    int K;
+    Layouts lay;
+};
+
 template <int BM, int BN, int BK, int WM, int WN, int EPI, int NST = 2>
 static int launch_gemm(const bf16_t *X, const bf16_t *W, const float *bias, const bf16_t *res, const float *gamma,
                        const float *beta, float eps, bf16_t *out, int M, int N, int K, hipStream_t st,
-                       const bf16_t *Wimg = nullptr, bool xpacked = false, bool respacked = false, bool opacked = false) {
+                       const bf16_t *Wimg, Layouts lay) {
     constexpr int lds = gemm_lds_bytes<BM, BN, BK, WM, WN, NST>();
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = gemm_bf16_kernel<BM, BN, BK, WM, WN, EPI, NST>;
@@ -1968,12 +1990,12 @@ static int launch_gemm(const bf16_t *X, const bf16_t *W, const float *bias, cons
     const int grid = ((mtiles + 7) / 8) * 8 * ntiles;
     if (Wimg && ntiles != 1) return fail(TSIM_EINVAL, "gemm: a packed W image needs BN == N");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), lds, st, X, W, bias, res, gamma, beta, eps, out, M, N, K,
-                       mtiles, ntiles, Wimg, xpacked ? 1 : 0, respacked ? 1 : 0, opacked ? 1 : 0);
+                       mtiles, ntiles, Wimg, (int)lay.x, (int)lay.res, (int)lay.out);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-template <int EPI, bool PK, bool XPK = false>
+template <int EPI, bool PK, bool XPK>
 static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_t *out, int M, int N, hipStream_t st) {
     constexpr int lds = X2_NSTAGE * X2_BN * X2_BK * 2 + 8192;   // ring | bias (N <= 2048)
     if (N > 2048) return fail(TSIM_EUNSUPPORTED, "gemm_xres2: N=%d > 2048", N);
@@ -2007,7 +2029,6 @@ static int gemm_xres2(const bf16_t *X, const bf16_t *W, const float *bias, bf16_
 // Bound: 12 KiB of W + 4 KiB of rows per k-step and workgroup at the CU's 64 B/clk L2 path = 256 cycles per k-step.
 // =====================================================================================================
 typedef __attribute__((ext_vector_type(4))) uint32_t lt_u32x4;
-constexpr int LT_PF = 12;   // k-steps in flight (4 loads each: vmcnt <= 63 allows 16; K / 16 must be a multiple)
 
 // The GEMM part of one ln_tail wave: acc = bias + X W^T + res for token rows m0 .. m0 + 31 and features 96 wn .. + 95, in the
 // calling wave's registers (lane = token row r + 32 h, as the MFMA leaves them).
@@ -2188,8 +2209,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // same bits as from every other form.
 // Image: [row block][wave wn][i * 4 + gq][lane] float4 = acc[i][4 gq .. 4 gq + 3] (48 KiB per row block, coalesced KiB stores).
 // =====================================================================================================
-constexpr int LS_MAX_BLOCKS = 256;   // ln_tail's limit of 8 192 rows: the image buffer's capacity (tsim_encoder_create)
-
 template <int PF, int S>
 __global__ __launch_bounds__(256 / S) __attribute__((amdgpu_waves_per_eu(1, 1))) void ln_split_gemm_kernel(
     const bf16_t *__restrict__ X, const bf16_t *__restrict__ Wimg32, const float *__restrict__ bias, const bf16_t *__restrict__ res,
@@ -2228,68 +2247,53 @@ __global__ __launch_bounds__(256) void ln_split_finish_kernel(const float4 *__re
     lt_layernorm(acc, red, gamma, beta, eps, out, M, wn, m0, opacked);
 }
 
-// The LayerNorm GEMM of width 384 for M <= 8 192 rows: ln_tail, or ln_split where blocks x slices still fit one round of the
-// chip's 256 CUs (img: LS_MAX_BLOCKS row blocks of image; null: ln_tail only)
-static int ln_tail_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
-                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, float *img, bool respacked,
-                        bool opacked) {
-    const int rpk = respacked ? 1 : 0, opk = opacked ? 1 : 0;
-    if (K % (16 * LT_PF) != 0) return fail(TSIM_EUNSUPPORTED, "ln_tail_gemm: K=%d", K);
-    const int nb = (M + 31) / 32;
-    const int S = !img || nb > LS_MAX_BLOCKS ? 1 : nb <= 64 ? 4 : nb <= 128 ? 2 : 1;
-    if (S == 1) {
-        hipLaunchKernelGGL(ln_tail_gemm_kernel<LT_PF>, dim3((unsigned)nb), dim3(256), 0, st, X, Wimg32, bias, res, gamma, beta, eps,
-                           out, M, K, xpacked ? 1 : 0, rpk, opk);
+// Rows [0, M) of g (M <= 8 192) as one TSIM_SEG_LN_TAIL / _SPLIT2 / _SPLIT4 segment.  img: ln_split's accumulator images
+static int ln_tail_gemm(const LnGemm &g, int M, int form, float *img, hipStream_t st) {
+    if (g.K % (16 * LT_PF) != 0) return fail(TSIM_EUNSUPPORTED, "ln_tail_gemm: K=%d", g.K);
+    const int nb = (M + 31) / 32, xpk = g.lay.x, rpk = g.lay.res, opk = g.lay.out;
+    if (form == TSIM_SEG_LN_TAIL) {
+        hipLaunchKernelGGL(ln_tail_gemm_kernel<LT_PF>, dim3((unsigned)nb), dim3(256), 0, st, g.X, g.Wf, g.bias, g.res, g.gamma, g.beta,
+                           g.eps, g.out, M, g.K, xpk, rpk, opk);
         TSIM_HIP_CHECK(hipGetLastError());
         return TSIM_OK;
     }
     float4 *im = reinterpret_cast<float4 *>(img);
-    if (S == 4)
-        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 4>), dim3((unsigned)(nb * 4)), dim3(64), 0, st, X, Wimg32, bias, res, im, M, K,
-                           xpacked ? 1 : 0, rpk);
+    if (form == TSIM_SEG_LN_SPLIT4)
+        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 4>), dim3((unsigned)(nb * 4)), dim3(64), 0, st, g.X, g.Wf, g.bias, g.res, im, M,
+                           g.K, xpk, rpk);
     else
-        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 2>), dim3((unsigned)(nb * 2)), dim3(128), 0, st, X, Wimg32, bias, res, im, M,
-                           K, xpacked ? 1 : 0, rpk);
+        hipLaunchKernelGGL((ln_split_gemm_kernel<LT_PF, 2>), dim3((unsigned)(nb * 2)), dim3(128), 0, st, g.X, g.Wf, g.bias, g.res, im, M,
+                           g.K, xpk, rpk);
     TSIM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(ln_split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, im, gamma, beta, eps, out, M, opk);
+    hipLaunchKernelGGL(ln_split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, im, g.gamma, g.beta, g.eps, g.out, M, opk);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-// LayerNorm GEMM of width 384 over rows [0, M) in workgroups of NW * 32 token rows (the last one may be partial)
+// Rows [0, M) of g in workgroups of NW * 32 token rows (the last one may be partial)
 template <int NW, int NST>
-static int ln_rows_gemm(const bf16_t *X, const bf16_t *Wimg32, const float *bias, const bf16_t *res, const float *gamma,
-                        const float *beta, float eps, bf16_t *out, int M, int K, hipStream_t st, bool xpacked, bool respacked, bool opacked) {
+static int ln_rows_gemm(const LnGemm &g, int M, hipStream_t st) {
     constexpr int lds = NST * (NW * 32 * LR_BK * 2 + LR_WBYTES);   // <8, 3>: 120 KiB
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = ln_rows_gemm_kernel<NW, NST>;
     static DevOnce lds_once;
     TSIM_MAX_LDS(lds_once, kern, lds);
-    if (K % LR_BK != 0 || K < NST * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: K=%d", K);
+    if (g.K % LR_BK != 0 || g.K < NST * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: K=%d", g.K);
     if (((int64_t)M + 256) * 768 >= (1ll << 32)) return fail(TSIM_EUNSUPPORTED, "ln_rows_gemm: %d rows of 384 exceed 4 GiB", M);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((M + NW * 32 - 1) / (NW * 32))), dim3(NW * 64), lds, st, X, Wimg32, bias, res, gamma,
-                       beta, eps, out, M, K, xpacked ? 1 : 0, respacked ? 1 : 0, opacked ? 1 : 0);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((M + NW * 32 - 1) / (NW * 32))), dim3(NW * 64), lds, st, g.X, g.Wf, g.bias, g.res, g.gamma,
+                       g.beta, g.eps, g.out, M, g.K, (int)g.lay.x, (int)g.lay.res, (int)g.lay.out);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-// Whole 256-token blocks of an M-row hidden-384 LayerNorm GEMM that go to ln_rows_gemm (or ln_rows_xres2): whole rounds of 256
-// blocks, and a last round that is at least half full
-static int ln_rows_blocks(int M) {
-    const int t256 = M / 256;
-    return (t256 % 256) >= 128 ? t256 : (t256 / 256) * 256;
-}
-
-// ln_rows_xres2: LayerNorm GEMM of the first `blocks` 256-token blocks + the projection [M, 384] x W2^T -> out2 [M, N2] of ALL M rows
-// (the rows behind the whole blocks must have been written to xout before: gemm_res_ln(.., tail_only))
+// ln_rows_xres2: the first `blocks` 256-token blocks of g (output block-packed) + the projection [M, 384] x W2^T -> out2 [M, N2] of
+// ALL M rows (the rows behind the whole blocks must have been written to g.out before: ln384_gemm runs those segments first)
 template <int EPI>
-static int ln_rows_xres2(const bf16_t *X, const bf16_t *Wimg32, const float *lbias, const bf16_t *res, const float *gamma,
-                         const float *beta, float eps, bf16_t *xout, int blocks, int K, bool xpacked, bool respacked, const bf16_t *W2,
-                         const float *bias2, bf16_t *out2, int M, int N2, hipStream_t st) {
+static int ln_rows_xres2(const LnGemm &g, int blocks, const bf16_t *W2, const float *bias2, bf16_t *out2, int M, int N2, hipStream_t st) {
     constexpr int lds = X2_NSTAGE * X2_BN * X2_BK * 2 + 6144 + 2 * 384 * 4;   // W ring (over the LayerNorm ring) | bias2 | gamma | beta
     static_assert(lds <= 160 * 1024, "LDS budget");
     if (N2 % X2_BN != 0 || N2 > 1536) return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: N=%d", N2);
-    if (K % LR_BK != 0 || K < 3 * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: K=%d", K);
+    if (g.K % LR_BK != 0 || g.K < 3 * LR_BK) return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: K=%d", g.K);
     if (blocks <= 0 || (int64_t)blocks * 256 > M) return fail(TSIM_EINVAL, "ln_rows_xres2: %d blocks of %d rows", blocks, M);
     if (((int64_t)M + 256) * N2 * 2 >= (1ll << 32) || ((int64_t)M + 256) * 768 >= (1ll << 32))
         return fail(TSIM_EUNSUPPORTED, "ln_rows_xres2: output of %d x %d exceeds 4 GiB", M, N2);
@@ -2297,93 +2301,195 @@ static int ln_rows_xres2(const bf16_t *X, const bf16_t *Wimg32, const float *lbi
     static DevOnce lds_once;
     TSIM_MAX_LDS(lds_once, kern, lds);
     const int rem_blocks = (M - blocks * 256 + 255) / 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, st, X, Wimg32, lbias, res, gamma, beta, eps, xout, K,
-                       xpacked ? 1 : 0, respacked ? 1 : 0, W2, bias2, out2, M, N2, rem_blocks);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, st, g.X, g.Wf, g.bias, g.res, g.gamma, g.beta, g.eps, g.out, g.K,
+                       (int)g.lay.x, (int)g.lay.res, W2, bias2, out2, M, N2, rem_blocks);
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;
 }
 
-// The block-packed qkv / h1 layout (packed_off) needs gemm_xres2 as the producer on both projections
-static bool use_packed_layout(int H, int F) {
-    return H == 384 && (3 * H) % X2_BN == 0 && F % X2_BN == 0 && F <= 2048;
-}
-
-template <int EPI>
-static int gemm_plain(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, bf16_t *out, int M, int N,
-                      int K, hipStream_t st) {
-    if (K == 384 && N % XR_BN == 0 && N <= 2048) return gemm_xres2<EPI, false>(X, W, bias, out, M, N, st);   // (its bias image holds 2048)
-    if (K >= 768 && gemm_pp_supported(N, K))
-        return gemm_pp(EPI == EPI_GELU ? PP_EPI_GELU : PP_EPI_BIAS, X, Wp ? Wp : W, Wp != nullptr, bias, out, M, N, K, st);
-    if (N % 128 == 0)
-        return launch_gemm<128, 128, 64, 2, 2, EPI>(X, W, bias, nullptr, nullptr, nullptr, 0.f, out, M, N, K, st);
-    return launch_gemm<128, 64, 64, 2, 2, EPI>(X, W, bias, nullptr, nullptr, nullptr, 0.f, out, M, N, K, st);
-}
-
-static int gemm_res_ln(const bf16_t *X, const bf16_t *W, const bf16_t *Wp, const float *bias, const bf16_t *res,
-                       const float *gamma, const float *beta, float eps, bf16_t *out, int M, int N, int K, float *ybuf,
-                       hipStream_t st, const bf16_t *Wimg = nullptr, const bf16_t *Wimg32 = nullptr, bool xpacked = false,
-                       float *lnimg = nullptr, bool respacked = false, bool opacked = false, bool tail_only = false) {
-    // tail_only: the rows of ln_rows_blocks(M) whole blocks are left to the caller (ln_rows_xres2), only the rows behind them run
-    // respacked / opacked: the residual comes / the output goes in the block-packed layout (the residual stream between the layers
-    // of the hidden-384 BERT path).  Row offsets below are multiples of 32: a block starts at the same element in both layouts.
-    if ((xpacked || respacked || opacked) && N != 384) return fail(TSIM_EINVAL, "gemm_res_ln: the packed layouts are a hidden-384 form");
-    if (ybuf && N >= 512 && N % 256 == 0 && gemm_pp_supported(N, K)) {
-        // wide rows: a workgroup cannot own whole 768-feature rows at a 256-token tile, so the projection writes
-        // fp32 sums and a row kernel adds the residual and normalises (HBM-bound, 8 B per element)
-        int rc = gemm_pp(PP_EPI_F32, X, Wp ? Wp : W, Wp != nullptr, bias, ybuf, M, N, K, st);
-        if (rc) return rc;
-        return res_ln_rows(ybuf, res, gamma, beta, eps, out, nullptr, nullptr, M, N, st);
-    }
-    switch (N) {
-        case 384: {
-            // 256-token tiles, one 32-token row block per wave (ln_rows_gemm_kernel), for whole rounds of 256 tiles and for a last
-            // round that is at least half full; everything else — and every small batch — goes through the forms below.  All
-            // forms give a row the same bits (bit-wise large-vs-small-batch test).
-            bool after_rows = false;   // the rest below is the remainder of a ln_rows launch: a true tail
-            if (Wimg32) {
-                const int use = ln_rows_blocks(M);
-                if (use > 0) {
-                    // (a four-slot ring with the second half of the waves issuing behind their MFMAs measured equal, 68.5 vs 66-68 us
-                    // per launch)
-                    int rc = tail_only ? TSIM_OK
-                                       : ln_rows_gemm<8, 3>(X, Wimg32, bias, res, gamma, beta, eps, out, use * 256, K, st, xpacked, respacked, opacked);
-                    const int m1 = use * 256;
-                    if (rc || m1 == M) return rc;
-                    X += (int64_t)m1 * K; res += (int64_t)m1 * N; out += (int64_t)m1 * N; M -= m1;
-                    after_rows = true;
-                }
-                // few rows (a remainder, or a small batch): one round of 32-row workgroups (or of 32-row x feature-slice
-                // workgroups) that stream W straight into registers
-                if (M <= LS_MAX_BLOCKS * 32 && K % (16 * LT_PF) == 0)
-                    return ln_tail_gemm(X, Wimg32, bias, res, gamma, beta, eps, out, M, K, st, xpacked, lnimg, respacked, opacked);
-            }
-            // 128-token tiles, one workgroup per CU: mt tiles take ceil(mt/256) rounds and a nearly empty last round costs a full
-            // one.  A small remainder is launched separately with 64-token tiles (2x more, 2x shorter workgroups).
-            // (64-token tiles throughout measured slower: 64 x 384 x 32-k with two workgroups per CU 2.96 ms per forward, 64 x 384
-            // x 64-k 3.08, against 2.74: the W tile is re-staged for half as many tokens)
-            const int mt = (M + 127) / 128, full = (mt / 256) * 256, rem = mt - full;
+// T rows of g, segment by segment (ln384_segments).  chained: the whole blocks are left to the caller's ln_rows_xres2 launch,
+// which needs the rows behind them written first: only those run here.
+static int ln384_gemm(const LnGemm &g, int T, bool chained, float *lnimg, hipStream_t st) {
+    tsim_route_segment seg[TSIM_ROUTE_MAX_SEGS];
+    const int n = ln384_segments(T, g.K, chained, seg);
+    for (int i = 0; i < n; ++i) {
+        const int r0 = seg[i].row0, rows = seg[i].rows;   // (r0 is a multiple of 32: a row block starts at the same element in both layouts)
+        LnGemm s = g;
+        s.X += (int64_t)r0 * g.K, s.res += (int64_t)r0 * 384, s.out += (int64_t)r0 * 384;
+        int rc = TSIM_OK;
+        switch (seg[i].form) {
+            case TSIM_SEG_LN_ROWS_CHAINED: break;
+            // (a four-slot ring with the second half of the waves issuing behind their MFMAs measured equal, 68.5 vs 66-68 us per launch)
+            case TSIM_SEG_LN_ROWS: rc = ln_rows_gemm<8, 3>(s, rows, st); break;
             // (four 32-k ring slots instead of two 64-k ones — prefetch distance 3 — measured 2.5 % SLOWER per forward: the deep
             // path issues a k-tile's DMA pieces in one burst ahead of the MFMAs instead of behind each k-step's)
-            auto main_launch = [&](int rows) {
-                return launch_gemm<128, 384, 64, 2, 4, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, rows, N, K, st, Wimg, xpacked, respacked, opacked);
-            };
-            if (rem > 0 && rem <= 96 && (full > 0 || after_rows)) {
-                const int m_main = full * 128;
-                if (full > 0) {
-                    int rc = main_launch(m_main);
-                    if (rc) return rc;
-                }
-                // remainder launch: 64 token rows (eight waves) per workgroup.  (A three-slot ring measured no different:
-                // 2.744-2.751 vs 2.751-2.752 ms per forward.)
-                return launch_gemm<64, 384, 64, 2, 4, EPI_RES_LN>(X + (int64_t)m_main * K, W, bias, res + (int64_t)m_main * N,
-                                                                  gamma, beta, eps, out + (int64_t)m_main * N, M - m_main, N, K, st, Wimg, xpacked, respacked, opacked);
-            }
-            return main_launch(M);
+            case TSIM_SEG_BF16_128x384:
+                rc = launch_gemm<128, 384, 64, 2, 4, EPI_RES_LN>(s.X, s.W, s.bias, s.res, s.gamma, s.beta, s.eps, s.out, rows, 384, s.K, st, s.Wk, s.lay);
+                break;
+            // 64 token rows (eight waves) per workgroup.  (A three-slot ring measured no different: 2.744-2.751 vs 2.751-2.752 ms per forward.)
+            case TSIM_SEG_BF16_64x384:
+                rc = launch_gemm<64, 384, 64, 2, 4, EPI_RES_LN>(s.X, s.W, s.bias, s.res, s.gamma, s.beta, s.eps, s.out, rows, 384, s.K, st, s.Wk, s.lay);
+                break;
+            default: rc = ln_tail_gemm(s, rows, seg[i].form, lnimg, st);
         }
-        case 768: return launch_gemm<64, 768, 32, 1, 8, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, M, N, K, st);
-        case 64: return launch_gemm<128, 64, 64, 4, 2, EPI_RES_LN>(X, W, bias, res, gamma, beta, eps, out, M, N, K, st);
-        default: return fail(TSIM_EUNSUPPORTED, "encoder: hidden size %d has no fused LayerNorm GEMM (64, 384, 768)", N);
+        if (rc) return rc;
     }
+    return TSIM_OK;
+}
+
+// =====================================================================================================
+// The forward's stages: embedding, one layer function per family of the plan, pooling, classification head
+// =====================================================================================================
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+static int embed_rows(tsim_encoder *e, const int32_t *tok_ids, const int32_t *tok_type, const int32_t *tok_pos, const int32_t *tok_col,
+                      int T, int max_len, hipStream_t st) {
+    const tsim_encoder_config &c = e->cfg;
+    // column of a token inside its sequence: tok_col when given (MPNet), else tok_pos (BERT: position == column)
+    const int32_t *colp = tok_col ? tok_col : tok_pos;
+    const int col_limit = tok_col || c.arch == TSIM_ARCH_BERT ? max_len : c.max_pos;   // MPNet / RoBERTa without tok_col: pos is not a column
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b,
+                           c.ln_eps, T, c.hidden, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, tok_type, tok_type ? e->n_types : 0);
+    };
+    auto go = [&](auto v) { tok_type ? launch(embed_ln_kernel<decltype(v)::value, true>) : launch(embed_ln_kernel<decltype(v)::value, false>); };
+    c.hidden == 64 ? go(int_c<1>{}) : c.hidden == 384 ? go(int_c<6>{}) : c.hidden == 768 ? go(int_c<12>{}) : go(int_c<16>{});   // values per lane
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+struct Forward {   // the layers of one call: what they share, and one function per family of the plan
+    tsim_encoder *e;
+    const int32_t *cu_seqlens, *col;   // col: MPNet's token columns (relative-position bias); null otherwise
+    int T, B, H, F, chain;             // chain: chain_blocks of T
+    float eps;
+    dim3 agrid;                        // attention: (sequences, groups of four heads, blocks of 32 queries), xcd_map = 1
+    hipStream_t st;
+    using Layer = tsim_encoder::Layer;
+
+    int attention() const {
+        const int heads = e->cfg.heads, dh = H / heads;
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col, e->relb, e->relw, H, heads, 1.0f / sqrtf((float)dh), e->ctx, B, 1);
+        };
+        auto go = [&](auto d) {
+            constexpr int D = decltype(d)::value;
+            if (e->cfg.arch == TSIM_ARCH_MPNET) launch(attention_kernel<D, true, false>);
+            else if (e->plan.family == TSIM_FAMILY_H384_PACKED) launch(attention_kernel<D, false, true>);
+            else launch(attention_kernel<D, false, false>);
+        };
+        dh == 16 ? go(int_c<16>{}) : dh == 32 ? go(int_c<32>{}) : go(int_c<64>{});
+        TSIM_HIP_CHECK(hipGetLastError());
+        return TSIM_OK;
+    }
+
+    int ffn1_rowmajor(const Layer &L) const {   // FFN1 of the families whose h1 is row-major
+        switch (const int form = e->plan.form[TSIM_ROUTE_FFN1]) {
+            case TSIM_FORM_XRES2: return gemm_xres2<EPI_GELU, false, false>(e->x1, L.w1, L.b1, e->h1, T, F, st);
+            case TSIM_FORM_PP_256: case TSIM_FORM_PP_128: return gemm_pp(PP_EPI_GELU, e->x1, L.w1, 0, L.b1, e->h1, T, F, H, st);   // (the tile: gemm_pp_tile_width)
+            case TSIM_FORM_BF16_128x128:
+                return launch_gemm<128, 128, 64, 2, 2, EPI_GELU>(e->x1, L.w1, L.b1, nullptr, nullptr, nullptr, 0.f, e->h1, T, F, H, st, nullptr, ALL_ROW_MAJOR);
+            case TSIM_FORM_BF16_128x64:
+                return launch_gemm<128, 64, 64, 2, 2, EPI_GELU>(e->x1, L.w1, L.b1, nullptr, nullptr, nullptr, 0.f, e->h1, T, F, H, st, nullptr, ALL_ROW_MAJOR);
+            default: return fail(TSIM_EINVAL, "encoder: FFN1 form %d is not a row-major one", form);
+        }
+    }
+
+    // Projections on MXFP8 operands (v_mfma_scale_f32_32x32x64_f8f6f4); x0's image comes fused from the previous layer's LayerNorm
+    // kernel, for layer 0 from the stand-alone quantiser
+    int layer_mx(int l) const {
+        const Layer &L = e->layers[l];
+        int rc;
+        if (l == 0 && (rc = quant_mx(e->x0, T, H, e->aq, e->as, st))) return rc;
+        if ((rc = gemm_pp_mx(PP_EPI_BIAS, e->aq, e->as, L.qqkv, 1, L.sqkv, L.bqkv, e->qkv, nullptr, T, 3 * H, H, st))) return rc;
+        if ((rc = attention()) || (rc = quant_mx(e->ctx, T, H, e->aq, e->as, st))) return rc;
+        if ((rc = gemm_pp_mx(PP_EPI_F32, e->aq, e->as, L.qo, 1, L.so, L.bo, e->ybuf, nullptr, T, H, H, st))) return rc;
+        if ((rc = res_ln_rows(e->ybuf, e->x0, L.g1, L.be1, eps, e->x1, e->aq, e->as, T, H, st))) return rc;
+        if ((rc = gemm_pp_mx(PP_EPI_GELU_MX, e->aq, e->as, L.q1, 1, L.s1, L.b1, e->hq, e->hs, T, F, H, st))) return rc;
+        if ((rc = gemm_pp_mx(PP_EPI_F32, e->hq, e->hs, L.q2, 1, L.s2, L.b2, e->ybuf, nullptr, T, H, F, st))) return rc;
+        return res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, eps, e->x0, e->aq, e->as, T, H, st);
+    }
+
+    // Hidden 768 / 1024 in bf16.  Wide rows: a workgroup cannot own whole 768-feature rows at a 256-token tile, so the O and FFN2
+    // projections write fp32 sums and a row kernel adds the residual and normalises (HBM-bound, 8 B per element)
+    int layer_pp(int l) const {
+        const Layer &L = e->layers[l];
+        const bool pq = e->plan.form[TSIM_ROUTE_QKV] == TSIM_FORM_PP_256_PACKED_W, po = e->plan.form[TSIM_ROUTE_O] == TSIM_FORM_PP_RES_LN_PACKED_W;
+        int rc;
+        if ((rc = gemm_pp(PP_EPI_BIAS, e->x0, pq ? L.pqkv : L.wqkv, pq, L.bqkv, e->qkv, T, 3 * H, H, st)) || (rc = attention())) return rc;
+        if ((rc = gemm_pp(PP_EPI_F32, e->ctx, po ? L.po : L.wo, po, L.bo, e->ybuf, T, H, H, st))) return rc;
+        if ((rc = res_ln_rows(e->ybuf, e->x0, L.g1, L.be1, eps, e->x1, nullptr, nullptr, T, H, st)) || (rc = ffn1_rowmajor(L))) return rc;
+        if ((rc = gemm_pp(PP_EPI_F32, e->h1, L.w2, 0, L.b2, e->ybuf, T, H, F, st))) return rc;
+        return res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, eps, e->x0, nullptr, nullptr, T, H, st);
+    }
+
+    // Hidden 384, both families.  chain > 0 (packed family only): the O-projection's launch runs FFN1 too, and FFN2's the next
+    // layer's QKV; the rows behind the whole blocks go first (their LayerNorm launches as ever), the projection's items of those
+    // rows are shared out.
+    int layer_384(int l) const {
+        const Layer &L = e->layers[l];
+        const bool pk = e->plan.family == TSIM_FAMILY_H384_PACKED, last = l + 1 == e->cfg.num_layers, chain_qkv = chain > 0 && !last;
+        // The residual stream is block-packed between the layers of the packed family (group_off): x1 always, x0 except as the
+        // embedding kernel leaves it (layer 0 reads it row-major) and as the last layer leaves it (pooling, heads and the
+        // last_hidden copy read it row-major).
+        const Layout packed = pk ? BLOCK_PACKED : ROW_MAJOR, x0_in = pk && l > 0 ? BLOCK_PACKED : ROW_MAJOR, x0_out = pk && !last ? BLOCK_PACKED : ROW_MAJOR;
+        int rc;
+        if (chain > 0 && l > 0) rc = TSIM_OK;   // the previous layer's FFN2 launch has written this layer's qkv
+        else if (!pk) rc = gemm_xres2<EPI_BIAS, false, false>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
+        else if (x0_in == BLOCK_PACKED) rc = gemm_xres2<EPI_BIAS, true, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
+        else rc = gemm_xres2<EPI_BIAS, true, false>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
+        if (rc || (rc = attention())) return rc;
+        const LnGemm o = {e->ctx, L.wo, L.lo, L.lo32, L.bo, e->x0, L.g1, L.be1, eps, e->x1, H, {ROW_MAJOR, x0_in, packed}};
+        if ((rc = ln384_gemm(o, T, chain > 0, e->lnimg, st))) return rc;
+        if (chain > 0) rc = ln_rows_xres2<EPI_GELU>(o, chain, L.w1, L.b1, e->h1, T, F, st);
+        else rc = pk ? gemm_xres2<EPI_GELU, true, true>(e->x1, L.w1, L.b1, e->h1, T, F, st) : ffn1_rowmajor(L);
+        if (rc) return rc;
+        const LnGemm f2 = {e->h1, L.w2, L.l2, L.l232, L.b2, e->x1, L.g2, L.be2, eps, e->x0, F, {packed, packed, x0_out}};
+        if ((rc = ln384_gemm(f2, T, chain_qkv, e->lnimg, st)) || !chain_qkv) return rc;
+        return ln_rows_xres2<EPI_BIAS>(f2, chain, e->layers[l + 1].wqkv, e->layers[l + 1].bqkv, e->qkv, T, 3 * H, st);
+    }
+
+    int layer_h64(int l) const {   // hidden 64: gemm_bf16's 128-token tiles throughout
+        const Layer &L = e->layers[l];
+        int rc;
+        if ((rc = launch_gemm<128, 64, 64, 2, 2, EPI_BIAS>(e->x0, L.wqkv, L.bqkv, nullptr, nullptr, nullptr, 0.f, e->qkv, T, 3 * H, H, st, nullptr, ALL_ROW_MAJOR))) return rc;
+        if ((rc = attention()) || (rc = launch_gemm<128, 64, 64, 4, 2, EPI_RES_LN>(e->ctx, L.wo, L.bo, e->x0, L.g1, L.be1, eps, e->x1, T, H, H, st, nullptr, ALL_ROW_MAJOR))) return rc;
+        if ((rc = ffn1_rowmajor(L))) return rc;
+        return launch_gemm<128, 64, 64, 4, 2, EPI_RES_LN>(e->h1, L.w2, L.b2, e->x1, L.g2, L.be2, eps, e->x0, T, H, F, st, nullptr, ALL_ROW_MAJOR);
+    }
+};
+
+// pool_packed_kernel<NP, MODE, NORM> over the final hidden state (x0): NP by the width, MODE = TSIM_POOL_*, NORM = Normalize fused
+static int pool_rows(const tsim_encoder *e, const int32_t *cu_seqlens, int B, int mode, bool norm, float *px, unit_t *pu, int ld_unit,
+                     float *unit_rho_max, hipStream_t st) {
+    const int H = e->cfg.hidden;
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, e->x0, cu_seqlens, B, H, px, pu, ld_unit, pu ? unit_rho_max : nullptr);
+    };
+    auto by_width = [&](auto m, auto n) {
+        H <= 512 ? launch(pool_packed_kernel<1, decltype(m)::value, decltype(n)::value>) : launch(pool_packed_kernel<2, decltype(m)::value, decltype(n)::value>);
+    };
+    auto by_mode = [&](auto n) {
+        mode == TSIM_POOL_MEAN ? by_width(int_c<TSIM_POOL_MEAN>{}, n) : mode == TSIM_POOL_CLS ? by_width(int_c<TSIM_POOL_CLS>{}, n)
+        : mode == TSIM_POOL_MAX ? by_width(int_c<TSIM_POOL_MAX>{}, n) : by_width(int_c<TSIM_POOL_MEAN_SQRT_LEN>{}, n);
+    };
+    norm ? by_mode(std::true_type{}) : by_mode(std::false_type{});
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+// Sequence-classification logits from the CLS rows of the final hidden state (x0); sequences without tokens read zeros
+static int cls_head(const tsim_encoder *e, const int32_t *cu_seqlens, int B, float *logits_f32, hipStream_t st) {
+    const int H = e->cfg.hidden;
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((B + CLS_ROWS - 1) / CLS_ROWS)), dim3((unsigned)H), 0, st, e->x0, cu_seqlens, B, H, e->head_wpT,
+                           e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32);
+    };
+    if (e->head_act == TSIM_ACT_RELU) H <= CLS_MAX_H ? launch(cls_head_wide_kernel<CLS_MAX_H, TSIM_ACT_RELU>) : launch(cls_head_wide_kernel<CLS_WIDE_H, TSIM_ACT_RELU>);
+    else H <= CLS_MAX_H ? launch(cls_head_kernel) : launch(cls_head_wide_kernel<CLS_WIDE_H, TSIM_ACT_TANH>);
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
 }
 
 }  // namespace tsim
@@ -2397,28 +2503,31 @@ extern "C" int tsim_chain_items_host(int blocks, int rem_blocks, int ntiles, int
     return p.n;
 }
 
+extern "C" int tsim_encoder_route_host(const tsim_encoder_config *cfg, int32_t T, int32_t layer, tsim_encoder_route *out) {
+    TSIM_REQUIRE(cfg && out, "encoder_route_host: null pointer");
+    TSIM_REQUIRE(T >= 0 && layer >= 0 && layer < cfg->num_layers, "encoder_route_host: T=%d layer=%d of %d", T, layer, cfg->num_layers);
+    if (int rc = encoder_plan(*cfg, out)) return rc;
+    out->chain_blocks = chain_blocks(*out, cfg->ffn, T);
+    out->qkv_chained = out->chain_blocks > 0 && layer > 0;
+    if (out->form[TSIM_ROUTE_O] == TSIM_FORM_LN384) {   // (as layer_384 asks for them)
+        out->n_seg[0] = ln384_segments(T, cfg->hidden, out->chain_blocks > 0, out->seg[0]);
+        out->n_seg[1] = ln384_segments(T, cfg->ffn, out->chain_blocks > 0 && layer + 1 < cfg->num_layers, out->seg[1]);
+    }
+    return TSIM_OK;
+}
+
 extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_encoder_weights_host *w,
                                    tsim_encoder **out) {
     TSIM_REQUIRE(cfg && w && out, "encoder_create: null pointer");
+    EncoderPlan plan;
+    if (int rc = encoder_plan(*cfg, &plan)) return rc;
     const int H = cfg->hidden, F = cfg->ffn, L = cfg->num_layers;
-    TSIM_REQUIRE(H == 64 || H == 384 || H == 768 || H == 1024, "encoder_create: hidden=%d unsupported (64, 384, 768, 1024)", H);
-    TSIM_REQUIRE(cfg->heads > 0 && H % cfg->heads == 0, "encoder_create: heads=%d does not divide hidden=%d", cfg->heads, H);
-    const int dh = H / cfg->heads;
-    TSIM_REQUIRE(dh == 16 || dh == 32 || dh == 64, "encoder_create: head_dim=%d unsupported (16, 32, 64)", dh);
-    TSIM_REQUIRE(F > 0 && F % 64 == 0 && L > 0 && cfg->max_tokens > 0 && cfg->max_seqs > 0, "encoder_create: bad ffn/layers/capacity");
-    // FFN2 runs with K = ffn: the hidden-384 LayerNorm GEMM of large batches (ln_rows_gemm) needs three 32-wide k-tiles, the
-    // ping-pong GEMM of hidden 768 / 1024 two 64-wide ones, and hidden 1024 has no other FFN2 kernel
-    if (H != 64 && F < 128)
-        return fail(TSIM_EUNSUPPORTED, "encoder_create: ffn=%d unsupported at hidden=%d (a multiple of 64, at least 128)", F, H);
-    TSIM_REQUIRE(cfg->arch == TSIM_ARCH_BERT || cfg->arch == TSIM_ARCH_MPNET || cfg->arch == TSIM_ARCH_ROBERTA, "encoder_create: unknown arch");
     TSIM_REQUIRE(w->word_emb && w->pos_emb && w->emb_ln_g && w->emb_ln_b && w->layers, "encoder_create: missing weights");
     TSIM_REQUIRE(cfg->arch != TSIM_ARCH_MPNET || w->rel_bias, "encoder_create: MPNet needs rel_bias");
-    const bool mx = cfg->weight_dtype == TSIM_W_MXFP8;
-    TSIM_REQUIRE(cfg->weight_dtype == TSIM_W_BF16 || mx, "encoder_create: unknown weight_dtype %d", cfg->weight_dtype);
-    if (mx && !(gemm_pp_mx_supported(H, H) && gemm_pp_mx_supported(3 * H, H) && gemm_pp_mx_supported(F, H) && gemm_pp_mx_supported(H, F)))
-        return fail(TSIM_EUNSUPPORTED, "encoder_create: MXFP8 projections need hidden and ffn to be multiples of 256 (got %d, %d)", H, F);
+    const bool mx = plan.images & TSIM_IMG_MXFP8;
     tsim_encoder *e = new tsim_encoder();
     e->cfg = *cfg;
+    e->plan = plan;
     e->Tp = (cfg->max_tokens + 127) / 128 * 128 + 128;
     int rc = TSIM_OK;
     auto bail = [&](int code) {
@@ -2465,25 +2574,22 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
             if ((rc = repack(d.qo, H, H, &t))) return bail(rc); d.qo = (uint8_t *)t;
             if ((rc = repack(d.q1, F, H, &t))) return bail(rc); d.q1 = (uint8_t *)t;
             if ((rc = repack(d.q2, H, F, &t))) return bail(rc); d.q2 = (uint8_t *)t;
-        } else if (H >= 512 && H % 256 == 0 && gemm_pp_supported(H, H) && gemm_pp_supported(F, H) && gemm_pp_supported(H, F)) {
+        } else if (plan.images & TSIM_IMG_PP_QKV_O) {
             if ((rc = repack(d.wqkv, 3 * H, H * 2, (void **)&d.pqkv))) return bail(rc);
             if ((rc = repack(d.wo, H, H * 2, (void **)&d.po))) return bail(rc);
         }
-        if (!mx && H == 384 && F % 64 == 0) {   // LayerNorm GEMM (BN = 384, BK = 64): W as contiguous k-tile images
-            if ((rc = dev_alloc(e, (size_t)H * H * 2, (void **)&d.lo))) return bail(rc);
-            if ((rc = dev_alloc(e, (size_t)H * F * 2, (void **)&d.l2))) return bail(rc);
-            hipLaunchKernelGGL(pack_gemm_w_kernel, dim3((unsigned)((H * H / 8 + 255) / 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const uint4 *>(d.wo), reinterpret_cast<uint4 *>(d.lo), 384, 64, H);
-            hipLaunchKernelGGL(pack_gemm_w_kernel, dim3((unsigned)((H * F / 8 + 255) / 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const uint4 *>(d.w2), reinterpret_cast<uint4 *>(d.l2), 384, 64, F);
-            if ((rc = dev_alloc(e, (size_t)H * H * 2, (void **)&d.lo32))) return bail(rc);
-            if ((rc = dev_alloc(e, (size_t)H * F * 2, (void **)&d.l232))) return bail(rc);
-            hipLaunchKernelGGL(pack_frag_w_kernel, dim3((unsigned)((H * H / 8 + 255) / 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const uint4 *>(d.wo), reinterpret_cast<uint4 *>(d.lo32), 384, H);
-            hipLaunchKernelGGL(pack_frag_w_kernel, dim3((unsigned)((H * F / 8 + 255) / 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const uint4 *>(d.w2), reinterpret_cast<uint4 *>(d.l232), 384, F);
-            if (hipGetLastError() != hipSuccess) return bail(fail(TSIM_EHIP, "LayerNorm GEMM weight packing failed"));
-        }
+        // hidden-384 LayerNorm GEMM: the O and FFN2 matrices [H, K] as contiguous k-tile LDS images (BN = 384, BK = 64) ...
+        auto image = [&](auto kern, const bf16_t *src, int K, bf16_t **dst, auto... tile) {
+            const int r2 = dev_alloc(e, (size_t)H * K * 2, (void **)dst);
+            if (!r2) hipLaunchKernelGGL(kern, dim3((unsigned)((H * K / 8 + 255) / 256)), dim3(256), 0, 0, reinterpret_cast<const uint4 *>(src),
+                                        reinterpret_cast<uint4 *>(*dst), tile..., K);
+            return r2;
+        };
+        if ((plan.images & TSIM_IMG_LN_KTILE) && ((rc = image(pack_gemm_w_kernel, d.wo, H, &d.lo, 384, 64)) || (rc = image(pack_gemm_w_kernel, d.w2, F, &d.l2, 384, 64))))
+            return bail(rc);
+        if ((plan.images & TSIM_IMG_LN_FRAG) && ((rc = image(pack_frag_w_kernel, d.wo, H, &d.lo32, 384)) || (rc = image(pack_frag_w_kernel, d.w2, F, &d.l232, 384))))
+            return bail(rc);   // ... and as MFMA fragment images
+        if (hipGetLastError() != hipSuccess) return bail(fail(TSIM_EHIP, "LayerNorm GEMM weight packing failed"));
         std::vector<float> bq(3 * (size_t)H);
         memcpy(bq.data(), lw.bq, H * 4);
         memcpy(bq.data() + H, lw.bk, H * 4);
@@ -2504,11 +2610,11 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
         if ((rc = dev_alloc(e, a.n * 2, (void **)a.p))) return bail(rc);
         if (hipMemset(*a.p, 0, a.n * 2) != hipSuccess) return bail(fail(TSIM_EHIP, "hipMemset failed"));
     }
-    if (H >= 512 && H % 256 == 0 && gemm_pp_supported(H, H)) {
+    if (plan.buffers & TSIM_BUF_YBUF) {
         if ((rc = dev_alloc(e, Tp * H * 4, (void **)&e->ybuf))) return bail(rc);
         if (hipMemset(e->ybuf, 0, Tp * H * 4) != hipSuccess) return bail(fail(TSIM_EHIP, "hipMemset failed"));
     }
-    if (!mx && H == 384 && F % 64 == 0) {   // ln_split's accumulator images: every row block a forward can hand to ln_tail_gemm
+    if (plan.buffers & TSIM_BUF_LNIMG) {   // ln_split's accumulator images: every row block a forward can hand to ln_tail_gemm
         const size_t blocks = (Tp + 31) / 32 < (size_t)LS_MAX_BLOCKS ? (Tp + 31) / 32 : (size_t)LS_MAX_BLOCKS;   // (a forward has T <= max_tokens < Tp rows)
         const size_t bytes = blocks * 4 * 12 * 64 * 16;
         if ((rc = dev_alloc(e, bytes, (void **)&e->lnimg))) return bail(rc);
@@ -2516,7 +2622,7 @@ extern "C" int tsim_encoder_create(const tsim_encoder_config *cfg, const tsim_en
     }
     if ((size_t)cfg->max_seqs * H * 4 > Tp * 3 * H * 2 && (rc = dev_alloc(e, (size_t)cfg->max_seqs * H * 4, (void **)&e->head_x)))
         return bail(rc);
-    if (mx) {
+    if (plan.buffers & TSIM_BUF_MX_ACT) {
         struct { uint8_t **p; size_t n; } qb[] = {{&e->aq, Tp * H}, {&e->as, Tp * H / 32}, {&e->hq, Tp * F}, {&e->hs, Tp * F / 32}};
         for (auto &a : qb) {
             if ((rc = dev_alloc(e, a.n, (void **)a.p))) return bail(rc);
@@ -2636,123 +2742,33 @@ extern "C" int tsim_encoder_forward_ex(tsim_encoder *e, const int32_t *tok_ids, 
     if (B == 0) return TSIM_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const tsim_encoder_config &c = e->cfg;
-    const int H = c.hidden, F = c.ffn, dh = H / c.heads;
-    const bool mx = c.weight_dtype == TSIM_W_MXFP8;
+    const int H = c.hidden;
     int rc;
     if (T > 0) {
-        const unsigned g = (unsigned)((T + 3) / 4);
-        // column of a token inside its sequence: tok_col when given (MPNet), else tok_pos (BERT: position == column)
-        const int32_t *colp = tok_col ? tok_col : tok_pos;
-        const int col_limit = tok_col || c.arch == TSIM_ARCH_BERT ? max_len : c.max_pos;   // MPNet / RoBERTa without tok_col: pos is not a column
-#define EMBED(V) hipLaunchKernelGGL(embed_ln_kernel<V>, dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, nullptr, 0)
-#define EMBED_T(V) hipLaunchKernelGGL((embed_ln_kernel<V, true>), dim3(g), dim3(256), 0, st, tok_ids, tok_pos, e->word, e->pos, e->type0, e->emb_g, e->emb_b, c.ln_eps, T, H, e->x0, c.vocab, c.max_pos, colp, col_limit, e->err_flags, tok_type, e->n_types)
-        if (tok_type) {
-            if (H == 64) EMBED_T(1); else if (H == 384) EMBED_T(6); else if (H == 768) EMBED_T(12); else EMBED_T(16);
-        } else if (H == 64) EMBED(1); else if (H == 384) EMBED(6); else if (H == 768) EMBED(12); else EMBED(16);
-#undef EMBED_T
-#undef EMBED
-        TSIM_HIP_CHECK(hipGetLastError());
-        const float scale = 1.0f / sqrtf((float)dh);
-        const bool rel = c.arch == TSIM_ARCH_MPNET;
-        // qkv and h1 in the block-packed layout (packed_off) when gemm_xres2 produces them: hidden 384, BERT family
-        const bool pk = !mx && !rel && use_packed_layout(H, F);
-        const int32_t *col = rel ? (tok_col ? tok_col : tok_pos) : nullptr;
+        if ((rc = embed_rows(e, tok_ids, tok_type, tok_pos, tok_col, T, max_len, st))) return rc;
         const int qblocks = (max_len + 31) / 32 > 0 ? (max_len + 31) / 32 : 1;
-        const dim3 agrid((unsigned)(((B + 7) / 8) * 8), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks);   // xcd_map = 1
-        bool qkv_chained = false;
+        const Forward f = {e, cu_seqlens, c.arch == TSIM_ARCH_MPNET ? (tok_col ? tok_col : tok_pos) : nullptr, T, B, H, c.ffn, chain_blocks(e->plan, c.ffn, T),
+                           c.ln_eps, dim3((unsigned)(((B + 7) / 8) * 8), (unsigned)((c.heads + 3) / 4), (unsigned)qblocks), st};
         for (int l = 0; l < c.num_layers; ++l) {
-            const tsim_encoder::Layer &L = e->layers[l];
-            // The residual stream is block-packed between the layers of the pk path (group_off): x1 always, x0 except as the
-            // embedding kernel leaves it (layer 0 reads it row-major) and as the last layer leaves it (pooling, heads and the
-            // last_hidden copy read it row-major).
-            const bool x0pk = pk && l > 0, x0pk_next = pk && l + 1 < c.num_layers;
-            if (mx) {   // projections on MXFP8 operands (v_mfma_scale_f32_32x32x64_f8f6f4); x0's image comes fused from the
-                        // previous layer's LayerNorm kernel, for layer 0 from the stand-alone quantiser
-                if (l == 0 && (rc = quant_mx(e->x0, T, H, e->aq, e->as, st))) return rc;
-                if ((rc = gemm_pp_mx(PP_EPI_BIAS, e->aq, e->as, L.qqkv, 1, L.sqkv, L.bqkv, e->qkv, nullptr, T, 3 * H, H, st))) return rc;
-            } else if (pk) {
-                if (!qkv_chained) {   // (chained: the previous layer's FFN2 launch has written this layer's qkv)
-                    rc = x0pk ? gemm_xres2<EPI_BIAS, true, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st)
-                              : gemm_xres2<EPI_BIAS, true>(e->x0, L.wqkv, L.bqkv, e->qkv, T, 3 * H, st);
-                    if (rc) return rc;
-                }
-            } else if ((rc = gemm_plain<EPI_BIAS>(e->x0, L.wqkv, L.pqkv, L.bqkv, e->qkv, T, 3 * H, H, st))) return rc;
-#define ATT(D)                                                                                                 \
-    do {                                                                                                       \
-        if (rel)                                                                                               \
-            hipLaunchKernelGGL((attention_kernel<D, true>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col,  \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
-        else if (pk)                                                                                           \
-            hipLaunchKernelGGL((attention_kernel<D, false, true>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col, \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
-        else                                                                                                   \
-            hipLaunchKernelGGL((attention_kernel<D, false>), agrid, dim3(256), 0, st, e->qkv, cu_seqlens, col, \
-                               e->relb, e->relw, H, c.heads, scale, e->ctx, B, 1);                                         \
-    } while (0)
-            if (dh == 16) ATT(16); else if (dh == 32) ATT(32); else ATT(64);
-#undef ATT
-            TSIM_HIP_CHECK(hipGetLastError());
-            if (mx) {
-                if ((rc = quant_mx(e->ctx, T, H, e->aq, e->as, st))) return rc;
-                if ((rc = gemm_pp_mx(PP_EPI_F32, e->aq, e->as, L.qo, 1, L.so, L.bo, e->ybuf, nullptr, T, H, H, st))) return rc;
-                if ((rc = res_ln_rows(e->ybuf, e->x0, L.g1, L.be1, c.ln_eps, e->x1, e->aq, e->as, T, H, st))) return rc;
-                if ((rc = gemm_pp_mx(PP_EPI_GELU_MX, e->aq, e->as, L.q1, 1, L.s1, L.b1, e->hq, e->hs, T, F, H, st))) return rc;
-                if ((rc = gemm_pp_mx(PP_EPI_F32, e->hq, e->hs, L.q2, 1, L.s2, L.b2, e->ybuf, nullptr, T, H, F, st))) return rc;
-                if ((rc = res_ln_rows(e->ybuf, e->x1, L.g2, L.be2, c.ln_eps, e->x0, e->aq, e->as, T, H, st))) return rc;
-                continue;
+            switch (e->plan.family) {
+                case TSIM_FAMILY_PP_MX: rc = f.layer_mx(l); break;
+                case TSIM_FAMILY_PP: rc = f.layer_pp(l); break;
+                case TSIM_FAMILY_H64: rc = f.layer_h64(l); break;
+                default: rc = f.layer_384(l);
             }
-            // Chained launches (ln_rows_xres2): wherever the LayerNorm GEMM has whole 256-token blocks for ln_rows_gemm, those blocks'
-            // workgroups run the next projection too — O-projection -> FFN1, FFN2 -> the next layer's QKV.  The rows behind the
-            // whole blocks go first (their LayerNorm launches as before), the projection's items of those rows are shared out.
-            // Only whole rounds of 256 blocks are chained: the stand-alone projection always runs on 256 persistent workgroups, and a
-            // chained launch of 128 .. 255 (or 384) blocks would run it on a half-empty round.
-            const int chain_blocks = pk && F <= 1536 && ln_rows_blocks(T) % 256 == 0 ? ln_rows_blocks(T) : 0;
-            if (chain_blocks > 0 && L.lo32) {
-                if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk, true))) return rc;
-                if ((rc = ln_rows_xres2<EPI_GELU>(e->ctx, L.lo32, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, chain_blocks, H, false, x0pk,
-                                                  L.w1, L.b1, e->h1, T, F, st))) return rc;
-            } else {
-                if ((rc = gemm_res_ln(e->ctx, L.wo, L.po, L.bo, e->x0, L.g1, L.be1, c.ln_eps, e->x1, T, H, H, e->ybuf, st, L.lo, L.lo32, false, e->lnimg, x0pk, pk))) return rc;
-                if (pk) {
-                    if ((rc = gemm_xres2<EPI_GELU, true, true>(e->x1, L.w1, L.b1, e->h1, T, F, st))) return rc;
-                } else if ((rc = gemm_plain<EPI_GELU>(e->x1, L.w1, nullptr, L.b1, e->h1, T, F, H, st))) return rc;
-            }
-            qkv_chained = chain_blocks > 0 && L.l232 && x0pk_next;
-            if (qkv_chained) {
-                const tsim_encoder::Layer &Ln = e->layers[l + 1];
-                if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, true, true))) return rc;
-                if ((rc = ln_rows_xres2<EPI_BIAS>(e->h1, L.l232, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, chain_blocks, F, true, true,
-                                                  Ln.wqkv, Ln.bqkv, e->qkv, T, 3 * H, st))) return rc;
-            } else if ((rc = gemm_res_ln(e->h1, L.w2, nullptr, L.b2, e->x1, L.g2, L.be2, c.ln_eps, e->x0, T, H, F, e->ybuf, st, L.l2, L.l232, pk, e->lnimg, pk, x0pk_next))) return rc;
+            if (rc) return rc;
         }
         if (last_hidden_bf16)
             TSIM_HIP_CHECK(hipMemcpyAsync(last_hidden_bf16, e->x0, (size_t)T * H * 2, hipMemcpyDeviceToDevice, st));
     }
     if (pooled_f32 || unit_bf16) {
-        const unsigned g = (unsigned)((B + 3) / 4);
-#define POOL(V) hipLaunchKernelGGL(pool_packed_kernel<V>, dim3(g), dim3(256), 0, st, e->x0, cu_seqlens, B, H, pooled_f32, (unit_t *)unit_bf16, ld_unit, unit_bf16 ? unit_rho_max : nullptr)
         if (H % 8 != 0 || H > 1024 || (unit_bf16 && ld_unit % 8 != 0))
             return fail(TSIM_EUNSUPPORTED, "encoder: pooling needs a hidden size that is a multiple of 8, at most 1024 (got %d)", H);
         if (((uintptr_t)pooled_f32 | (uintptr_t)unit_bf16) & 15)
             return fail(TSIM_EINVAL, "encoder: pooled / unit outputs must be 16-byte aligned");
-        if (H <= 512) POOL(1); else POOL(2);
-#undef POOL
-        TSIM_HIP_CHECK(hipGetLastError());
+        if ((rc = pool_rows(e, cu_seqlens, B, TSIM_POOL_MEAN, false, pooled_f32, (unit_t *)unit_bf16, ld_unit, unit_rho_max, st))) return rc;
     }
-    if (logits_f32) {   // CLS rows straight from the final hidden state (x0); sequences without tokens read zeros
-        const dim3 cgrid((unsigned)((B + CLS_ROWS - 1) / CLS_ROWS)), cblock((unsigned)H);
-#define CLS_WIDE(MAXH, ACT)                                                                                       \
-    hipLaunchKernelGGL((cls_head_wide_kernel<MAXH, ACT>), cgrid, cblock, 0, st, e->x0, cu_seqlens, B, H, e->head_wpT, \
-                       e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32)
-        if (e->head_act == TSIM_ACT_RELU) {
-            if (H <= CLS_MAX_H) CLS_WIDE(CLS_MAX_H, TSIM_ACT_RELU); else CLS_WIDE(CLS_WIDE_H, TSIM_ACT_RELU);
-        } else if (H <= CLS_MAX_H) {
-            hipLaunchKernelGGL(cls_head_kernel, cgrid, cblock, 0, st, e->x0, cu_seqlens,
-                               B, H, e->head_wpT, e->head_bp, e->head_wc, e->head_bc, e->n_labels, logits_f32);
-        } else CLS_WIDE(CLS_WIDE_H, TSIM_ACT_TANH);
-#undef CLS_WIDE
-        TSIM_HIP_CHECK(hipGetLastError());
-    }
+    if (logits_f32) return cls_head(e, cu_seqlens, B, logits_f32, st);
     return TSIM_OK;
 }
 
@@ -2793,16 +2809,7 @@ extern "C" int tsim_encoder_forward_head(tsim_encoder *e, const int32_t *tok_ids
     float *px = d_out ? (e->head_x ? e->head_x : reinterpret_cast<float *>(e->qkv)) : emb_f32;
     unit_t *pu = d_out ? nullptr : static_cast<unit_t *>(unit_f16);
     const bool norm = !d_out && head->normalize;
-    const unsigned g = (unsigned)((B + 3) / 4);
-#define POOL(NP, M, N) hipLaunchKernelGGL((pool_packed_kernel<NP, M, N>), dim3(g), dim3(256), 0, st, e->x0, cu_seqlens, B, H, px, pu, ld_unit, pu ? unit_rho_max : nullptr)
-#define POOL_NP(M, N) do { if (H <= 512) POOL(1, M, N); else POOL(2, M, N); } while (0)
-#define POOL_M(N) do { switch (mode) { case TSIM_POOL_MEAN: POOL_NP(TSIM_POOL_MEAN, N); break; case TSIM_POOL_CLS: POOL_NP(TSIM_POOL_CLS, N); break; \
-                                       case TSIM_POOL_MAX: POOL_NP(TSIM_POOL_MAX, N); break; default: POOL_NP(TSIM_POOL_MEAN_SQRT_LEN, N); } } while (0)
-    if (norm) POOL_M(true); else POOL_M(false);
-#undef POOL_M
-#undef POOL_NP
-#undef POOL
-    TSIM_HIP_CHECK(hipGetLastError());
+    if (int rc = pool_rows(e, cu_seqlens, B, mode, norm, px, pu, ld_unit, unit_rho_max, st)) return rc;
     if (d_out)
         return dense_rows_launch(px, B, H, head->dense_w, head->dense_b, d_out, head->dense_act, head->normalize, emb_f32,
                                  static_cast<unit_t *>(unit_f16), ld_unit, unit_f16 ? unit_rho_max : nullptr, st);

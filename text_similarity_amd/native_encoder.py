@@ -41,6 +41,30 @@ def layer_names(cfg: EncoderConfig, l: int) -> Dict[str, str]:
     return a
 
 
+def config_c(cfg: EncoderConfig, max_tokens: int, max_seqs: int, weight_dtype: str = "bf16") -> "_lib.EncoderConfigC":
+    if cfg.arch not in ("bert", "mpnet") or cfg.pos_offset not in (0, cfg.pad_id + 1) or (cfg.pos_offset and cfg.arch != "bert"):
+        raise ValueError(f"arch {cfg.arch!r} with pos_offset {cfg.pos_offset} (pad_id {cfg.pad_id}): position rows start "
+                         "at 0 (BERT, DistilBERT) or at pad_id + 1 (MPNet, RoBERTa family)")
+    arch = _lib.ARCH_MPNET if cfg.arch == "mpnet" else _lib.ARCH_ROBERTA if cfg.pos_offset else _lib.ARCH_BERT
+    return _lib.EncoderConfigC(arch=arch, num_layers=cfg.num_layers, hidden=cfg.hidden, heads=cfg.heads, ffn=cfg.ffn,
+                               vocab=cfg.vocab, max_pos=cfg.max_pos, pad_id=cfg.pad_id, rel_buckets=cfg.rel_buckets,
+                               ln_eps=cfg.ln_eps, max_tokens=max_tokens, max_seqs=max_seqs,
+                               weight_dtype=_lib.W_MXFP8 if weight_dtype == "mxfp8" else _lib.W_BF16)
+
+
+def encoder_route(cfg: EncoderConfig, tokens: int, layer: int = 0, weight_dtype: str = "bf16") -> SimpleNamespace:
+    """The kernels an encoder of ``cfg`` runs in layer ``layer`` of a forward of ``tokens`` tokens (tsim_encoder_route_host: no
+    GPU, nothing is created): family, form[4] (QKV, O, FFN1, FFN2), images, buffers, chain_blocks, qkv_chained and
+    segments = ([(form, row0, rows), ...] of O, ... of FFN2), in the constants of ``_lib``.  A configuration that
+    ``NativeEncoder`` would refuse raises the same ValueError."""
+    r = _lib.EncoderRouteC()
+    cc = config_c(cfg, max(int(tokens), 1), 1, weight_dtype)
+    _lib.check(_lib.lib().tsim_encoder_route_host(C.byref(cc), int(tokens), int(layer), C.byref(r)), "encoder_route_host")
+    return SimpleNamespace(family=r.family, form=list(r.form), images=r.images, buffers=r.buffers, chain_blocks=r.chain_blocks,
+                           qkv_chained=bool(r.qkv_chained),
+                           segments=tuple([(s.form, s.row0, s.rows) for s in r.seg[i][:r.n_seg[i]]] for i in range(2)))
+
+
 class SentenceHead:
     """What the native forward runs after the last layer instead of the mean pool (include/tsim.h tsim_sentence_head):
     a pooling mode ('mean' | 'cls' | 'max' | 'mean_sqrt_len'), an optional Dense (``dense_w`` [d_out, hidden] and
@@ -120,16 +144,7 @@ class NativeEncoder:
         if cfg.arch == "mpnet":
             ew.rel_bias = _ptr(w["encoder.relative_attention_bias.weight"])
         ew.layers = layers
-        if cfg.arch not in ("bert", "mpnet") or cfg.pos_offset not in (0, cfg.pad_id + 1) or (cfg.pos_offset and cfg.arch != "bert"):
-            raise ValueError(f"arch {cfg.arch!r} with pos_offset {cfg.pos_offset} (pad_id {cfg.pad_id}): position rows start "
-                             "at 0 (BERT, DistilBERT) or at pad_id + 1 (MPNet, RoBERTa family)")
-        arch = _lib.ARCH_MPNET if cfg.arch == "mpnet" else _lib.ARCH_ROBERTA if cfg.pos_offset else _lib.ARCH_BERT
-        cc = _lib.EncoderConfigC(arch=arch,
-                                 num_layers=cfg.num_layers, hidden=cfg.hidden, heads=cfg.heads, ffn=cfg.ffn,
-                                 vocab=cfg.vocab, max_pos=cfg.max_pos, pad_id=cfg.pad_id,
-                                 rel_buckets=cfg.rel_buckets, ln_eps=cfg.ln_eps, max_tokens=self.max_tokens,
-                                 max_seqs=self.max_seqs,
-                                 weight_dtype=_lib.W_MXFP8 if weight_dtype == "mxfp8" else _lib.W_BF16)
+        cc = config_c(cfg, self.max_tokens, self.max_seqs, weight_dtype)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().tsim_encoder_create(C.byref(cc), C.byref(ew), C.byref(handle)), "encoder_create")
