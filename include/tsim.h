@@ -467,6 +467,43 @@ int tsim_int8_rescore_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, cons
                            int32_t *out_status, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Product quantisation (PQ): a learned 8-bit code per sub-vector, scored against the FLOAT query by table lookups (asymmetric
+ * distance computation, ADC; faiss' `IndexPQ` with nbits = 8).  The float query is never quantised.
+ * Codebooks.  codebooks [M, 256, dsub] float32 contiguous on the device, dsub = d / M, finite (not checked here): 1 <= d <= 1024,
+ * 1 <= M <= 64, d % M == 0 and dsub <= 64 (else TSIM_EINVAL).
+ * Codes.  A code row is M bytes, byte m the centroid number of sub-vector m.  Rows lie tsim_pq_code_bytes(M) bytes apart — M rounded
+ * up to a multiple of 16 (0 for an M outside 1..64) — or further: ldc and ld_code are in BYTES, multiples of 16 and
+ * >= tsim_pq_code_bytes(M), and the rows start on a 16-byte boundary (else TSIM_EINVAL).  The bytes from M to tsim_pq_code_bytes(M)
+ * are zero in everything the library writes; what it READS may hold anything there: they are never used as sub-quantisers.
+ * tsim_pq_encode_rows: x [rows, d] float32 (TSIM_F32) or bf16 (TSIM_BF16), row stride ld_in >= d elements -> codes, the first
+ * tsim_pq_code_bytes(M) bytes of each row.  Per sub-vector, dist_j in float64: dist = 0, then for i = 0 .. dsub - 1 in that order
+ * t = (double)x_i - (double)c_ji, p = t t, dist = dist + p — each one rounded IEEE operation, no FMA.  The code is the first j with
+ * dist_j < best, best = +inf at the start: ties go to the lower j; a sub-vector holding a NaN or an infinity gets code 0.
+ * tsim_pq_tables: per query of eq_f32 [Q, d] (row stride ldq_f32 >= d) the INTEGER lookup table.  L[m][j] in float64 by the same
+ * ordered, uncontracted operations: space TSIM_SPACE_DOT sum_i q_i c_ji, TSIM_SPACE_L2 -dist as above (other spaces: TSIM_EINVAL).
+ * A = max |L| over the query's table; A zero, NaN or infinite: the table is all zero and e = 0.  Otherwise with A < 2^x
+ * (x = ilogb(A) + 1): e = 23 - ceil(log2 M) - x and T[m][j] = (int32) rint(L[m][j] 2^e), half to even.  tables [Q, M, 256] int32
+ * (16-byte aligned), exps [Q] int32 = e.  Then sum_m max_j |T[m][j]| <= 2^23 + M / 2 < 2^24.  Q == 0 is legal.
+ * tsim_pq_adc_topk: score(q, r) = sum_m tables[q][m][code_r[m]], an int32 independent of the order of the additions (tables whose
+ * sum_m max_j |T| exceeds 2^24 are outside the contract: the running lists carry scores as float32).  TSIM_SPACE_DOT: the top k by
+ * (score desc, row asc), out_val [Q, k] int32 = score, N < k padded with (INT32_MIN, -1).  TSIM_SPACE_L2 (scores <= 0): ordered by
+ * (-score asc, row asc), out_val = -score, padded with (INT32_MAX, -1).  out_idx [Q, k] int64 = row + idx_offset; N == 0 is legal
+ * (c_codes may be NULL then).  The value v of query q stands for the float v 2^-exps[q].  1 <= k <= TSIM_TOPK_MAX_K, N < 2^31 - 64,
+ * Q <= 65535 per call.  A workgroup serves one query and one chunk of rows: it copies the query's table into LDS (M KiB), every
+ * lane loads a code row once with 16-byte loads and sums M LDS lookups; a running sorted list per (chunk of rows, query), one
+ * merge workgroup per query.  workspace: tsim_pq_adc_topk_workspace_bytes(Q, N, M, k) — pure host, 0 for Q <= 0, N < 0, M outside 1..64
+ * or k outside 1..TSIM_TOPK_MAX_K, non-decreasing in Q, N and k, never above 64 MiB + what one list per query takes; it does not
+ * hold the tables, which are the caller's (Q M KiB: callers slice large query sets).  The call reads nothing back from the device. */
+int tsim_pq_code_bytes(int M);
+int tsim_pq_encode_rows(const void *x, int x_dtype, int64_t rows, int d, int64_t ld_in, const float *codebooks, int M, uint8_t *codes,
+                        int64_t ld_code, void *stream);
+int tsim_pq_tables(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *codebooks, int d, int M, int32_t *tables,
+                   int32_t *exps, void *stream);
+size_t tsim_pq_adc_topk_workspace_bytes(int64_t Q, int64_t N, int M, int k);
+int tsim_pq_adc_topk(int space, const int32_t *tables, int64_t Q, const uint8_t *c_codes, int64_t ldc, int64_t N, int M, int k,
+                     int32_t *out_val, int64_t *out_idx, int64_t idx_offset, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Inverted-file (IVF) scan: the best k of each query among the rows of the LISTS it probes (faiss' `IndexIVFFlat` after its coarse
  * quantiser; what makes one query cheaper than a pass over the corpus).  rows_f32 [N, d] float32, row stride ld_rows >= d, holds
  * the rows in LIST order: list l is rows [list_off[l], list_off[l+1]), list_off int64 [nlist+1].  row_ids int32 [N] gives, for each

@@ -792,6 +792,220 @@ def int8_rescore_topk(eq_f32: torch.Tensor, c_codes: torch.Tensor, d: int, cand:
                          return_status)
 
 
+# ------------------------------------------------------------------------------------------------- product quantisation
+PQ_MAX_M = 64                   # include/tsim.h: 1 <= M <= 64 sub-quantisers of 256 centroids, d % M == 0, d / M <= 64
+PQ_MAX_DSUB = 64
+PQ_SPACES = {"ip": _lib.SPACE_DOT, "l2": _lib.SPACE_L2}
+PQ_TABLE_BUDGET = 64 << 20      # int32 tables of one call (M KiB a query): larger query sets are searched in slices
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def pq_code_bytes(M: int) -> int:
+    """Bytes between the rows of a [rows, pq_code_bytes(M)] uint8 PQ code matrix: M rounded up to a multiple of 16."""
+    b = _lib.lib().tsim_pq_code_bytes(int(M))
+    if b == 0:
+        raise ValueError(f"PQ codes take 1 <= M <= {PQ_MAX_M}, got M={M}")
+    return b
+
+
+_PQ_ROWS = dict(dtype=torch.uint8, width_fn=pq_code_bytes, made_by="pq_encode_rows / pq_codes_from_numpy")
+
+
+def _check_codebooks(what, codebooks, dev, d=None, trusted=False):
+    """float32 [M, 256, dsub] contiguous and finite on ``dev`` -> (codebooks, d, M).  ``trusted``: the caller (GpuPQIndex) has
+    checked these codebooks for finiteness where they entered, so the search path does not read the device back."""
+    if not isinstance(codebooks, torch.Tensor):
+        codebooks = torch.as_tensor(np.asarray(codebooks, dtype=np.float32))
+    if codebooks.dim() != 3 or codebooks.shape[1] != 256 or not codebooks.dtype.is_floating_point:
+        raise ValueError(f"{what}: codebooks must be float [M, 256, dsub], got {codebooks.dtype} {tuple(codebooks.shape)}")
+    M, dsub = codebooks.shape[0], codebooks.shape[2]
+    if not (1 <= M <= PQ_MAX_M and 1 <= dsub <= PQ_MAX_DSUB and M * dsub <= MAX_CODE_DIM):
+        raise ValueError(f"{what}: codebooks [M={M}, 256, dsub={dsub}] need 1 <= M <= {PQ_MAX_M}, dsub <= {PQ_MAX_DSUB} and "
+                         f"M dsub <= {MAX_CODE_DIM}")
+    if d is not None and M * dsub != d:
+        raise ValueError(f"{what}: rows of width {d} against codebooks for width {M * dsub}")
+    if not codebooks.is_cuda:
+        _need_gpu(codebooks)
+    if dev is not None and codebooks.device != dev:
+        raise ValueError(f"{what}: operands on different devices ({dev} vs {codebooks.device})")
+    codebooks = codebooks.to(torch.float32).contiguous()
+    if not trusted and not bool(torch.isfinite(codebooks).all()):
+        raise ValueError(f"{what}: codebooks must be finite")
+    return codebooks, M * dsub, M
+
+
+def _pq_space(what, space):
+    if space not in PQ_SPACES:
+        raise ValueError(f"{what}: space must be 'ip' or 'l2', got {space!r}")
+    return PQ_SPACES[space]
+
+
+def pq_encode_rows(x: torch.Tensor, codebooks, out: Optional[torch.Tensor] = None, _trusted: bool = False) -> torch.Tensor:
+    """[rows, d] float32/bf16 -> uint8 [rows, pq_code_bytes(M)]: byte m of a row is the number of the centroid of
+    ``codebooks`` [M, 256, d / M] nearest to the row's sub-vector m, zero from byte M on.  The squared distance is summed in
+    float64 in element order without FMA; ties go to the lower centroid number and a sub-vector holding a NaN or an infinity
+    gets code 0.  Strided row views are read in place.  ``out``: a uint8 [rows, >= pq_code_bytes(M)] tensor (or row view, stride
+    a multiple of 16) whose first pq_code_bytes(M) columns are written."""
+    what = "pq_encode_rows"
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise ValueError(f"{what} expects a 2-D tensor")
+    if not x.dtype.is_floating_point:
+        raise ValueError(f"{what} expects float rows, got {x.dtype}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    rows, d = x.shape
+    codebooks, _, M = _check_codebooks(what, codebooks, x.device, d, _trusted)
+    cb = pq_code_bytes(M)
+    if out is None:
+        out = torch.empty((rows, cb), dtype=torch.uint8, device=x.device)
+        ld = cb
+    else:
+        ld = _check_code_rows(what, "out", out, M, x.device, **_PQ_ROWS)
+        if out.shape[0] != rows:
+            raise ValueError(f"{what}: out has {out.shape[0]} rows, x {rows}")
+    dt = _lib.TSIM_F32 if x.dtype == torch.float32 else _lib.TSIM_BF16
+    if rows:
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().tsim_pq_encode_rows(x.data_ptr(), dt, rows, d, _row_stride(x), codebooks.data_ptr(), M, out.data_ptr(),
+                                                      ld, _stream(x)), what)
+    return out
+
+
+def pq_codes_from_numpy(a, M: int, device=None) -> torch.Tensor:
+    """A ``[rows, M]`` uint8 array or tensor of centroid numbers (faiss' ``ProductQuantizer.compute_codes`` with nbits = 8) -> the
+    padded device layout uint8 [rows, pq_code_bytes(M)], zero from column M on.  A numpy array goes to ``device`` (default: the
+    current one)."""
+    cb = pq_code_bytes(M)
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.uint8:
+            raise ValueError(f"pq_codes_from_numpy: expected uint8 [rows, {M}], got {a.dtype} {a.shape}")
+        a = torch.from_numpy(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+    _need_gpu(a)
+    if a.dtype != torch.uint8 or a.dim() != 2 or a.shape[1] != int(M):
+        raise ValueError(f"pq_codes_from_numpy: expected uint8 [rows, {M}], got {a.dtype} {tuple(a.shape)}")
+    out = torch.zeros((a.shape[0], cb), dtype=torch.uint8, device=a.device)
+    out[:, :int(M)] = a
+    return out
+
+
+def pq_decode_rows(codes: torch.Tensor, codebooks) -> torch.Tensor:
+    """uint8 [rows, >= M] codes -> float32 [rows, d]: every sub-vector replaced by its centroid (a gather, no kernel of ours)."""
+    _need_gpu(codes)
+    codebooks, d, M = _check_codebooks("pq_decode_rows", codebooks, codes.device)
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] < M:
+        raise ValueError(f"pq_decode_rows: codes must be uint8 [rows, >= {M}], got {codes.dtype} {tuple(codes.shape)}")
+    sub = torch.arange(M, device=codes.device)
+    return codebooks[sub, codes[:, :M].long()].reshape(codes.shape[0], d)
+
+
+def _pq_queries(what, eq_f32, d):
+    _need_gpu(eq_f32)
+    if eq_f32.dtype != torch.float32 or eq_f32.dim() != 2 or eq_f32.shape[1] != d or eq_f32.stride(1) != 1:
+        raise ValueError(f"{what}: eq_f32 must be float32 [Q, {d}] with unit inner stride")
+    if eq_f32.shape[0] > 1 and eq_f32.stride(0) < d:
+        eq_f32 = eq_f32.contiguous()
+    return eq_f32
+
+
+def pq_tables(eq_f32: torch.Tensor, codebooks, space: str, _trusted: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The integer lookup tables of every query: (tables int32 [Q, M, 256], exps int32 [Q]).  L[m][j] in float64 is the inner
+    product of the query's sub-vector m with centroid j (``space="ip"``) or minus their squared distance (``"l2"``);
+    tables = rint(L 2^e) with e = 23 - ceil(log2 M) - (ilogb(max |L|) + 1) per query, so that every sum of M entries is an exact
+    int32 below 2^24.  A query whose table holds a NaN or an infinity, or nothing but zeros, gets a zero table and e = 0."""
+    what = "pq_tables"
+    sp = _pq_space(what, space)
+    _need_gpu(eq_f32)
+    codebooks, d, M = _check_codebooks(what, codebooks, eq_f32.device, None, _trusted)
+    eq_f32 = _pq_queries(what, eq_f32, d)
+    Q = eq_f32.shape[0]
+    tables = torch.empty((Q, M, 256), dtype=torch.int32, device=eq_f32.device)
+    exps = torch.empty((Q,), dtype=torch.int32, device=eq_f32.device)
+    if Q:
+        with torch.cuda.device(eq_f32.device):
+            _lib.check(_lib.lib().tsim_pq_tables(sp, eq_f32.data_ptr(), _row_stride(eq_f32), Q, codebooks.data_ptr(), d, M,
+                                                 tables.data_ptr(), exps.data_ptr(), _stream(eq_f32)), what)
+    return tables, exps
+
+
+def pq_adc_topk_tables(tables: torch.Tensor, codes: torch.Tensor, k: int, space: str = "ip", idx_offset: int = 0):
+    """The scan on its own: ``tables`` int32 [Q, M, 256] contiguous (from :func:`pq_tables`, or any whose per-query
+    sum_m max_j |T[m][j]| stays within 2^24) against ``codes`` -> (value int32 [Q, k], idx int64 [Q, k]).  value = sum_m
+    tables[q][m][codes[r][m]]: "ip" ordered by (value desc, row asc), padded with (-2**31, -1); "l2" (tables <= 0) returns
+    -sum ordered by (value asc, row asc), padded with (2**31 - 1, -1)."""
+    what = "pq_adc_topk"
+    sp = _pq_space(what, space)
+    _need_gpu(tables, codes)
+    if tables.dtype != torch.int32 or tables.dim() != 3 or tables.shape[2] != 256 or not tables.is_contiguous():
+        raise ValueError(f"{what}: tables must be contiguous int32 [Q, M, 256]")
+    Q, M = tables.shape[0], tables.shape[1]
+    ldc = _check_code_rows(what, "codes", codes, M, tables.device, **_PQ_ROWS)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    N = codes.shape[0]
+    val = torch.empty((Q, k), dtype=torch.int32, device=tables.device)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=tables.device)
+    if Q == 0:
+        return val, idx
+    L = _lib.lib()
+    with torch.cuda.device(tables.device):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_pq_adc_topk_workspace_bytes(step, N, M, k)
+        if nbytes == 0:
+            raise ValueError(f"{what}: unsupported shape Q={Q} N={N} M={M} k={k}")
+        ws = _workspace(tables.device, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = L.tsim_pq_adc_topk(sp, tables.data_ptr() + q0 * M * 1024, nq, codes.data_ptr() if N else 0, ldc, N, M, k,
+                                    val.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset, ws.data_ptr(), ws.numel(),
+                                    _stream(tables))
+            _lib.check(rc, what)
+    return val, idx
+
+
+def pq_values_to_float(val: torch.Tensor, exps: torch.Tensor, space: str) -> torch.Tensor:
+    """int32 values of :func:`pq_adc_topk_tables` and the queries' exponents -> float32(float64(v) 2^-e); padding becomes -inf
+    ("ip") or +inf ("l2")."""
+    pad, inf = (INT32_MIN, float("-inf")) if space == "ip" else (INT32_MAX, float("inf"))
+    scale = ((1023 - exps.to(torch.int64)) << 52).view(torch.float64)     # 2^-e exactly: it need not be a float32
+    f = (val.to(torch.float64) * scale[:, None]).to(torch.float32)
+    return torch.where(val == pad, torch.full_like(f, inf), f)
+
+
+def pq_adc_topk(eq_f32: torch.Tensor, codebooks, codes: torch.Tensor, k: int, space: str = "ip", idx_offset: int = 0,
+                raw: bool = False, _trusted: bool = False):
+    """Exact ADC top-k of float queries against PQ codes: (scores float32 [Q, k], idx int64 [Q, k]).  The score of a row is the
+    sum of the M integer table entries its code bytes select (:func:`pq_tables`), turned back into float32(float64(v) 2^-e):
+    the inner product of the query with the row's reconstruction ("ip", ordered by (score desc, row asc), padded with
+    (-inf, -1)) or their squared distance ("l2", ordered by (distance asc, row asc), padded with (+inf, -1)), each within
+    2^-18 or so of the table's largest entry.  The order is exact for the integer scores.  ``raw=True`` returns
+    (value int32 [Q, k], idx, exps int32 [Q]) instead.  ``codes``: uint8 from :func:`pq_encode_rows` or
+    :func:`pq_codes_from_numpy` (row views with a stride that is a multiple of 16 bytes are read in place; bytes at positions
+    >= M are ignored).  Tables are built for PQ_TABLE_BUDGET bytes of queries at a time.
+
+    To refine, keep the float rows and re-score the returned ``idx`` with ``ops.dot_list_topk`` / ``ops.l2_list_topk`` /
+    ``ops.cosine_list_topk(eq_f32, ec_f32, cand)``: they take a first stage's candidates as they stand."""
+    what = "pq_adc_topk"
+    _pq_space(what, space)
+    _need_gpu(eq_f32, codes)
+    codebooks, d, M = _check_codebooks(what, codebooks, eq_f32.device, None, _trusted)
+    eq_f32 = _pq_queries(what, eq_f32, d)
+    Q = eq_f32.shape[0]
+    step = max(1, min(MAX_QUERIES_PER_CALL, PQ_TABLE_BUDGET // (M * 1024)))
+    vals, idxs, exps = [], [], []
+    for q0 in range(0, max(Q, 1), step):
+        tables, e = pq_tables(eq_f32[q0:q0 + step], codebooks, space, _trusted=True)
+        v, i = pq_adc_topk_tables(tables, codes, k, space, idx_offset)
+        vals.append(v), idxs.append(i), exps.append(e)
+    val, idx, exp = (torch.cat(t) if len(t) > 1 else t[0] for t in (vals, idxs, exps))
+    if raw:
+        return val, idx, exp
+    return pq_values_to_float(val, exp, space), idx
+
+
 # ------------------------------------------------------------------------------------------------- exact range search
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins

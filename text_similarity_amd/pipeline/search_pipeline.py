@@ -25,6 +25,7 @@ import os
 from .. import ops
 from ..index import GpuFlatIndex
 from ..ivf_index import GpuIVFIndex
+from ..pq_index import GpuPQIndex
 
 
 SCORE_FUNCTIONS = {"cosine": "cosine", "dot": "dot", "dot_product": "dot"}
@@ -246,10 +247,12 @@ class SemanticSearchPipeline(SearchPipeline):
     ``max_num_results`` up to 1024 (the reference's bound is ``ef`` = 50, search_pipeline.py:131); width <= 768.
     ``score_function='dot'`` keeps an inner-product index (``GpuFlatIndex(space='ip')``); an index file of the other space
     at ``index_path`` raises ``ValueError``.  ``index_type='ivf'`` (with ``nlist=``, ``nprobe=``) keeps a
-    :class:`text_similarity_amd.ivf_index.GpuIVFIndex` instead: approximate, exact within the lists it probes."""
+    :class:`text_similarity_amd.ivf_index.GpuIVFIndex` instead: approximate, exact within the lists it probes.
+    ``index_type='pq'`` (with ``pq_m=``) keeps a :class:`text_similarity_amd.pq_index.GpuPQIndex`, trained on the corpus embeddings
+    when the index is built: ``pq_m`` bytes a row, any width up to 1024, no filters and no removal."""
 
     def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat", nlist: int = 1024,
-                 nprobe: int = 8, **kwargs):
+                 nprobe: int = 8, pq_m: int = 8, **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
         self.score_function = resolve_score_function(score_function, self.model)
@@ -259,9 +262,12 @@ class SemanticSearchPipeline(SearchPipeline):
             self.index = GpuFlatIndex(space=space, dim=hidden, device=self.params.device)
         elif index_type == "ivf":   # approximate: each query is scored against the nprobe of nlist lists nearest to it
             self.index = GpuIVFIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, device=self.params.device)
+        elif index_type == "pq":    # approximate: rows are replaced by pq_m learned bytes
+            self.index = GpuPQIndex(space=space, dim=hidden, M=pq_m, device=self.params.device)
         else:
-            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf'")
-        if os.path.exists(os.path.join(self.index_path, "index.bin")):
+            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq'")
+        self.index_type = index_type
+        if os.path.exists(os.path.join(self.index_path, getattr(self.index, "_FILE_NAME", "index.bin"))):
             self.index.load_index(self.index_path)
         else:
             self._index(self.corpus)
@@ -269,6 +275,11 @@ class SemanticSearchPipeline(SearchPipeline):
     def _index(self, corpus):
         os.makedirs(self.index_path, exist_ok=True)
         corpus_embeddings = self.encode_corpus(corpus)
+        if self.index_type == "pq":
+            self.index.train(corpus_embeddings)
+            self.index.add_items(corpus_embeddings, list(range(corpus_embeddings.shape[0])))
+            self.index.save_index(self.index_path)
+            return
         self.index.init_index(max_elements=len(corpus), ef_construction=getattr(self.params, "ef_construction", 0),
                               M=getattr(self.params, "M", 0))
         self.index.add_items(corpus_embeddings, list(range(corpus_embeddings.shape[0])))
@@ -277,7 +288,11 @@ class SemanticSearchPipeline(SearchPipeline):
 
     def _search(self, queries, max_num_results: int, filter=None):
         query_embeddings = self.encode_corpus(queries)
-        if filter is None:
+        if self.index_type == "pq":
+            if filter is not None:
+                raise NotImplementedError("GpuPQIndex has no filtered search: index_type='flat' does")
+            scores, labels = self.index.search(query_embeddings, max_num_results)
+        elif filter is None:
             labels, scores = self.index.search(query_embeddings, max_num_results)
         else:   # (labels of this index are corpus positions; the forms GpuFlatIndex.search takes)
             labels, scores = self.index.search(query_embeddings, max_num_results, filter=filter)
@@ -295,11 +310,14 @@ class SemanticSearchPipeline(SearchPipeline):
             text = [text]
         embeddings = self.encode_corpus(list(text))
         first = len(self.corpus)
-        self.index.resize_index(self.index.get_current_count() + embeddings.shape[0])
+        if self.index_type != "pq":   # (GpuPQIndex grows on its own)
+            self.index.resize_index(self.index.get_current_count() + embeddings.shape[0])
         self.index.add_items(embeddings, list(range(first, first + embeddings.shape[0])))
         self.corpus = list(self.corpus) + list(text)
 
     def remove_from_index(self, ids):
+        if self.index_type == "pq":
+            raise NotImplementedError("GpuPQIndex has no deletion: index_type='flat' does")
         for id in ids:
             try:
                 self.index.mark_deleted(id)
