@@ -540,6 +540,44 @@ int tsim_ivf_scan_topk(int space, const float *eq_f32, int64_t ldq_f32, int64_t 
                        int64_t max_list_len, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * IVF-PQ: PQ codes in inverted lists, by default of each row's RESIDUAL to its list centroid (faiss' `IndexIVFPQ` with 8-bit
+ * codes).  (d, M) and codebooks as for tsim_pq_*; centroids [nlist, d] float32, row stride ld_cent >= d, finite (not checked);
+ * list_off, row_ids and probes as for tsim_ivf_scan_topk, the code rows in list order, ldc >= tsim_pq_code_bytes(M) bytes apart.
+ * A probes entry < 0 or >= nlist is padding: its table is not written and never read.
+ * Encoding.  A row x of list l has the code tsim_pq_encode_rows gives r, r_i = float32(x_i - c_l,i) (one rounded subtraction),
+ * or x itself when the index does not code residuals; then tsim_pq_tables (one table a query, no bias) serves the scan.
+ * tsim_ivfpq_tables, the tables of residual codes:
+ *   TSIM_SPACE_DOT: tables [Q, M, 256] with L as tsim_pq_tables, and bias [Q, nprobe]: B[j] = sum_{i < d} (double)q_i
+ *     (double)c_{l_j},i in that order, no FMA.  A = max(max |L|, max over valid probes |B|), x = ilogb(A) + 1,
+ *     e = 23 - ceil(log2(M + 1)) - x, T = rint(L 2^e), bias = rint(B 2^e), half to even; the bias of a padding probe is 0.
+ *   TSIM_SPACE_L2: tables [Q nprobe, M, 256], one per (query, probe) pair: L_p[m][j] = -dist(rq_m, c_mj) with
+ *     rq_i = float32(q_i - c_l,i); A = max |L_p| over all valid pairs of the QUERY (one exponent a query),
+ *     e = 23 - ceil(log2 M) - x.  bias may be NULL; when given it is zeroed.
+ *   A query with a NaN or an infinity among these entries, or with A == 0, gets zero tables, zero biases and e = 0.  exps [Q].
+ *   workspace: tsim_ivfpq_tables_workspace_bytes(Q, nprobe) (0 for Q <= 0, nprobe < 1 or Q nprobe >= 2^31 - 1; needed by
+ *   TSIM_SPACE_L2 only).  Q == 0 is legal.
+ * tsim_ivfpq_scan_topk: score(q, r in probe j) = bias[q nprobe + j] (0 when bias is NULL) + sum_m T[m][code_r[m]], T the table of
+ *   pair q nprobe + j (tables_per_pair != 0) or of query q.  |bias| + sum_m max_j |T| must stay below 2^24.  The exact top k over
+ *   the rows of the probed lists: TSIM_SPACE_DOT by (score desc, id asc), out_val = score, padded (INT32_MIN, -1); TSIM_SPACE_L2 by
+ *   (-score asc, id asc), out_val = -score, padded (INT32_MAX, -1); out_idx = row_ids value + idx_offset.  A negative row_ids entry
+ *   is a tombstone (loaded, scored, dropped); list_off and out_status (TSIM_IVF_ST_*) behave as in tsim_ivf_scan_topk, and so does
+ *   the hint max_list_len, with segments of TSIM_IVFPQ_SEG rows.  workspace: tsim_ivfpq_scan_workspace_bytes(Q, nprobe,
+ *   max_list_len, k), 0 for bad arguments, non-decreasing in each.  The calls read nothing back from the device. */
+#ifndef TSIM_IVFPQ_SEG /* (a variant build may set another multiple of 256 to measure it: tools/bench_ivfpq.py --scan-only) */
+#define TSIM_IVFPQ_SEG 4096
+#endif
+size_t tsim_ivfpq_tables_workspace_bytes(int64_t Q, int nprobe);
+int tsim_ivfpq_tables(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *centroids, int64_t ld_cent,
+                      int64_t nlist, const int64_t *probes, int nprobe, const float *codebooks, int d, int M, int32_t *tables,
+                      int32_t *bias, int32_t *exps, void *workspace, size_t workspace_bytes, void *stream);
+size_t tsim_ivfpq_scan_workspace_bytes(int64_t Q, int nprobe, int64_t max_list_len, int k);
+int tsim_ivfpq_scan_topk(int space, const int32_t *tables, int tables_per_pair, const int32_t *bias, int64_t Q,
+                         const uint8_t *c_codes, int64_t ldc, int64_t N, int M, const int64_t *list_off, int64_t nlist,
+                         const int32_t *row_ids, const int64_t *probes, int nprobe, int64_t max_list_len, int k, int32_t *out_val,
+                         int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

@@ -14,6 +14,7 @@ TSIM_I32, TSIM_I64 = 2, 3        # index dtypes of the candidate lists (tsim_*_l
 LIST_ST_ROW, LIST_ST_LIMS = 1, 2  # include/tsim.h TSIM_LIST_ST_*
 IVF_ST_LIST, IVF_ST_OFF = 1, 2    # include/tsim.h TSIM_IVF_ST_*
 IVF_SEG = 512                     # include/tsim.h TSIM_IVF_SEG
+IVFPQ_SEG = 4096                  # include/tsim.h TSIM_IVFPQ_SEG
 ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
 W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
@@ -167,6 +168,14 @@ _SIGS = {
     "tsim_ivf_scan_topk": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tsim_ivfpq_tables_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "tsim_ivfpq_tables": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "tsim_ivfpq_scan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int]),
+    "tsim_ivfpq_scan_topk": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_cosine_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_time_next_topk": (None, [C.c_void_p, C.c_void_p]),

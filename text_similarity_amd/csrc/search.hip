@@ -1886,6 +1886,7 @@ static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, cons
 #include "int8_search.h"    // int8 embeddings: calibrated quantiser, exact inner-product top-k on the int8 MFMA, re-score
 #include "ivf_search.h"     // inverted lists: exact scan of the contiguous lists each query probes
 #include "pq_search.h"      // product quantisation: the PQ encoder, integer lookup tables, exact ADC top-k in the code-search frame
+#include "ivfpq_search.h"   // IVF-PQ: residual tables and the exact ADC scan of the PQ-coded lists each query probes
 
 extern "C" int tsim_cosine_topk_plan(int64_t Q, int64_t N, int ld, int k, int32_t plan[4]) {
     if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_MAX_K || !plan || tsim_pad_dim(ld) != ld)

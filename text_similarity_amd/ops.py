@@ -1006,6 +1006,156 @@ def pq_adc_topk(eq_f32: torch.Tensor, codebooks, codes: torch.Tensor, k: int, sp
     return pq_values_to_float(val, exp, space), idx
 
 
+# ------------------------------------------------------------------------------------------------- IVF-PQ
+IVFPQ_SEG = _lib.IVFPQ_SEG      # include/tsim.h TSIM_IVFPQ_SEG: rows of one segment of a PQ-coded inverted list
+IVFPQ_TABLE_BUDGET = 256 << 20  # int32 tables of one ivfpq_search slice (l2 with residuals: nprobe M KiB a query)
+
+
+def _ivfpq_lists(what, list_off, row_ids, probes, Q, N):
+    if list_off.dtype != torch.int64 or list_off.dim() != 1 or list_off.numel() < 2 or not list_off.is_contiguous():
+        raise ValueError(f"{what}: list_off must be a contiguous int64 [nlist + 1] tensor")
+    if row_ids.dtype != torch.int32 or row_ids.shape != (N,) or not row_ids.is_contiguous():
+        raise ValueError(f"{what}: row_ids must be a contiguous int32 [{N}] tensor")
+    _ivfpq_probes(what, probes, Q)
+    return list_off.numel() - 1
+
+
+def _ivfpq_probes(what, probes, Q):
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != Q or probes.shape[1] < 1 or not probes.is_contiguous():
+        raise ValueError(f"{what}: probes must be a contiguous int64 [{Q}, nprobe >= 1] tensor")
+
+
+def ivfpq_tables(eq_f32: torch.Tensor, centroids: torch.Tensor, probes: torch.Tensor, codebooks, space: str, _trusted: bool = False):
+    """The integer tables of residual PQ codes (include/tsim.h tsim_ivfpq_tables): ``(tables, bias, exps)``.  "ip": tables int32
+    [Q, M, 256] as :func:`pq_tables` and bias int32 [Q, nprobe], the query's inner product with each probed centroid, on one
+    exponent e = 23 - ceil(log2(M + 1)) - (ilogb(A) + 1), A the largest of the table entries and the valid probes' products.
+    "l2": tables [Q, nprobe, M, 256], one per (query, probe) pair, of minus the squared distances of the residual query
+    float32(q - c) to the codebook entries, on ONE exponent per query (A over all its valid pairs); bias is None.  ``probes``
+    int64 [Q, nprobe], entries < 0 or >= nlist are padding (their tables are not written).  A query with a NaN or an infinity
+    among its entries, or with nothing but zeros, gets zero tables, zero biases and e = 0."""
+    what = "ivfpq_tables"
+    sp = _pq_space(what, space)
+    _need_gpu(eq_f32, centroids, probes)
+    dev = eq_f32.device
+    codebooks, d, M = _check_codebooks(what, codebooks, dev, None, _trusted)
+    eq_f32 = _pq_queries(what, eq_f32, d)
+    if centroids.dtype != torch.float32 or centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1 \
+            or centroids.stride(1) != 1 or (centroids.shape[0] > 1 and centroids.stride(0) < d):
+        raise ValueError(f"{what}: centroids must be float32 [nlist >= 1, {d}] with unit inner stride")
+    Q, nlist = eq_f32.shape[0], centroids.shape[0]
+    _ivfpq_probes(what, probes, Q)
+    nprobe = probes.shape[1]
+    l2 = space == "l2"
+    tables = torch.empty((Q, nprobe, M, 256) if l2 else (Q, M, 256), dtype=torch.int32, device=dev)
+    bias = None if l2 else torch.empty((Q, nprobe), dtype=torch.int32, device=dev)
+    exps = torch.empty((Q,), dtype=torch.int32, device=dev)
+    if Q:
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            nbytes = L.tsim_ivfpq_tables_workspace_bytes(Q, nprobe)
+            if nbytes == 0:
+                raise ValueError(f"{what}: unsupported shape Q={Q} nprobe={nprobe}")
+            ws = _workspace(dev, nbytes) if l2 else None
+            _lib.check(L.tsim_ivfpq_tables(sp, eq_f32.data_ptr(), _row_stride(eq_f32), Q, centroids.data_ptr(), _row_stride(centroids),
+                                           nlist, probes.data_ptr(), nprobe, codebooks.data_ptr(), d, M, tables.data_ptr(),
+                                           0 if l2 else bias.data_ptr(), exps.data_ptr(), ws.data_ptr() if l2 else 0,
+                                           ws.numel() if l2 else 0, _stream(eq_f32)), what)
+    return tables, bias, exps
+
+
+def ivfpq_scan_topk(space: str, tables: torch.Tensor, bias: Optional[torch.Tensor], codes: torch.Tensor, list_off: torch.Tensor,
+                    row_ids: torch.Tensor, probes: torch.Tensor, k: int, idx_offset: int = 0, return_status: bool = False,
+                    max_list_len: Optional[int] = None):
+    """Exact ADC top-k over the PQ-coded inverted lists each query probes (include/tsim.h tsim_ivfpq_scan_topk): (value int32
+    [Q, k], idx int64 [Q, k]).  ``tables`` int32 contiguous, [Q, M, 256] (one a query) or [Q, nprobe, M, 256] (one a pair);
+    ``bias`` int32 [Q, nprobe] or None; ``codes`` uint8 code rows in LIST order; ``list_off``, ``row_ids``, ``probes``, the status
+    bits and the hint ``max_list_len`` as in :func:`ivf_scan_topk`.  value = bias + sum_m table[m][code[m]]: "ip" by (value
+    desc, id asc), padded (-2**31, -1); "l2" returns -value by (value asc, id asc), padded (2**31 - 1, -1).  |bias| +
+    sum_m max_j |T| must stay below 2**24."""
+    what = "ivfpq_scan_topk"
+    sp = _pq_space(what, space)
+    _need_gpu(tables, codes, list_off, row_ids, probes)
+    dev = tables.device
+    if tables.dtype != torch.int32 or tables.dim() not in (3, 4) or tables.shape[-1] != 256 or not tables.is_contiguous():
+        raise ValueError(f"{what}: tables must be contiguous int32 [Q, M, 256] or [Q, nprobe, M, 256]")
+    per_pair = tables.dim() == 4
+    Q, M = tables.shape[0], tables.shape[-2]
+    N = codes.shape[0]
+    ldc = _check_code_rows(what, "codes", codes, M, dev, **_PQ_ROWS)
+    nlist = _ivfpq_lists(what, list_off, row_ids, probes, Q, N)
+    nprobe = probes.shape[1]
+    if per_pair and tables.shape[1] != nprobe:
+        raise ValueError(f"{what}: tables hold {tables.shape[1]} pairs a query, probes {nprobe}")
+    if bias is not None:
+        _need_gpu(bias)
+        if bias.dtype != torch.int32 or bias.shape != (Q, nprobe) or not bias.is_contiguous():
+            raise ValueError(f"{what}: bias must be a contiguous int32 [{Q}, {nprobe}] tensor")
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k={k} outside 1..{MAX_K}")
+    hint = max(1, N // nlist) if max_list_len is None else int(max_list_len)
+    if hint < 0:
+        raise ValueError(f"{what}: max_list_len={hint} < 0")
+    val = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q == 0:
+        return (val, idx, status) if return_status else (val, idx)
+    if N == 0:
+        raise ValueError(f"{what}: no rows")
+    L = _lib.lib()
+    tstride = (nprobe if per_pair else 1) * M * 1024
+    with torch.cuda.device(dev):
+        step = min(Q, MAX_QUERIES_PER_CALL)
+        nbytes = L.tsim_ivfpq_scan_workspace_bytes(step, nprobe, hint, k)
+        while step > 1 and nbytes > IVF_MAX_WORKSPACE + 1024:      # (+ the flag word and the alignment of the two halves)
+            step = (step + 1) // 2
+            nbytes = L.tsim_ivfpq_scan_workspace_bytes(step, nprobe, hint, k)
+        ws = _workspace(dev, nbytes)
+        for q0 in range(0, Q, step):
+            nq = min(step, Q - q0)
+            rc = L.tsim_ivfpq_scan_topk(sp, tables.data_ptr() + q0 * tstride, int(per_pair),
+                                        bias.data_ptr() + q0 * nprobe * 4 if bias is not None else 0, nq, codes.data_ptr(), ldc, N, M,
+                                        list_off.data_ptr(), nlist, row_ids.data_ptr(), probes.data_ptr() + q0 * nprobe * 8, nprobe,
+                                        hint, k, val.data_ptr() + q0 * k * 4, idx.data_ptr() + q0 * k * 8, idx_offset,
+                                        status.data_ptr() + q0 * 4 if return_status else 0, ws.data_ptr(), ws.numel(), _stream(tables))
+            _lib.check(rc, what)
+    return (val, idx, status) if return_status else (val, idx)
+
+
+def ivfpq_search(eq_f32: torch.Tensor, centroids: torch.Tensor, codebooks, codes: torch.Tensor, list_off: torch.Tensor,
+                 row_ids: torch.Tensor, probes: torch.Tensor, k: int, space: str = "ip", by_residual: bool = True,
+                 idx_offset: int = 0, max_list_len: Optional[int] = None, raw: bool = False, _trusted: bool = False,
+                 table_budget: int = IVFPQ_TABLE_BUDGET):
+    """IVF-PQ search of float queries: (scores float32 [Q, k], ids int64 [Q, k]) over the lists ``probes`` names, exact for the
+    integer scores of :func:`ivfpq_tables` (``by_residual``) or :func:`pq_tables` (codes of the rows themselves) under (score desc,
+    id asc) — "l2": (distance asc, id asc) — and turned into floats by :func:`pq_values_to_float`.  ``raw=True`` returns (value
+    int32, ids, exps int32 [Q]).  The queries are searched in slices whose tables stay within ``table_budget`` bytes (l2 with
+    residuals: nprobe M KiB a query); the exponent is per query, so the result does not depend on the slicing."""
+    what = "ivfpq_search"
+    _pq_space(what, space)
+    _need_gpu(eq_f32, codes)
+    codebooks, d, M = _check_codebooks(what, codebooks, eq_f32.device, None, _trusted)
+    eq_f32 = _pq_queries(what, eq_f32, d)
+    Q = eq_f32.shape[0]
+    _ivfpq_probes(what, probes, Q)
+    per_query = M * 1024 * (probes.shape[1] if by_residual and space == "l2" else 1)
+    step = max(1, min(MAX_QUERIES_PER_CALL, int(table_budget) // per_query))
+    vals, idxs, exps = [], [], []
+    for q0 in range(0, max(Q, 1), step):
+        qs, pr = eq_f32[q0:q0 + step], probes[q0:q0 + step]
+        if by_residual:
+            tables, bias, e = ivfpq_tables(qs, centroids, pr, codebooks, space, _trusted=True)
+        else:
+            (tables, e), bias = pq_tables(qs, codebooks, space, _trusted=True), None
+        v, i = ivfpq_scan_topk(space, tables, bias, codes, list_off, row_ids, pr, k, idx_offset, max_list_len=max_list_len)
+        vals.append(v), idxs.append(i), exps.append(e)
+    val, idx, exp = (torch.cat(t) if len(t) > 1 else t[0] for t in (vals, idxs, exps))
+    if raw:
+        return val, idx, exp
+    return pq_values_to_float(val, exp, space), idx
+
+
 # ------------------------------------------------------------------------------------------------- exact range search
 RANGE_SLOT_CAP = _lib.RANGE_SLOT_CAP    # include/tsim.h TSIM_RANGE_SLOT_CAP: rows one query may collect before the exact pass takes over
 RANGE_MERGE_MAX_LISTS = _lib.RANGE_MERGE_MAX_LISTS    # include/tsim.h TSIM_RANGE_MERGE_MAX_LISTS: results one range_merge call joins

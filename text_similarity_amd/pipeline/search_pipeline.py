@@ -26,6 +26,7 @@ from .. import ops
 from ..index import GpuFlatIndex
 from ..ivf_index import GpuIVFIndex
 from ..pq_index import GpuPQIndex
+from ..ivfpq_index import GpuIVFPQIndex
 
 
 SCORE_FUNCTIONS = {"cosine": "cosine", "dot": "dot", "dot_product": "dot"}
@@ -249,7 +250,9 @@ class SemanticSearchPipeline(SearchPipeline):
     at ``index_path`` raises ``ValueError``.  ``index_type='ivf'`` (with ``nlist=``, ``nprobe=``) keeps a
     :class:`text_similarity_amd.ivf_index.GpuIVFIndex` instead: approximate, exact within the lists it probes.
     ``index_type='pq'`` (with ``pq_m=``) keeps a :class:`text_similarity_amd.pq_index.GpuPQIndex`, trained on the corpus embeddings
-    when the index is built: ``pq_m`` bytes a row, any width up to 1024, no filters and no removal."""
+    when the index is built: ``pq_m`` bytes a row, any width up to 1024, no filters and no removal.  ``index_type='ivfpq'`` (with
+    ``nlist=``, ``nprobe=``, ``pq_m=``) keeps a :class:`text_similarity_amd.ivfpq_index.GpuIVFPQIndex`, trained the same way: ``pq_m``
+    bytes a row in ``nlist`` lists of which a query reads ``nprobe``; removal works, filters do not."""
 
     def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat", nlist: int = 1024,
                  nprobe: int = 8, pq_m: int = 8, **kwargs):
@@ -264,8 +267,10 @@ class SemanticSearchPipeline(SearchPipeline):
             self.index = GpuIVFIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, device=self.params.device)
         elif index_type == "pq":    # approximate: rows are replaced by pq_m learned bytes
             self.index = GpuPQIndex(space=space, dim=hidden, M=pq_m, device=self.params.device)
+        elif index_type == "ivfpq":   # approximate: pq_m learned bytes a row, in lists of which a query reads nprobe
+            self.index = GpuIVFPQIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, M=pq_m, device=self.params.device)
         else:
-            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq'")
+            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq', 'ivfpq'")
         self.index_type = index_type
         if os.path.exists(os.path.join(self.index_path, getattr(self.index, "_FILE_NAME", "index.bin"))):
             self.index.load_index(self.index_path)
@@ -275,7 +280,7 @@ class SemanticSearchPipeline(SearchPipeline):
     def _index(self, corpus):
         os.makedirs(self.index_path, exist_ok=True)
         corpus_embeddings = self.encode_corpus(corpus)
-        if self.index_type == "pq":
+        if self.index_type in ("pq", "ivfpq"):
             self.index.train(corpus_embeddings)
             self.index.add_items(corpus_embeddings, list(range(corpus_embeddings.shape[0])))
             self.index.save_index(self.index_path)
@@ -292,6 +297,8 @@ class SemanticSearchPipeline(SearchPipeline):
             if filter is not None:
                 raise NotImplementedError("GpuPQIndex has no filtered search: index_type='flat' does")
             scores, labels = self.index.search(query_embeddings, max_num_results)
+        elif self.index_type == "ivfpq":   # ((values, labels) as GpuPQIndex; a filter raises there)
+            scores, labels = self.index.search(query_embeddings, max_num_results, filter=filter)
         elif filter is None:
             labels, scores = self.index.search(query_embeddings, max_num_results)
         else:   # (labels of this index are corpus positions; the forms GpuFlatIndex.search takes)
