@@ -578,6 +578,55 @@ int tsim_ivfpq_scan_topk(int space, const int32_t *tables, int tables_per_pair, 
                          int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Graph index: beam search over a fixed-degree proximity graph (the family of hnswlib's base layer and of CAGRA), and the
+ * rank-based pruning that makes such a graph out of an exact kNN graph.
+ * tsim_graph_search.  rows_f32 [N, d] float32 (row stride ld_rows >= d), eq_f32 [Q, d] (ldq_f32 >= d), space and scores as for the
+ * list entries above, bit for bit.  graph int32 [N, R] contiguous, 1 <= R <= TSIM_GRAPH_MAX_DEGREE: row r's neighbours.  entries int32
+ * [n_entries], 1 <= n_entries <= TSIM_GRAPH_MAX_ENTRIES: the rows every query starts from.  In both, a negative id is padding and an
+ * id >= N is never dereferenced and sets TSIM_GRAPH_ST_ROW in out_status[q].  row_ids int32 [N] (may be NULL): a negative entry marks
+ * the row a tombstone.  k <= ef <= TSIM_GRAPH_MAX_EF, 1 <= width <= TSIM_GRAPH_MAX_WIDTH, max_iters >= 1, 1 <= d <= 768 (Euclidean
+ * <= 767), N < 2^31 - 64.  Per query:
+ *   1. visited = {}; the beam is empty, holds at most ef (score, row) entries and is ordered by (score desc, row asc), Euclidean by
+ *      (dist^2 asc, row asc);
+ *   2. every distinct usable entry point joins visited, is scored and offered to the beam;
+ *   3. at most max_iters times: the parents are the best `width` beam entries not yet expanded, chosen at the start of the iteration
+ *      (none: stop); they are marked expanded; every neighbour graph[parent][0 .. R) of every parent that is usable and not in
+ *      visited joins visited and is scored — a NaN score is dropped, the row stays visited; the beam becomes the best ef of (beam +
+ *      the rows just scored); a row pushed out of the beam stays visited;
+ *   4. if the cap ended the loop while an unexpanded entry was left, TSIM_GRAPH_ST_ITERS is set;
+ *   5. the first k beam entries that are no tombstones are the result (tombstones are traversed and route the search; they are never
+ *      returned): out_scores [Q, k], out_idx [Q, k] = row_ids[row] when row_ids is given, else row + idx_offset; fewer than k pad
+ *      with -inf / -1 (Euclidean +inf / -1).
+ * The beam's rows are distinct and its order total, so the result is a function of the arguments alone.  visited is exact: an
+ * open-addressing table in LDS of the smallest power of two >= 2 (n_entries + max_iters width R) slots, the most rows a query can
+ * visit, and at least 64.  The table may take TSIM_GRAPH_MAX_TABLE_BYTES (16 384 visits); a call that needs more is TSIM_EINVAL
+ * with a message.  It is sized per call: a small max_iters leaves LDS for several workgroups a CU.
+ * tsim_graph_search_lds_bytes: the LDS of one workgroup of such a call (TSIM_GRAPH_STATIC_LDS_BYTES for the beam and the staging + the
+ * table), pure host, 0 for arguments outside the ranges above, non-decreasing in each argument; the call is accepted iff it is
+ * <= TSIM_GRAPH_STATIC_LDS_BYTES + TSIM_GRAPH_MAX_TABLE_BYTES.  out_status [Q] int32 (may be NULL): written, not accumulated.
+ * One workgroup per query; no workspace; the call reads nothing back from the device.
+ * tsim_graph_prune.  knn int32 [N, K0] contiguous, 1 <= K0 <= TSIM_GRAPH_PRUNE_MAX_K0: each row's nearest other rows, best first
+ * (entries < 0 or >= N are unusable).  D[i][b] = #{a < b : knn[i][a] usable and knn[i][b] among knn[knn[i][a]][0 .. b)} — the number
+ * of two-hop detours through a better-ranked neighbour — and D[i][b] = K0 for an unusable knn[i][b].  out_forward int32 [N, R],
+ * 1 <= R <= min(K0, TSIM_GRAPH_MAX_DEGREE): the R entries of knn[i] of smallest (D, b), in that order, unusable ones as -1.
+ * out_detours int32 [N, K0] (may be NULL): D. */
+#define TSIM_GRAPH_MAX_DEGREE 64
+#define TSIM_GRAPH_MAX_ENTRIES 256
+#define TSIM_GRAPH_MAX_WIDTH 4
+#define TSIM_GRAPH_MAX_EF 1024
+#define TSIM_GRAPH_MAX_TABLE_BYTES 131072
+#define TSIM_GRAPH_STATIC_LDS_BYTES 18432
+#define TSIM_GRAPH_PRUNE_MAX_K0 128
+#define TSIM_GRAPH_ST_ROW 1   /* the graph or the entry points held an id >= N that the query met */
+#define TSIM_GRAPH_ST_ITERS 2 /* max_iters ended the search with an unexpanded beam entry left */
+size_t tsim_graph_search_lds_bytes(int n_entries, int R, int width, int max_iters);
+int tsim_graph_search(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *rows_f32, int64_t ld_rows, int64_t N,
+                      int d, const int32_t *graph, int R, const int32_t *entries, int n_entries, const int32_t *row_ids, int ef,
+                      int width, int max_iters, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status,
+                      void *stream);
+int tsim_graph_prune(const int32_t *knn, int64_t N, int K0, int R, int32_t *out_forward, int32_t *out_detours, void *stream);
+
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before
  * and `stop` right after the launch of its dominant kernel (cos_topk_partial) on the call's stream.  Both are
  * hipEvent_t handles passed as void*; the hook is cleared by that call.  Pass NULLs to cancel. */

@@ -525,6 +525,131 @@ def ivf_scan_topk(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, list
     return (scores, idx, status) if return_status else (scores, idx)
 
 
+# ------------------------------------------------------------------------------------------------- graph index
+GRAPH_ST_ROW, GRAPH_ST_ITERS = _lib.GRAPH_ST_ROW, _lib.GRAPH_ST_ITERS
+GRAPH_MAX_DEGREE, GRAPH_MAX_ENTRIES, GRAPH_MAX_WIDTH, GRAPH_MAX_EF = 64, 256, 4, 1024     # include/tsim.h TSIM_GRAPH_MAX_*
+GRAPH_PRUNE_MAX_K0 = 128                                                                  # TSIM_GRAPH_PRUNE_MAX_K0
+GRAPH_LDS_LIMIT = _lib.GRAPH_STATIC_LDS_BYTES + _lib.GRAPH_MAX_TABLE_BYTES                # what one workgroup may take
+
+
+def graph_search_lds_bytes(n_entries: int, R: int, width: int, max_iters: int) -> int:
+    """LDS of one workgroup of :func:`graph_search` (include/tsim.h tsim_graph_search_lds_bytes): pure host, 0 for arguments
+    out of range; a call is accepted iff this is <= GRAPH_LDS_LIMIT."""
+    return int(_lib.lib().tsim_graph_search_lds_bytes(int(n_entries), int(R), int(width), int(max_iters)))
+
+
+def graph_max_iters(n_entries: int, R: int, width: int) -> int:
+    """The largest max_iters whose visited table fits the LDS limit: a query visits at most n_entries + max_iters width R
+    rows and the table holds GRAPH_MAX_TABLE_BYTES / 8 of them."""
+    return max(0, (_lib.GRAPH_MAX_TABLE_BYTES // 8 - int(n_entries)) // (int(width) * int(R)))
+
+
+def graph_search(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, graph: torch.Tensor, entries: torch.Tensor, k: int,
+                 ef: int, width: int = 4, max_iters: Optional[int] = None, row_ids: Optional[torch.Tensor] = None,
+                 idx_offset: int = 0, return_status: bool = False):
+    """Beam search of every query over a proximity graph (include/tsim.h tsim_graph_search states the algorithm): scores [Q,k]
+    f32 and ids [Q,k] i64 ordered by (score desc, row asc) — ``space`` 'cosine' | 'dot' | 'l2' (squared distances, ascending) — with
+    the bits of :func:`cosine_list_topk` / :func:`dot_list_topk` / :func:`l2_list_topk`, so a result is a subset of the exact
+    search's.  ``graph`` int32 [N,R] (R <= 64; negative: padding), ``entries`` int32 [E] (E <= 256) the rows every query starts
+    from, ``row_ids`` int32 [N] the id reported for each row (negative: a tombstone — traversed, never returned; None: row +
+    ``idx_offset``).  ``ef`` (k <= ef <= 1024) is the beam, ``width`` (1..4) the beam entries expanded per iteration,
+    ``max_iters`` the cap on iterations (default: the largest the LDS limit allows, :func:`graph_max_iters`).  An id >= N met by
+    a query sets status bit ``GRAPH_ST_ROW``, a search cut by ``max_iters`` ``GRAPH_ST_ITERS``; ``return_status`` adds the int32
+    [Q] status."""
+    what = "graph_search"
+    if space not in IVF_SPACES:
+        raise ValueError(f"{what}: space {space!r}: one of {tuple(IVF_SPACES)}")
+    _need_gpu(eq_f32, rows_f32, graph, entries)
+    dev = eq_f32.device
+    for t, name in ((eq_f32, "eq_f32"), (rows_f32, "rows_f32")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be float32 [rows, d] with unit inner stride")
+    Q, d = eq_f32.shape
+    N = rows_f32.shape[0]
+    if rows_f32.shape[1] != d:
+        raise ValueError(f"{what}: query rows are {d} wide, stored rows {rows_f32.shape[1]}")
+    if space == "l2":
+        _l2_dim(d, what)
+    if graph.dtype != torch.int32 or graph.dim() != 2 or graph.shape[0] != N or not graph.is_contiguous():
+        raise ValueError(f"{what}: graph must be a contiguous int32 [{N}, R] tensor")
+    if entries.dtype != torch.int32 or entries.dim() != 1 or not entries.is_contiguous():
+        raise ValueError(f"{what}: entries must be a contiguous int32 [E] tensor")
+    if row_ids is not None:
+        _need_gpu(row_ids)
+        if row_ids.dtype != torch.int32 or row_ids.shape != (N,) or not row_ids.is_contiguous():
+            raise ValueError(f"{what}: row_ids must be a contiguous int32 [{N}] tensor")
+    k, ef, width, R, E = int(k), int(ef), int(width), int(graph.shape[1]), int(entries.numel())
+    if max_iters is None:
+        max_iters = max(1, graph_max_iters(E, max(R, 1), min(max(width, 1), GRAPH_MAX_WIDTH)))
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    if Q == 0:
+        return (scores, idx, status) if return_status else (scores, idx)
+    if N == 0:
+        raise ValueError(f"{what}: no rows")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        rc = L.tsim_graph_search(IVF_SPACES[space], eq_f32.data_ptr(), _row_stride(eq_f32), Q, rows_f32.data_ptr(), _row_stride(rows_f32),
+                                 N, d, graph.data_ptr(), R, entries.data_ptr(), E, row_ids.data_ptr() if row_ids is not None else 0,
+                                 ef, width, int(max_iters), k, scores.data_ptr(), idx.data_ptr(), idx_offset,
+                                 status.data_ptr() if return_status else 0, _stream(eq_f32))
+        _lib.check(rc, what)
+    return (scores, idx, status) if return_status else (scores, idx)
+
+
+def graph_prune(knn: torch.Tensor, R: int, return_detours: bool = False):
+    """The forward lists [N,R] int32 of an exact kNN graph ``knn`` int32 [N,K0] (K0 <= 128, best first): the R entries of each
+    row with the fewest two-hop detours through better-ranked neighbours, ties by rank (include/tsim.h tsim_graph_prune; CAGRA's
+    rank-based pruning).  ``return_detours`` adds the counts [N,K0] int32."""
+    what = "graph_prune"
+    _need_gpu(knn)
+    if knn.dtype != torch.int32 or knn.dim() != 2 or not knn.is_contiguous():
+        raise ValueError(f"{what}: knn must be a contiguous int32 [N, K0] tensor")
+    N, K0 = knn.shape
+    fwd = torch.empty((N, int(R)), dtype=torch.int32, device=knn.device)
+    det = torch.empty((N, K0), dtype=torch.int32, device=knn.device) if return_detours else None
+    if N:
+        with torch.cuda.device(knn.device):
+            rc = _lib.lib().tsim_graph_prune(knn.data_ptr(), N, K0, int(R), fwd.data_ptr(), det.data_ptr() if return_detours else 0,
+                                             _stream(knn))
+            _lib.check(rc, what)
+    return (fwd, det) if return_detours else fwd
+
+
+def graph_merge_reverse(fwd: torch.Tensor) -> torch.Tensor:
+    """The final graph rows [N,R] int32 of forward lists ``fwd`` [N,R]: row j is the first R distinct ids of fwd[j][:R/2] ++
+    Rev[j][:R/2] ++ fwd[j][R/2:], -1 padded, where Rev[j] lists the sources i of the edges i -> j ordered by (the position of j in
+    fwd[i], i).  Integers only (torch stable sorts on the tensor's device), so it is exact by construction."""
+    N, R = fwd.shape
+    h = R // 2
+    dev = fwd.device
+    F = fwd.to(torch.int64)
+    dst = F.t().reshape(-1)                                     # edges in (position, source) order
+    src = torch.arange(N, device=dev).repeat(R)
+    ok = dst >= 0
+    dst, src = dst[ok], src[ok]
+    dst, o = torch.sort(dst, stable=True)
+    src = src[o]
+    start = torch.searchsorted(dst, torch.arange(N, device=dev))
+    rank = torch.arange(dst.numel(), device=dev) - start[dst]
+    rev = torch.full((N, max(h, 1)), -1, dtype=torch.int64, device=dev)
+    keep = rank < h
+    rev[dst[keep], rank[keep]] = src[keep]
+    cat = torch.cat([F[:, :h], rev[:, :h], F[:, h:]], dim=1)
+    sv, o = torch.sort(cat, dim=1, stable=True)
+    dup_sorted = torch.zeros_like(sv, dtype=torch.bool)
+    dup_sorted[:, 1:] = sv[:, 1:] == sv[:, :-1]
+    dup = torch.zeros_like(dup_sorted).scatter_(1, o, dup_sorted)
+    good = (cat >= 0) & ~dup
+    place = torch.cumsum(good, dim=1) - 1
+    sel = good & (place < R)
+    out = torch.full((N, R), -1, dtype=torch.int64, device=dev)
+    rows = torch.arange(N, device=dev)[:, None].expand_as(cat)
+    out[rows[sel], place[sel]] = cat[sel]
+    return out.to(torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------- code searches: the shared frame
 MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit and the int8 codes
 

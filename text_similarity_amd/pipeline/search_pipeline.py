@@ -24,6 +24,7 @@ import os
 
 from .. import ops
 from ..index import GpuFlatIndex
+from ..graph_index import GpuGraphIndex
 from ..ivf_index import GpuIVFIndex
 from ..pq_index import GpuPQIndex
 from ..ivfpq_index import GpuIVFPQIndex
@@ -252,7 +253,10 @@ class SemanticSearchPipeline(SearchPipeline):
     ``index_type='pq'`` (with ``pq_m=``) keeps a :class:`text_similarity_amd.pq_index.GpuPQIndex`, trained on the corpus embeddings
     when the index is built: ``pq_m`` bytes a row, any width up to 1024, no filters and no removal.  ``index_type='ivfpq'`` (with
     ``nlist=``, ``nprobe=``, ``pq_m=``) keeps a :class:`text_similarity_amd.ivfpq_index.GpuIVFPQIndex`, trained the same way: ``pq_m``
-    bytes a row in ``nlist`` lists of which a query reads ``nprobe``; removal works, filters do not."""
+    bytes a row in ``nlist`` lists of which a query reads ``nprobe``; removal works, filters do not.  ``index_type='graph'`` keeps a
+    :class:`text_similarity_amd.graph_index.GpuGraphIndex`, the family of the reference's hnswlib index, and for it ``ef`` /
+    ``ef_construction`` / ``M`` are NOT unused: ``M`` sets the graph's degree, ``ef_construction`` the width of the kNN graph the build
+    prunes and ``ef`` the beam of a search, as that class documents; removal works (tombstones), filters do not."""
 
     def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat", nlist: int = 1024,
                  nprobe: int = 8, pq_m: int = 8, **kwargs):
@@ -269,11 +273,17 @@ class SemanticSearchPipeline(SearchPipeline):
             self.index = GpuPQIndex(space=space, dim=hidden, M=pq_m, device=self.params.device)
         elif index_type == "ivfpq":   # approximate: pq_m learned bytes a row, in lists of which a query reads nprobe
             self.index = GpuIVFPQIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, M=pq_m, device=self.params.device)
+        elif index_type == "graph":   # approximate: a beam search over a proximity graph; ef / ef_construction / M mean something
+            self.index = GpuGraphIndex(space=space, dim=hidden, M=getattr(self.params, "M", 0),
+                                       ef_construction=getattr(self.params, "ef_construction", 0), device=self.params.device)
+            self.index.set_ef(getattr(self.params, "ef", 0))
         else:
-            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq', 'ivfpq'")
+            raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq', 'ivfpq', 'graph'")
         self.index_type = index_type
         if os.path.exists(os.path.join(self.index_path, getattr(self.index, "_FILE_NAME", "index.bin"))):
             self.index.load_index(self.index_path)
+            if index_type == "graph":   # (the beam is a parameter of the search, not of the file)
+                self.index.set_ef(getattr(self.params, "ef", 0))
         else:
             self._index(self.corpus)
 

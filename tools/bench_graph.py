@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""GpuGraphIndex against GpuFlatIndex and GpuIVFIndex on the GPU box: python tools/bench_graph.py [--N N] [--d D] [--Q ...]
+[--ef ...] [--width ...] [--M M] [--ef-construction C] [--k K] [--nlist L] [--nprobe P] [--rounds R] [--iters I] [--data ...]
+
+Three corpora, all seeded: ``mixture``, the Gaussian mixture of tools/bench_ivf.py (--components centres of unit variance per
+element, rows = centre + sigma * noise, queries fresh draws from it); ``gauss``, isotropic standard-normal rows and queries —
+data without clusters, where an inverted file has nothing to hold on to; and ``manifold`` (not in the default set), rows on a
+--latent-dimensional linear manifold (standard-normal latents through a fixed random [latent, d] map, plus 0.05 noise per
+element): connected, of low intrinsic dimension, the shape a proximity graph is made for.  Per corpus one JSON line for the build (seconds of
+the self-search, the pruning and the reverse merge) and one per cell (Q, ef, width):
+  graph_ms / ivf_ms / flat_ms   ms per ``search`` call on the same queries: median [min, max] over R rounds, the three indexes
+                                ALTERNATING inside every round, I calls timed per round between device events;
+  recall10, ivf_recall10        recall@10 against the flat result on a fixed set of 256 queries;
+  cut                           the share of those queries whose search the iteration cap ended (TSIM_GRAPH_ST_ITERS).
+Not part of bench.py."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from text_similarity_amd import ops
+from text_similarity_amd.graph_index import _OPS_SPACE, GpuGraphIndex
+from text_similarity_amd.index import GpuFlatIndex
+from text_similarity_amd.ivf_index import GpuIVFIndex
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--N", type=int, default=1_000_000)
+ap.add_argument("--d", type=int, default=384)
+ap.add_argument("--Q", nargs="+", type=int, default=[1, 16, 256])
+ap.add_argument("--ef", nargs="+", type=int, default=[32, 64, 128])
+ap.add_argument("--width", nargs="+", type=int, default=[1, 4])
+ap.add_argument("--M", type=int, default=16)
+ap.add_argument("--ef-construction", type=int, default=0)
+ap.add_argument("--k", type=int, default=10)
+ap.add_argument("--nlist", type=int, default=1024)
+ap.add_argument("--nprobe", type=int, default=8)
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--space", default="cosine", choices=GpuGraphIndex.SPACES)
+ap.add_argument("--components", type=int, default=4096)
+ap.add_argument("--sigma", type=float, default=1.0)
+ap.add_argument("--latent", type=int, default=16)
+ap.add_argument("--data", nargs="+", default=["mixture", "gauss"], choices=["mixture", "gauss", "manifold"])
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("bench_graph.py measures on the GPU: no device found")
+dev = "cuda:0"
+d, N = a.d, a.N
+g = torch.Generator(device=dev).manual_seed(97)
+centres = torch.randn((a.components, d), generator=g, device=dev)
+lift = torch.randn((a.latent, d), generator=g, device=dev)
+
+
+def draw(kind, n):
+    noise = torch.randn((n, d), generator=g, device=dev)
+    if kind == "gauss":
+        return noise
+    if kind == "manifold":
+        return torch.randn((n, a.latent), generator=g, device=dev) @ lift + 0.05 * noise
+    return centres[torch.randint(0, a.components, (n,), generator=g, device=dev)] + a.sigma * noise
+
+
+def timed(run, iters, warm=2):
+    for _ in range(warm):
+        run()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        run()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def spread(v):
+    return [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]
+
+
+def wall(f):
+    torch.cuda.synchronize()
+    t = time.time()
+    out = f()
+    torch.cuda.synchronize()
+    return out, round(time.time() - t, 3)
+
+
+def recall(got, truth):
+    return round(float((got[:, :, None] == truth[:, None, :]).any(2).float().sum(1).mean()) / truth.shape[1], 4)
+
+
+for kind in a.data:
+    flat = GpuFlatIndex(a.space, d, device=dev)
+    flat.init_index(N)
+    ivf = GpuIVFIndex(a.space, d, a.nlist, nprobe=min(a.nprobe, a.nlist), device=dev, seed=1)
+    gr = GpuGraphIndex(a.space, d, M=a.M, ef_construction=a.ef_construction, device=dev)
+    g.manual_seed(1000 + N % 997)
+    ivf.train(draw(kind, min(N, 64 * a.nlist)), niter=10, max_points_per_list=64)
+    for r0 in range(0, N, 1 << 20):
+        x = draw(kind, min(1 << 20, N - r0))
+        ids = torch.arange(r0, r0 + x.shape[0]).numpy()
+        for ix in (flat, ivf, gr):
+            ix.add_items(x, ids)
+    del x
+    knn, t_knn = wall(gr.knn_graph)
+    fwd, t_prune = wall(lambda: ops.graph_prune(knn, gr.R))
+    _, t_merge = wall(lambda: ops.graph_merge_reverse(fwd))
+    del fwd
+    _, t_rest = wall(lambda: gr.build(knn))
+    del knn
+    t_build = round(t_knn + t_rest, 3)
+    deg = float((gr.graph >= 0).sum(1).float().mean())
+    print(json.dumps({"data": kind, "space": a.space, "N": N, "d": d, "R": gr.R, "K0": gr.K0, "entries": int(gr.entries.numel()),
+                      "build_s": t_build, "knn_s": t_knn, "prune_s": t_prune, "merge_s": t_merge, "mean_degree": round(deg, 2)}),
+          flush=True)
+    q_all = draw(kind, max(256, max(a.Q)))
+    truth = flat.search(q_all[:256], 10)[0]
+    ivf_recall = recall(ivf.search(q_all[:256], 10)[0], truth)
+    for ef in a.ef:
+        for width in a.width:
+            gr.set_ef(ef)
+            gr.width = width
+            efu, iters = gr.search_params(10)
+            rc = recall(gr.search(q_all[:256], 10)[0], truth)
+            st = ops.graph_search(_OPS_SPACE[a.space], q_all[:256].contiguous(), gr._f32[:N], gr.graph, gr.entries, 10, efu, width=width,
+                                  max_iters=iters, return_status=True)[2]
+            cut = round(float((st & ops.GRAPH_ST_ITERS).bool().float().mean()), 4)
+            lds = ops.graph_search_lds_bytes(int(gr.entries.numel()), gr.R, width, iters)
+            for Q in a.Q:
+                q = q_all[:Q].contiguous()
+                t_gr, t_ivf, t_flat = [], [], []
+                for r in range(a.rounds):
+                    runs = [(t_gr, lambda: gr.search(q, a.k)), (t_ivf, lambda: ivf.search(q, a.k)), (t_flat, lambda: flat.search(q, a.k))]
+                    for into, run in (runs if r % 2 == 0 else runs[::-1]):
+                        into.append(timed(run, a.iters))
+                print(json.dumps({"data": kind, "N": N, "d": d, "k": a.k, "R": gr.R, "ef": ef, "width": width, "max_iters": iters,
+                                  "lds_bytes": lds, "Q": Q, "graph_ms": spread(t_gr), "ivf_ms": spread(t_ivf), "flat_ms": spread(t_flat),
+                                  "recall10": rc, "cut": cut, "ivf_recall10": ivf_recall, "nlist": a.nlist, "nprobe": ivf.nprobe}),
+                      flush=True)
+    del flat, ivf, gr, truth
+    torch.cuda.empty_cache()
