@@ -606,6 +606,17 @@ int tsim_ivfpq_scan_topk(int space, const int32_t *tables, int tables_per_pair, 
  * table), pure host, 0 for arguments outside the ranges above, non-decreasing in each argument; the call is accepted iff it is
  * <= TSIM_GRAPH_STATIC_LDS_BYTES + TSIM_GRAPH_MAX_TABLE_BYTES.  out_status [Q] int32 (may be NULL): written, not accumulated.
  * One workgroup per query; no workspace; the call reads nothing back from the device.
+ * tsim_graph_search_seeded.  The same search with entry points per QUERY, given in two levels: step 2 takes, for query q, the rows
+ * seeds[probes[q][p]][s] for all p < n_probe, s < n_seeds — 1 <= n_probe n_seeds <= TSIM_GRAPH_MAX_ENTRIES of them (n_entries of
+ * the table sizing above) — and every other step is tsim_graph_search's.  seeds int32 [n_lists, n_seeds] contiguous (may be NULL):
+ * row l holds the rows a search entering through list l starts from.  seeds == NULL: n_lists and n_seeds are ignored, n_seeds = 1,
+ * n_lists = N and a probe IS a row — the plain entries [Q, E] form.  probes int32 [Q, n_probe] (row stride ld_probes >= n_probe; may be
+ * NULL): the lists of each query.  The id rule holds at both levels: a negative probe or seed is padding, a probe >= n_lists or a
+ * seed >= N is never dereferenced and sets TSIM_GRAPH_ST_ROW; repeats are harmless (visited dedupes them).  Exactly one of probes
+ * and centroids is given.  probes == NULL: centroids float32 [n_lists, d] (row stride ld_centroids >= d), 1 <= n_lists <=
+ * TSIM_GRAPH_MAX_COARSE_LISTS, and the kernel finds the probes first: the n_probe centroids of best score to the query in the
+ * index's space — the scores of the list entries above, bit for bit — ordered by (score desc, list asc), a NaN score dropped, -1
+ * where fewer are usable.  out_probes int32 [Q, n_probe] contiguous (may be NULL): the probes the query used, given or found.
  * tsim_graph_prune.  knn int32 [N, K0] contiguous, 1 <= K0 <= TSIM_GRAPH_PRUNE_MAX_K0: each row's nearest other rows, best first
  * (entries < 0 or >= N are unusable).  D[i][b] = #{a < b : knn[i][a] usable and knn[i][b] among knn[knn[i][a]][0 .. b)} — the number
  * of two-hop detours through a better-ranked neighbour — and D[i][b] = K0 for an unusable knn[i][b].  out_forward int32 [N, R],
@@ -618,13 +629,19 @@ int tsim_ivfpq_scan_topk(int space, const int32_t *tables, int tables_per_pair, 
 #define TSIM_GRAPH_MAX_TABLE_BYTES 131072
 #define TSIM_GRAPH_STATIC_LDS_BYTES 18432
 #define TSIM_GRAPH_PRUNE_MAX_K0 128
-#define TSIM_GRAPH_ST_ROW 1   /* the graph or the entry points held an id >= N that the query met */
+#define TSIM_GRAPH_MAX_COARSE_LISTS 4096 /* centroids the seeded search's own coarse phase takes */
+#define TSIM_GRAPH_ST_ROW 1   /* the graph, the entry points or the seeds held an id >= N, or the probes one >= n_lists, that the query met */
 #define TSIM_GRAPH_ST_ITERS 2 /* max_iters ended the search with an unexpanded beam entry left */
 size_t tsim_graph_search_lds_bytes(int n_entries, int R, int width, int max_iters);
 int tsim_graph_search(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *rows_f32, int64_t ld_rows, int64_t N,
                       int d, const int32_t *graph, int R, const int32_t *entries, int n_entries, const int32_t *row_ids, int ef,
                       int width, int max_iters, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status,
                       void *stream);
+int tsim_graph_search_seeded(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *rows_f32, int64_t ld_rows,
+                             int64_t N, int d, const int32_t *graph, int R, const int32_t *seeds, int64_t n_lists, int n_seeds,
+                             const int32_t *probes, int64_t ld_probes, int n_probe, const float *centroids, int64_t ld_centroids,
+                             const int32_t *row_ids, int ef, int width, int max_iters, int k, float *out_scores, int64_t *out_idx,
+                             int64_t idx_offset, int32_t *out_status, int32_t *out_probes, void *stream);
 int tsim_graph_prune(const int32_t *knn, int64_t N, int K0, int R, int32_t *out_forward, int32_t *out_detours, void *stream);
 
 /* Measurement hook (bench.py): the NEXT tsim_cosine_topk call of the calling thread records `start` right before

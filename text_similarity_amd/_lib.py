@@ -18,6 +18,7 @@ IVFPQ_SEG = 4096                  # include/tsim.h TSIM_IVFPQ_SEG
 GRAPH_ST_ROW, GRAPH_ST_ITERS = 1, 2   # include/tsim.h TSIM_GRAPH_ST_*
 GRAPH_MAX_TABLE_BYTES = 131072    # include/tsim.h TSIM_GRAPH_MAX_TABLE_BYTES
 GRAPH_STATIC_LDS_BYTES = 18432    # include/tsim.h TSIM_GRAPH_STATIC_LDS_BYTES
+GRAPH_MAX_COARSE_LISTS = 4096     # include/tsim.h TSIM_GRAPH_MAX_COARSE_LISTS
 ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
 W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
@@ -183,6 +184,10 @@ _SIGS = {
     "tsim_graph_search": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
                                     C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_void_p, C.c_void_p]),
+    "tsim_graph_search_seeded": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsim_graph_prune": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsim_cosine_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),

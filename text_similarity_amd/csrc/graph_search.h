@@ -25,6 +25,8 @@
 //     flight together, and the four waves' batches overlap).
 // An iteration is two dependent memory round trips — the parents' graph rows (one lane per neighbour), then the neighbours'
 // rows — plus the scoring and one merge of at most 256 entries into the beam.
+// Entry points come shared (tsim_graph_search: entries [E], the same for every query) or per query (tsim_graph_search_seeded:
+// GraphSeeds below) — one kernel, instantiated for either; they differ before and in the entry step (it == -1) only.
 // House rule for ids: a negative id is padding, an id >= N is never dereferenced and raises TSIM_GRAPH_ST_ROW; a tombstone
 // (row_ids[row] < 0) is traversed like any row and dropped only from the OUTPUT.
 #pragma once
@@ -73,14 +75,31 @@ __device__ __forceinline__ int graph_slot(const int *tab, unsigned mask, int shi
     }
 }
 
-template <typename T, bool COS>
+// Per-query entry points (tsim_graph_search_seeded), in two levels: query q enters through the lists probes[q][0 .. P) and a
+// list l through the rows seeds[l][0 .. S) (seeds null: S = 1 and a probe is a row), E = P S ids.  probes null: the kernel finds
+// them first, the P of the T centroids of best score to the query, through the beam's own running list.
+struct GraphSeeds {
+    const int32_t *seeds, *probes;
+    const void *centroids;   // T rows of the stored rows' type
+    int64_t T, ld_probes, ld_centroids;
+    int S, P, pp;   // pp: sl_list_len(P)
+    int32_t *out_probes;
+};
+
+using GraphShared = const int32_t *__restrict__;   // the entry points every query starts from
+
+// EN = GraphShared: tsim_graph_search (the code it had before the seeded form existed: profiles/graph_entries_ab.txt compares
+// the code objects); EN = GraphSeeds: tsim_graph_search_seeded, which differs before and in the entry step only.
+template <typename T, bool COS, typename EN>
 __global__ __launch_bounds__(256) void graph_search_kernel(int64_t Q, int64_t N, const T *__restrict__ xq, int64_t ldq,
                                                            const T *__restrict__ xr, int64_t ldr, int d,
-                                                           const int32_t *__restrict__ graph, int R, const int32_t *__restrict__ entries,
-                                                           int E, const int32_t *__restrict__ row_ids, int ef, int width, int max_iters,
+                                                           const int32_t *__restrict__ graph, int R, EN entries, int E,
+                                                           const int32_t *__restrict__ row_ids, int ef, int width, int max_iters,
                                                            int slots, int shift, int k, int kp, float *__restrict__ out_s,
                                                            int64_t *__restrict__ out_i, int64_t idx_offset,
                                                            int32_t *__restrict__ status) {
+    constexpr bool SEEDED = std::is_same<EN, GraphSeeds>::value;
+    [[maybe_unused]] const EN &sd = entries;
     extern __shared__ __attribute__((aligned(16))) int graph_tab[];
     SlList<int, false> top = sl_shared_list<int, false>();
     __shared__ unsigned long long open_s[TSIM_GRAPH_MAX_EF / 64];   // beam entries not yet expanded, one bit each
@@ -97,7 +116,32 @@ __global__ __launch_bounds__(256) void graph_search_kernel(int64_t Q, int64_t N,
             nnew_s = 0;
             st_s = 0;
         }
+        if constexpr (SEEDED) {   // the query's P probes into stage, which nothing uses before the entry step
+            if (sd.probes) {
+                if (tid < sd.P) stage[tid] = sd.probes[q * sd.ld_probes + tid];
+            } else {
+                // the P best centroids: the running list, blocks of 256 centroids, eight to a wave's batch as below
+                const T *xc = static_cast<const T *>(sd.centroids);
+                const int pp = sd.pp, nc = (int)sd.T;
+                top.reset(pp);
+                for (int c0 = 0; c0 < nc; c0 += GRAPH_STAGE) {   // workgroup-uniform
+                    const int n = nc - c0 < GRAPH_STAGE ? nc - c0 : GRAPH_STAGE;
+                    const SlBound<int> w = top.bound(sd.P);
+                    for (int b = wave * 8; b < n; b += 32) {   // wave-uniform
+                        const int nvalid = n - b < 8 ? n - b : 8;
+                        const int row = c0 + b + (lane < nvalid ? lane : 0);
+                        const float s = exact_score_batch<T, COS, 8>(eqr, xc, sd.ld_centroids, row, 0, nvalid, d, lane);
+                        if (lane < nvalid) top.offer(s, row, w);
+                    }
+                    top.flush(pp);
+                }
+                if (tid < sd.P) stage[tid] = top.top_i[tid] == sl_pad<int>() ? -1 : top.top_i[tid];
+                __syncthreads();   // (the list is read: the reset below may overwrite it)
+            }
+        }
         top.reset(kp);   // (a barrier)
+        if constexpr (SEEDED)
+            if (sd.out_probes && tid < sd.P) sd.out_probes[q * sd.P + tid] = stage[tid];
         int bits = 0;
         for (int it = -1;; ++it) {   // it == -1: the entry points
             int cnt = E;
@@ -141,7 +185,20 @@ __global__ __launch_bounds__(256) void graph_search_kernel(int64_t Q, int64_t N,
                 cnt = np * R;
             }
             const int t = tid < cnt ? tid : 0;
-            const int id = it < 0 ? entries[t] : graph[(int64_t)par_s[t / R] * R + t % R];
+            int id;
+            if constexpr (SEEDED) {
+                if (it < 0) {   // workgroup-uniform
+                    const int l = stage[t / sd.S];
+                    const bool ok = l >= 0 && l < sd.T;
+                    if (tid < cnt && l >= sd.T) bits |= TSIM_GRAPH_ST_ROW;
+                    id = !ok ? -1 : sd.seeds ? sd.seeds[(int64_t)l * sd.S + t % sd.S] : l;
+                    __syncthreads();   // everyone has read its probe: stage takes the rows of the step
+                } else {
+                    id = graph[(int64_t)par_s[t / R] * R + t % R];
+                }
+            } else {
+                id = it < 0 ? entries[t] : graph[(int64_t)par_s[t / R] * R + t % R];
+            }
             if (tid < cnt && id >= N) bits |= TSIM_GRAPH_ST_ROW;
             if (tid < cnt && id >= 0 && id < N && graph_visit(graph_tab, mask, shift, id)) stage[atomicAdd(&nnew_s, 1)] = id;
             __syncthreads();
@@ -278,21 +335,85 @@ extern "C" int tsim_graph_search(int space, const float *eq_f32, int64_t ldq_f32
     const size_t lds = (size_t)slots * 4;
     static DevOnce once_cos, once_dot, once_l2;
     if (space == TSIM_SPACE_COSINE) {
-        TSIM_MAX_LDS(once_cos, (graph_search_kernel<float, true>), TSIM_GRAPH_MAX_TABLE_BYTES);
-        hipLaunchKernelGGL((graph_search_kernel<float, true>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32, ld_rows, d,
-                           graph, R, entries, n_entries, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
+        TSIM_MAX_LDS(once_cos, (graph_search_kernel<float, true, GraphShared>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<float, true, GraphShared>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32,
+                           ld_rows, d, graph, R, entries, n_entries, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
                            idx_offset, out_status);
     } else if (space == TSIM_SPACE_DOT) {
-        TSIM_MAX_LDS(once_dot, (graph_search_kernel<float, false>), TSIM_GRAPH_MAX_TABLE_BYTES);
-        hipLaunchKernelGGL((graph_search_kernel<float, false>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32, ld_rows,
-                           d, graph, R, entries, n_entries, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
+        TSIM_MAX_LDS(once_dot, (graph_search_kernel<float, false, GraphShared>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<float, false, GraphShared>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32,
+                           ld_rows, d, graph, R, entries, n_entries, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
                            idx_offset, out_status);
     } else {   // (float32 rows read through l2_f32: with_score_mode says why)
-        TSIM_MAX_LDS(once_l2, (graph_search_kernel<l2_f32, false>), TSIM_GRAPH_MAX_TABLE_BYTES);
-        hipLaunchKernelGGL((graph_search_kernel<l2_f32, false>), dim3(grid), dim3(256), lds, st, Q, N,
+        TSIM_MAX_LDS(once_l2, (graph_search_kernel<l2_f32, false, GraphShared>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<l2_f32, false, GraphShared>), dim3(grid), dim3(256), lds, st, Q, N,
                            reinterpret_cast<const l2_f32 *>(eq_f32), ldq_f32, reinterpret_cast<const l2_f32 *>(rows_f32), ld_rows, d, graph,
                            R, entries, n_entries, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx, idx_offset,
                            out_status);
+    }
+    TSIM_HIP_CHECK(hipGetLastError());
+    return TSIM_OK;
+}
+
+extern "C" int tsim_graph_search_seeded(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *rows_f32,
+                                        int64_t ld_rows, int64_t N, int d, const int32_t *graph, int R, const int32_t *seeds,
+                                        int64_t n_lists, int n_seeds, const int32_t *probes, int64_t ld_probes, int n_probe,
+                                        const float *centroids, int64_t ld_centroids, const int32_t *row_ids, int ef, int width,
+                                        int max_iters, int k, float *out_scores, int64_t *out_idx, int64_t idx_offset,
+                                        int32_t *out_status, int32_t *out_probes, void *stream) {
+    using namespace tsim;
+    const char *what = "graph_search_seeded";
+    TSIM_REQUIRE(eq_f32 && rows_f32 && graph && out_scores && out_idx, "%s: null pointer", what);
+    TSIM_REQUIRE((probes != nullptr) != (centroids != nullptr), "%s: exactly one of probes and centroids must be given", what);
+    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT || space == TSIM_SPACE_L2, "%s: unknown space %d", what, space);
+    TSIM_REQUIRE(Q > 0 && N > 0, "%s: bad shape Q=%lld N=%lld", what, (long long)Q, (long long)N);
+    TSIM_REQUIRE(R >= 1 && R <= GRAPH_MAX_R, "%s: degree R=%d outside 1..%d", what, R, GRAPH_MAX_R);
+    const int S = seeds ? n_seeds : 1;          // without a seed table a probe is a row
+    const int64_t T = seeds ? n_lists : N;
+    TSIM_REQUIRE(S >= 1 && n_probe >= 1 && (int64_t)S * n_probe <= GRAPH_MAX_E,
+                 "%s: %d probes of %d seeds: the entry points must number 1..%d", what, n_probe, S, GRAPH_MAX_E);
+    TSIM_REQUIRE(T >= 1 && T < (1ll << 31) - 64, "%s: %lld lists, outside 1..2^31-65", what, (long long)T);
+    TSIM_REQUIRE(!centroids || T <= TSIM_GRAPH_MAX_COARSE_LISTS, "%s: the kernel's coarse phase takes at most %d centroids, not %lld",
+                 what, TSIM_GRAPH_MAX_COARSE_LISTS, (long long)T);
+    TSIM_REQUIRE(!probes || ld_probes >= n_probe, "%s: probes row stride %lld < n_probe=%d", what, (long long)ld_probes, n_probe);
+    TSIM_REQUIRE(width >= 1 && width <= GRAPH_MAX_WIDTH, "%s: width=%d outside 1..%d", what, width, GRAPH_MAX_WIDTH);
+    TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
+    TSIM_REQUIRE(ef >= k && ef <= TSIM_GRAPH_MAX_EF, "%s: ef=%d outside k=%d..%d", what, ef, k, TSIM_GRAPH_MAX_EF);
+    TSIM_REQUIRE(max_iters >= 1, "%s: max_iters=%d < 1", what, max_iters);
+    TSIM_REQUIRE(d >= 1 && d <= 64 * XS_MAXI, "%s: d=%d outside 1..%d", what, d, 64 * XS_MAXI);
+    TSIM_REQUIRE(space != TSIM_SPACE_L2 || d < 64 * XS_MAXI, "%s: d=%d (the Euclidean space takes d <= %d)", what, d, 64 * XS_MAXI - 1);
+    TSIM_REQUIRE(ldq_f32 >= d && ld_rows >= d && (!centroids || ld_centroids >= d), "%s: float32 row strides %lld/%lld/%lld < d=%d", what,
+                 (long long)ldq_f32, (long long)ld_rows, (long long)ld_centroids, d);
+    TSIM_REQUIRE(N < (1ll << 31) - 64 && Q < (1ll << 31), "%s: too large for 32-bit row ids (N=%lld, Q=%lld)", what, (long long)N,
+                 (long long)Q);
+    const int E = S * n_probe;
+    const int64_t slots = graph_table_slots(E, R, width, max_iters);
+    TSIM_REQUIRE(slots <= GRAPH_MAX_SLOTS,
+                 "%s: a query may visit %d + %d * %d * %d rows; the visited table holds at most %lld (%d B of LDS): lower max_iters", what,
+                 E, max_iters, width, R, (long long)(GRAPH_MAX_SLOTS / 2), TSIM_GRAPH_MAX_TABLE_BYTES);
+    int shift = 32;
+    while ((1ll << (32 - shift)) < slots) --shift;
+    hipStream_t st = as_stream(stream);
+    const int kp = sl_list_len(ef);
+    const unsigned grid = (unsigned)(Q < 65536 ? Q : 65536);
+    const size_t lds = (size_t)slots * 4;
+    const GraphSeeds sd{seeds, probes, centroids, T, ld_probes, ld_centroids, S, n_probe, sl_list_len(n_probe), out_probes};
+    static DevOnce once_cos, once_dot, once_l2;
+    if (space == TSIM_SPACE_COSINE) {
+        TSIM_MAX_LDS(once_cos, (graph_search_kernel<float, true, GraphSeeds>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<float, true, GraphSeeds>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32,
+                           ld_rows, d, graph, R, sd, E, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
+                           idx_offset, out_status);
+    } else if (space == TSIM_SPACE_DOT) {
+        TSIM_MAX_LDS(once_dot, (graph_search_kernel<float, false, GraphSeeds>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<float, false, GraphSeeds>), dim3(grid), dim3(256), lds, st, Q, N, eq_f32, ldq_f32, rows_f32,
+                           ld_rows, d, graph, R, sd, E, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx,
+                           idx_offset, out_status);
+    } else {   // (float32 rows, and centroids, read through l2_f32)
+        TSIM_MAX_LDS(once_l2, (graph_search_kernel<l2_f32, false, GraphSeeds>), TSIM_GRAPH_MAX_TABLE_BYTES);
+        hipLaunchKernelGGL((graph_search_kernel<l2_f32, false, GraphSeeds>), dim3(grid), dim3(256), lds, st, Q, N,
+                           reinterpret_cast<const l2_f32 *>(eq_f32), ldq_f32, reinterpret_cast<const l2_f32 *>(rows_f32), ld_rows, d, graph,
+                           R, sd, E, row_ids, ef, width, max_iters, (int)slots, shift, k, kp, out_scores, out_idx, idx_offset, out_status);
     }
     TSIM_HIP_CHECK(hipGetLastError());
     return TSIM_OK;

@@ -20,11 +20,23 @@ pruned by detour count (:func:`ops.graph_prune`) and merged with its reverse edg
 entry points are ``min(n_entries, n)`` rows drawn by a ``torch.Generator`` seeded with ``seed``, stored in the index and its file.
 The build is a self-search of the corpus: about a second for 1 M rows at the flat search's rate, plus the pruning.
 
+Entry points (``entry``).  ``'shared'`` (default): the ``n_entries`` drawn rows above, the same for every query.  On a clustered
+corpus the kNN graph falls apart into islands and a query whose island holds no entry point finds nothing; ``'coarse'`` starts
+every query inside its own neighbourhood instead: the build clusters the live rows into ``nlist`` lists (0: ``max(1, min(4096,
+int(sqrt(n))))``, never more than ``n``) with :func:`ivf_index.kmeans_centroids` — ``GpuIVFIndex``'s quantiser, bit for bit — or takes
+``build(centroids=...)`` as given, and keeps a seed table ``[nlist, seeds_per_list]``: the stored rows of best score to each
+centroid by the index's exact search, rank order, -1 where it pads.  A query enters through the seeds of its ``nprobe`` best
+centroids (``set_nprobe``; ``nprobe * seeds_per_list`` in 1..256), :func:`ops.graph_search_seeded`.  The probes come from the
+search kernel's own coarse phase, or — past ``COARSE_KERNEL_MAX_LISTS`` centroids or ``COARSE_KERNEL_MAX_QUERIES`` queries a
+call — from the exact flat search of the queries against the centroids; both give the same probes.  A seed may be a
+tombstone: tombstones route.
+
 NOT incremental: ``add_items`` after a build marks the graph stale and the next search rebuilds it whole.  ``mark_deleted`` sets
 a tombstone: the row is still traversed (it routes the search) and never returned; a rebuild compacts tombstones away.
 
 On disk (``index.bin``, a numpy ``.npz`` without pickling): rows, labels, tombstones, the graph, the entry points, the
-parameters and ``kind = 'graph'``; a file of another space or kind raises ``ValueError``.
+parameters and ``kind = 'graph'``; with ``entry='coarse'`` also the centroids, the seed table, ``entry``, ``nlist``, ``nprobe`` and
+``seeds_per_list`` (a file without them loads as ``'shared'``); a file of another space or kind raises ``ValueError``.
 
 Not here (``NotImplementedError``; ``GpuFlatIndex`` has them): ``filter=``, range and radius search.
 """
@@ -40,6 +52,13 @@ from . import ops
 
 _OPS_SPACE = {"cosine": "cosine", "ip": "dot", "euclidean": "l2"}
 _BUILD_CHUNK = 16384        # queries of one self-search call
+# entry='coarse': where the probes come from.  The kernel's coarse phase costs a query 0.04 ms at 256 centroids, 0.09 - 0.11 at
+# 1 024 and 0.31 - 0.34 at 4 096 (it scores them with the exact kernel, a workgroup a query); the flat search of the queries against
+# the centroids, in launches of its own, 0.09 - 0.16 ms whatever their number (DESIGN.md "Graph index", *Per-query entry points*:
+# 1 M x 384, Q = 1 / 16 / 256).  So the kernel up to 1 024 lists.  COARSE_KERNEL_MAX_QUERIES is no measured crossover: no call of more
+# than 256 queries was measured, and beyond what was measured the index takes the flat route, whose cost does not grow with nlist.
+COARSE_KERNEL_MAX_LISTS = 1024
+COARSE_KERNEL_MAX_QUERIES = 256
 
 
 def degree_params(M: int, ef_construction: int) -> Tuple[int, int]:
@@ -55,7 +74,8 @@ class GpuGraphIndex:
     KIND = "graph"
 
     def __init__(self, space: str = "cosine", dim: int = 0, M: int = 16, ef_construction: int = 0, ef: int = 64, width: int = 4,
-                 n_entries: int = 64, max_iters: Optional[int] = None, device: Optional[torch.device] = None, seed: int = 0):
+                 n_entries: int = 64, max_iters: Optional[int] = None, device: Optional[torch.device] = None, seed: int = 0,
+                 entry: str = "shared", nlist: int = 0, nprobe: int = 8, seeds_per_list: int = 4):
         if space not in self.SPACES:
             raise ValueError(f"GpuGraphIndex implements the spaces {self.SPACES}, not {space!r}")
         self.space = space
@@ -67,6 +87,14 @@ class GpuGraphIndex:
         if not 1 <= int(n_entries) <= ops.GRAPH_MAX_ENTRIES:
             raise ValueError(f"n_entries={n_entries} outside 1..{ops.GRAPH_MAX_ENTRIES}")
         self.width, self.n_entries, self.max_iters, self.seed = int(width), int(n_entries), max_iters, int(seed)
+        if entry not in ("shared", "coarse"):
+            raise ValueError(f"entry={entry!r}: 'shared' or 'coarse'")
+        if int(nlist) < 0:
+            raise ValueError(f"nlist={nlist} < 0")
+        self.entry, self.nlist, self.seeds_per_list = entry, int(nlist), int(seeds_per_list)
+        self.nprobe = int(nprobe)                      # (entry='shared' ignores it and seeds_per_list, whatever they are)
+        self._check_entry_budget()
+        self.coarse = "auto"                           # 'kernel' | 'flat': force one route of the probes (tools/bench_graph.py)
         self.ef = 1
         self.set_ef(ef)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
@@ -78,6 +106,10 @@ class GpuGraphIndex:
         self.graph: Optional[torch.Tensor] = None      # [n, R] int32, or None: stale
         self.entries: Optional[torch.Tensor] = None    # [E] int32
         self._row_ids = None                           # int32 [n] with -1 at the tombstones, or None: rebuild it
+        self.centroids: Optional[torch.Tensor] = None  # entry='coarse': [T, d] float32, stale with the graph
+        self.seeds: Optional[torch.Tensor] = None      # [T, seeds_per_list] int32
+        self._given_centroids = None                   # what build(centroids=...) installed: kept across rebuilds
+        self._coarse_ops = None                        # the centroids as the operands of the space's exact search
 
     # ------------------------------------------------------------------ hnswlib-shaped surface
     def init_index(self, max_elements: int, ef_construction: int = 0, M: int = 0):
@@ -97,6 +129,16 @@ class GpuGraphIndex:
         if ef > ops.GRAPH_MAX_EF:
             raise ValueError(f"ef={ef} outside 1..{ops.GRAPH_MAX_EF}")
         self.ef = ef
+
+    def _check_entry_budget(self, nprobe: Optional[int] = None):
+        """entry='coarse': a query starts from nprobe * seeds_per_list rows, 1..256 of them."""
+        n = self.nprobe if nprobe is None else int(nprobe)
+        if self.entry == "coarse" and (n < 1 or self.seeds_per_list < 1 or n * self.seeds_per_list > ops.GRAPH_MAX_ENTRIES):
+            raise ValueError(f"nprobe={n} * seeds_per_list={self.seeds_per_list} outside 1..{ops.GRAPH_MAX_ENTRIES}")
+
+    def set_nprobe(self, n: int):
+        self._check_entry_budget(n)
+        self.nprobe = int(n)
 
     def resize_index(self, new_size: int):
         self._reserve(int(new_size))
@@ -149,37 +191,73 @@ class GpuGraphIndex:
         return labels.cpu().numpy(), (1.0 - scores).cpu().numpy()
 
     # ------------------------------------------------------------------ build
-    def _self_search(self, x: torch.Tensor, k: int) -> torch.Tensor:
-        """idx [n, k] int64 of the exact search of the rows against themselves, in the index's space."""
-        d = self.dim
+    def _operands(self, x: torch.Tensor):
+        """``x`` as the stored operand of the space's exact search."""
         if self.space == "cosine":
-            half, rho = ops.l2norm_rows(x, return_rho=True)
-            run = lambda a, b: ops.cosine_topk(half[a:b], half, d, k, eq_f32=x[a:b], ec_f32=x, rho_c=rho)[1]
+            return ops.l2norm_rows(x, return_rho=True)
+        return ops.dot_scaled_rows(x) if self.space == "ip" else ops.l2_rows(x)
+
+    def _exact_search(self, q: torch.Tensor, x: torch.Tensor, k: int, operands=None) -> torch.Tensor:
+        """idx [Q, k] int64 of the exact search of the rows ``q`` against the rows ``x`` (``operands``: ``_operands(x)``), -1 where
+        it pads: (score desc, row asc), so a tie goes to the lower row."""
+        d = self.dim
+        operands = self._operands(x) if operands is None else operands
+        if self.space == "cosine":
+            half, rho = operands
+            qhalf = (lambda a, b: half[a:b]) if q is x else (lambda a, b: ops.l2norm_rows(q[a:b]))      # (the self-search of the build)
+            run = lambda a, b: ops.cosine_topk(qhalf(a, b), half, d, k, eq_f32=q[a:b], ec_f32=x, rho_c=rho)[1]
         elif self.space == "ip":
-            half, rho, scale = ops.dot_scaled_rows(x)
-            run = lambda a, b: ops.dot_topk(ops.l2norm_rows(x[a:b]), half, d, k, eq_f32=x[a:b], ec_f32=x, rho_c=rho, scale_c=scale)[1]
+            half, rho, scale = operands
+            run = lambda a, b: ops.dot_topk(ops.l2norm_rows(q[a:b]), half, d, k, eq_f32=q[a:b], ec_f32=x, rho_c=rho, scale_c=scale)[1]
         else:
-            half, rho, scale = ops.l2_rows(x)
-            run = lambda a, b: ops.l2_topk(ops.l2_query_rows(x[a:b], scale), half, d, k, eq_f32=x[a:b], ec_f32=x, rho_c=rho,
+            half, rho, scale = operands
+            run = lambda a, b: ops.l2_topk(ops.l2_query_rows(q[a:b], scale), half, d, k, eq_f32=q[a:b], ec_f32=x, rho_c=rho,
                                            scale_c=scale)[1]
-        n = x.shape[0]
+        n = q.shape[0]
         return torch.cat([run(a, min(a + _BUILD_CHUNK, n)) for a in range(0, n, _BUILD_CHUNK)], dim=0)
+
+    def build_coarse(self, centroids=None):
+        """(Re)build the coarse quantiser of ``entry='coarse'`` for the stored rows: the centroids (``centroids`` [T, d]: installed
+        as given, and again at every rebuild; else k-means) and the seed table."""
+        self._check_entry_budget()
+        n, S = self._n, self.seeds_per_list
+        x = self._f32[:n]
+        if centroids is not None:
+            c = torch.as_tensor(np.asarray(centroids) if not isinstance(centroids, torch.Tensor) else centroids)
+            c = c.to(self.device, dtype=torch.float32).contiguous()
+            if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != self.dim:
+                raise ValueError(f"centroids must have shape (nlist >= 1, {self.dim}), got {tuple(c.shape)}")
+            self._given_centroids = c
+        if self._given_centroids is not None:
+            c = self._given_centroids
+        else:
+            from .ivf_index import kmeans_centroids
+            nlist = self.nlist if self.nlist > 0 else max(1, min(ops.GRAPH_MAX_COARSE_LISTS, int(n ** 0.5)))
+            c = kmeans_centroids(x, min(nlist, n), self.space, self.seed)
+        self.centroids, self._coarse_ops = c, self._operands(c)
+        ks = min(S, n)
+        seeds = torch.full((c.shape[0], S), -1, dtype=torch.int32, device=self.device)
+        seeds[:, :ks] = self._exact_search(c, x, ks).to(torch.int32)
+        self.seeds = seeds
 
     def knn_graph(self) -> torch.Tensor:
         """G0 [n, K0] int32 of the stored rows (tombstones compacted away first): each row's K0 best other rows, best first."""
         self._compact()
         n, K0 = self._n, self.K0
-        idx = self._self_search(self._f32[:n], K0 + 1)
+        idx = self._exact_search(self._f32[:n], self._f32[:n], K0 + 1)
         own = idx == torch.arange(n, device=self.device)[:, None]
         drop = torch.where(own.any(1), own.to(torch.int8).argmax(1), torch.full((n,), K0, device=self.device))
         keep = torch.arange(K0 + 1, device=self.device)[None, :] != drop[:, None]
         return idx[keep].view(n, K0).to(torch.int32).contiguous()
 
-    def build(self, knn: Optional[torch.Tensor] = None):
+    def build(self, knn: Optional[torch.Tensor] = None, centroids=None):
         """(Re)build the graph and the entry points from the stored live rows.  ``knn``: what :meth:`knn_graph` returned for them
-        (tools/bench_graph.py times the stages apart)."""
+        (tools/bench_graph.py times the stages apart).  ``centroids`` (``entry='coarse'``): :meth:`build_coarse`."""
+        if centroids is not None and self.entry != "coarse":
+            raise ValueError("build(centroids=...) needs entry='coarse'")
         self._compact()
         n = self._n
+        self.centroids = self.seeds = self._coarse_ops = None
         if n == 0:
             self.graph = torch.zeros((0, self.R), dtype=torch.int32, device=self.device)
             self.entries = torch.zeros((0,), dtype=torch.int32, device=self.device)
@@ -189,14 +267,28 @@ class GpuGraphIndex:
         E = min(self.n_entries, n)
         self.entries = torch.randperm(n, generator=g)[:E].sort()[0].to(torch.int32).to(self.device)
         self._row_ids = None
+        if self.entry == "coarse":
+            self.build_coarse(centroids)
 
     def search_params(self, k: int) -> Tuple[int, int]:
         """(ef, max_iters) a search for ``k`` results uses (module docstring)."""
         ef = max(self.ef, int(k))
         E = max(1, min(self.n_entries, self._n))
+        if self.entry == "coarse":
+            E = self._n_probe() * self.seeds_per_list
         fit = ops.graph_max_iters(E, self.R, self.width)
         iters = (3 * ef + 2 * self.width - 1) // (2 * self.width) + 8 if self.max_iters is None else int(self.max_iters)
         return ef, max(1, min(iters, fit))
+
+    def _n_probe(self) -> int:
+        return self.nprobe if self.centroids is None else min(self.nprobe, int(self.centroids.shape[0]))
+
+    def _kernel_coarse(self, Q: int) -> bool:
+        """Whether the search kernel finds the probes itself (module docstring); the other route gives the same probes."""
+        T = int(self.centroids.shape[0])
+        if T > ops.GRAPH_MAX_COARSE_LISTS or self.coarse == "flat":
+            return False
+        return self.coarse == "kernel" or (T <= COARSE_KERNEL_MAX_LISTS and Q <= COARSE_KERNEL_MAX_QUERIES)
 
     # ------------------------------------------------------------------ device-level API
     def search(self, data, k: int, filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -219,9 +311,21 @@ class GpuGraphIndex:
         if self._n_dead and self._row_ids is None:
             ids = torch.arange(n, dtype=torch.int32, device=self.device)
             self._row_ids = torch.where(self._dead[:n], torch.full_like(ids, -1), ids)
+        if self.entry == "coarse" and self.centroids is None:      # (a graph loaded or built before the entry mode was set)
+            self.build_coarse()
         ef, iters = self.search_params(k)
-        s, i = ops.graph_search(_OPS_SPACE[self.space], qf, self._f32[:n], self.graph, self.entries, k, ef, width=self.width,
-                                max_iters=iters, row_ids=self._row_ids if self._n_dead else None)
+        row_ids = self._row_ids if self._n_dead else None
+        if self.entry == "coarse":
+            P = self._n_probe()
+            if self._kernel_coarse(qf.shape[0]):
+                how = dict(centroids=self.centroids, n_probe=P)
+            else:
+                how = dict(probes=self._exact_search(qf, self.centroids, P, self._coarse_ops).to(torch.int32))
+            s, i = ops.graph_search_seeded(_OPS_SPACE[self.space], qf, self._f32[:n], self.graph, k, ef, seeds=self.seeds,
+                                           width=self.width, max_iters=iters, row_ids=row_ids, **how)
+        else:
+            s, i = ops.graph_search(_OPS_SPACE[self.space], qf, self._f32[:n], self.graph, self.entries, k, ef, width=self.width,
+                                    max_iters=iters, row_ids=row_ids)
         lab = torch.where(i >= 0, self._labels[i.clamp(min=0)], torch.full_like(i, -1))
         return lab, s
 
@@ -250,11 +354,19 @@ class GpuGraphIndex:
         rows = self._f32[:n].cpu().numpy() if n else np.zeros((0, self.dim), np.float32)
         labels = self._labels[:n].cpu().numpy() if n else np.zeros((0,), np.int64)
         dead = self._dead[:n].cpu().numpy() if n else np.zeros((0,), bool)
+        coarse = {}
+        if self.entry == "coarse":
+            if self.centroids is None and n:
+                self.build_coarse()
+            coarse = dict(entry=np.array(self.entry), nlist=np.int64(self.nlist), nprobe=np.int64(self.nprobe),
+                          seeds_per_list=np.int64(self.seeds_per_list), given_centroids=np.bool_(self._given_centroids is not None),
+                          centroids=self.centroids.cpu().numpy() if n else np.zeros((0, self.dim), np.float32),
+                          seeds=self.seeds.cpu().numpy() if n else np.zeros((0, self.seeds_per_list), np.int32))
         with open(path, "wb") as f:
             np.savez(f, rows_f32=rows, labels=labels, dead=dead, graph=self.graph.cpu().numpy(), entries=self.entries.cpu().numpy(),
                      dim=np.int64(self.dim), space=np.array(self.space), R=np.int64(self.R), K0=np.int64(self.K0), ef=np.int64(self.ef),
                      width=np.int64(self.width), n_entries=np.int64(self.n_entries), seed=np.int64(self.seed),
-                     kind=np.array(self.KIND))
+                     kind=np.array(self.KIND), **coarse)
 
     def load_index(self, path: str, max_elements: int = 0):
         if os.path.isdir(path):
@@ -284,6 +396,21 @@ class GpuGraphIndex:
         self.entries = torch.from_numpy(np.ascontiguousarray(z["entries"], dtype=np.int32)).to(self.device)
         if self.graph.shape != (n, self.R):
             raise ValueError(f"{path}: the graph is {tuple(self.graph.shape)}, the rows want ({n}, {self.R})")
+        self.entry = str(z["entry"]) if "entry" in z.files else "shared"
+        self.centroids = self.seeds = self._coarse_ops = self._given_centroids = None
+        if self.entry == "coarse":
+            self.nlist = int(z["nlist"]) if "nlist" in z.files else 0
+            self.seeds_per_list = int(z["seeds_per_list"])
+            self.set_nprobe(int(z["nprobe"]))
+        if self.entry == "coarse" and n:      # (an empty index holds no quantiser: the first build makes it)
+            self.centroids = torch.from_numpy(np.ascontiguousarray(z["centroids"], dtype=np.float32)).to(self.device)
+            self.seeds = torch.from_numpy(np.ascontiguousarray(z["seeds"], dtype=np.int32)).to(self.device)
+            if self.centroids.dim() != 2 or self.centroids.shape[0] < 1 or self.centroids.shape[1] != self.dim or \
+                    self.seeds.shape != (self.centroids.shape[0], self.seeds_per_list):
+                raise ValueError(f"{path}: centroids {tuple(self.centroids.shape)} and seeds {tuple(self.seeds.shape)} do not fit")
+            self._coarse_ops = self._operands(self.centroids)
+            if "given_centroids" in z.files and bool(z["given_centroids"]):
+                self._given_centroids = self.centroids
 
     # ------------------------------------------------------------------ internals
     def _check_dim(self):

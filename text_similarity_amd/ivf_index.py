@@ -35,6 +35,30 @@ from . import ops
 _OPS_SPACE = {"cosine": "cosine", "ip": "dot", "euclidean": "l2"}
 
 
+def kmeans_centroids(x: torch.Tensor, nlist: int, space: str, seed: int, niter: int = 20,
+                     max_points_per_list: int = 256) -> torch.Tensor:
+    """Centres [nlist, d] float32 of the device rows ``x`` [n >= nlist, d]: Lloyd's iterations of
+    :class:`pipeline.clustering.ClusteringPipeline` on a sample of at most ``max_points_per_list * nlist`` rows drawn with
+    ``seed``, on the unit rows for ``'cosine'``.  The coarse quantiser of :class:`GpuIVFIndex` and of
+    :class:`graph_index.GpuGraphIndex` (``entry='coarse'``): the same rows, ``nlist`` and seed give the same bits in both."""
+    m = int(max_points_per_list) * int(nlist)
+    if x.shape[0] > m:
+        g = torch.Generator(device="cpu").manual_seed(int(seed))
+        x = x[torch.randperm(x.shape[0], generator=g)[:m].sort()[0].to(x.device)]
+    if space == "cosine":
+        x = x / x.norm(dim=1, keepdim=True).clamp(min=1e-12)
+    from .pipeline.clustering import ClusteringPipeline
+    km = ClusteringPipeline(int(nlist), params=None, model=None, max_iter=int(niter), seed=int(seed))
+    # fit's update step is a scatter-add, which adds in whatever order its atomics land unless torch is asked for its
+    # deterministic form: with it, the same rows and seed give the same centres bit for bit — and so the same lists
+    was, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        return km.fit(x.contiguous()).cluster_centers_.contiguous()
+    finally:
+        torch.use_deterministic_algorithms(was, warn_only=warn)
+
+
 def pack_lists(list_numbers: torch.Tensor, nlist: int):
     """The packed layout of ``n`` rows with list numbers in [0, nlist): ``(order int64 [n], list_off int64 [nlist+1], row_ids int32
     [n])``.  ``order`` is the stable sort of the list numbers — position p of the packed form holds row ``order[p]``, the rows of
@@ -170,22 +194,7 @@ class GpuIVFIndex:
                 self._check_dim()
             if x.shape[1] != self.dim:
                 raise ValueError(f"expected width {self.dim}, got {x.shape[1]}")
-            m = int(max_points_per_list) * self.nlist
-            if x.shape[0] > m:
-                g = torch.Generator(device="cpu").manual_seed(self.seed)
-                x = x[torch.randperm(x.shape[0], generator=g)[:m].sort()[0].to(self.device)]
-            if self.space == "cosine":
-                x = x / x.norm(dim=1, keepdim=True).clamp(min=1e-12)
-            from .pipeline.clustering import ClusteringPipeline
-            km = ClusteringPipeline(self.nlist, params=None, model=None, max_iter=int(niter), seed=self.seed)
-            # fit's update step is a scatter-add, which adds in whatever order its atomics land unless torch is asked for its
-            # deterministic form: with it, the same rows and seed give the same centres bit for bit — and so the same lists
-            was, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
-            torch.use_deterministic_algorithms(True, warn_only=True)
-            try:
-                c = km.fit(x.contiguous()).cluster_centers_.contiguous()
-            finally:
-                torch.use_deterministic_algorithms(was, warn_only=warn)
+            c = kmeans_centroids(x, self.nlist, self.space, self.seed, niter=niter, max_points_per_list=max_points_per_list)
         self.centroids = c
         if self.space == "cosine":
             self._coarse_ops = ops.l2norm_rows(c, return_rho=True)

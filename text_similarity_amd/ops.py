@@ -529,6 +529,7 @@ def ivf_scan_topk(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, list
 GRAPH_ST_ROW, GRAPH_ST_ITERS = _lib.GRAPH_ST_ROW, _lib.GRAPH_ST_ITERS
 GRAPH_MAX_DEGREE, GRAPH_MAX_ENTRIES, GRAPH_MAX_WIDTH, GRAPH_MAX_EF = 64, 256, 4, 1024     # include/tsim.h TSIM_GRAPH_MAX_*
 GRAPH_PRUNE_MAX_K0 = 128                                                                  # TSIM_GRAPH_PRUNE_MAX_K0
+GRAPH_MAX_COARSE_LISTS = _lib.GRAPH_MAX_COARSE_LISTS                                      # TSIM_GRAPH_MAX_COARSE_LISTS
 GRAPH_LDS_LIMIT = _lib.GRAPH_STATIC_LDS_BYTES + _lib.GRAPH_MAX_TABLE_BYTES                # what one workgroup may take
 
 
@@ -596,6 +597,89 @@ def graph_search(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, graph
                                  status.data_ptr() if return_status else 0, _stream(eq_f32))
         _lib.check(rc, what)
     return (scores, idx, status) if return_status else (scores, idx)
+
+
+def graph_search_seeded(space: str, eq_f32: torch.Tensor, rows_f32: torch.Tensor, graph: torch.Tensor, k: int, ef: int, *,
+                        probes: Optional[torch.Tensor] = None, centroids: Optional[torch.Tensor] = None,
+                        n_probe: Optional[int] = None, seeds: Optional[torch.Tensor] = None, width: int = 4,
+                        max_iters: Optional[int] = None, row_ids: Optional[torch.Tensor] = None, idx_offset: int = 0,
+                        return_status: bool = False, return_probes: bool = False):
+    """:func:`graph_search` with entry points per QUERY, in two levels (include/tsim.h tsim_graph_search_seeded): query q starts
+    from ``seeds[probes[q][p]][s]`` for all p, s.  ``seeds`` int32 [T,S] contiguous: the rows a search entering through list l
+    starts from; None: a probe IS a row (S = 1, T = N) and ``probes`` is the plain [Q,E] table of entry points.  Exactly one of
+    ``probes`` int32 [Q,P] (unit inner stride; rows may be strided) and ``centroids`` float32 [T,d] (T <= GRAPH_MAX_COARSE_LISTS)
+    with ``n_probe`` = P: with centroids the kernel finds the probes itself, the P centroids of best score to the query ordered by
+    (score desc, list asc), NaN dropped, -1 padded — the ids of the list search of the query against the centroids.  1 <= P S <=
+    256.  A negative probe or seed is padding; a probe >= T or a seed >= N is never dereferenced and sets ``GRAPH_ST_ROW``.
+    ``max_iters`` defaults to ``graph_max_iters(P S, R, width)``.  ``return_probes`` adds the int32 [Q,P] probes used.  Everything
+    else is :func:`graph_search`'s."""
+    what = "graph_search_seeded"
+    if space not in IVF_SPACES:
+        raise ValueError(f"{what}: space {space!r}: one of {tuple(IVF_SPACES)}")
+    if (probes is None) == (centroids is None):
+        raise ValueError(f"{what}: exactly one of probes and centroids must be given")
+    _need_gpu(eq_f32, rows_f32, graph)
+    dev = eq_f32.device
+    for t, name in ((eq_f32, "eq_f32"), (rows_f32, "rows_f32")) + (((centroids, "centroids"),) if centroids is not None else ()):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be float32 [rows, d] with unit inner stride")
+    Q, d = eq_f32.shape
+    N = rows_f32.shape[0]
+    if rows_f32.shape[1] != d:
+        raise ValueError(f"{what}: query rows are {d} wide, stored rows {rows_f32.shape[1]}")
+    if space == "l2":
+        _l2_dim(d, what)
+    if graph.dtype != torch.int32 or graph.dim() != 2 or graph.shape[0] != N or not graph.is_contiguous():
+        raise ValueError(f"{what}: graph must be a contiguous int32 [{N}, R] tensor")
+    T, S = N, 1
+    if seeds is not None:
+        _need_gpu(seeds)
+        if seeds.dtype != torch.int32 or seeds.dim() != 2 or not seeds.is_contiguous():
+            raise ValueError(f"{what}: seeds must be a contiguous int32 [T, S] tensor")
+        T, S = int(seeds.shape[0]), int(seeds.shape[1])
+    if probes is not None:
+        _need_gpu(probes)
+        if probes.dtype != torch.int32 or probes.dim() != 2 or probes.shape[0] != Q or probes.stride(1) != 1:
+            raise ValueError(f"{what}: probes must be int32 [{Q}, P] with unit inner stride")
+        if n_probe is not None and int(n_probe) != probes.shape[1]:
+            raise ValueError(f"{what}: n_probe={n_probe}, probes hold {probes.shape[1]} a query")
+        P = int(probes.shape[1])
+    else:
+        _need_gpu(centroids)
+        if n_probe is None:
+            raise ValueError(f"{what}: centroids need n_probe")
+        if centroids.shape != (T, d):
+            raise ValueError(f"{what}: centroids must have shape ({T}, {d}), got {tuple(centroids.shape)}")
+        P = int(n_probe)
+    if row_ids is not None:
+        _need_gpu(row_ids)
+        if row_ids.dtype != torch.int32 or row_ids.shape != (N,) or not row_ids.is_contiguous():
+            raise ValueError(f"{what}: row_ids must be a contiguous int32 [{N}] tensor")
+    k, ef, width, R = int(k), int(ef), int(width), int(graph.shape[1])
+    if max_iters is None:
+        max_iters = max(1, graph_max_iters(P * S, max(R, 1), min(max(width, 1), GRAPH_MAX_WIDTH)))
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    status = torch.zeros((Q,), dtype=torch.int32, device=dev) if return_status else None
+    used = torch.full((Q, max(P, 0)), -1, dtype=torch.int32, device=dev) if return_probes else None
+    out = (scores, idx) + ((status,) if return_status else ()) + ((used,) if return_probes else ())
+    if Q == 0:
+        return out
+    if N == 0:
+        raise ValueError(f"{what}: no rows")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        rc = L.tsim_graph_search_seeded(IVF_SPACES[space], eq_f32.data_ptr(), _row_stride(eq_f32), Q, rows_f32.data_ptr(),
+                                        _row_stride(rows_f32), N, d, graph.data_ptr(), R, seeds.data_ptr() if seeds is not None else 0, T,
+                                        S, probes.data_ptr() if probes is not None else 0,
+                                        _row_stride(probes) if probes is not None else 0, P,
+                                        centroids.data_ptr() if centroids is not None else 0,
+                                        _row_stride(centroids) if centroids is not None else 0,
+                                        row_ids.data_ptr() if row_ids is not None else 0, ef, width, int(max_iters), k, scores.data_ptr(),
+                                        idx.data_ptr(), idx_offset, status.data_ptr() if return_status else 0,
+                                        used.data_ptr() if return_probes else 0, _stream(eq_f32))
+        _lib.check(rc, what)
+    return out
 
 
 def graph_prune(knn: torch.Tensor, R: int, return_detours: bool = False):

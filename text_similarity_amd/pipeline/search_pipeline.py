@@ -256,15 +256,21 @@ class SemanticSearchPipeline(SearchPipeline):
     bytes a row in ``nlist`` lists of which a query reads ``nprobe``; removal works, filters do not.  ``index_type='graph'`` keeps a
     :class:`text_similarity_amd.graph_index.GpuGraphIndex`, the family of the reference's hnswlib index, and for it ``ef`` /
     ``ef_construction`` / ``M`` are NOT unused: ``M`` sets the graph's degree, ``ef_construction`` the width of the kNN graph the build
-    prunes and ``ef`` the beam of a search, as that class documents; removal works (tombstones), filters do not."""
+    prunes and ``ef`` the beam of a search, as that class documents; removal works (tombstones), filters do not.  ``graph_entry='coarse'``
+    (default ``'shared'``) starts every query from the seed rows of its ``nprobe`` nearest of ``nlist`` k-means centroids instead of
+    from entry points shared by all queries — what a corpus clustered by topic needs (``nlist`` None: the index's own default,
+    about sqrt(n)).  ``nlist`` None means 1024 for ``'ivf'`` and ``'ivfpq'``."""
 
-    def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat", nlist: int = 1024,
-                 nprobe: int = 8, pq_m: int = 8, **kwargs):
+    def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat",
+                 nlist: Optional[int] = None, nprobe: int = 8, pq_m: int = 8, graph_entry: str = "shared", **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
         self.score_function = resolve_score_function(score_function, self.model)
         hidden = getattr(self.params.model_parameters, "hidden_size", None) or self.model.get_sentence_embedding_dimension()
         space = "ip" if self.score_function == "dot" else "cosine"
+        if graph_entry != "shared" and index_type != "graph":
+            raise ValueError(f"graph_entry={graph_entry!r} needs index_type='graph'")
+        graph_nlist, nlist = (0 if nlist is None else nlist), (1024 if nlist is None else nlist)
         if index_type == "flat":
             self.index = GpuFlatIndex(space=space, dim=hidden, device=self.params.device)
         elif index_type == "ivf":   # approximate: each query is scored against the nprobe of nlist lists nearest to it
@@ -275,7 +281,8 @@ class SemanticSearchPipeline(SearchPipeline):
             self.index = GpuIVFPQIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, M=pq_m, device=self.params.device)
         elif index_type == "graph":   # approximate: a beam search over a proximity graph; ef / ef_construction / M mean something
             self.index = GpuGraphIndex(space=space, dim=hidden, M=getattr(self.params, "M", 0),
-                                       ef_construction=getattr(self.params, "ef_construction", 0), device=self.params.device)
+                                       ef_construction=getattr(self.params, "ef_construction", 0), device=self.params.device,
+                                       entry=graph_entry, nlist=graph_nlist, nprobe=nprobe)
             self.index.set_ef(getattr(self.params, "ef", 0))
         else:
             raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq', 'ivfpq', 'graph'")

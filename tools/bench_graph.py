@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GpuGraphIndex against GpuFlatIndex and GpuIVFIndex on the GPU box: python tools/bench_graph.py [--N N] [--d D] [--Q ...]
 [--ef ...] [--width ...] [--M M] [--ef-construction C] [--k K] [--nlist L] [--nprobe P] [--rounds R] [--iters I] [--data ...]
+[--entry shared coarse] [--seeds-per-list S] [--coarse kernel flat]
 
 Three corpora, all seeded: ``mixture``, the Gaussian mixture of tools/bench_ivf.py (--components centres of unit variance per
 element, rows = centre + sigma * noise, queries fresh draws from it); ``gauss``, isotropic standard-normal rows and queries —
@@ -12,6 +13,14 @@ the self-search, the pruning and the reverse merge) and one per cell (Q, ef, wid
                                 ALTERNATING inside every round, I calls timed per round between device events;
   recall10, ivf_recall10        recall@10 against the flat result on a fixed set of 256 queries;
   cut                           the share of those queries whose search the iteration cap ended (TSIM_GRAPH_ST_ITERS).
+With ``--entry coarse`` a second graph index with entry='coarse' (the same rows and kNN graph; --nlist lists, --nprobe probes,
+--seeds-per-list seeds) joins the alternation: the build line gains ``coarse_build_s`` (centroids and seed table) and ``nlist``,
+every cell
+  coarse_ms                     {route: ms} for each --coarse route of the probes (kernel: the search kernel's own coarse phase; flat:
+                                the exact flat search of the queries against the centroids, then the kernel), and ``given``: the
+                                search with the probes handed in ready — a route minus ``given`` is what its coarse phase costs;
+  coarse_recall10, coarse_cut   as recall10 and cut.
+--entry shared (the default) prints the lines this tool printed before the option existed.
 Not part of bench.py."""
 import argparse
 import json
@@ -45,6 +54,9 @@ ap.add_argument("--components", type=int, default=4096)
 ap.add_argument("--sigma", type=float, default=1.0)
 ap.add_argument("--latent", type=int, default=16)
 ap.add_argument("--data", nargs="+", default=["mixture", "gauss"], choices=["mixture", "gauss", "manifold"])
+ap.add_argument("--entry", nargs="+", default=["shared"], choices=["shared", "coarse"])
+ap.add_argument("--seeds-per-list", type=int, default=4)
+ap.add_argument("--coarse", nargs="+", default=["kernel", "flat"], choices=["kernel", "flat"])
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_graph.py measures on the GPU: no device found")
@@ -98,12 +110,16 @@ for kind in a.data:
     flat.init_index(N)
     ivf = GpuIVFIndex(a.space, d, a.nlist, nprobe=min(a.nprobe, a.nlist), device=dev, seed=1)
     gr = GpuGraphIndex(a.space, d, M=a.M, ef_construction=a.ef_construction, device=dev)
+    gc = None
+    if "coarse" in a.entry:
+        gc = GpuGraphIndex(a.space, d, M=a.M, ef_construction=a.ef_construction, device=dev, entry="coarse", nlist=a.nlist,
+                           nprobe=a.nprobe, seeds_per_list=a.seeds_per_list)
     g.manual_seed(1000 + N % 997)
     ivf.train(draw(kind, min(N, 64 * a.nlist)), niter=10, max_points_per_list=64)
     for r0 in range(0, N, 1 << 20):
         x = draw(kind, min(1 << 20, N - r0))
         ids = torch.arange(r0, r0 + x.shape[0]).numpy()
-        for ix in (flat, ivf, gr):
+        for ix in (flat, ivf, gr) + ((gc,) if gc is not None else ()):
             ix.add_items(x, ids)
     del x
     knn, t_knn = wall(gr.knn_graph)
@@ -111,12 +127,17 @@ for kind in a.data:
     _, t_merge = wall(lambda: ops.graph_merge_reverse(fwd))
     del fwd
     _, t_rest = wall(lambda: gr.build(knn))
+    extra = {}
+    if gc is not None:
+        gc.build(knn)
+        _, t_coarse = wall(gc.build_coarse)      # (again, alone: the centroids and the seed table)
+        extra = {"coarse_build_s": t_coarse, "nlist": int(gc.centroids.shape[0]), "seeds_per_list": gc.seeds_per_list}
     del knn
     t_build = round(t_knn + t_rest, 3)
     deg = float((gr.graph >= 0).sum(1).float().mean())
     print(json.dumps({"data": kind, "space": a.space, "N": N, "d": d, "R": gr.R, "K0": gr.K0, "entries": int(gr.entries.numel()),
-                      "build_s": t_build, "knn_s": t_knn, "prune_s": t_prune, "merge_s": t_merge, "mean_degree": round(deg, 2)}),
-          flush=True)
+                      "build_s": t_build, "knn_s": t_knn, "prune_s": t_prune, "merge_s": t_merge, "mean_degree": round(deg, 2),
+                      **extra}), flush=True)
     q_all = draw(kind, max(256, max(a.Q)))
     truth = flat.search(q_all[:256], 10)[0]
     ivf_recall = recall(ivf.search(q_all[:256], 10)[0], truth)
@@ -130,16 +151,41 @@ for kind in a.data:
                                   max_iters=iters, return_status=True)[2]
             cut = round(float((st & ops.GRAPH_ST_ITERS).bool().float().mean()), 4)
             lds = ops.graph_search_lds_bytes(int(gr.entries.numel()), gr.R, width, iters)
+            if gc is not None:
+                gc.set_ef(ef)
+                gc.width = width
+                _, c_iters = gc.search_params(10)
+                c_rc = recall(gc.search(q_all[:256], 10)[0], truth)
+                P = gc._n_probe()
+                probes_all = gc._exact_search(q_all.contiguous(), gc.centroids, P, gc._coarse_ops).to(torch.int32)
+                st = ops.graph_search_seeded(_OPS_SPACE[a.space], q_all[:256].contiguous(), gc._f32[:N], gc.graph, 10, efu, seeds=gc.seeds,
+                                             probes=probes_all[:256], width=width, max_iters=c_iters, return_status=True)[2]
+                c_cut = round(float((st & ops.GRAPH_ST_ITERS).bool().float().mean()), 4)
             for Q in a.Q:
                 q = q_all[:Q].contiguous()
                 t_gr, t_ivf, t_flat = [], [], []
+                t_co = {route: [] for route in a.coarse + ["given"]} if gc is not None else {}
+
+                def coarse_run(route):
+                    if route == "given":
+                        pr = probes_all[:Q]
+                        return lambda: ops.graph_search_seeded(_OPS_SPACE[a.space], q, gc._f32[:N], gc.graph, a.k, max(ef, a.k),
+                                                               seeds=gc.seeds, probes=pr, width=width, max_iters=c_iters)
+
+                    def run():
+                        gc.coarse = route
+                        return gc.search(q, a.k)
+                    return run
                 for r in range(a.rounds):
                     runs = [(t_gr, lambda: gr.search(q, a.k)), (t_ivf, lambda: ivf.search(q, a.k)), (t_flat, lambda: flat.search(q, a.k))]
+                    runs += [(t_co[route], coarse_run(route)) for route in t_co]
                     for into, run in (runs if r % 2 == 0 else runs[::-1]):
                         into.append(timed(run, a.iters))
                 print(json.dumps({"data": kind, "N": N, "d": d, "k": a.k, "R": gr.R, "ef": ef, "width": width, "max_iters": iters,
                                   "lds_bytes": lds, "Q": Q, "graph_ms": spread(t_gr), "ivf_ms": spread(t_ivf), "flat_ms": spread(t_flat),
-                                  "recall10": rc, "cut": cut, "ivf_recall10": ivf_recall, "nlist": a.nlist, "nprobe": ivf.nprobe}),
-                      flush=True)
-    del flat, ivf, gr, truth
+                                  "recall10": rc, "cut": cut, "ivf_recall10": ivf_recall, "nlist": a.nlist, "nprobe": ivf.nprobe,
+                                  **({"coarse_ms": {route: spread(v) for route, v in t_co.items()}, "coarse_recall10": c_rc,
+                                      "coarse_cut": c_cut, "coarse_max_iters": c_iters, "seeds_per_list": gc.seeds_per_list}
+                                     if gc is not None else {})}), flush=True)
+    del flat, ivf, gr, gc, truth
     torch.cuda.empty_cache()

@@ -4,7 +4,10 @@ against the restatement of tests/graph_cases.py: scores (float32 bits), ids, sta
 identical.  A search case draws a space, a width of the rows, N, R, E, Q, k, ef, the expansion width, a cap on the iterations
 that may or may not cut the search, a crafted graph (ring, repeats, self-loops, padding, ids >= N, an unreachable island), entry
 points with padding and repeats, and now and then tombstones, NaN rows, duplicate rows or an id offset.  A prune case draws N, K0,
-R and a kNN graph with repeats, padding and ids >= N.
+R and a kNN graph with repeats, padding and ids >= N.  Every fourth case from the second on is a SEEDED search
+(ops.graph_search_seeded against tests/graph_seed_cases.py): the same draws with per-query entry points instead — a seed table
+[T, S] and probes [Q, P] with padding, repeats and ids past their tables, or no seed table (probes as rows), or centroids, some of
+them NaN or duplicates, for the kernel's own coarse phase (then the probes are compared too).
 Usage: python tools/fuzz_graph.py [cases] [seed]"""
 import os
 import sys
@@ -15,6 +18,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np
 import torch
 from graph_cases import detours, forward_lists, graph_search_ref, merge_reverse, random_graph, random_rows
+from graph_seed_cases import graph_search_seeded_ref
 from list_cases import same_bits
 from text_similarity_amd import ops
 
@@ -68,6 +72,32 @@ for case in range(cases):
         ids = rng.permutation(N).astype(np.int32)
         ids[rng.random(N) < 0.3] = -1
     off = 11 if kind == "offset" else 0
+    if case % 4 == 1:
+        how = str(rng.choice(["probes", "rows", "centroids"]))
+        T = N if how == "rows" else int(rng.choice([1, 7, 256, 257, 1000]))
+        S = 1 if how == "rows" else int(rng.choice([s for s in (1, 2, 4, 64, 256) if s <= E]))
+        P = E // S
+        iters = max(1, min(iters, ops.graph_max_iters(P * S, R, width)))
+        seeds = None if how == "rows" else rng.integers(-1, N + 1, size=(T, S))
+        kw = {}
+        if how == "centroids":
+            cent = random_rows(rng, T, d, dup=True)
+            cent[rng.random(T) < 0.1, 0] = np.nan
+            kw = dict(centroids=cent, n_probe=P)
+        else:
+            kw = dict(probes=rng.integers(-1, T + 2, size=(Q, P)))
+        rs, ri, rst, rp = graph_search_seeded_ref(space, q, c, g, ef, width, iters, k, seeds=seeds, row_ids=ids, idx_offset=off, **kw)
+        dkw = {name: (dev(v, np.float32 if name == "centroids" else np.int32) if isinstance(v, np.ndarray) else v) for name, v in kw.items()}
+        s, i, st, pr = ops.graph_search_seeded(space, dev(q), dev(c), dev(g), k, ef, seeds=None if seeds is None else dev(seeds, np.int32),
+                                               width=width, max_iters=iters, row_ids=None if ids is None else dev(ids), idx_offset=off,
+                                               return_status=True, return_probes=True, **dkw)
+        torch.cuda.synchronize()
+        ok = same_bits(s.cpu().numpy(), rs) and np.array_equal(i.cpu().numpy(), ri) and np.array_equal(st.cpu().numpy(), rst) and \
+            np.array_equal(pr.cpu().numpy(), rp)
+        bad += not ok
+        print(f"case {case:3d} seeded {space:6s} {how:9s} d={d:3d} N={N:5d} R={R:2d} T={T:4d} S={S:3d} P={P:3d} Q={Q:2d} k={k:4d} ef={ef:4d} "
+              f"w={width} iters={iters:5d} {kind:6s} {'ok' if ok else 'MISMATCH'}  ({time.time() - t0:.0f} s)", flush=True)
+        continue
     rs, ri, rst = graph_search_ref(space, q, c, g, e, ef, width, iters, k, row_ids=ids, idx_offset=off)
     s, i, st = ops.graph_search(space, dev(q), dev(c), dev(g), dev(e, np.int32), k, ef, width=width, max_iters=iters,
                                 row_ids=None if ids is None else dev(ids), idx_offset=off, return_status=True)
