@@ -388,6 +388,47 @@ int tsim_l2_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const flo
                       void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Community detection, the de-overlap step (sentence-transformers' `util.community_detection`, "fast clustering": every group
+ * of at least min_size rows within a threshold of a centre row, largest first, no row in two groups; no cluster count is
+ * needed).  The candidate communities are the segments of an exact range search of the rows against themselves (above); what
+ * is left is sequential by definition and runs here on the device.
+ * Input: a CSR in PRIORITY order.  lims int64 [C+1], members int32 [T]: community c lists members[lims[c] .. lims[c+1]), in the
+ * order its members are to be kept.  N: the number of rows; min_size >= 1.
+ * Definition.  taken = {}; for c = 0 .. C-1: free = the entries of c whose row is not in taken; if len(free) >= min_size, c is
+ * accepted and its free rows join taken.  A row listed twice in one community is tested twice and counts twice.
+ * Output: accept int32 [C] (1 = accepted) and keep uint8 [T] (1 iff the entry is a free entry of an ACCEPTED community, else
+ * 0): the caller compacts.  status: ONE int32 word, 0 or the TSIM_COMMUNITY_ST_* bits.
+ *   - a negative member is padding and is skipped;
+ *   - a member >= N is never dereferenced; it is dropped (keep 0, not counted) and sets TSIM_COMMUNITY_ST_ROW;
+ *   - lims are replaced by their running maximum clamped to [0, T] before anything reads them, as the list search does: a
+ *     decreasing pair gives an EMPTY community (never accepted: min_size >= 1), and a changed word sets
+ *     TSIM_COMMUNITY_ST_LIMS.
+ * Two forms with the same results (csrc/community_select.h has the argument):
+ *   tsim_community_select_rounds runs rounds first_round .. first_round + max_rounds - 1 of the parallel form: per round one
+ *     claim launch (every undecided community counts its free members — fewer than min_size rejects it for good — and offers
+ *     its rank to each of them with an atomic minimum) and one decide launch (a community accepts iff it won every member it
+ *     claimed).  The highest-priority undecided community is decided in every round, so C rounds always suffice; a chain of L
+ *     communities each sharing a row with the next needs L.  undecided int32 [max_rounds]: word r receives the number of
+ *     communities still undecided after round first_round + r — the host reads it and stops at the first 0 (further rounds are
+ *     harmless).  first_round == 0 initialises first: status, accept, keep and the workspace; max_rounds == 0 then only
+ *     initialises.  The rounds of one de-overlap are numbered consecutively over however many calls, with the SAME arguments and
+ *     workspace, untouched in between.  first_round + max_rounds <= 2^30.
+ *   tsim_community_select_finish decides every community still undecided in ONE workgroup, in order, and leaves *undecided
+ *     (one word) 0.  After an initialising call without rounds it is the whole de-overlap.
+ * tsim_community_select_workspace_bytes(C, N): pure host, 0 for C < 0, N <= 0 or sizes beyond the limits, non-decreasing in each
+ * argument: (C + 1) 8 + C 4 + N 12 bytes and alignment.  Limits: C < 2^31 - 1, N < 2^31 - 64, T < 2^40.  C == 0 and T == 0 are
+ * legal (members and keep may be NULL when T == 0).  No call reads device memory back. */
+#define TSIM_COMMUNITY_ST_ROW 1  /* a community listed a member >= N */
+#define TSIM_COMMUNITY_ST_LIMS 2 /* a lims word was decreasing or outside [0, T] */
+size_t tsim_community_select_workspace_bytes(int64_t C, int64_t N);
+int tsim_community_select_rounds(const int64_t *lims, const int32_t *members, int64_t C, int64_t T, int64_t N, int min_size,
+                                 int64_t first_round, int max_rounds, int32_t *accept, uint8_t *keep, int32_t *status,
+                                 int32_t *undecided, void *workspace, size_t workspace_bytes, void *stream);
+int tsim_community_select_finish(const int64_t *lims, const int32_t *members, int64_t C, int64_t T, int64_t N, int min_size,
+                                 int32_t *accept, uint8_t *keep, int32_t *status, int32_t *undecided, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Binary embeddings: sign-bit codes, exact Hamming top-k and the re-score of its candidates (sentence-transformers'
  * `quantize_embeddings(precision="ubinary")` with `semantic_search_faiss(..., rescore=True)`; faiss' `IndexBinaryFlat`).
  * Codes.  A code row is the `np.packbits(x > 0, axis=1)` bytes of the float row: element 8j is bit 7 of byte j, the last byte

@@ -13,6 +13,7 @@ TSIM_F32, TSIM_BF16 = 0, 1
 TSIM_I32, TSIM_I64 = 2, 3        # index dtypes of the candidate lists (tsim_*_list_topk)
 LIST_ST_ROW, LIST_ST_LIMS = 1, 2  # include/tsim.h TSIM_LIST_ST_*
 IVF_ST_LIST, IVF_ST_OFF = 1, 2    # include/tsim.h TSIM_IVF_ST_*
+COMMUNITY_ST_ROW, COMMUNITY_ST_LIMS = 1, 2   # include/tsim.h TSIM_COMMUNITY_ST_*
 IVF_SEG = 512                     # include/tsim.h TSIM_IVF_SEG
 IVFPQ_SEG = 4096                  # include/tsim.h TSIM_IVFPQ_SEG
 GRAPH_ST_ROW, GRAPH_ST_ITERS = 1, 2   # include/tsim.h TSIM_GRAPH_ST_*
@@ -189,6 +190,11 @@ _SIGS = {
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsim_graph_prune": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsim_community_select_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "tsim_community_select_rounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tsim_community_select_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_cosine_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_time_next_topk": (None, [C.c_void_p, C.c_void_p]),

@@ -26,6 +26,7 @@ HOT_KERNELS = ("l2_rows_kernel", "l2_query_rows_kernel", "l2_negate_scores", "fl
                "code_merge", "code_rescore", "pack_sign_rows", "hamming_partial",
                "quantize_int8_rows", "int8_ip_partial", "ivf_prep", "ivf_partial", "pq_encode_rows", "pq_tables", "pq_adc_partial",
                "ivfpq_tables", "ivfpq_scan_partial", "graph_search_kernel", "graph_prune_kernel",
+               "community_claim", "community_decide", "community_finish",
                "embed_ln_kernel", "cls_head_kernel", "cls_head_wide_kernel")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(os.path.dirname(HERE), "include")]

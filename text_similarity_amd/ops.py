@@ -1426,9 +1426,15 @@ def _threshold_array(what, threshold, Q: int, dev):
     return threshold.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset, return_status):
+def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, scale_c, idx_offset, return_status,
+           centre_min: Optional[int] = None, max_members: Optional[int] = None):
     """cosine_range (scale_c is None), dot_range and l2_range (space SPACE_L2: the half rows are one element wider than the
-    float32 rows, the threshold is the squared radius and the scores that come back are squared distances)."""
+    float32 rows, the threshold is the squared radius and the scores that come back are squared distances).
+    ``centre_min`` (community_detection): only the queries with at least that many hits are materialised — the others get a
+    zero-length segment in the fill's lims, which the fill never overruns (csrc/range_search.h: range_fill_kernel copies
+    min(hits, segment) entries of a status-1 query, range_bf_kernel tests every position against the segment and
+    range_bf_sort_kernel leaves segments of fewer than two entries alone, the status-2 path) — and the running total is held
+    against ``max_members`` BEFORE the slice's output is allocated."""
     _need_gpu(eq_unit, ec_half, eq_f32, ec_f32)
     l2 = space == _lib.SPACE_L2
     if eq_unit.dtype != UNIT_DTYPE or ec_half.dtype != UNIT_DTYPE:
@@ -1480,8 +1486,15 @@ def _range(what, space, eq_unit, ec_half, d, threshold, eq_f32, ec_f32, rho_c, s
                     rc = (L.tsim_dot_range_scan if tau_q is None else L.tsim_dot_range_scan_tau)(*head, scale_c.data_ptr(), rho_p, *tail)
                 _lib.check(rc, what)
                 sl = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
-                torch.cumsum(counts[q0:q0 + nq], 0, out=sl[1:])
+                if centre_min is None:
+                    torch.cumsum(counts[q0:q0 + nq], 0, out=sl[1:])
+                else:
+                    cnt = counts[q0:q0 + nq]
+                    torch.cumsum(torch.where(cnt >= centre_min, cnt, torch.zeros_like(cnt)), 0, out=sl[1:])
                 t_slice = int(sl[-1].item())       # the one host read: the fill's output is allocated from it
+                if max_members is not None and total + t_slice > max_members:
+                    raise ValueError(f"{what}: the candidate communities hold more than max_members={max_members} rows: the "
+                                     "threshold is too low for this corpus (or min_size too small)")
                 s = torch.empty((t_slice,), dtype=torch.float32, device=dev)
                 i = torch.empty((t_slice,), dtype=torch.int64, device=dev)
                 if t_slice:
@@ -1597,6 +1610,157 @@ def range_merge(results, total: Optional[int] = None, ascending: bool = False):
                              lims_out.data_ptr(), T, out_s.data_ptr(), out_i.data_ptr(), _stream(out_s)),
                        "range_merge")
     return lims_out, out_s, out_i
+
+
+# ------------------------------------------------------------------------------------------------- community detection
+COMMUNITY_ST_ROW, COMMUNITY_ST_LIMS = _lib.COMMUNITY_ST_ROW, _lib.COMMUNITY_ST_LIMS      # include/tsim.h TSIM_COMMUNITY_ST_*
+COMMUNITY_MAX_ROUNDS = 2048     # default round budget of community_select before the serial finish (DESIGN.md §7 has the counts)
+COMMUNITY_ROUND_BATCH = 4       # rounds launched before the first host read of the undecided counts; every batch doubles ...
+COMMUNITY_ROUND_BATCH_MAX = 64  # ... up to this many (the rounds past the deciding one find nothing to do)
+
+
+def community_select(lims: torch.Tensor, members: torch.Tensor, N: int, min_size: int, max_rounds: Optional[int] = None):
+    """The de-overlap of candidate communities (include/tsim.h): ``lims`` int64 [C+1] and ``members`` int32 [T] are a CSR in
+    PRIORITY order over rows 0 .. N-1; walking it in order, a community is accepted iff at least ``min_size`` of its entries are
+    rows no accepted community before it has taken, and it takes those.  Returns ``(accept int32 [C], keep uint8 [T],
+    rounds_used, status)``: ``keep`` marks the entries that ended up in an accepted community, ``status`` is an int (0 or the
+    COMMUNITY_ST_* bits: a member >= N, which is dropped; a non-monotone ``lims`` pair, which is an empty community).  A negative
+    member is padding.  The parallel form runs in rounds — each decides at least the first community still undecided — in
+    batches of COMMUNITY_ROUND_BATCH, doubling up to COMMUNITY_ROUND_BATCH_MAX, with one read of the device's undecided counts
+    after each batch, until nothing is undecided or ``max_rounds`` (default COMMUNITY_MAX_ROUNDS) are used up; what is left then is finished by one workgroup in order.  ``max_rounds=0`` is
+    that serial form alone.  The results do not depend on ``max_rounds``; ``rounds_used`` counts the rounds up to the one that
+    decided the last community (``max_rounds`` when the serial finish ran)."""
+    _need_gpu(lims, members)
+    if lims.dtype != torch.int64 or lims.dim() != 1 or lims.numel() < 1 or not lims.is_contiguous():
+        raise ValueError("community_select: lims must be a contiguous int64 [C+1]")
+    if members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous():
+        raise ValueError("community_select: members must be a contiguous int32 [T]")
+    max_rounds = COMMUNITY_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    N, min_size = int(N), int(min_size)
+    if N <= 0 or min_size < 1 or max_rounds < 0:
+        raise ValueError(f"community_select: N={N} (> 0), min_size={min_size} (>= 1), max_rounds={max_rounds} (>= 0)")
+    dev = lims.device
+    C, T = lims.numel() - 1, members.numel()
+    accept = torch.zeros((C,), dtype=torch.int32, device=dev)
+    keep = torch.zeros((T,), dtype=torch.uint8, device=dev)
+    if C == 0:
+        return accept, keep, 0, 0
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        left = torch.zeros((COMMUNITY_ROUND_BATCH_MAX,), dtype=torch.int32, device=dev)
+        ws = torch.empty((L.tsim_community_select_workspace_bytes(C, N),), dtype=torch.uint8, device=dev)
+        st = _stream(lims)
+        head = (lims.data_ptr(), members.data_ptr(), C, T, N, min_size)
+        tail = (accept.data_ptr(), keep.data_ptr(), status.data_ptr(), left.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        rounds, undecided, batch = 0, C, COMMUNITY_ROUND_BATCH
+        if max_rounds == 0:
+            _lib.check(L.tsim_community_select_rounds(*head, 0, 0, *tail), "community_select")
+        while undecided and rounds < max_rounds:
+            n = min(batch, max_rounds - rounds)
+            batch = min(2 * batch, COMMUNITY_ROUND_BATCH_MAX)
+            _lib.check(L.tsim_community_select_rounds(*head, rounds, n, *tail), "community_select")
+            for v in left[:n].tolist():      # the host read of the batch
+                rounds += 1
+                undecided = v
+                if not v:
+                    break
+        if undecided:
+            _lib.check(L.tsim_community_select_finish(*head, *tail), "community_select")
+        return accept, keep, rounds, int(status.item())
+
+
+def community_detection(eq_unit: Optional[torch.Tensor], eq_f32: torch.Tensor, d: int, threshold: float, min_size: int,
+                        space: str = "cosine", rho: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                        max_members: int = 1 << 27, max_rounds: Optional[int] = None, return_info: bool = False):
+    """Community detection ("fast clustering", sentence-transformers' ``util.community_detection`` with its tie orders fixed)
+    over the rows ``eq_f32`` [N, d]: every group of at least ``min_size`` rows scoring >= ``threshold`` against a centre row,
+    largest first, no row in two groups; no cluster count is needed.  The score s(i, j) is exactly what :func:`cosine_range`
+    (``space='cosine'``) or :func:`dot_range` (``'dot'``) reports for query row i against corpus row j.
+      1. hits(i) = the rows j with s(i, j) >= threshold, ordered by (score desc, index asc); row i is a centre iff it has at
+         least ``min_size`` hits, and hits(i) is its candidate community;
+      2. the candidates are ordered by (size desc, centre index asc);
+      3. in that order a candidate keeps the rows no accepted candidate before it took, and is accepted iff at least
+         ``min_size`` are left (:func:`community_select`, on the device);
+      4. the accepted ones are ordered by (size desc, position in 2 asc); members keep the order of 1.
+    Returns, on the device, ``(lims int64 [K+1], members int64 [M], centres int64 [K], labels int64 [N])``: community c is
+    ``members[lims[c]:lims[c+1]]`` around row ``centres[c]`` (which another community may have taken), ``labels[i]`` its number
+    or -1.  ``return_info=True`` adds a dict: ``scores`` float32 [M] (each member's score against its centre), ``rounds`` (of
+    the de-overlap), ``candidates`` (the number of centres) and ``candidate_members`` (their hits, what ``max_members`` bounds).
+    ``eq_unit``: cosine — :func:`l2norm_rows` of the rows, with ``rho`` its residual word (optional); dot — the corpus operand,
+    ``(eq_unit, rho, scale)`` = :func:`dot_scaled_rows` of the rows (the query operand is made here).  None: made here.
+    Step 1 runs in slices of MAX_RANGE_QUERIES_PER_CALL rows; only the centres' hits are materialised, and their number is held
+    against ``max_members`` before anything is allocated for them: a ValueError says the threshold is too low for the corpus
+    (every row of a dense region lists the whole region: the candidates grow with the SQUARE of a cluster's size).  2 and 4
+    are stable sorts on the device."""
+    centre, plims, pmem, pscore = community_candidates(eq_unit, eq_f32, d, threshold, min_size, space, rho, scale, max_members)
+    N, dev = eq_f32.shape[0], eq_f32.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    C, T = centre.numel(), pmem.numel()
+    seg = torch.repeat_interleave(torch.arange(C, **i64), plims[1:] - plims[:-1])      # priority position of every entry
+    accept, keep, rounds, _ = community_select(plims, pmem.to(torch.int32), max(N, 1), int(min_size), max_rounds)
+    keep = keep.bool()
+    kseg = seg[keep]
+    ksize = torch.zeros((C,), **i64).index_add_(0, kseg, torch.ones_like(kseg))
+    acc = torch.nonzero(accept).reshape(-1)                                      # accepted, in priority order
+    acc = acc[torch.sort(ksize[acc], stable=True, descending=True)[1]]           # (size desc, priority position asc)
+    K = acc.numel()
+    rank = torch.full((C,), -1, **i64)
+    rank[acc] = torch.arange(K, **i64)
+    o = torch.sort(rank[kseg], stable=True)[1]               # entries grouped by final community, their order kept
+    members = pmem[keep][o]
+    out_lims = torch.zeros((K + 1,), **i64)
+    torch.cumsum(ksize[acc], 0, out=out_lims[1:])
+    labels = torch.full((N,), -1, **i64)
+    labels[members] = rank[kseg][o]
+    out = (out_lims, members, centre[acc], labels)
+    if return_info:
+        out += ({"scores": pscore[keep][o], "rounds": rounds, "candidates": C, "candidate_members": T},)
+    return out
+
+
+def community_candidates(eq_unit: Optional[torch.Tensor], eq_f32: torch.Tensor, d: int, threshold: float, min_size: int,
+                         space: str = "cosine", rho: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                         max_members: int = 1 << 27):
+    """Steps 1 and 2 of :func:`community_detection` (same arguments): ``(centres int64 [C], lims int64 [C+1], members int64
+    [T], scores float32 [T])`` — the candidate communities in priority order, (size desc, centre index asc), as a CSR: what
+    :func:`community_select` takes (with the members as int32)."""
+    what = "community_detection"
+    _need_gpu(eq_f32)
+    if space not in ("cosine", "dot"):
+        raise ValueError(f"{what}: space={space!r}: one of 'cosine', 'dot'")
+    min_size = int(min_size)
+    if min_size < 1:
+        raise ValueError(f"{what}: min_size={min_size} < 1")
+    if eq_f32.dim() != 2 or eq_f32.dtype != torch.float32:
+        raise ValueError(f"{what}: eq_f32 must be float32 [N, d]")
+    N, dev = eq_f32.shape[0], eq_f32.device
+    if space == "cosine":
+        if eq_unit is None:
+            eq_unit, rho = l2norm_rows(eq_f32, return_rho=True)
+        q_unit, scale = eq_unit, None
+        sp = _lib.SPACE_COSINE
+    else:
+        if eq_unit is None:
+            eq_unit, rho, scale = dot_scaled_rows(eq_f32)
+        elif rho is None or scale is None:
+            raise ValueError(f"{what}: space='dot' needs (eq_unit, rho, scale) from dot_scaled_rows, or none of them")
+        q_unit = l2norm_rows(eq_f32)
+        sp = _lib.SPACE_DOT
+    lims, scores, idx = _range(what, sp, q_unit, eq_unit, d, threshold, eq_f32, eq_f32, rho, scale, 0, False,
+                               centre_min=min_size, max_members=int(max_members))
+    i64 = dict(dtype=torch.int64, device=dev)
+    sizes = lims[1:] - lims[:-1]
+    centre = torch.nonzero(sizes > 0).reshape(-1)           # (min_size >= 1: a centre has a hit; the others got no segment)
+    order = torch.sort(sizes[centre], stable=True, descending=True)[1]
+    centre = centre[order]                                   # priority order: (size desc, centre index asc)
+    csize = sizes[centre]
+    C, T = centre.numel(), idx.numel()
+    plims = torch.zeros((C + 1,), **i64)
+    torch.cumsum(csize, 0, out=plims[1:])
+    seg = torch.repeat_interleave(torch.arange(C, **i64), csize)                 # priority position of every entry
+    src = torch.arange(T, **i64) - plims[:-1][seg] + lims[:-1][centre][seg]      # where the range search left it
+    return centre, plims, idx[src], scores[src]
 
 
 def packed_result_bytes(Q: int, k: int) -> int:

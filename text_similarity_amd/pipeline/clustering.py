@@ -9,7 +9,14 @@ fixture uses: tests/golden/kmeans.npz pins labels / centres / inertia against sk
 k-means++ seeded from ``seed`` (sklearn's own k-means++ draws from its private RNG stream and cannot be reproduced).
 An emptied cluster keeps its centre (sklearn relocates it to a far point; with k-means++ starts this does not occur on
 the fixtures).  ``__call__`` returns ``{cluster_id: [row indices or texts]}`` (the reference builds that dict and forgets
-to return it, clustering.py:20-23)."""
+to return it, clustering.py:20-23).
+
+``method="community"`` clusters WITHOUT a cluster count (the reference keeps a ``method=`` argument and its topic pipeline turns
+to a density method for the same reason: k is not known): community detection over the corpus' cosine scores
+(:func:`ops.community_detection`) — every group of at least ``min_community_size`` rows scoring >= ``threshold`` against a
+centre row, largest first, no row in two groups.  ``n_clusters`` is ignored; ``fit`` sets ``labels_`` (-1: noise, a row in no
+community), ``cluster_centers_`` (the centre ROWS, not means) and ``n_iter_`` (the rounds of the de-overlap); ``inertia_`` stays
+None; ``__call__`` returns the same dict without the noise."""
 from __future__ import annotations
 
 from collections import defaultdict
@@ -23,12 +30,17 @@ from .search_pipeline import Pipeline
 
 
 class ClusteringPipeline(Pipeline):
-    def __init__(self, n_clusters, *args, method="k-means", max_iter: int = 300, seed: int = 0, init=None, **kwargs):
+    def __init__(self, n_clusters, *args, method="k-means", max_iter: int = 300, seed: int = 0, init=None,
+                 threshold: Optional[float] = None, min_community_size: int = 10, **kwargs):
         super().__init__(*args, **kwargs)
-        if method != "k-means":
-            raise ValueError("only k-means is implemented (as in the reference)")
+        if method not in ("k-means", "community"):
+            raise ValueError(f"method={method!r}: 'k-means' (as in the reference) or 'community'")
+        if method == "community" and threshold is None:
+            raise ValueError("method='community' needs threshold= (the score two rows of one community must reach)")
         self.method = method
-        self.n_clusters = int(n_clusters)
+        self.threshold = threshold
+        self.min_community_size = int(min_community_size)
+        self.n_clusters = int(n_clusters) if n_clusters is not None else 0
         self.max_iter = max_iter
         self.seed = seed
         self.init = init
@@ -77,6 +89,14 @@ class ClusteringPipeline(Pipeline):
             emb = emb.cuda()
         x = emb.float().contiguous()
         n, d = x.shape
+        if self.method == "community":
+            _, _, centres, labels, info = ops.community_detection(None, x, d, self.threshold, self.min_community_size,
+                                                                  return_info=True)
+            self.labels_ = labels
+            self.cluster_centers_ = x[centres]
+            self.inertia_ = None
+            self.n_iter_ = info["rounds"]
+            return self
         k = min(self.n_clusters, n)
         init = self.init if init is None else init
         if init is not None:
@@ -110,6 +130,8 @@ class ClusteringPipeline(Pipeline):
         self.fit(emb)
         results = defaultdict(list)
         for text_id, cluster_id in enumerate(self.labels_.tolist()):
+            if cluster_id < 0:      # (method='community': noise)
+                continue
             results[cluster_id].append(texts[text_id] if texts is not None else text_id)
         return dict(results)
 

@@ -211,6 +211,22 @@ class SentenceMiningPipeline(SearchPipeline):
         qid, idx, scores = _sort_columns([qid, idx, scores], ((1, False), (0, False), (2, True)))
         return list(zip(scores.cpu().tolist(), qid.cpu().tolist(), idx.cpu().tolist()))
 
+    def communities(self, threshold: float, min_community_size: int = 10) -> List[list]:
+        """Community detection over the corpus ("fast clustering"; no cluster count needed): every group of at least
+        ``min_community_size`` entries scoring >= ``threshold`` (``score_function``) against a centre entry, largest first, no
+        entry in two groups — ``[[(corpus_idx, text, score_to_centre), ...], ...]``.  A group lists its members by (score to
+        the centre desc, index asc), so the centre itself leads it (unless a larger group took it).  The definition, with its
+        tie orders, is :func:`ops.community_detection`'s; the de-overlap runs on the device.  The corpus is embedded in ONE
+        piece and ``corpus_chunk_size`` does not apply: every row is scored against every row."""
+        emb = self.encode_corpus(documents=self.corpus)
+        cf = emb.to(self.params.device, dtype=torch.float32).contiguous()
+        space = "dot" if self.score_function == "dot" else "cosine"
+        lims, members, _, _, info = ops.community_detection(None, cf, cf.shape[1], threshold, min_community_size, space=space,
+                                                            return_info=True)
+        lims, members, scores = lims.cpu().tolist(), members.cpu().tolist(), info["scores"].cpu().tolist()
+        return [[(members[t], self.corpus[members[t]], scores[t]) for t in range(lims[c], lims[c + 1])]
+                for c in range(len(lims) - 1)]
+
     def _search(self, queries, corpus=None, max_num_results: int = 10, return_embeddings: bool = False, candidates=None
                 ) -> Dict[int, Union[list, torch.Tensor]]:
         query_embeddings = self.encode_corpus(documents=queries, return_embeddings=return_embeddings)
