@@ -386,6 +386,16 @@ int tsim_l2_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q, const flo
                       const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k, float *out_scores,
                       int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
                       void *stream);
+/* The same search over a corpus of IEEE HALF rows: the second stage of a refine search (faiss IndexRefine(SQfp16)), whose row
+ * store keeps half the bytes of the float32 rows.  space: TSIM_SPACE_COSINE / _DOT / _L2 (anything else: TSIM_EINVAL).  eq_f32
+ * [Q, d] float32 as above; ec_f16 [N, d] IEEE half, row stride ldc_f16 >= d counted in ELEMENTS — any stride, odd ones included,
+ * so a row need only be 2-byte aligned.  The score is the score of the float32 entry of the same space for the same query
+ * against the rows widened to float32, bit for bit (the widening is exact; subnormal halves are kept, not flushed).  Lists,
+ * padding, status bits, order, limits on k and d, workspace and argument errors: those of the three entries above. */
+int tsim_list_topk_f16(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_f16, int64_t ldc_f16, int64_t N,
+                       int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k, float *out_scores,
+                       int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace, size_t workspace_bytes,
+                       void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Community detection, the de-overlap step (sentence-transformers' `util.community_detection`, "fast clustering": every group

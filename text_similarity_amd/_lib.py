@@ -147,6 +147,9 @@ _SIGS = {
                         C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                         C.c_void_p])
        for name in ("tsim_cosine_list_topk", "tsim_dot_list_topk", "tsim_l2_list_topk")},
+    "tsim_list_topk_f16": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                     C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "tsim_code_bytes": (C.c_int, [C.c_int]),
     "tsim_pack_sign_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "tsim_hamming_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),

@@ -1,6 +1,13 @@
 // Exact top-k within candidate lists (included by search.hip, after the helpers it uses): each query is scored against its OWN
-// list of corpus rows — the indirect form of the brute-force pass.  No half rows, no MFMA selection, no guard: every listed row
-// is scored with the exact definitions above (wave_scores: cosine of the float32 rows, float32(q.c), -dist^2 through l2_f32).
+// list of corpus rows — the indirect form of the brute-force pass.  No MFMA selection, no guard: every listed row is scored
+// with the exact definitions above (wave_scores: cosine of the float32 rows, float32(q.c), -dist^2 through l2_f32).
+//
+// Corpus rows.  float32, or IEEE half (tsim_list_topk_f16: the row store of a refine stage).  The query is float32 either way
+// and its type T carries the metric; the corpus element type C only says how an element is loaded.  A half is widened exactly
+// (v_cvt_f32_f16, subnormals kept by the default mode), so a half row scores the bits the float32 kernel gives on the widened
+// row.  A lane reads its elements j = lane + 64 i as SINGLE halves: a row stride may be odd, so a row is only 2-byte aligned and
+// a pair load (4 bytes) would be misaligned for every other row; a wave's 64 halves are one contiguous 128-byte segment per
+// load instruction either way, NI instructions a row as for float32 rows, and no regrouping of pairs across lanes is needed.
 //
 // Lists.  cand[0..T) holds row numbers (int32 or int64); query q owns cand[lims[q] .. lims[q+1]) (CSR), or every query owns
 // cand[0..T) (shared).  A negative entry is padding; an entry >= N is never dereferenced and raises TSIM_LIST_ST_ROW in the
@@ -79,9 +86,9 @@ __device__ __forceinline__ int64_t list_first_q(const int64_t *L, int64_t Q, int
     return lo;
 }
 
-template <typename T, bool COS, typename CI>
+template <typename T, bool COS, typename CI, typename C>
 __global__ __launch_bounds__(256) void list_partial_kernel(int64_t Q, int64_t N, int64_t Tn, const T *__restrict__ xq, int64_t ldq,
-                                                           const T *__restrict__ xc, int64_t ldc, int d, const void *__restrict__ cand,
+                                                           const C *__restrict__ xc, int64_t ldc, int d, const void *__restrict__ cand,
                                                            const int64_t *__restrict__ L, int64_t nch, int64_t spc, int k, int kp,
                                                            float *__restrict__ ls_s, int *__restrict__ ls_i,
                                                            int32_t *__restrict__ status) {
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(256) void list_partial_kernel(int64_t Q, int64_t N,
                 const int64_t r = list_entry<CI>(cand, b + (e < nb ? e : g0));
                 const bool usable = r >= 0 && r < N;
                 const int row = usable ? (int)r : 0;   // clamped: the row is loaded and scored, the score dropped
-                const float s = wave_scores<T, COS>(eqr, xc, ldc, row, nvalid, d, lane);
+                const float s = wave_scores<T, COS, C>(eqr, xc, ldc, row, nvalid, d, lane);
                 if (e < nb) {
                     if (usable) top.offer(s, row, w);
                     beyond |= r >= N;
@@ -182,17 +189,17 @@ static void plan_workspace_list(int64_t Q, int64_t T, int k, ListWs *w) {
     w->total = o;
 }
 
-static int list_topk(int sm, const char *what, const float *eq_f32, int64_t ldq_f32, int64_t Q, const float *ec_f32, int64_t ldc_f32,
-                     int64_t N, int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
+// ec: float32 rows, or rows of IEEE half when `half_rows` (ldc in elements of that type either way)
+static int list_topk(int sm, const char *what, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec, bool half_rows,
+                     int64_t ldc, int64_t N, int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
                      float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace,
                      size_t workspace_bytes, void *stream) {
-    TSIM_REQUIRE(eq_f32 && ec_f32 && out_scores && out_idx && (cand || T == 0), "%s: null pointer", what);
+    TSIM_REQUIRE(eq_f32 && ec && out_scores && out_idx && (cand || T == 0), "%s: null pointer", what);
     TSIM_REQUIRE(Q > 0 && N > 0 && T >= 0, "%s: bad shape Q=%lld N=%lld T=%lld", what, (long long)Q, (long long)N, (long long)T);
     TSIM_REQUIRE(k >= 1 && k <= TOPK_LARGE_MAX_K, "%s: k=%d outside 1..%d", what, k, TOPK_LARGE_MAX_K);
     TSIM_REQUIRE(d >= 1 && d <= 64 * XS_MAXI, "%s: d=%d outside 1..%d", what, d, 64 * XS_MAXI);
     TSIM_REQUIRE(sm != SM_L2 || d < 64 * XS_MAXI, "%s: d=%d (the Euclidean space takes d <= %d)", what, d, 64 * XS_MAXI - 1);
-    TSIM_REQUIRE(ldq_f32 >= d && ldc_f32 >= d, "%s: float32 row strides %lld/%lld < d=%d", what, (long long)ldq_f32,
-                 (long long)ldc_f32, d);
+    TSIM_REQUIRE(ldq_f32 >= d && ldc >= d, "%s: row strides %lld/%lld < d=%d", what, (long long)ldq_f32, (long long)ldc, d);
     TSIM_REQUIRE((lims != nullptr) != (shared != 0), "%s: pass lims (one list per query) or shared = 1 (one list for all), not %s", what,
                  lims ? "both" : "neither");
     TSIM_REQUIRE(cand_dtype == TSIM_I32 || cand_dtype == TSIM_I64, "%s: unknown index dtype %d (TSIM_I32, TSIM_I64)", what, cand_dtype);
@@ -219,16 +226,22 @@ static int list_topk(int sm, const char *what, const float *eq_f32, int64_t ldq_
     if (nsl > 0) {
         const dim3 grid((unsigned)nch, (unsigned)(lims ? std::min<int64_t>(Q, 4) : std::min<int64_t>(Q, 65535)));
         // (not with_score_mode: its unit-row branch would instantiate a kernel for half rows that no entry can reach)
-        auto launch = [&](auto rows, auto cosc, auto ci) {
+        auto launch = [&](auto rows, auto cosc, auto ci, auto crow) {
             using RT = decltype(rows);
             using CI = decltype(ci);
-            hipLaunchKernelGGL((list_partial_kernel<RT, decltype(cosc)::value, CI>), grid, dim3(256), 0, st, Q, N, T,
-                               reinterpret_cast<const RT *>(eq_f32), ldq_f32, reinterpret_cast<const RT *>(ec_f32), ldc_f32, d, cand, clean,
-                               nch, spc, k, kp, ls_s, ls_i, out_status);
+            using CT = decltype(crow);
+            hipLaunchKernelGGL((list_partial_kernel<RT, decltype(cosc)::value, CI, CT>), grid, dim3(256), 0, st, Q, N, T,
+                               reinterpret_cast<const RT *>(eq_f32), ldq_f32, reinterpret_cast<const CT *>(ec), ldc, d, cand, clean, nch,
+                               spc, k, kp, ls_s, ls_i, out_status);
         };
-        auto by_dtype = [&](auto rows, auto cosc) {
-            if (cand_dtype == TSIM_I32) launch(rows, cosc, int32_t{});
-            else launch(rows, cosc, int64_t{});
+        auto by_dtype = [&](auto rows, auto cosc) {   // (the corpus rows: the query's type, or unit_t = IEEE half)
+            if (half_rows) {
+                if (cand_dtype == TSIM_I32) launch(rows, cosc, int32_t{}, unit_t{});
+                else launch(rows, cosc, int64_t{}, unit_t{});
+            } else {
+                if (cand_dtype == TSIM_I32) launch(rows, cosc, int32_t{}, rows);
+                else launch(rows, cosc, int64_t{}, rows);
+            }
         };
         if (sm == SM_COS) by_dtype(float{}, std::true_type{});
         else if (sm == SM_DOT) by_dtype(float{}, std::false_type{});
@@ -258,7 +271,7 @@ extern "C" int tsim_cosine_list_topk(const float *eq_f32, int64_t ldq_f32, int64
                                      int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
                                      float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-    return tsim::list_topk(tsim::SM_COS, "cosine_list_topk", eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, cand, cand_dtype, T, lims, shared,
+    return tsim::list_topk(tsim::SM_COS, "cosine_list_topk", eq_f32, ldq_f32, Q, ec_f32, false, ldc_f32, N, d, cand, cand_dtype, T, lims, shared,
                            k, out_scores, out_idx, idx_offset, out_status, workspace, workspace_bytes, stream);
 }
 
@@ -266,7 +279,7 @@ extern "C" int tsim_dot_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t 
                                   int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
                                   float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace,
                                   size_t workspace_bytes, void *stream) {
-    return tsim::list_topk(tsim::SM_DOT, "dot_list_topk", eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, cand, cand_dtype, T, lims, shared, k,
+    return tsim::list_topk(tsim::SM_DOT, "dot_list_topk", eq_f32, ldq_f32, Q, ec_f32, false, ldc_f32, N, d, cand, cand_dtype, T, lims, shared, k,
                            out_scores, out_idx, idx_offset, out_status, workspace, workspace_bytes, stream);
 }
 
@@ -274,6 +287,17 @@ extern "C" int tsim_l2_list_topk(const float *eq_f32, int64_t ldq_f32, int64_t Q
                                  int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
                                  float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace,
                                  size_t workspace_bytes, void *stream) {
-    return tsim::list_topk(tsim::SM_L2, "l2_list_topk", eq_f32, ldq_f32, Q, ec_f32, ldc_f32, N, d, cand, cand_dtype, T, lims, shared, k,
+    return tsim::list_topk(tsim::SM_L2, "l2_list_topk", eq_f32, ldq_f32, Q, ec_f32, false, ldc_f32, N, d, cand, cand_dtype, T, lims, shared, k,
+                           out_scores, out_idx, idx_offset, out_status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tsim_list_topk_f16(int space, const float *eq_f32, int64_t ldq_f32, int64_t Q, const void *ec_f16, int64_t ldc_f16,
+                                  int64_t N, int d, const void *cand, int cand_dtype, int64_t T, const int64_t *lims, int shared, int k,
+                                  float *out_scores, int64_t *out_idx, int64_t idx_offset, int32_t *out_status, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    TSIM_REQUIRE(space == TSIM_SPACE_COSINE || space == TSIM_SPACE_DOT || space == TSIM_SPACE_L2,
+                 "list_topk_f16: unknown space %d (TSIM_SPACE_COSINE, TSIM_SPACE_DOT, TSIM_SPACE_L2)", space);
+    const int sm = space == TSIM_SPACE_COSINE ? tsim::SM_COS : space == TSIM_SPACE_DOT ? tsim::SM_DOT : tsim::SM_L2;
+    return tsim::list_topk(sm, "list_topk_f16", eq_f32, ldq_f32, Q, ec_f16, true, ldc_f16, N, d, cand, cand_dtype, T, lims, shared, k,
                            out_scores, out_idx, idx_offset, out_status, workspace, workspace_bytes, stream);
 }

@@ -289,11 +289,13 @@ __device__ __forceinline__ double add_square_unfused(double acc, double diff) {
     return acc + sq;
 }
 
-// per-lane partial sums of the query against one row: dot (and |row|^2 for COS); L2: the squared differences in `dot`
-template <typename T, bool COS, int NI>
-__device__ __forceinline__ void exact_partials(const ExactQuery<T> &q, const T *row, int d, int lane, double &dot, double &cc) {
+// per-lane partial sums of the query against one row: dot (and |row|^2 for COS); L2: the squared differences in `dot`.
+// C is the element type of the corpus row.  It only says how an element is loaded (float32 rows: T itself; rows of IEEE half:
+// unit_t, widened exactly by load_as_f32); the metric stays with T, the query's type, which ExactQuery carries.
+template <typename T, bool COS, int NI, typename C = T>
+__device__ __forceinline__ void exact_partials(const ExactQuery<T> &q, const C *row, int d, int lane, double &dot, double &cc) {
     double c[NI];
-    row_elems_f64<T, NI>(c, row, d, lane);
+    row_elems_f64<C, NI>(c, row, d, lane);
     dot = 0.0;
     cc = 0.0;
 #pragma unroll
@@ -349,14 +351,14 @@ __device__ __forceinline__ void butterfly_reduce_scatter(double (&acc)[NV], int 
     }
 }
 
-template <typename T, bool COS, int NB>
-__device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const T *xc, int64_t ldc, int my_i, int t0, int nvalid,
+template <typename T, bool COS, int NB, typename C = T>
+__device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const C *xc, int64_t ldc, int my_i, int t0, int nvalid,
                                                    int d, int lane) {
     constexpr int NV = (COS ? 2 : 1) * NB;
     static_assert(NV >= 2 && NV <= 32 && (NV & (NV - 1)) == 0, "batch size");
     constexpr int LOG = NV == 32 ? 5 : NV == 16 ? 4 : NV == 8 ? 3 : NV == 4 ? 2 : 1;
     double acc[NV];
-    const T *rows[NB];
+    const C *rows[NB];
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         const int t = t0 + u < nvalid ? t0 + u : t0;   // past the end: repeat a valid one, result unused
@@ -366,7 +368,7 @@ __device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
             double dot, cc;
-            exact_partials<T, COS, XS_MAXI / 2>(q, rows[u], d, lane, dot, cc);
+            exact_partials<T, COS, XS_MAXI / 2, C>(q, rows[u], d, lane, dot, cc);
             if constexpr (COS) { acc[2 * u] = dot; acc[2 * u + 1] = cc; }
             else acc[u] = dot;
         }
@@ -374,7 +376,7 @@ __device__ __forceinline__ float exact_score_batch(const ExactQuery<T> &q, const
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
             double dot, cc;
-            exact_partials<T, COS, XS_MAXI>(q, rows[u], d, lane, dot, cc);
+            exact_partials<T, COS, XS_MAXI, C>(q, rows[u], d, lane, dot, cc);
             if constexpr (COS) { acc[2 * u] = dot; acc[2 * u + 1] = cc; }
             else acc[u] = dot;
         }
@@ -1232,13 +1234,13 @@ __device__ __forceinline__ SlList<I, DEDUP> sl_shared_list() {
 }
 
 // Exact scores of the rows held by lanes 0 .. nvalid-1 (my_i), eight at a time (exact_score_batch: the bits of exact_score).
-template <typename T, bool COS>
-__device__ __forceinline__ float wave_scores(const ExactQuery<T> &q, const T *xc, int64_t ldc, int my_i, int nvalid, int d,
+template <typename T, bool COS, typename C = T>
+__device__ __forceinline__ float wave_scores(const ExactQuery<T> &q, const C *xc, int64_t ldc, int my_i, int nvalid, int d,
                                              int lane) {
     constexpr int NB = 8;
     float mine = 0.f;
     for (int t0 = 0; t0 < nvalid; t0 += NB) {
-        const float s = exact_score_batch<T, COS, NB>(q, xc, ldc, my_i, t0, nvalid, d, lane);
+        const float s = exact_score_batch<T, COS, NB, C>(q, xc, ldc, my_i, t0, nvalid, d, lane);
         if (lane >= t0 && lane < t0 + NB) mine = s;
     }
     return mine;

@@ -1,7 +1,8 @@
 """GpuIVFPQIndex — inverted lists of product-quantisation codes resident in HBM (faiss' ``IndexIVFPQ`` with 8-bit codes, the
 IVFADC of the PQ paper): the rows are clustered into ``nlist`` lists as in :class:`GpuIVFIndex`, each row is stored as the ``M``
 bytes of the PQ code of its RESIDUAL to its list's centroid (``by_residual=True``, the default; else of the row itself), and a
-query is scored by table lookups against the ``nprobe`` lists nearest to it only.  It keeps no float rows: that is its point.
+query is scored by table lookups against the ``nprobe`` lists nearest to it only.  Without ``refine=`` it keeps no float rows:
+that is its point.
 
 ``space``: ``"ip"``, ``"l2"`` (squared Euclidean distance, smaller is better) or ``"cosine"`` — ip with rows normalised before
 they are assigned and encoded and queries before their tables (:meth:`GpuPQIndex.normalise`) — in :class:`GpuPQIndex`'s sense;
@@ -21,8 +22,13 @@ row asc) — l2: (distance asc, row asc) — and returns ``(values, labels)`` as
 without pickling with ``kind = 'ivfpq'`` and the codes under ``ivfpq_codes`` (so that ``GpuPQIndex.load_index`` refuses it); a file
 of another kind, space, width or M raises ``ValueError``.
 
-Not here (``NotImplementedError``; ``GpuFlatIndex`` has them): ``filter=``, range and radius search.  No OPQ rotation, no
-precomputed tables, no refine stage.
+Refine stage (faiss' ``IndexRefineFlat`` over ``IndexIVFPQ``): ``refine="float32"`` or ``"float16"`` keeps the rows as given
+(before the cosine normalisation) in arrival order beside the codes, compacted with them, exactly as :class:`GpuPQIndex`
+describes; ``search(q, k, rescore_multiplier=mult)`` re-scores the ``min(k * mult, ops.MAX_K, live rows)`` best rows of the scan
+exactly against them with the query as given.  The file gains ``refine`` and ``refine_rows``; loading adopts them.
+
+Not here (``NotImplementedError``; ``GpuFlatIndex`` has them): ``filter=``, range and radius search.  No OPQ rotation and no
+precomputed tables.
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ from typing import Iterable, Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _refine, ops
 from .ivf_index import GpuIVFIndex, pack_lists
 from .pq_index import GpuPQIndex
 
@@ -65,10 +71,12 @@ class GpuIVFPQIndex:
     _FILE_NAME = "ivfpq_index.bin"
 
     def __init__(self, space: str = "ip", dim: int = 0, nlist: int = 1, nprobe: int = 1, M: int = 8, by_residual: bool = True,
-                 device: Optional[torch.device] = None, seed: int = 0):
+                 device: Optional[torch.device] = None, seed: int = 0, refine: Optional[str] = None):
         if space not in self.SPACES:
             raise ValueError(f"GpuIVFPQIndex implements the spaces {self.SPACES}, not {space!r}")
         self.device = torch.device(device) if device is not None else torch.device("cuda")
+        self.refine = _refine.check_refine("GpuIVFPQIndex", refine, space, int(dim))
+        self._store = None if self.refine is None else _refine.RowStore(self.refine, space, int(dim), self.device)
         self._pq = GpuPQIndex(space=space, dim=dim, M=M, device=self.device, seed=seed)      # (checks dim and M)
         self.space, self.dim, self.M, self.seed = space, int(dim), int(M), int(seed)
         self.by_residual = bool(by_residual)
@@ -199,7 +207,13 @@ class GpuIVFPQIndex:
 
     def add_items(self, data, ids: Optional[Iterable[int]] = None, num_threads: int = -1):
         self._need_trained()
-        x = self._rows(data)
+        kept = None
+        if self._store is not None:      # the rows as given; one that is not finite in the store's dtype raises before anything is added
+            raw = _refine.raw_queries(data, self.dim, self.device)
+            kept = self._store.convert(raw)
+            x = self._pq._prepared(raw)
+        else:
+            x = self._rows(data)
         n = x.shape[0]
         if ids is None:
             ids = np.arange(self._n, self._n + n)
@@ -207,6 +221,8 @@ class GpuIVFPQIndex:
         if lab.numel() != n:
             raise ValueError("ids and data disagree in length")
         self._reserve(self._n + n)
+        if kept is not None:
+            self._store.put(self._n, kept)
         for r0 in range(0, n, _ENCODE_CHUNK):
             xs = x[r0:r0 + _ENCODE_CHUNK]
             lists = self._coarse(xs, 1)[:, 0]
@@ -229,27 +245,41 @@ class GpuIVFPQIndex:
         self._n_dead += k
 
     # ------------------------------------------------------------------ results out
-    def search(self, data, k: int, filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, data, k: int, filter=None, rescore_multiplier: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(values [Q,k] float32, labels [Q,k] int64), best first, over the ``nprobe`` lists nearest to each query: ip and cosine by
-        (score desc, arrival row asc), padded with (-inf, -1); l2 by (squared distance asc, row asc), padded with (+inf, -1)."""
+        (score desc, arrival row asc), padded with (-inf, -1); l2 by (squared distance asc, row asc), padded with (+inf, -1).
+        ``rescore_multiplier`` (an integer >= 1; needs ``refine=``): the ``min(k * rescore_multiplier, ops.MAX_K, live rows)`` best
+        rows of the scan are re-scored exactly against the stored rows with the query as given; the values are then the exact
+        float32 scores of the space (module docstring)."""
         if filter is not None:
             raise NotImplementedError("GpuIVFPQIndex has no filtered search: GpuFlatIndex.search(filter=...) does")
         self._need_trained()
         self._compact()
-        q = self._rows(data).contiguous()
         k = int(k)
+        q_raw = None
+        if rescore_multiplier is not None:
+            mult = _refine.check_multiplier(rescore_multiplier, self._store)
+            if not 1 <= k <= ops.MAX_K:
+                raise ValueError(f"k={k} outside 1..{ops.MAX_K}")
+            q_raw = _refine.raw_queries(data, self.dim, self.device)
+            q = self._pq._prepared(q_raw).contiguous()
+        else:
+            q = self._rows(data).contiguous()
         if self._n == 0 or q.shape[0] == 0:
             return (torch.full((q.shape[0], k), float("inf" if self.space == "l2" else "-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device))
         codes, list_off, row_ids, longest = self._pack()
         probes = self._coarse(q, self.nprobe).contiguous()
-        val, idx = ops.ivfpq_search(q, self.centroids, self._pq.codebooks, codes, list_off, row_ids, probes, k, self._adc_space,
+        m = k if q_raw is None else min(k * mult, ops.MAX_K, self._n)
+        val, idx = ops.ivfpq_search(q, self.centroids, self._pq.codebooks, codes, list_off, row_ids, probes, m, self._adc_space,
                                     by_residual=self.by_residual, max_list_len=longest, _trusted=True)
+        if q_raw is not None:
+            val, idx = self._store.rescore(q_raw, self._n, idx, k)
         return val, torch.where(idx >= 0, self._labels[idx.clamp(min=0)], torch.full_like(idx, -1))
 
-    def knn_query(self, data, k: int = 1, filter=None) -> Tuple[np.ndarray, np.ndarray]:
+    def knn_query(self, data, k: int = 1, filter=None, rescore_multiplier: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(labels [Q,k] int64, values [Q,k] float32) as numpy arrays, best first: ``GpuPQIndex.knn_query``'s conventions."""
-        val, lab = self.search(data, k, filter=filter)
+        val, lab = self.search(data, k, filter=filter, rescore_multiplier=rescore_multiplier)
         return lab.cpu().numpy(), val.cpu().numpy()
 
     def reconstruct(self, labels) -> torch.Tensor:
@@ -297,7 +327,7 @@ class GpuIVFPQIndex:
             np.savez(f, ivfpq_codes=np.ascontiguousarray(codes), labels=labels, lists=lists, centroids=self.centroids.cpu().numpy(),
                      codebooks=self._pq.codebooks.cpu().numpy(), space=np.array(self.space), dim=np.int64(self.dim), M=np.int64(self.M),
                      nlist=np.int64(self.nlist), nprobe=np.int64(self.nprobe), by_residual=np.int64(self.by_residual),
-                     kind=np.array(self.KIND))
+                     kind=np.array(self.KIND), **_refine.save_fields(self._store, n))
 
     def load_index(self, path: str, max_elements: int = 0):
         z = np.load(self._file(path), allow_pickle=False)
@@ -314,6 +344,7 @@ class GpuIVFPQIndex:
         if (codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != self.M or labels.shape != (n,) or lists.shape != (n,)
                 or cent.shape != (nlist, self.dim) or (n and (lists.min() < 0 or lists.max() >= nlist))):
             raise ValueError(f"{path}: malformed IVF-PQ index")
+        store, kept = _refine.load_store(z, path, n, self.space, self.dim, self.device)
         if nlist != self.nlist:
             self.nlist = nlist
             if not self._wide:
@@ -324,7 +355,10 @@ class GpuIVFPQIndex:
         self.train(centroids=cent, codebooks=z["codebooks"])
         self._codes = self._list = self._labels = self._dead = None
         self._n = self._n_dead = 0
+        self._store, self.refine = store, None if store is None else store.kind      # (the file decides, as for nlist)
         self._reserve(max(n, int(max_elements)))
+        if n and store is not None:
+            store.put(0, torch.from_numpy(kept).to(self.device))
         if n:
             self._codes[:n] = ops.pq_codes_from_numpy(codes, self.M, device=self.device)
             self._labels[:n] = torch.from_numpy(labels).to(self.device)
@@ -348,6 +382,8 @@ class GpuIVFPQIndex:
             labels[:self._n] = self._labels[:self._n]
             dead[:self._n] = self._dead[:self._n]
         self._codes, self._list, self._labels, self._dead = codes, lists, labels, dead
+        if self._store is not None:
+            self._store.reserve(new_cap, self._n)
 
     def _compact(self):
         if self._n_dead == 0:
@@ -357,6 +393,8 @@ class GpuIVFPQIndex:
         self._codes[:m] = self._codes[keep]
         self._list[:m] = self._list[keep]
         self._labels[:m] = self._labels[keep]
+        if self._store is not None:
+            self._store.compact(keep)
         self._dead[:self._n] = False
         self._n, self._n_dead = m, 0
         self._packed = None

@@ -4,6 +4,7 @@ torch is used for allocation, stream identity and host<->device copies only.  Ev
 CUDA (ROCm) tensors and raises otherwise: there is no CPU path in the product."""
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -368,12 +369,14 @@ def _list_operands(what, cand, lims, Q, N, dev, assume_unique):
     return (key % (N + 1)).contiguous(), new_lims, bad
 
 
-def _list_topk(what, fn_name, eq_f32, ec_f32, cand, lims, k, idx_offset, return_status, assume_unique):
+def _list_topk(what, fn_name, eq_f32, ec_f32, cand, lims, k, idx_offset, return_status, assume_unique, f16_space=None):
+    """``f16_space``: the corpus (still called ``ec_f32`` here) holds float16 rows and ``fn_name`` takes the space first."""
     _need_gpu(eq_f32, ec_f32)
     dev = eq_f32.device
-    for t, name in ((eq_f32, "eq_f32"), (ec_f32, "ec_f32")):
-        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"{what}: {name} must be float32 [rows, d] with unit inner stride")
+    for t, name, dt in ((eq_f32, "eq_f32", torch.float32),
+                        (ec_f32, "ec_f32" if f16_space is None else "ec_f16", torch.float32 if f16_space is None else torch.float16)):
+        if t.dtype != dt or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{what}: {name} must be {str(dt)[6:]} [rows, d] with unit inner stride")
     Q, d = eq_f32.shape
     N = ec_f32.shape[0]
     if ec_f32.shape[1] != d:
@@ -405,6 +408,8 @@ def _list_topk(what, fn_name, eq_f32, ec_f32, cand, lims, k, idx_offset, return_
             nbytes = L.tsim_list_topk_workspace_bytes(step, T, k)
         ws = _workspace(dev, nbytes)
         fn = getattr(L, fn_name)
+        if f16_space is not None:
+            fn = functools.partial(fn, f16_space)
         for q0 in range(0, Q, step):
             nq = min(step, Q - q0)
             rc = fn(eq_f32.data_ptr() + q0 * ldq * 4, ldq, nq, ec_f32.data_ptr(), ldc, N, d, cand.data_ptr() if T else 0, dt, T,
@@ -449,6 +454,41 @@ def l2_list_topk(eq_f32: torch.Tensor, ec_f32: torch.Tensor, cand: torch.Tensor,
         _l2_dim(eq_f32.shape[1], "l2_list_topk")
     return _list_topk("l2_list_topk", "tsim_l2_list_topk", eq_f32, ec_f32, cand, lims, k, idx_offset, return_status,
                       assume_unique)
+
+
+def f16_rows(x: torch.Tensor) -> torch.Tensor:
+    """[rows, d] float rows -> ``torch.float16`` [rows, d] on the device, each element rounded to nearest, ties to even: the bits of
+    numpy's ``astype(np.float16)`` (subnormals included).  The row store of a refine stage (:func:`f16_list_topk`).  A row
+    that is not finite after the rounding — an element beyond +-65 504 (it would become inf), inf or NaN — raises
+    ``ValueError``.  The conversion is torch's; it runs once per added row, never in a search."""
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise ValueError("f16_rows expects a 2-D tensor")
+    if not x.dtype.is_floating_point:
+        raise ValueError(f"f16_rows: rows must be floating point, not {x.dtype}")
+    out = x.to(torch.float16).contiguous()
+    if out.numel() and not bool(torch.isfinite(out).all()):
+        bad = int((~torch.isfinite(out)).any(dim=1).nonzero()[0])
+        raise ValueError(f"f16_rows: row {bad} is not finite in float16 (|x| > 65504, inf or NaN)")
+    return out
+
+
+F16_LIST_SPACES = {"cosine": _lib.SPACE_COSINE, "dot": _lib.SPACE_DOT, "l2": _lib.SPACE_L2}
+
+
+def f16_list_topk(space: str, eq_f32: torch.Tensor, ec_f16: torch.Tensor, cand: torch.Tensor, lims: Optional[torch.Tensor] = None,
+                  k: int = 10, idx_offset: int = 0, return_status: bool = False, assume_unique: bool = False):
+    """:func:`cosine_list_topk` / :func:`dot_list_topk` / :func:`l2_list_topk` (``space`` "cosine" / "dot" / "l2") over a corpus of
+    FLOAT16 rows (``ec_f16`` [N, d] ``torch.float16``, unit inner stride, any row stride; :func:`f16_rows` makes them): the
+    second stage of a refine search whose row store keeps half the bytes.  The float32 query is scored against the rows
+    widened to float32 — exactly, subnormals kept — so the result holds the bits the float32 op gives on ``ec_f16.float()``.
+    Lists, padding, status and errors are those of the float32 ops."""
+    if space not in F16_LIST_SPACES:
+        raise ValueError(f"f16_list_topk: space must be one of {sorted(F16_LIST_SPACES)}, not {space!r}")
+    if space == "l2" and isinstance(eq_f32, torch.Tensor) and eq_f32.dim() == 2:
+        _l2_dim(eq_f32.shape[1], "f16_list_topk")
+    return _list_topk("f16_list_topk", "tsim_list_topk_f16", eq_f32, ec_f16, cand, lims, k, idx_offset, return_status, assume_unique,
+                      f16_space=F16_LIST_SPACES[space])
 
 
 # ------------------------------------------------------------------------------------------------- inverted lists

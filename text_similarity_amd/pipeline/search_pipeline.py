@@ -275,10 +275,15 @@ class SemanticSearchPipeline(SearchPipeline):
     prunes and ``ef`` the beam of a search, as that class documents; removal works (tombstones), filters do not.  ``graph_entry='coarse'``
     (default ``'shared'``) starts every query from the seed rows of its ``nprobe`` nearest of ``nlist`` k-means centroids instead of
     from entry points shared by all queries — what a corpus clustered by topic needs (``nlist`` None: the index's own default,
-    about sqrt(n)).  ``nlist`` None means 1024 for ``'ivf'`` and ``'ivfpq'``."""
+    about sqrt(n)).  ``nlist`` None means 1024 for ``'ivf'`` and ``'ivfpq'``.  ``refine='float32'`` / ``'float16'`` (``'pq'`` and
+    ``'ivfpq'`` only; any other ``index_type`` raises ``ValueError``) is handed to the index, which then keeps the embeddings beside
+    the codes, and every search re-scores the ``max_num_results * rescore_multiplier`` best rows of the code search exactly
+    (the index's ``search(..., rescore_multiplier=)``).  The default of 4 is a stated default, not a measured optimum; it is
+    unused without ``refine``.  An index file at ``index_path`` whose ``refine`` differs raises ``ValueError``."""
 
     def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat",
-                 nlist: Optional[int] = None, nprobe: int = 8, pq_m: int = 8, graph_entry: str = "shared", **kwargs):
+                 nlist: Optional[int] = None, nprobe: int = 8, pq_m: int = 8, graph_entry: str = "shared",
+                 refine: Optional[str] = None, rescore_multiplier: int = 4, **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
         self.score_function = resolve_score_function(score_function, self.model)
@@ -286,15 +291,19 @@ class SemanticSearchPipeline(SearchPipeline):
         space = "ip" if self.score_function == "dot" else "cosine"
         if graph_entry != "shared" and index_type != "graph":
             raise ValueError(f"graph_entry={graph_entry!r} needs index_type='graph'")
+        if refine is not None and index_type not in ("pq", "ivfpq"):
+            raise ValueError(f"refine={refine!r} needs index_type='pq' or 'ivfpq', not {index_type!r}")
+        self.refine, self.rescore_multiplier = refine, int(rescore_multiplier)
         graph_nlist, nlist = (0 if nlist is None else nlist), (1024 if nlist is None else nlist)
         if index_type == "flat":
             self.index = GpuFlatIndex(space=space, dim=hidden, device=self.params.device)
         elif index_type == "ivf":   # approximate: each query is scored against the nprobe of nlist lists nearest to it
             self.index = GpuIVFIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, device=self.params.device)
         elif index_type == "pq":    # approximate: rows are replaced by pq_m learned bytes
-            self.index = GpuPQIndex(space=space, dim=hidden, M=pq_m, device=self.params.device)
+            self.index = GpuPQIndex(space=space, dim=hidden, M=pq_m, device=self.params.device, refine=refine)
         elif index_type == "ivfpq":   # approximate: pq_m learned bytes a row, in lists of which a query reads nprobe
-            self.index = GpuIVFPQIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, M=pq_m, device=self.params.device)
+            self.index = GpuIVFPQIndex(space=space, dim=hidden, nlist=nlist, nprobe=nprobe, M=pq_m, device=self.params.device,
+                                       refine=refine)
         elif index_type == "graph":   # approximate: a beam search over a proximity graph; ef / ef_construction / M mean something
             self.index = GpuGraphIndex(space=space, dim=hidden, M=getattr(self.params, "M", 0),
                                        ef_construction=getattr(self.params, "ef_construction", 0), device=self.params.device,
@@ -305,6 +314,8 @@ class SemanticSearchPipeline(SearchPipeline):
         self.index_type = index_type
         if os.path.exists(os.path.join(self.index_path, getattr(self.index, "_FILE_NAME", "index.bin"))):
             self.index.load_index(self.index_path)
+            if index_type in ("pq", "ivfpq") and self.index.refine != refine:   # (the file decides what the index holds)
+                raise ValueError(f"{self.index_path} holds an index with refine={self.index.refine!r}, not {refine!r}")
             if index_type == "graph":   # (the beam is a parameter of the search, not of the file)
                 self.index.set_ef(getattr(self.params, "ef", 0))
         else:
@@ -326,12 +337,13 @@ class SemanticSearchPipeline(SearchPipeline):
 
     def _search(self, queries, max_num_results: int, filter=None):
         query_embeddings = self.encode_corpus(queries)
+        mult = self.rescore_multiplier if self.refine is not None else None
         if self.index_type == "pq":
             if filter is not None:
                 raise NotImplementedError("GpuPQIndex has no filtered search: index_type='flat' does")
-            scores, labels = self.index.search(query_embeddings, max_num_results)
+            scores, labels = self.index.search(query_embeddings, max_num_results, rescore_multiplier=mult)
         elif self.index_type == "ivfpq":   # ((values, labels) as GpuPQIndex; a filter raises there)
-            scores, labels = self.index.search(query_embeddings, max_num_results, filter=filter)
+            scores, labels = self.index.search(query_embeddings, max_num_results, filter=filter, rescore_multiplier=mult)
         elif filter is None:
             labels, scores = self.index.search(query_embeddings, max_num_results)
         else:   # (labels of this index are corpus positions; the forms GpuFlatIndex.search takes)

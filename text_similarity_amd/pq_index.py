@@ -15,10 +15,17 @@ centres on a seeded sample of the rows, as ``GpuIVFIndex.train`` does for its li
 searching before training raises.  ``search`` is exact for the integer ADC scores of :func:`ops.pq_adc_topk` under (score desc,
 row asc) — l2: (distance asc, row asc) — and returns them as float32.
 
-No deletions, no filters, no sharding, no residual or IVF-PQ encoding, no OPQ rotation and no built-in refine stage here
-(DESIGN.md §7).  To refine, keep the float rows and pass the first stage's labels as they stand to ``ops.dot_list_topk`` /
-``ops.l2_list_topk`` / ``ops.cosine_list_topk(eq_f32, ec_f32, cand)``.  On disk: one numpy ``.npz`` written without pickling,
-holding the codebooks, the codes ``[n, M]`` uint8, the labels, ``space``, ``dim`` and ``M``.
+Refine stage (faiss' ``IndexRefineFlat`` / ``IndexRefine(SQfp16)``).  ``refine="float32"`` or ``"float16"`` keeps the rows as
+they were given (before the cosine normalisation) beside the codes, as float32 or as the float16 of :func:`ops.f16_rows`
+(``dim <= 768``, ``"l2"`` 767: the widths the list search takes).  ``search(q, k, rescore_multiplier=mult)`` then takes the
+``min(k * mult, ops.MAX_K, rows held)`` best rows of the ADC search as candidates and re-scores them exactly against the
+stored rows with the query as given — ``ops.cosine_list_topk`` / ``dot_list_topk`` / ``l2_list_topk`` on a float32 store,
+``ops.f16_list_topk`` on a float16 one — and returns the exact float32 scores of the index's space.  Without
+``rescore_multiplier`` a search is the ADC search, store or not.
+
+No deletions, no filters, no sharding, no residual or IVF-PQ encoding and no OPQ rotation here.  On disk: one
+numpy ``.npz`` written without pickling, holding the codebooks, the codes ``[n, M]`` uint8, the labels, ``space``, ``dim`` and
+``M``, and with a store ``refine`` and ``refine_rows`` ``[n, dim]``; loading adopts the file's ``refine``.
 """
 from __future__ import annotations
 
@@ -27,7 +34,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _refine, ops
 from ._code_index import _CodeIndex
 
 K_CENTROIDS = 256
@@ -37,7 +44,8 @@ class GpuPQIndex(_CodeIndex):
     SPACES = ("ip", "l2", "cosine")
     _CODE_DTYPE, _NP_DTYPE, _FILE_NAME = torch.uint8, np.uint8, "pq_index.bin"
 
-    def __init__(self, space: str = "ip", dim: int = 0, M: int = 8, device: Optional[torch.device] = None, seed: int = 0):
+    def __init__(self, space: str = "ip", dim: int = 0, M: int = 8, device: Optional[torch.device] = None, seed: int = 0,
+                 refine: Optional[str] = None):
         if space not in self.SPACES:
             raise ValueError(f"GpuPQIndex implements the spaces {self.SPACES}, not {space!r}")
         dim, M = int(dim), int(M)
@@ -48,6 +56,8 @@ class GpuPQIndex(_CodeIndex):
         self.space, self.M, self.dsub, self.seed = space, M, dim // M, int(seed)
         self._adc_space = "l2" if space == "l2" else "ip"
         self.codebooks: Optional[torch.Tensor] = None    # [M, 256, dsub] float32 on the device, finite
+        self.refine = _refine.check_refine("GpuPQIndex", refine, space, dim)
+        self._store = None if self.refine is None else _refine.RowStore(self.refine, space, dim, self.device)
 
     @property
     def is_trained(self) -> bool:
@@ -80,7 +90,9 @@ class GpuPQIndex(_CodeIndex):
             raise ValueError(f"expected rows of width {self.dim}, got {tuple(x.shape)}")
         if not x.dtype.is_floating_point:
             raise ValueError(f"expected float rows, got {x.dtype}")
-        x = x.to(self.device, dtype=torch.float32)
+        return self._prepared(x.to(self.device, dtype=torch.float32))
+
+    def _prepared(self, x: torch.Tensor) -> torch.Tensor:
         return self.normalise(x) if self.space == "cosine" else x
 
     def train(self, data=None, niter: int = 20, max_points_per_centroid: int = 256, codebooks=None, init_codebooks=None):
@@ -139,20 +151,56 @@ class GpuPQIndex(_CodeIndex):
             return ops.pq_codes_from_numpy(x.to(self.device), self.M)
         return ops.pq_encode_rows(self._rows(x), self.codebooks, _trusted=True)
 
-    def search(self, data, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def add_items(self, data, ids=None):
+        """Rows in (float rows are encoded; uint8 rows [n, M] are codes).  With a row store the rows as given are kept too: codes
+        alone raise ``ValueError`` then (there is no row to keep), and so does a row that is not finite in the store's dtype —
+        before anything is added."""
+        if self._store is None:
+            return super().add_items(data, ids)
+        x = data if isinstance(data, torch.Tensor) else torch.as_tensor(np.asarray(data))
+        if x.dtype == torch.uint8:
+            raise ValueError(f"refine={self.refine!r} keeps the rows: add float rows, not uint8 codes")
+        self._need_trained()
+        kept = self._store.convert(_refine.raw_queries(x, self.dim, self.device))
+        at = self._n
+        super().add_items(x, ids)
+        self._store.put(at, kept)
+
+    def _reserve(self, n: int):
+        super()._reserve(n)
+        if self._store is not None:
+            self._store.reserve(self._codes.shape[0], self._n)
+
+    def search(self, data, k: int, rescore_multiplier: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(values [Q,k] float32, labels [Q,k] int64) of float queries [Q, dim], best first: ip and cosine by (score desc, row
         asc), padded with (-inf, -1); l2 by (squared distance asc, row asc), padded with (+inf, -1).  The values are those of
-        :func:`ops.pq_adc_topk` with the index's codebooks and codes."""
+        :func:`ops.pq_adc_topk` with the index's codebooks and codes.  ``rescore_multiplier`` (an integer >= 1; needs
+        ``refine=``): the ``min(k * rescore_multiplier, ops.MAX_K, rows held)`` best of that search are re-scored exactly
+        against the stored rows with the query as given, and the values are the exact float32 scores of the space (module
+        docstring)."""
         self._need_trained()
+        k = int(k)
+        if rescore_multiplier is not None:
+            mult = _refine.check_multiplier(rescore_multiplier, self._store)
+            q_raw = _refine.raw_queries(data, self.dim, self.device)
+            m = min(k * mult, ops.MAX_K, self._n)
+            if not 1 <= k <= ops.MAX_K:
+                raise ValueError(f"k={k} outside 1..{ops.MAX_K}")
+            if m == 0 or q_raw.shape[0] == 0:
+                return _refine.padded(q_raw.shape[0], k, self.space, self.device)
+            _, cand = ops.pq_adc_topk(self._prepared(q_raw).contiguous(), self.codebooks, self._codes[:self._n], m, self._adc_space,
+                                      _trusted=True)
+            val, idx = self._store.rescore(q_raw, self._n, cand, k)
+            return val, self._to_labels(idx)
         q = self._rows(data).contiguous()
         codes = self._codes[:self._n] if self._n else torch.zeros((0, self._cb), dtype=torch.uint8, device=self.device)
-        val, idx = ops.pq_adc_topk(q, self.codebooks, codes, int(k), self._adc_space, _trusted=True)
+        val, idx = ops.pq_adc_topk(q, self.codebooks, codes, k, self._adc_space, _trusted=True)
         return val, self._to_labels(idx)
 
-    def knn_query(self, data, k: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    def knn_query(self, data, k: int = 1, rescore_multiplier: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(labels [Q,k] int64, values [Q,k] float32) as numpy arrays, best first — the order of ``GpuFlatIndex.knn_query``;
         the values are :meth:`search`'s (scores for ip and cosine, squared distances for l2)."""
-        val, lab = self.search(data, k)
+        val, lab = self.search(data, k, rescore_multiplier)
         return lab.cpu().numpy(), val.cpu().numpy()
 
     def reconstruct(self, labels) -> torch.Tensor:
@@ -172,7 +220,7 @@ class GpuPQIndex(_CodeIndex):
         codes, labels = self._stored(self.M)
         with open(self._file(path), "wb") as f:
             np.savez(f, pq_codes=np.ascontiguousarray(codes), labels=labels, codebooks=self.codebooks.cpu().numpy(),
-                     space=np.array(self.space), dim=np.int64(self.dim), M=np.int64(self.M))
+                     space=np.array(self.space), dim=np.int64(self.dim), M=np.int64(self.M), **_refine.save_fields(self._store, self._n))
 
     def load_index(self, path: str, max_elements: int = 0):
         z = np.load(self._file(path), allow_pickle=False)
@@ -184,8 +232,12 @@ class GpuPQIndex(_CodeIndex):
         codes, labels = z["pq_codes"], z["labels"].astype(np.int64)
         if codes.dtype != np.uint8 or codes.ndim != 2 or codes.shape[1] != self.M or labels.shape != (codes.shape[0],):
             raise ValueError(f"{path}: malformed PQ index")
+        store, kept = _refine.load_store(z, path, codes.shape[0], self.space, self.dim, self.device)
         self._set_codebooks(z["codebooks"])
+        self._store, self.refine = store, None if store is None else store.kind      # (the file decides)
         self._restore(codes, labels, max_elements)
+        if store is not None and codes.shape[0]:
+            store.put(0, torch.from_numpy(kept).to(self.device))
 
     @staticmethod
     def _pad_codes(codes, dim, device=None):   # (_CodeIndex._restore hands the index's dim; the row width is the codes' own)

@@ -3,6 +3,8 @@
 against the oracle of tests/list_cases.py: scores (float32 bits), indices and status words must be identical.  Every case
 draws a space, a width, Q, N, k, the form of the lists (shared / CSR / 2-D, int32 / int64), their lengths (around k, the
 wave, the LDS block and TSIM_LIST_SLICE), and sprinkles padding, repeats and rows beyond the corpus into them.
+Half of the cases keep the corpus as FLOAT16 rows (ops.f16_list_topk; a row stride of d + 1 or d, rows of subnormal halves among
+the kinds): the result must equal the oracle on the widened rows AND the float32 op on them, bit for bit.
 Usage: python tools/fuzz_list.py [cases] [seed]"""
 import os
 import sys
@@ -30,9 +32,13 @@ for case in range(cases):
     form = str(rng.choice(["shared", "csr", "2d"]))
     dt = np.int32 if rng.random() < 0.5 else np.int64
     uniq = bool(rng.random() < 0.5)
-    kind = str(rng.choice(["normal", "dups", "zeros"]))
+    half = bool(rng.random() < 0.5)
+    kind = str(rng.choice(["normal", "dups", "zeros"] + (["subnormal"] if half else [])))
     c = rng.standard_normal((N, d)).astype(np.float32)
     q = rng.standard_normal((Q, d)).astype(np.float32)
+    if kind == "subnormal":      # multiples of 2^-24 below the smallest normal half, and queries of that size
+        c = (rng.integers(-1023, 1024, size=(N, d)) * 2.0 ** -24).astype(np.float32)
+        q *= np.float32(2.0 ** -14)
     if kind == "dups":
         c[rng.choice(N, min(N, 300), replace=False)] = q[0]
     elif kind == "zeros":
@@ -59,15 +65,25 @@ for case in range(cases):
         for j, x in enumerate(lists):
             cand[j, :len(x)] = x
         lims = None
+    if half:
+        c = c.astype(np.float16).astype(np.float32)      # the widened rows: what the oracle and the float32 op see
     rs, ri, rst = list_topk_ref(space, q, c, lists, k, idx_offset=11, unique=not uniq)
     qf, cf = torch.from_numpy(q).cuda(), torch.from_numpy(c).cuda()
-    s, i, st = FN[space](qf, cf, torch.from_numpy(cand.astype(dt)).cuda(), None if lims is None else torch.from_numpy(lims).cuda(), k=k,
-                         idx_offset=11, return_status=True, assume_unique=uniq)
+    args = (torch.from_numpy(cand.astype(dt)).cuda(), None if lims is None else torch.from_numpy(lims).cuda())
+    kw = dict(k=k, idx_offset=11, return_status=True, assume_unique=uniq)
+    s, i, st = FN[space](qf, cf, *args, **kw)
     torch.cuda.synchronize()
     s, i, st = s.cpu().numpy(), i.cpu().numpy(), st.cpu().numpy()
     ok = same_bits(s, rs) and np.array_equal(i, ri) and np.array_equal(st, rst)
+    if half:
+        ld = d + int(rng.integers(0, 2))
+        buf = torch.full((N, ld), float("nan"), dtype=torch.float16, device="cuda")
+        buf[:, :d] = cf.half()
+        hs, hi, hst = ops.f16_list_topk(space, qf, buf[:, :d], *args, **kw)
+        torch.cuda.synchronize()
+        ok = ok and same_bits(hs.cpu().numpy(), rs) and np.array_equal(hi.cpu().numpy(), ri) and np.array_equal(hst.cpu().numpy(), rst)
     bad += not ok
-    print(f"case {case:3d} {space:6s} d={d:3d} Q={Q:3d} N={N:6d} k={k:4d} {form:6s} {np.dtype(dt).name:5s} unique={not uniq!s:5s} {kind:6s} "
+    print(f"case {case:3d} {space:6s} d={d:3d} Q={Q:3d} N={N:6d} k={k:4d} {form:6s} {np.dtype(dt).name:5s} unique={not uniq!s:5s} {kind:9s} {'f16' if half else 'f32'} "
           f"entries={sum(len(x) for x in lists) if form != 'shared' else len(cand):7d} {'ok' if ok else 'MISMATCH'}  ({time.time() - t0:.0f} s)",
           flush=True)
 print(f"fuzz_list: {cases - bad}/{cases} cases exact")
