@@ -439,6 +439,50 @@ int tsim_community_select_finish(const int64_t *lims, const int32_t *members, in
                                  size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HDBSCAN (`hdbscan.HDBSCAN` / `sklearn.cluster.HDBSCAN` with metric="euclidean", cluster_selection_method="eom"): density
+ * clustering without a cluster count or a threshold.  Two stages: the minimum spanning tree of the mutual-reachability graph
+ * over all row pairs (O(N^2 d), on the device) and the tree stage (O(N log N), on the host).
+ *
+ * tsim_mst_prim: Prim's algorithm from row 0, everything in SQUARED distances.  rows_f32 [N, d] float32 on the device, rows
+ * ld_rows elements apart.  d2(a, b) is the float32 value tsim_l2_topk_ex and the list entries return for the pair, bit for bit.
+ * w(a, b) = max(d2(a, b), core2[a], core2[b]) with core2 float32 [N] on the device (the squared core distances: the last
+ * column of the rows' exact Euclidean top-min_samples against themselves); core2 == NULL: w = d2, the plain Euclidean tree.
+ *   best[j] = +inf, from[j] = -1, cur = 0, the tree = {0}.  Step t = 0 .. N-2, for every row j outside the tree: if
+ *   w(cur, j) < best[j] (STRICT: the earlier endpoint keeps a tie, a NaN never updates) then best[j] = w(cur, j), from[j] = cur;
+ *   next = the row outside the tree with the smallest (best[j], j) — the lower row wins a tie;
+ *   out_from[t] = from[next], out_to[t] = next, out_w2[t] = best[next]; next joins the tree and becomes cur.
+ * out_from, out_to int32 [N-1] and out_w2 float32 [N-1] on the device.  N == 1 writes nothing and launches nothing.  Rows are
+ * expected finite; on any input the call makes exactly N - 1 steps and reads nothing outside rows_f32[0 .. N) and core2[0 .. N)
+ * (if every best is +inf the lowest free row is taken with from = -1).  Two launches per step, enqueued by the host without a
+ * read in between: one scores the free rows against row cur (a 64-row group inside the tree is not loaded), one reduces the
+ * workgroups' minima and moves cur, a device word.  Limits: 1 <= d <= 767, ld_rows >= d, 1 <= N < 2^31 - 64, else TSIM_EINVAL
+ * before any launch; a workspace below tsim_mst_prim_workspace_bytes(N) (pure host; 0 beyond the limits; 8 N bytes, 8 per 256
+ * rows and alignment) is TSIM_ENOMEM.
+ *
+ * tsim_hdbscan_tree_labels: the tree stage with cluster_selection_method="eom", allow_single_cluster=False,
+ * cluster_selection_epsilon=0, on HOST pointers (host-only code, no GPU).  from, to int32 [N-1], w2 float32 [N-1]: the edges
+ * above, squared; N >= 1; min_cluster_size >= 2.  out_labels int32 [N]: the cluster of every row, -1 for noise;
+ * *out_n_clusters: the cluster count.
+ *   1. The edges are ordered by (w2 asc, step asc) and merged by union-find: merge k makes node N + k with the component of
+ *      `from` as its left child, the component of `to` as its right child, distance sqrt((double)w2).
+ *   2. Condensing, breadth-first from the root, left child before right: lambda = 1 / distance (+inf at distance 0); a child of
+ *      fewer than min_cluster_size rows sheds its rows at that lambda; when both children are large enough two new clusters
+ *      are numbered, left first; otherwise the larger child continues its parent's cluster.
+ *   3. stability(c) = sum over the condensed rows of c, in their order, of (lambda - birth(c)) size, in float64.
+ *   4. By descending cluster number, the root never selected: a cluster whose children's summed stability is strictly greater
+ *      takes that sum and is unselected, otherwise its descendants are unselected.
+ *   5. A row's label is the rank (ascending cluster number) of the selected cluster it fell out of or of its nearest selected
+ *      ancestor; -1 without one.
+ * Edges that are no spanning tree of 0 .. N-1 (an endpoint out of range, a cycle) are TSIM_EINVAL; nothing is read or written
+ * out of bounds.  tests/hdbscan_cases.py restates both stages in numpy; tests/golden/hdbscan.npz pins the labels against
+ * scikit-learn on separated clusters. */
+size_t tsim_mst_prim_workspace_bytes(int64_t N);
+int tsim_mst_prim(const float *rows_f32, int64_t ld_rows, int64_t N, int d, const float *core2, int32_t *out_from, int32_t *out_to,
+                  float *out_w2, void *workspace, size_t workspace_bytes, void *stream);
+int tsim_hdbscan_tree_labels(const int32_t *from, const int32_t *to, const float *w2, int64_t N, int min_cluster_size,
+                             int32_t *out_labels, int32_t *out_n_clusters);
+
+/* ---------------------------------------------------------------------------------------------
  * Binary embeddings: sign-bit codes, exact Hamming top-k and the re-score of its candidates (sentence-transformers'
  * `quantize_embeddings(precision="ubinary")` with `semantic_search_faiss(..., rescore=True)`; faiss' `IndexBinaryFlat`).
  * Codes.  A code row is the `np.packbits(x > 0, axis=1)` bytes of the float row: element 8j is bit 7 of byte j, the last byte

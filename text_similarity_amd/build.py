@@ -19,14 +19,14 @@ TAG = os.environ.get("TSIM_BUILD_TAG", "")
 OBJ = os.path.join(CSRC, "_obj" + ("_" + TAG if TAG else ""))
 LIB = os.path.join(HERE, "libtsim" + ("_" + TAG if TAG else "") + ".so")
 SOURCES = ["common.hip", "search.hip", "k1_kl16.hip", "k1_d384.hip", "k1_kl32.hip", "k1_collect.hip", "gemm_pp.hip", "encoder.hip",
-           "wordpiece.cpp"]   # (host-only C++: the ASCII WordPiece tokenizer)
+           "wordpiece.cpp", "hdbscan_tree.cpp"]   # (host-only C++: the ASCII WordPiece tokenizer, the tree stage of HDBSCAN)
 HOT_KERNELS = ("l2_rows_kernel", "l2_query_rows_kernel", "l2_negate_scores", "flag_all_kernel", "cos_topk_partial", "cos_topk_finalize", "gemm_bf16", "gemm_xres", "ln_rows_gemm", "ln_rows_xres2", "ln_tail_gemm", "gemm_pp", "attention_kernel",
                "pool_packed_kernel", "dense_rows_kernel", "widen_finalize", "bf_partial", "bf_merge",
                "topk_merge_large", "list_prep", "list_partial", "list_merge", "range_setup", "range_finalize", "range_bf", "range_fill", "range_merge", "span_pool_kernel",
                "code_merge", "code_rescore", "pack_sign_rows", "hamming_partial",
                "quantize_int8_rows", "int8_ip_partial", "ivf_prep", "ivf_partial", "pq_encode_rows", "pq_tables", "pq_adc_partial",
                "ivfpq_tables", "ivfpq_scan_partial", "graph_search_kernel", "graph_prune_kernel",
-               "community_claim", "community_decide", "community_finish",
+               "community_claim", "community_decide", "community_finish", "mst_step", "mst_pick",
                "embed_ln_kernel", "cls_head_kernel", "cls_head_wide_kernel")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(os.path.dirname(HERE), "include")]

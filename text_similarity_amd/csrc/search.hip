@@ -1891,6 +1891,7 @@ static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, cons
 #include "ivfpq_search.h"   // IVF-PQ: residual tables and the exact ADC scan of the PQ-coded lists each query probes
 #include "graph_search.h"   // graph index: beam search over a proximity graph with the exact scores, and the kNN-graph pruning
 #include "community_select.h"   // community detection: the de-overlap of candidate communities, in rounds or in one workgroup
+#include "mst_prim.h"       // HDBSCAN: Prim's minimum spanning tree of the mutual-reachability graph, on the exact squared distances
 
 extern "C" int tsim_cosine_topk_plan(int64_t Q, int64_t N, int ld, int k, int32_t plan[4]) {
     if (Q <= 0 || N <= 0 || k <= 0 || k > TOPK_MAX_K || !plan || tsim_pad_dim(ld) != ld)

@@ -1803,6 +1803,107 @@ def community_candidates(eq_unit: Optional[torch.Tensor], eq_f32: torch.Tensor, 
     return centre, plims, idx[src], scores[src]
 
 
+# ------------------------------------------------------------------------------------------------- HDBSCAN
+def mst_prim(rows: torch.Tensor, core2: Optional[torch.Tensor] = None):
+    """Prim's minimum spanning tree over the float32 rows [N, d] from row 0 (include/tsim.h tsim_mst_prim), in SQUARED distances:
+    the weight of a pair is ``max(d2(a, b), core2[a], core2[b])`` with d2 the float32 value :func:`l2_topk` returns for it, or d2
+    alone without ``core2`` (float32 [N]).  Returns ``(from int32 [N-1], to int32 [N-1], w2 float32 [N-1])`` on the device, edge t
+    joining row ``to[t]`` to the tree at its nearest endpoint ``from[t]`` (the earlier one on a tie; the lower row joins first on
+    a tie).  The rows may be a strided view with unit inner stride.  d <= 767.  Nothing is read back."""
+    _need_gpu(rows)
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("mst_prim: rows must be float32 [N, d] with N >= 1")
+    if rows.stride(1) != 1 and rows.shape[1] > 1:
+        rows = rows.contiguous()
+    N, d = rows.shape
+    _l2_dim(d, "mst_prim")
+    dev = rows.device
+    if core2 is not None:
+        _need_gpu(rows, core2)
+        if core2.dtype != torch.float32 or core2.shape != (N,):
+            raise ValueError(f"mst_prim: core2 must be float32 [{N}]")
+        core2 = core2.contiguous()
+    frm = torch.empty((N - 1,), dtype=torch.int32, device=dev)
+    to = torch.empty((N - 1,), dtype=torch.int32, device=dev)
+    w2 = torch.empty((N - 1,), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, L.tsim_mst_prim_workspace_bytes(N))
+        _lib.check(L.tsim_mst_prim(rows.data_ptr(), _row_stride(rows), N, d, core2.data_ptr() if core2 is not None else 0,
+                                   frm.data_ptr(), to.data_ptr(), w2.data_ptr(), ws.data_ptr(), ws.numel(), _stream(rows)), "mst_prim")
+    return frm, to, w2
+
+
+def hdbscan_tree_labels(frm, to, w2, N: int, min_cluster_size: int):
+    """The host tree stage of HDBSCAN (include/tsim.h tsim_hdbscan_tree_labels) on numpy edges: ``(labels int32 [N], n_clusters)``.
+    ValueError where the edges are no spanning tree of rows 0 .. N-1."""
+    frm = np.ascontiguousarray(frm, dtype=np.int32)
+    to = np.ascontiguousarray(to, dtype=np.int32)
+    w2 = np.ascontiguousarray(w2, dtype=np.float32)
+    N, min_cluster_size = int(N), int(min_cluster_size)
+    if N < 1 or frm.shape != (N - 1,) or to.shape != (N - 1,) or w2.shape != (N - 1,):
+        raise ValueError(f"hdbscan_tree_labels: N={N} needs {N - 1} edges, got {frm.shape}, {to.shape}, {w2.shape}")
+    if min_cluster_size < 2:
+        raise ValueError(f"hdbscan_tree_labels: min_cluster_size={min_cluster_size} < 2")
+    labels = np.empty((N,), dtype=np.int32)
+    n_clusters = np.zeros((1,), dtype=np.int32)
+    rc = _lib.lib().tsim_hdbscan_tree_labels(frm.ctypes.data, to.ctypes.data, w2.ctypes.data, N, min_cluster_size, labels.ctypes.data,
+                                             n_clusters.ctypes.data)
+    if rc == 1:
+        raise ValueError("hdbscan_tree_labels: the edges are not a spanning tree of rows 0 .. N-1 (an endpoint out of range or a cycle)")
+    if rc != 0:
+        raise _lib.TsimError(f"hdbscan_tree_labels failed (code {rc})")
+    return labels, int(n_clusters[0])
+
+
+def hdbscan_unit_rows(rows: torch.Tensor) -> torch.Tensor:
+    """The float32 unit rows ``x / |x|.clamp(min=1e-12)`` that ``hdbscan(metric='cosine')`` clusters."""
+    return (rows / rows.norm(dim=1, keepdim=True).clamp(min=1e-12)).contiguous()
+
+
+def hdbscan(rows: torch.Tensor, min_cluster_size: int, min_samples: Optional[int] = None, metric: str = "euclidean",
+            return_info: bool = False):
+    """HDBSCAN (``hdbscan.HDBSCAN`` / ``sklearn.cluster.HDBSCAN`` with ``cluster_selection_method='eom'``) over the float32 rows
+    [N, d]: ``labels`` int64 [N] on the device, -1 for noise; neither a cluster count nor a threshold is needed.
+      1. ``core2`` = the squared distance of every row to its ``min_samples``-th nearest row, itself included: the last column of
+         :func:`l2_topk` of the rows against themselves (``min_samples`` defaults to ``min_cluster_size``);
+      2. the minimum spanning tree of the mutual-reachability graph, :func:`mst_prim` with ``core2``;
+      3. the N - 1 edges are read back once and the tree stage runs on the host (:func:`hdbscan_tree_labels`).
+    ``metric='cosine'`` runs the same on the float32 unit rows (:func:`hdbscan_unit_rows`): Euclidean distance on those is
+    monotone in cosine.  ``return_info=True`` adds a dict: ``from``, ``to``, ``w2`` (the edges, on the device), ``core2`` and
+    ``n_clusters``.  ValueError: ``min_cluster_size < 2``, ``min_samples`` outside 1 .. min(N, MAX_K), non-finite rows, d > 767,
+    another metric.  include/tsim.h has the definition and its tie rules; tests/golden/hdbscan.npz pins parity with
+    scikit-learn on separated clusters."""
+    what = "hdbscan"
+    _need_gpu(rows)
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError(f"{what}: metric={metric!r}: 'euclidean' or 'cosine'")
+    if rows.dim() != 2 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError(f"{what}: rows must be [N, d] with N >= 1")
+    N, d = rows.shape
+    _l2_dim(d, what)
+    min_cluster_size = int(min_cluster_size)
+    min_samples = min_cluster_size if min_samples is None else int(min_samples)
+    if min_cluster_size < 2:
+        raise ValueError(f"{what}: min_cluster_size={min_cluster_size} < 2")
+    if not 1 <= min_samples <= min(N, MAX_K):
+        raise ValueError(f"{what}: min_samples={min_samples} outside 1..min(N, {MAX_K}) = {min(N, MAX_K)}")
+    x = rows.float().contiguous()
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError(f"{what}: the rows hold a NaN or an infinity")
+    if metric == "cosine":
+        x = hdbscan_unit_rows(x)
+    ec, rho, maxnorm = l2_rows(x)
+    dist, _ = l2_topk(l2_query_rows(x, maxnorm), ec, d, min_samples, x, x, rho, maxnorm)
+    core2 = dist[:, min_samples - 1].contiguous()
+    frm, to, w2 = mst_prim(x, core2)
+    labels, n_clusters = hdbscan_tree_labels(frm.cpu().numpy(), to.cpu().numpy(), w2.cpu().numpy(), N, min_cluster_size)
+    out = torch.from_numpy(labels.astype(np.int64)).to(x.device)
+    if return_info:
+        return out, {"from": frm, "to": to, "w2": w2, "core2": core2, "n_clusters": n_clusters}
+    return out
+
+
 def packed_result_bytes(Q: int, k: int) -> int:
     """Bytes of one rank's result buffer: [Q,k] float32 scores, then (8-byte aligned) [Q,k] int64 indices."""
     return (Q * k * 4 + 7) // 8 * 8 + Q * k * 8

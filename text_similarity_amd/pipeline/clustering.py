@@ -16,7 +16,13 @@ to a density method for the same reason: k is not known): community detection ov
 (:func:`ops.community_detection`) — every group of at least ``min_community_size`` rows scoring >= ``threshold`` against a
 centre row, largest first, no row in two groups.  ``n_clusters`` is ignored; ``fit`` sets ``labels_`` (-1: noise, a row in no
 community), ``cluster_centers_`` (the centre ROWS, not means) and ``n_iter_`` (the rounds of the de-overlap); ``inertia_`` stays
-None; ``__call__`` returns the same dict without the noise."""
+None; ``__call__`` returns the same dict without the noise.
+
+``method="hdbscan"`` is that density method itself (:func:`ops.hdbscan`: ``hdbscan.HDBSCAN(min_cluster_size, metric=...,
+cluster_selection_method="eom")``, the minimum spanning tree on the device): it needs neither a cluster count nor a threshold
+and its clusters have any shape.  ``min_cluster_size``, ``min_samples`` (default: ``min_cluster_size``) and ``metric``
+('euclidean' or 'cosine') are its parameters; ``fit`` sets ``labels_`` (-1: noise) and ``cluster_centers_`` (the MEAN of each
+cluster's rows); ``inertia_`` stays None and ``n_iter_`` 0; ``__call__`` returns the dict without the noise."""
 from __future__ import annotations
 
 from collections import defaultdict
@@ -31,15 +37,21 @@ from .search_pipeline import Pipeline
 
 class ClusteringPipeline(Pipeline):
     def __init__(self, n_clusters, *args, method="k-means", max_iter: int = 300, seed: int = 0, init=None,
-                 threshold: Optional[float] = None, min_community_size: int = 10, **kwargs):
+                 threshold: Optional[float] = None, min_community_size: int = 10, min_cluster_size: int = 15,
+                 min_samples: Optional[int] = None, metric: str = "euclidean", **kwargs):
         super().__init__(*args, **kwargs)
-        if method not in ("k-means", "community"):
-            raise ValueError(f"method={method!r}: 'k-means' (as in the reference) or 'community'")
+        if method not in ("k-means", "community", "hdbscan"):
+            raise ValueError(f"method={method!r}: 'k-means' (as in the reference), 'community' or 'hdbscan'")
+        if method == "hdbscan" and metric not in ("euclidean", "cosine"):
+            raise ValueError(f"metric={metric!r}: 'euclidean' or 'cosine'")
         if method == "community" and threshold is None:
             raise ValueError("method='community' needs threshold= (the score two rows of one community must reach)")
         self.method = method
         self.threshold = threshold
         self.min_community_size = int(min_community_size)
+        self.min_cluster_size = int(min_cluster_size)
+        self.min_samples = min_samples
+        self.metric = metric
         self.n_clusters = int(n_clusters) if n_clusters is not None else 0
         self.max_iter = max_iter
         self.seed = seed
@@ -97,6 +109,16 @@ class ClusteringPipeline(Pipeline):
             self.inertia_ = None
             self.n_iter_ = info["rounds"]
             return self
+        if self.method == "hdbscan":
+            labels, info = ops.hdbscan(x, self.min_cluster_size, self.min_samples, self.metric, return_info=True)
+            k = info["n_clusters"]
+            keep = labels >= 0
+            sums = torch.zeros((k, d), dtype=torch.float32, device=x.device).index_add_(0, labels[keep], x[keep])
+            self.labels_ = labels
+            self.cluster_centers_ = sums / torch.bincount(labels[keep], minlength=k).clamp(min=1).unsqueeze(1)
+            self.inertia_ = None
+            self.n_iter_ = 0
+            return self
         k = min(self.n_clusters, n)
         init = self.init if init is None else init
         if init is not None:
@@ -130,7 +152,7 @@ class ClusteringPipeline(Pipeline):
         self.fit(emb)
         results = defaultdict(list)
         for text_id, cluster_id in enumerate(self.labels_.tolist()):
-            if cluster_id < 0:      # (method='community': noise)
+            if cluster_id < 0:      # (method='community' and 'hdbscan': noise)
                 continue
             results[cluster_id].append(texts[text_id] if texts is not None else text_id)
         return dict(results)
