@@ -10,6 +10,15 @@
  *   - every pointer is a DEVICE pointer unless its name ends in _host; the caller owns all buffers;
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream); calls only enqueue
  *     work on it, they never synchronise and never allocate device memory (except tsim_encoder_create);
+ *   - EVERY launch, memset and async copy of a call goes to `stream`, nothing to any other stream; only tsim_encoder_create and
+ *     tsim_encoder_error_flags synchronise.  Calls on different streams may overlap when they are given different workspaces (and,
+ *     for the encoder, different handles);
+ *   - `workspace` (where an entry takes one) is scratch of at least the entry's *_workspace_bytes: its contents on entry are
+ *     UNSPECIFIED AND IGNORED — a call initialises what it reads, whatever an earlier call of any entry left there — and
+ *     meaningless afterwards.  The two two-call protocols are the exception stated at their entries: tsim_*_range_scan* ->
+ *     tsim_range_fill*, and tsim_community_select_rounds (first_round == 0 initialises) -> further rounds / _finish, keep their
+ *     state in the workspace, which must be untouched between the calls (tests/test_workspace_poison_gpu.py,
+ *     tests/test_side_stream_gpu.py; DESIGN.md section 3 lists every region with its first writer and first reader);
  *   - return value 0 = ok, otherwise a TSIM_E* code; tsim_last_error() gives the message for the calling
  *     thread;
  *   - "unit rows" are row-major IEEE half (float16) L2-normalised rows with a row stride of `ld` elements, ld a multiple
