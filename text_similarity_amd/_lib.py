@@ -20,6 +20,9 @@ GRAPH_ST_ROW, GRAPH_ST_ITERS = 1, 2   # include/tsim.h TSIM_GRAPH_ST_*
 GRAPH_MAX_TABLE_BYTES = 131072    # include/tsim.h TSIM_GRAPH_MAX_TABLE_BYTES
 GRAPH_STATIC_LDS_BYTES = 18432    # include/tsim.h TSIM_GRAPH_STATIC_LDS_BYTES
 GRAPH_MAX_COARSE_LISTS = 4096     # include/tsim.h TSIM_GRAPH_MAX_COARSE_LISTS
+GRAPH_INSERT_ST_ROW = 1           # include/tsim_graph_insert.h TSIM_GRAPH_INSERT_ST_ROW
+GRAPH_LINK_POOL = 256             # include/tsim_graph_insert.h TSIM_GRAPH_LINK_POOL
+GRAPH_LINK_ST_CUT, GRAPH_LINK_ST_ROW, GRAPH_LINK_ST_LIMS = 1, 2, 4   # include/tsim_graph_insert.h TSIM_GRAPH_LINK_ST_*
 ARCH_BERT, ARCH_MPNET, ARCH_ROBERTA = 0, 1, 2
 W_BF16, W_MXFP8 = 0, 1
 POOL_MEAN, POOL_CLS, POOL_MAX, POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
@@ -249,6 +252,16 @@ _SIGS = {
 
 DECLARED_SYMBOLS = tuple(_SIGS)
 
+# The entries of include/tsim_graph_insert.h: exported by the same library and bound like the others, in a table of their own
+# until they move into include/tsim.h and the table above.
+_GRAPH_INSERT_SIGS = {
+    "tsim_graph_insert_prune": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "tsim_graph_link_reverse": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+GRAPH_INSERT_SYMBOLS = tuple(_GRAPH_INSERT_SIGS)
+
 
 def lib() -> C.CDLL:
     """Load libtsim.so once.  Raises TsimError (never falls back) when it has not been built."""
@@ -258,7 +271,7 @@ def lib() -> C.CDLL:
             raise TsimError(f"{LIB_PATH} not found: build it with `python -m text_similarity_amd.build` "
                             "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in {**_SIGS, **_GRAPH_INSERT_SIGS}.items():
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -25,7 +25,7 @@ HOT_KERNELS = ("l2_rows_kernel", "l2_query_rows_kernel", "l2_negate_scores", "fl
                "topk_merge_large", "list_prep", "list_partial", "list_merge", "range_setup", "range_finalize", "range_bf", "range_fill", "range_merge", "span_pool_kernel",
                "code_merge", "code_rescore", "pack_sign_rows", "hamming_partial",
                "quantize_int8_rows", "int8_ip_partial", "ivf_prep", "ivf_partial", "pq_encode_rows", "pq_tables", "pq_adc_partial",
-               "ivfpq_tables", "ivfpq_scan_partial", "graph_search_kernel", "graph_prune_kernel",
+               "ivfpq_tables", "ivfpq_scan_partial", "graph_search_kernel", "graph_prune_kernel", "graph_insert_prune_kernel", "graph_link_reverse_kernel",
                "community_claim", "community_decide", "community_finish", "mst_step", "mst_pick",
                "embed_ln_kernel", "cls_head_kernel", "cls_head_wide_kernel")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -50,7 +50,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=(), only=None) 
                            "set TSIM_BUILD_TAG=<tag> to build libtsim_<tag>.so beside it")
     os.makedirs(OBJ, exist_ok=True)
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "tsim.h"))
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("tsim.h", "tsim_graph_insert.h")]
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     jobs = []
     for s in srcs:

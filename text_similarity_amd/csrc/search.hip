@@ -1890,6 +1890,7 @@ static void launch_finalize(int sm, const TopkPlan &p, const float *part_s, cons
 #include "pq_search.h"      // product quantisation: the PQ encoder, integer lookup tables, exact ADC top-k in the code-search frame
 #include "ivfpq_search.h"   // IVF-PQ: residual tables and the exact ADC scan of the PQ-coded lists each query probes
 #include "graph_search.h"   // graph index: beam search over a proximity graph with the exact scores, and the kNN-graph pruning
+#include "graph_insert.h"   // graph index, insertion: forward edges by detour count, reverse edges by the exact score, in place
 #include "community_select.h"   // community detection: the de-overlap of candidate communities, in rounds or in one workgroup
 #include "mst_prim.h"       // HDBSCAN: Prim's minimum spanning tree of the mutual-reachability graph, on the exact squared distances
 

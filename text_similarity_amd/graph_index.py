@@ -31,11 +31,23 @@ search kernel's own coarse phase, or — past ``COARSE_KERNEL_MAX_LISTS`` centro
 call — from the exact flat search of the queries against the centroids; both give the same probes.  A seed may be a
 tombstone: tombstones route.
 
-NOT incremental: ``add_items`` after a build marks the graph stale and the next search rebuilds it whole.  ``mark_deleted`` sets
-a tombstone: the row is still traversed (it routes the search) and never returned; a rebuild compacts tombstones away.
+Insertion (``incremental``).  ``False`` (default): ``add_items`` after a build marks the graph stale and the next search rebuilds
+it whole.  ``True``: ``add_items`` on a built graph INSERTS the new rows, in sub-batches of at most ``insert_batch`` rows (default
+1024), each seeing the graph with the earlier ones linked in (:func:`ops.graph_insert`; include/tsim_graph_insert.h states the
+step): the candidates of a new row are the index's own beam search of it over the graph as it stands — ``ef = k = K0``, the index's
+``width`` and entry mode, ``max_iters`` by the rule above for ``ef = K0`` (:meth:`insert_params`) — merged with its exact neighbours
+inside the sub-batch; the build's detour rule picks its R forward edges; and every row it chose re-ranks the back half of its own
+edges with the newcomers by exact score.  Nothing is rebuilt or compacted: labels, tombstones, entry points, centroids and seed
+table stay as they are (old seeds remain valid entry points; tombstones route the candidate search and are never linked to).
+``build()`` still rebuilds everything and compacts.  ``build(insert_from=m)`` is the sub-quadratic build: the exact build, entry
+points and quantiser included, over the first m live rows, the rest inserted by the same code path — id for id what "build over
+m rows, then incremental ``add_items`` of the rest" gives.
+``mark_deleted`` sets a tombstone: the row is still traversed (it routes the search) and never returned; a rebuild compacts
+tombstones away.
 
 On disk (``index.bin``, a numpy ``.npz`` without pickling): rows, labels, tombstones, the graph, the entry points, the
-parameters and ``kind = 'graph'``; with ``entry='coarse'`` also the centroids, the seed table, ``entry``, ``nlist``, ``nprobe`` and
+parameters (``incremental`` and ``insert_batch`` only from an incremental index: a file without them loads as non-incremental) and
+``kind = 'graph'``; with ``entry='coarse'`` also the centroids, the seed table, ``entry``, ``nlist``, ``nprobe`` and
 ``seeds_per_list`` (a file without them loads as ``'shared'``); a file of another space or kind raises ``ValueError``.
 
 Not here (``NotImplementedError``; ``GpuFlatIndex`` has them): ``filter=``, range and radius search.
@@ -75,7 +87,8 @@ class GpuGraphIndex:
 
     def __init__(self, space: str = "cosine", dim: int = 0, M: int = 16, ef_construction: int = 0, ef: int = 64, width: int = 4,
                  n_entries: int = 64, max_iters: Optional[int] = None, device: Optional[torch.device] = None, seed: int = 0,
-                 entry: str = "shared", nlist: int = 0, nprobe: int = 8, seeds_per_list: int = 4):
+                 entry: str = "shared", nlist: int = 0, nprobe: int = 8, seeds_per_list: int = 4, incremental: bool = False,
+                 insert_batch: int = 1024):
         if space not in self.SPACES:
             raise ValueError(f"GpuGraphIndex implements the spaces {self.SPACES}, not {space!r}")
         self.space = space
@@ -94,6 +107,9 @@ class GpuGraphIndex:
         self.entry, self.nlist, self.seeds_per_list = entry, int(nlist), int(seeds_per_list)
         self.nprobe = int(nprobe)                      # (entry='shared' ignores it and seeds_per_list, whatever they are)
         self._check_entry_budget()
+        if int(insert_batch) < 1:
+            raise ValueError(f"insert_batch={insert_batch} < 1")
+        self.incremental, self.insert_batch = bool(incremental), int(insert_batch)
         self.coarse = "auto"                           # 'kernel' | 'flat': force one route of the probes (tools/bench_graph.py)
         self.ef = 1
         self.set_ef(ef)
@@ -164,12 +180,18 @@ class GpuGraphIndex:
         lab = torch.as_tensor(np.asarray(list(ids), dtype=np.int64))
         if lab.numel() != n:
             raise ValueError("ids and data disagree in length")
+        n0 = self._n
+        insert = bool(n) and self.incremental and self.graph is not None and n0 > 0 and self.graph.shape[0] == n0
+        if insert and self.entry == "coarse" and self.centroids is None:      # (as search: a graph from before the entry mode was set)
+            self.build_coarse()
         self._reserve(self._n + n)
         self._f32[self._n:self._n + n] = x.to(self.device, dtype=torch.float32)
         self._labels[self._n:self._n + n] = lab.to(self.device)
         self._dead[self._n:self._n + n] = False
         self._n += n
-        if n:
+        if insert:
+            self._insert(n0)
+        elif n:
             self.graph = None      # stale: rebuilt, whole, before the next search
 
     def mark_deleted(self, label: int):
@@ -250,12 +272,23 @@ class GpuGraphIndex:
         keep = torch.arange(K0 + 1, device=self.device)[None, :] != drop[:, None]
         return idx[keep].view(n, K0).to(torch.int32).contiguous()
 
-    def build(self, knn: Optional[torch.Tensor] = None, centroids=None):
+    def build(self, knn: Optional[torch.Tensor] = None, centroids=None, insert_from: Optional[int] = None):
         """(Re)build the graph and the entry points from the stored live rows.  ``knn``: what :meth:`knn_graph` returned for them
-        (tools/bench_graph.py times the stages apart).  ``centroids`` (``entry='coarse'``): :meth:`build_coarse`."""
+        (tools/bench_graph.py times the stages apart).  ``centroids`` (``entry='coarse'``): :meth:`build_coarse`.  ``insert_from``
+        = m: the exact build over the first m live rows only, the rest inserted (module docstring)."""
         if centroids is not None and self.entry != "coarse":
             raise ValueError("build(centroids=...) needs entry='coarse'")
         self._compact()
+        if insert_from is not None and 0 < int(insert_from) < self._n:
+            if knn is not None:
+                raise ValueError("build(insert_from=...) makes its own kNN graph of the first rows")
+            n, self._n = self._n, int(insert_from)
+            try:
+                self.build(centroids=centroids)
+            finally:
+                self._n = n
+            self._insert(int(insert_from))
+            return
         n = self._n
         self.centroids = self.seeds = self._coarse_ops = None
         if n == 0:
@@ -269,6 +302,41 @@ class GpuGraphIndex:
         self._row_ids = None
         if self.entry == "coarse":
             self.build_coarse(centroids)
+
+    def insert_params(self) -> Tuple[int, int]:
+        """(ef, max_iters) of the candidate search of an insertion: ``ef = K0`` and :meth:`search_params`' rule for it, over the
+        entry points the graph has."""
+        E = self._n_probe() * self.seeds_per_list if self.entry == "coarse" else max(1, int(self.entries.numel()))
+        fit = ops.graph_max_iters(E, self.R, self.width)
+        iters = (3 * self.K0 + 2 * self.width - 1) // (2 * self.width) + 8 if self.max_iters is None else int(self.max_iters)
+        return self.K0, max(1, min(iters, fit))
+
+    def _insert(self, n0: int):
+        """Link the stored rows n0 .. _n - 1 into the graph over the rows before them, ``insert_batch`` rows at a time."""
+        n1 = self._n
+        graph = torch.empty((n1, self.R), dtype=torch.int32, device=self.device)
+        graph[:n0] = self.graph
+        ef, iters = self.insert_params()
+        for a in range(n0, n1, self.insert_batch):
+            b = min(self.insert_batch, n1 - a)
+            new = self._f32[a:a + b]
+            row_ids = None
+            if self._n_dead:
+                ids = torch.arange(a, dtype=torch.int32, device=self.device)
+                row_ids = torch.where(self._dead[:a], torch.full_like(ids, -1), ids)
+            if self.entry == "coarse":
+                P = self._n_probe()
+                if self._kernel_coarse(b):
+                    how = dict(seeded=dict(centroids=self.centroids, n_probe=P, seeds=self.seeds))
+                else:
+                    probes = self._exact_search(new, self.centroids, P, self._coarse_ops).to(torch.int32)
+                    how = dict(seeded=dict(probes=probes, seeds=self.seeds))
+            else:
+                how = dict(entries=self.entries)
+            ops.graph_insert(_OPS_SPACE[self.space], self._f32[:a + b], graph[:a + b], a, self.K0, width=self.width, max_iters=iters,
+                             row_ids=row_ids, ef=ef, **how)
+        self.graph = graph
+        self._row_ids = None
 
     def search_params(self, k: int) -> Tuple[int, int]:
         """(ef, max_iters) a search for ``k`` results uses (module docstring)."""
@@ -362,11 +430,13 @@ class GpuGraphIndex:
                           seeds_per_list=np.int64(self.seeds_per_list), given_centroids=np.bool_(self._given_centroids is not None),
                           centroids=self.centroids.cpu().numpy() if n else np.zeros((0, self.dim), np.float32),
                           seeds=self.seeds.cpu().numpy() if n else np.zeros((0, self.seeds_per_list), np.int32))
+        # (optional keys: a non-incremental index writes exactly the arrays of a file from before insertion existed)
+        insertion = dict(incremental=np.bool_(True), insert_batch=np.int64(self.insert_batch)) if self.incremental else {}
         with open(path, "wb") as f:
             np.savez(f, rows_f32=rows, labels=labels, dead=dead, graph=self.graph.cpu().numpy(), entries=self.entries.cpu().numpy(),
                      dim=np.int64(self.dim), space=np.array(self.space), R=np.int64(self.R), K0=np.int64(self.K0), ef=np.int64(self.ef),
                      width=np.int64(self.width), n_entries=np.int64(self.n_entries), seed=np.int64(self.seed),
-                     kind=np.array(self.KIND), **coarse)
+                     kind=np.array(self.KIND), **coarse, **insertion)
 
     def load_index(self, path: str, max_elements: int = 0):
         if os.path.isdir(path):
@@ -382,6 +452,8 @@ class GpuGraphIndex:
         self.R, self.K0, self.width = int(z["R"]), int(z["K0"]), int(z["width"])
         self.n_entries, self.seed = int(z["n_entries"]), int(z["seed"])
         self.set_ef(int(z["ef"]))
+        self.incremental = bool(z["incremental"]) if "incremental" in z.files else False
+        self.insert_batch = int(z["insert_batch"]) if "insert_batch" in z.files else 1024
         self._f32 = self._labels = self._dead = self._row_ids = None
         self._n = self._n_dead = 0
         rows = z["rows_f32"]

@@ -774,6 +774,174 @@ def graph_merge_reverse(fwd: torch.Tensor) -> torch.Tensor:
     return out.to(torch.int32)
 
 
+# ------------------------------------------------------------------------------------------------- graph index: insertion
+GRAPH_INSERT_ST_ROW = _lib.GRAPH_INSERT_ST_ROW                  # include/tsim_graph_insert.h
+GRAPH_LINK_POOL = _lib.GRAPH_LINK_POOL
+GRAPH_LINK_ST_CUT, GRAPH_LINK_ST_ROW, GRAPH_LINK_ST_LIMS = _lib.GRAPH_LINK_ST_CUT, _lib.GRAPH_LINK_ST_ROW, _lib.GRAPH_LINK_ST_LIMS
+
+
+def graph_insert_prune(cand: torch.Tensor, graph: torch.Tensor, R: Optional[int] = None, return_detours: bool = False):
+    """The forward rows [B,R] int32 of B new rows n .. n + B - 1 from their candidates ``cand`` int32 [B,K0] (best first, -1 padded)
+    over the graph ``graph`` int32 [n,R] of the rows before them (include/tsim_graph_insert.h tsim_graph_insert_prune):
+    :func:`graph_prune`'s detour rule with the neighbour lists that exist at insertion time — ``graph[c]`` for an old candidate,
+    the first R candidates of a batch row.  Returns (forward, status [B] int32) — ``GRAPH_INSERT_ST_ROW`` where a row held an id
+    >= n + B — with the counts [B,K0] int32 in between when ``return_detours``.  ``R`` defaults to the graph's degree (and must be
+    it)."""
+    what = "graph_insert_prune"
+    _need_gpu(cand, graph)
+    if cand.dtype != torch.int32 or cand.dim() != 2 or not cand.is_contiguous():
+        raise ValueError(f"{what}: cand must be a contiguous int32 [B, K0] tensor")
+    if graph.dtype != torch.int32 or graph.dim() != 2 or not graph.is_contiguous():
+        raise ValueError(f"{what}: graph must be a contiguous int32 [n, R] tensor")
+    B, K0 = cand.shape
+    n = int(graph.shape[0])
+    if R is not None and int(R) != graph.shape[1]:
+        raise ValueError(f"{what}: R={R}, the graph's rows hold {graph.shape[1]}")
+    R = int(graph.shape[1])
+    fwd = torch.empty((B, R), dtype=torch.int32, device=cand.device)
+    det = torch.empty((B, K0), dtype=torch.int32, device=cand.device) if return_detours else None
+    status = torch.zeros((B,), dtype=torch.int32, device=cand.device)
+    if B:
+        if n == 0:
+            raise ValueError(f"{what}: no graph rows")
+        with torch.cuda.device(cand.device):
+            rc = _lib.lib().tsim_graph_insert_prune(cand.data_ptr(), B, K0, graph.data_ptr(), n, R, fwd.data_ptr(),
+                                                    det.data_ptr() if return_detours else 0, status.data_ptr(), _stream(cand))
+            _lib.check(rc, what)
+    return (fwd, det, status) if return_detours else (fwd, status)
+
+
+def graph_link_reverse(space: str, rows_f32: torch.Tensor, graph: torch.Tensor, targets: torch.Tensor, in_lims: torch.Tensor,
+                       in_ids: torch.Tensor) -> torch.Tensor:
+    """Link incoming rows into the graph rows of ``targets``, IN PLACE (include/tsim_graph_insert.h tsim_graph_link_reverse):
+    target t keeps the first R/2 of its valid entries; its other entries and its incoming rows ``in_ids[in_lims[j] :
+    in_lims[j + 1]]`` (int32 / int64 [T+1], CSR in the targets' order) — without ids already kept and without repeats, the first
+    ``GRAPH_LINK_POOL`` of them — compete for the other R - R/2 places by their exact score against row t, the order and bits of
+    the list searches.  ``targets`` int32 [T]: distinct rows.  ``graph`` int32 [N,R] contiguous, updated; ``rows_f32`` [N,d].
+    Returns the status [T] int32: ``GRAPH_LINK_ST_CUT`` / ``_ROW`` / ``_LIMS``."""
+    what = "graph_link_reverse"
+    if space not in IVF_SPACES:
+        raise ValueError(f"{what}: space {space!r}: one of {tuple(IVF_SPACES)}")
+    _need_gpu(rows_f32, graph, targets, in_lims, in_ids)
+    if rows_f32.dtype != torch.float32 or rows_f32.dim() != 2 or rows_f32.stride(1) != 1:
+        raise ValueError(f"{what}: rows_f32 must be float32 [rows, d] with unit inner stride")
+    N, d = rows_f32.shape
+    if space == "l2":
+        _l2_dim(d, what)
+    if graph.dtype != torch.int32 or graph.dim() != 2 or graph.shape[0] != N or not graph.is_contiguous():
+        raise ValueError(f"{what}: graph must be a contiguous int32 [{N}, R] tensor")
+    if targets.dtype != torch.int32 or targets.dim() != 1 or not targets.is_contiguous():
+        raise ValueError(f"{what}: targets must be a contiguous int32 [T] tensor")
+    T = int(targets.numel())
+    if in_lims.dtype != torch.int64 or in_lims.shape != (T + 1,) or not in_lims.is_contiguous():
+        raise ValueError(f"{what}: in_lims must be a contiguous int64 [{T + 1}] tensor")
+    if in_ids.dtype != torch.int32 or in_ids.dim() != 1 or not in_ids.is_contiguous():
+        raise ValueError(f"{what}: in_ids must be a contiguous int32 [in_lims[T]] tensor")
+    status = torch.zeros((T,), dtype=torch.int32, device=graph.device)
+    if T:
+        if in_ids.numel() == 0:      # (nothing comes in, but a row may still be re-ranked: the kernel wants a pointer)
+            in_ids = torch.zeros((1,), dtype=torch.int32, device=graph.device)
+        with torch.cuda.device(graph.device):
+            rc = _lib.lib().tsim_graph_link_reverse(IVF_SPACES[space], rows_f32.data_ptr(), _row_stride(rows_f32), N, d, graph.data_ptr(),
+                                                    int(graph.shape[1]), targets.data_ptr(), T, in_lims.data_ptr(), in_ids.data_ptr(),
+                                                    status.data_ptr(), _stream(graph))
+            _lib.check(rc, what)
+    return status
+
+
+_LIST_TOPK = {"cosine": "cosine_list_topk", "dot": "dot_list_topk", "l2": "l2_list_topk"}
+
+
+def graph_insert_candidates(space: str, rows_f32: torch.Tensor, n: int, old_scores: torch.Tensor, old_idx: torch.Tensor, K0: int):
+    """Step 1 of :func:`graph_insert` behind the beam search: ``old_scores`` / ``old_idx`` [b,K0] are what the search of the new
+    rows ``rows_f32[n:]`` over the graph returned (rows, -1 padded).  Each new row's exact best ``min(K0 + 1, b)`` among the b new
+    rows come from the space's list search (ids n + j), the row itself dropped by the build's rule — itself, or the last entry when
+    duplicates pushed it out — and the candidates int32 [b,K0] are the first K0 of both by (score desc, id asc), 'l2' (dist^2 asc,
+    id asc), -1 padded.  Both searches return the same exact float32 scores, so the merge compares like with like."""
+    dev = rows_f32.device
+    new = rows_f32[n:]
+    b = new.shape[0]
+    kn = min(int(K0) + 1, b)
+    s, i = globals()[_LIST_TOPK[space]](new, new, torch.arange(b, dtype=torch.int32, device=dev), None, kn, idx_offset=n,
+                                        assume_unique=True)
+    own = i == (n + torch.arange(b, device=dev))[:, None]
+    drop = torch.where(own.any(1), own.to(torch.int8).argmax(1), torch.full((b,), kn - 1, device=dev))
+    keep = torch.arange(kn, device=dev)[None, :] != drop[:, None]
+    s, i = s[keep].view(b, kn - 1), i[keep].view(b, kn - 1)
+    ids = torch.cat([old_idx, i], dim=1)
+    sc = torch.cat([old_scores, s], dim=1)
+    # three stable sorts, the last key first: id, then score, then padding behind everything real
+    o = torch.sort(ids, dim=1, stable=True)[1]
+    ids, sc = ids.gather(1, o), sc.gather(1, o)
+    o = torch.sort(sc, dim=1, stable=True, descending=space != "l2")[1]
+    ids, sc = ids.gather(1, o), sc.gather(1, o)
+    o = torch.sort((ids < 0).to(torch.int8), dim=1, stable=True)[1]
+    ids = ids.gather(1, o)[:, :int(K0)]
+    if ids.shape[1] < int(K0):
+        ids = torch.cat([ids, torch.full((b, int(K0) - ids.shape[1]), -1, dtype=ids.dtype, device=dev)], dim=1)
+    return ids.to(torch.int32).contiguous()
+
+
+def graph_insert_incoming(forward: torch.Tensor, n: int):
+    """(targets int32 [T], in_lims int64 [T+1], in_ids int32) of the forward rows ``forward`` [b,R] of the new rows n .. n + b - 1:
+    the sorted distinct rows some new row chose, and for each the new rows that chose it ordered by (the position of the target in
+    the chooser's forward row, chooser) — :func:`graph_merge_reverse`'s order.  Integers only (a stable sort on the device)."""
+    b, R = forward.shape
+    dev = forward.device
+    dst = forward.t().reshape(-1)                                 # edges in (position, chooser) order
+    src = (int(n) + torch.arange(b, dtype=torch.int32, device=dev)).repeat(R)
+    ok = dst >= 0
+    dst, src = dst[ok], src[ok]
+    dst, o = torch.sort(dst, stable=True)
+    targets, counts = torch.unique_consecutive(dst, return_counts=True)
+    lims = torch.zeros((targets.numel() + 1,), dtype=torch.int64, device=dev)
+    lims[1:] = torch.cumsum(counts, 0)
+    return targets.to(torch.int32).contiguous(), lims, src[o].contiguous()
+
+
+def graph_insert(space: str, rows_f32: torch.Tensor, graph: torch.Tensor, n: int, K0: int, *, entries: Optional[torch.Tensor] = None,
+                 seeded: Optional[dict] = None, width: int = 4, max_iters: Optional[int] = None,
+                 row_ids: Optional[torch.Tensor] = None, ef: Optional[int] = None):
+    """One insertion step (include/tsim_graph_insert.h): link the b new rows ``rows_f32[n:]`` into the graph over ``rows_f32[:n]``.
+    ``graph`` int32 [n + b, R] contiguous holds that graph in its first n rows and is UPDATED IN PLACE: rows n .. n + b - 1 are
+    written, the rows some new row chose re-ranked.
+      1. candidates: :func:`graph_search` from ``entries``, or :func:`graph_search_seeded` with the keyword arguments ``seeded``
+         (probes / centroids / n_probe / seeds), of the new rows over ``graph[:n]`` with ``k = K0`` and a beam of ``ef`` (default
+         K0), ``width``, ``max_iters``, ``row_ids`` (int32 [n]: tombstones route and are not returned, so no new row links to
+         one; the ids must be the rows), merged with the exact search among the new rows (:func:`graph_insert_candidates`);
+      2. forward rows: :func:`graph_insert_prune`;
+      3. reverse edges: :func:`graph_link_reverse` over the targets of :func:`graph_insert_incoming`.
+    Returns (the new graph rows ``graph[n:]``, prune status [b], targets int32 [T], link status [T]).  Nothing is read back from
+    the device except the sizes of the edge lists."""
+    what = "graph_insert"
+    if space not in IVF_SPACES:
+        raise ValueError(f"{what}: space {space!r}: one of {tuple(IVF_SPACES)}")
+    if (entries is None) == (seeded is None):
+        raise ValueError(f"{what}: exactly one of entries and seeded must be given")
+    _need_gpu(rows_f32, graph)
+    n, K0 = int(n), int(K0)
+    total = rows_f32.shape[0]
+    if graph.dtype != torch.int32 or graph.dim() != 2 or graph.shape[0] != total or not graph.is_contiguous():
+        raise ValueError(f"{what}: graph must be a contiguous int32 [{total}, R] tensor")
+    if not 1 <= n < total:
+        raise ValueError(f"{what}: n={n} outside 1..{total - 1}: the step needs a graph and new rows")
+    R = int(graph.shape[1])
+    if not R <= K0 <= GRAPH_PRUNE_MAX_K0:
+        raise ValueError(f"{what}: K0={K0} outside R={R}..{GRAPH_PRUNE_MAX_K0}")
+    ef = K0 if ef is None else int(ef)
+    new, old, g_old = rows_f32[n:], rows_f32[:n], graph[:n]
+    if entries is not None:
+        s, i = graph_search(space, new, old, g_old, entries, K0, ef, width=width, max_iters=max_iters, row_ids=row_ids)
+    else:
+        s, i = graph_search_seeded(space, new, old, g_old, K0, ef, width=width, max_iters=max_iters, row_ids=row_ids, **seeded)
+    cand = graph_insert_candidates(space, rows_f32, n, s, i, K0)
+    fwd, st_prune = graph_insert_prune(cand, g_old)
+    graph[n:] = fwd
+    targets, lims, ids = graph_insert_incoming(fwd, n)
+    st_link = graph_link_reverse(space, rows_f32, graph, targets, lims, ids)
+    return graph[n:], st_prune, targets, st_link
+
+
 # ------------------------------------------------------------------------------------------------- code searches: the shared frame
 MAX_CODE_DIM = 1024             # include/tsim.h: 1 <= d <= 1024 for the sign-bit and the int8 codes
 

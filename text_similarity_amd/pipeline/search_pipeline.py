@@ -275,7 +275,9 @@ class SemanticSearchPipeline(SearchPipeline):
     prunes and ``ef`` the beam of a search, as that class documents; removal works (tombstones), filters do not.  ``graph_entry='coarse'``
     (default ``'shared'``) starts every query from the seed rows of its ``nprobe`` nearest of ``nlist`` k-means centroids instead of
     from entry points shared by all queries — what a corpus clustered by topic needs (``nlist`` None: the index's own default,
-    about sqrt(n)).  ``nlist`` None means 1024 for ``'ivf'`` and ``'ivfpq'``.  ``refine='float32'`` / ``'float16'`` (``'pq'`` and
+    about sqrt(n)).  ``graph_incremental=True`` (``'graph'`` only) makes ``add_to_index`` insert the new rows into the built graph, as
+hnswlib's ``add_items`` does, where the default rebuilds the graph at the next search (``GpuGraphIndex(incremental=)``; like
+``ef`` it is the pipeline's word, not the file's).  ``nlist`` None means 1024 for ``'ivf'`` and ``'ivfpq'``.  ``refine='float32'`` / ``'float16'`` (``'pq'`` and
     ``'ivfpq'`` only; any other ``index_type`` raises ``ValueError``) is handed to the index, which then keeps the embeddings beside
     the codes, and every search re-scores the ``max_num_results * rescore_multiplier`` best rows of the code search exactly
     (the index's ``search(..., rescore_multiplier=)``).  The default of 4 is a stated default, not a measured optimum; it is
@@ -283,7 +285,7 @@ class SemanticSearchPipeline(SearchPipeline):
 
     def __init__(self, index_path, *args, score_function: Optional[str] = None, index_type: str = "flat",
                  nlist: Optional[int] = None, nprobe: int = 8, pq_m: int = 8, graph_entry: str = "shared",
-                 refine: Optional[str] = None, rescore_multiplier: int = 4, **kwargs):
+                 graph_incremental: bool = False, refine: Optional[str] = None, rescore_multiplier: int = 4, **kwargs):
         super().__init__(*args, **kwargs)
         self.index_path = index_path
         self.score_function = resolve_score_function(score_function, self.model)
@@ -291,6 +293,8 @@ class SemanticSearchPipeline(SearchPipeline):
         space = "ip" if self.score_function == "dot" else "cosine"
         if graph_entry != "shared" and index_type != "graph":
             raise ValueError(f"graph_entry={graph_entry!r} needs index_type='graph'")
+        if graph_incremental and index_type != "graph":
+            raise ValueError(f"graph_incremental={graph_incremental!r} needs index_type='graph'")
         if refine is not None and index_type not in ("pq", "ivfpq"):
             raise ValueError(f"refine={refine!r} needs index_type='pq' or 'ivfpq', not {index_type!r}")
         self.refine, self.rescore_multiplier = refine, int(rescore_multiplier)
@@ -307,7 +311,7 @@ class SemanticSearchPipeline(SearchPipeline):
         elif index_type == "graph":   # approximate: a beam search over a proximity graph; ef / ef_construction / M mean something
             self.index = GpuGraphIndex(space=space, dim=hidden, M=getattr(self.params, "M", 0),
                                        ef_construction=getattr(self.params, "ef_construction", 0), device=self.params.device,
-                                       entry=graph_entry, nlist=graph_nlist, nprobe=nprobe)
+                                       entry=graph_entry, nlist=graph_nlist, nprobe=nprobe, incremental=bool(graph_incremental))
             self.index.set_ef(getattr(self.params, "ef", 0))
         else:
             raise ValueError(f"index_type={index_type!r}: one of 'flat', 'ivf', 'pq', 'ivfpq', 'graph'")
@@ -318,6 +322,7 @@ class SemanticSearchPipeline(SearchPipeline):
                 raise ValueError(f"{self.index_path} holds an index with refine={self.index.refine!r}, not {refine!r}")
             if index_type == "graph":   # (the beam is a parameter of the search, not of the file)
                 self.index.set_ef(getattr(self.params, "ef", 0))
+                self.index.incremental = bool(graph_incremental)
         else:
             self._index(self.corpus)
 

@@ -21,6 +21,16 @@ every cell
                                 search with the probes handed in ready — a route minus ``given`` is what its coarse phase costs;
   coarse_recall10, coarse_cut   as recall10 and cut.
 --entry shared (the default) prints the lines this tool printed before the option existed.
+
+``--insert B [--base M] [--insert-batch S]`` measures INSERTION instead (GpuGraphIndex(incremental=True)) and prints, per corpus,
+two JSON lines.  ``add``: B rows added to an index built over the first N - B rows, the two ways ALTERNATING inside every
+round and each timed to a synchronised search result —
+  insert_s    ``add_items`` of an incremental index (the rows are linked in), then one search of 256 queries;
+  rebuild_s   the behaviour without it: ``add_items`` marks the graph stale and that search rebuilds it over all N rows;
+median [min, max] over R rounds, both starting from the same built graph of N - B rows every time.  ``build``: the graph over all N
+rows the two ways, alternating — ``insert_build_s``, ``build(insert_from=M)`` (M default N / 2), and ``exact_build_s``,
+``build()`` — with, for both graphs, recall@10 against GpuFlatIndex on 256 fresh queries at every --ef (the first --width), and
+``orphans``: the share of the inserted rows that end with in-degree 0.
 Not part of bench.py."""
 import argparse
 import json
@@ -57,6 +67,9 @@ ap.add_argument("--data", nargs="+", default=["mixture", "gauss"], choices=["mix
 ap.add_argument("--entry", nargs="+", default=["shared"], choices=["shared", "coarse"])
 ap.add_argument("--seeds-per-list", type=int, default=4)
 ap.add_argument("--coarse", nargs="+", default=["kernel", "flat"], choices=["kernel", "flat"])
+ap.add_argument("--insert", type=int, default=0)
+ap.add_argument("--base", type=int, default=0)
+ap.add_argument("--insert-batch", type=int, default=1024)
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_graph.py measures on the GPU: no device found")
@@ -104,6 +117,72 @@ def wall(f):
 def recall(got, truth):
     return round(float((got[:, :, None] == truth[:, None, :]).any(2).float().sum(1).mean()) / truth.shape[1], 4)
 
+
+def bench_insert(kind):
+    B, M = a.insert, (a.base or N // 2)
+    mode = dict(entry=a.entry[0], nlist=a.nlist, nprobe=a.nprobe, seeds_per_list=a.seeds_per_list)
+    g.manual_seed(1000 + N % 997)
+    x = draw(kind, N)
+    q = draw(kind, 256)
+    flat = GpuFlatIndex(a.space, d, device=dev)
+    flat.add_items(x)
+    truth = flat.search(q, 10)[0]
+    del flat
+    made = {}
+    for inc in (True, False):       # two indexes over the first N - B rows, built alike
+        ix = GpuGraphIndex(a.space, d, M=a.M, ef_construction=a.ef_construction, device=dev, width=a.width[0], incremental=inc,
+                           insert_batch=a.insert_batch, **mode)
+        ix.init_index(N)
+        ix.add_items(x[:N - B])
+        ix.build()
+        made[inc] = (ix, ix.graph.clone())
+
+    def add(inc):
+        ix, graph = made[inc]
+        ix._n, ix.graph, ix._row_ids = N - B, graph.clone(), None      # back to the built index of N - B rows
+        torch.cuda.synchronize()
+        t = time.time()
+        ix.add_items(x[N - B:])
+        ix.search(q, 10)
+        torch.cuda.synchronize()
+        return time.time() - t
+    t_ins, t_reb = [], []
+    for r in range(a.rounds):
+        for into, inc in ((t_ins, True), (t_reb, False)) if r % 2 == 0 else ((t_reb, False), (t_ins, True)):
+            into.append(add(inc))
+    rec = {inc: recall(made[inc][0].search(q, 10)[0], truth) for inc in made}
+    print(json.dumps({"data": kind, "what": "add", "space": a.space, "N": N, "d": d, "B": B, "R": made[True][0].R, "K0": made[True][0].K0,
+                      "entry": a.entry[0], "insert_batch": a.insert_batch, "insert_s": spread(t_ins), "rebuild_s": spread(t_reb),
+                      "insert_recall10": rec[True], "rebuild_recall10": rec[False], "ef": made[True][0].ef}), flush=True)
+    ix = made[True][0]
+    del made
+    ix._n, ix.graph = N, None
+    t_by, t_ex, graphs = [], [], {}
+    for r in range(a.rounds):
+        for name in ("insert", "exact") if r % 2 == 0 else ("exact", "insert"):
+            _, t = wall((lambda: ix.build(insert_from=M)) if name == "insert" else ix.build)
+            (t_by if name == "insert" else t_ex).append(t)
+            graphs[name] = ix.graph
+    seen = torch.zeros((N,), dtype=torch.bool, device=dev)
+    seen[graphs["insert"][graphs["insert"] >= 0].long()] = True
+    rec = {}
+    for name, graph in graphs.items():
+        ix.graph = graph
+        for ef in a.ef:
+            ix.set_ef(ef)
+            rec[f"{name}_recall10_ef{ef}"] = recall(ix.search(q, 10)[0], truth)
+    print(json.dumps({"data": kind, "what": "build", "space": a.space, "N": N, "d": d, "insert_from": M, "R": ix.R, "K0": ix.K0,
+                      "entry": a.entry[0], "insert_batch": a.insert_batch, "width": ix.width, "insert_build_s": spread(t_by),
+                      "exact_build_s": spread(t_ex), **rec, "orphans": round(float((~seen[M:]).float().mean()), 4),
+                      "insert_mean_degree": round(float((graphs["insert"] >= 0).sum(1).float().mean()), 2),
+                      "exact_mean_degree": round(float((graphs["exact"] >= 0).sum(1).float().mean()), 2)}), flush=True)
+
+
+if a.insert:
+    for kind in a.data:
+        bench_insert(kind)
+        torch.cuda.empty_cache()
+    sys.exit(0)
 
 for kind in a.data:
     flat = GpuFlatIndex(a.space, d, device=dev)

@@ -8,6 +8,11 @@ R and a kNN graph with repeats, padding and ids >= N.  Every fourth case from th
 (ops.graph_search_seeded against tests/graph_seed_cases.py): the same draws with per-query entry points instead — a seed table
 [T, S] and probes [Q, P] with padding, repeats and ids past their tables, or no seed table (probes as rows), or centroids, some of
 them NaN or duplicates, for the kernel's own coarse phase (then the probes are compared too).
+Behind them come cases // 4 (at least one) INSERTION cases against tests/graph_insert_cases.py, drawn from a generator of their own
+so that the cases above keep their draws: in turn a prune case (ops.graph_insert_prune: N, B, K0, R, candidates with padding,
+repeats, batch rows and ids >= n + B), a link case (ops.graph_link_reverse: a space, a width, a crafted graph, targets and
+incoming lists with padding, repeats, ids >= N, NaN and duplicate rows, now and then a pool beyond 256 entries) and a whole
+insertion (ops.graph_insert, sub-batch after sub-batch, against insert_ref: the graph rows must be identical).
 Usage: python tools/fuzz_graph.py [cases] [seed]"""
 import os
 import sys
@@ -17,13 +22,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import torch
-from graph_cases import detours, forward_lists, graph_search_ref, merge_reverse, random_graph, random_rows
+import graph_insert_cases as gic
+from graph_cases import build_graph_ref, detours, forward_lists, graph_search_ref, merge_reverse, random_graph, random_rows
 from graph_seed_cases import graph_search_seeded_ref
 from list_cases import same_bits
 from text_similarity_amd import ops
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+rng = np.random.default_rng(seed)
 dev = lambda x, t=None: torch.from_numpy(np.ascontiguousarray(x, dtype=t)).cuda()
 bad = 0
 t0 = time.time()
@@ -106,5 +113,66 @@ for case in range(cases):
     bad += not ok
     print(f"case {case:3d} {space:6s} d={d:3d} N={N:5d} R={R:2d} E={E:3d} Q={Q:2d} k={k:4d} ef={ef:4d} w={width} iters={iters:5d} {kind:6s} "
           f"{'ok' if ok else 'MISMATCH'}  ({time.time() - t0:.0f} s)", flush=True)
+rng = np.random.default_rng([seed, 1])
+inserts = max(1, cases // 4)
+for case in range(inserts):
+    same = lambda t, a: np.array_equal(t.cpu().numpy(), a)
+    if case % 3 == 0:
+        n, B = int(rng.choice([1, 2, 65, 500])), int(rng.choice([1, 7, 300]))
+        K0 = int(rng.choice([1, 2, 8, 33, 64, 128]))
+        R = int(rng.integers(1, min(K0, 64) + 1))
+        graph = rng.integers(-1, n + B + 2, size=(n, R))
+        near = (rng.integers(0, n + B, size=(B, 1)) + rng.integers(0, 2 * K0 + 2, size=(B, K0))) % (n + B)
+        cand = np.where(rng.random((B, K0)) < rng.choice([0.0, 0.5, 0.95]), near, rng.integers(-1, n + B + 2, size=(B, K0)))
+        fwd, det, st = ops.graph_insert_prune(dev(cand, np.int32), dev(graph, np.int32), return_detours=True)
+        torch.cuda.synchronize()
+        F, D, rst = gic.insert_prune(cand, graph)
+        ok = same(fwd, F) and same(det, D) and same(st, rst)
+        what = f"insert-prune n={n:4d} B={B:3d} K0={K0:3d} R={R:2d}"
+    elif case % 3 == 1:
+        d = int(rng.choice([1, 63, 64, 65, 300, 384, 385, 767, 768]))
+        space = str(rng.choice(["cosine", "dot", "l2"] if d <= ops.L2_MAX_DIM else ["cosine", "dot"]))
+        N, R = int(rng.choice([2, 65, 400])), int(rng.choice([1, 2, 8, 33, 64]))
+        c = random_rows(rng, N, d, dup=True)
+        c[rng.choice(N, max(1, N // 20), replace=False), 0] = np.nan
+        graph = np.where(rng.random((N, R)) < 0.2, -1, rng.integers(0, N, size=(N, R)))
+        T = int(rng.integers(1, N + 1))
+        targets = np.sort(rng.choice(N, size=T, replace=False))
+        lens = rng.integers(0, int(rng.choice([4, 40, 700])), size=T)
+        lims = np.concatenate([[0], np.cumsum(lens)])
+        ids = rng.integers(-1, N + 2, size=int(lims[-1]))
+        g = dev(graph, np.int32)
+        st = ops.graph_link_reverse(space, dev(c), g, dev(targets, np.int32), dev(lims, np.int64), dev(ids, np.int32))
+        torch.cuda.synchronize()
+        G, rst = gic.link_reverse(space, c, graph, targets, lims, ids)
+        ok = same(g, G) and same(st, rst)
+        what = f"insert-link  {space:6s} d={d:3d} N={N:4d} R={R:2d} T={T:4d} in={int(lims[-1]):6d} cut={int((rst & gic.LINK_ST_CUT).any())}"
+    else:
+        d = int(rng.choice([8, 65, 384]))
+        space = str(rng.choice(["cosine", "dot", "l2"]))
+        n, B, batch = int(rng.choice([40, 300])), int(rng.choice([1, 30, 130])), int(rng.choice([1, 16, 64]))
+        R = int(rng.choice([2, 8, 16]))
+        K0 = int(rng.choice([R, 2 * R]))
+        width, E = int(rng.integers(1, 5)), int(rng.choice([1, 8]))
+        iters = int(rng.choice([2, 20]))
+        c = random_rows(rng, n + B, d, dup=True)
+        base = build_graph_ref(space, c[:n], min(K0, n - 1), R)
+        e = rng.choice(n, size=E, replace=False)
+        dead = rng.random(n) < 0.1
+        want = gic.insert_ref(space, c[:n], base, c[n:], K0, R, batch, width, iters, entries=e, dead=dead)
+        rows, graph = dev(c), torch.empty((n + B, R), dtype=torch.int32, device="cuda")
+        graph[:n] = dev(base, np.int32)
+        for a in range(n, n + B, batch):
+            b = min(batch, n + B - a)
+            row_ids = np.arange(a, dtype=np.int32)
+            row_ids[:n][dead] = -1
+            ops.graph_insert(space, rows[:a + b], graph[:a + b], a, K0, entries=dev(e, np.int32), width=width, max_iters=iters,
+                             row_ids=dev(row_ids) if dead.any() else None)
+        torch.cuda.synchronize()
+        ok = same(graph, want)
+        what = f"insert       {space:6s} d={d:3d} n={n:4d} B={B:3d} batch={batch:2d} R={R:2d} K0={K0:2d} w={width} iters={iters:2d}"
+    bad += not ok
+    print(f"case {cases + case:3d} {what} {'ok' if ok else 'MISMATCH'}  ({time.time() - t0:.0f} s)", flush=True)
+cases += inserts
 print(f"fuzz_graph: {cases - bad}/{cases} cases exact")
 sys.exit(1 if bad else 0)
